@@ -17,8 +17,11 @@ all-gather of one step overlap the next step's matrix work (every step is still 
 batch).  A caller with a dependency between steps gets the single-stream figure, reported next to it
 (`value_single_stream`).
 
-When K steps take less than 50 ms the timed region (exactly K steps between two fences) is repeated and the
-MEDIAN region is reported (`timed_regions`), so that a 3 ms measurement is not at the mercy of one hiccup.
+The timed region is exactly K = --steps steps after W = --warmup untimed ones, between two fences; `ms_per_step` is
+its duration / K.  It is never repeated or lengthened: every step draws fresh device noise, so what the last step
+computes depends on how many steps ran, and `--dump-outputs DIR` writes exactly that (same arguments, same inputs, same
+output: two builds compare output for output).  For a stable figure choose K so that the region is long: on MI355X
+the first ~16 ms after the warm-up run ~9 % slower (config 2: 200 steps read 0.082 ms, 20000 steps 0.075 ms).
 
 Rank 0 prints one JSON line.  Besides the contract fields it carries
   roofline      the matrix-core kernel with the largest launch time: algorithmic FLOPs per launch / its average
@@ -428,6 +431,23 @@ def c4_leg(dev, steps=40):
                 steps=steps, streams=1, dtype="bf16", roofline=roof, mfma_kernels=kernels)
 
 
+DUMP_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write `arrays` (name -> CPU tensor, scenes along dim 0) as out_dir/<name>.npy in float32.  Above DUMP_BYTES in
+    all, the same fixed, seeded sample of scenes (sorted) is taken from every array.  Returns a summary for the line."""
+    import numpy as np
+    B = next(iter(arrays.values())).shape[0]
+    n = min(B, (DUMP_BYTES - 4096) // sum(t[0].numel() * 4 for t in arrays.values()))     # (4096: the .npy headers)
+    idx = None if n == B else torch.randperm(B, generator=torch.Generator().manual_seed(seed))[:n].sort().values
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), (t if idx is None else t[idx]).float().numpy())
+    return dict(dir=out_dir, scenes=n, of_scenes=B, sample_seed=None if idx is None else seed,
+                arrays={k: [n, *t.shape[1:]] for k, t in arrays.items()})
+
+
 def self_launch(n_gpus, port, dry):
     """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nnodes=1
     --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>` as a CHILD process and return its exit
@@ -471,7 +491,12 @@ def main():
     ap.add_argument("--master-port", type=int, default=29533, help="rendezvous port of the self-launched N > 1 run")
     ap.add_argument("--dry-launch", action="store_true",
                     help="with --gpus N > 1 and no WORLD_SIZE: print the launch command (JSON) instead of running it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0: features, H) as DIR/<name>.npy "
+                         "in float32; a fixed, seeded sample of the scenes when that exceeds 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cfg = dict(CONFIGS[args.config])
     if args.batch_per_gpu:
         cfg["B"] = args.batch_per_gpu
@@ -525,7 +550,7 @@ def main():
             G.set_noise_mode("device", seed=99 + 1000 * rank)
             streams = [torch.cuda.current_stream()]
             graphs = []
-            runs = [lambda: block(f)[0]]
+            runs = [lambda: block(f)]
         else:
             streams = [torch.cuda.Stream(device=dev) for _ in range(S)] if S > 1 else [torch.cuda.current_stream()]
             # every rank and every stream draws its own noise (a shard is not a copy of another shard)
@@ -535,7 +560,7 @@ def main():
                       for i in range(S)]
             for gr in graphs:
                 gr.f_in.copy_(f)
-            runs = [(lambda gr=gr: gr()[0]) for gr in graphs]
+            runs = [(lambda gr=gr: gr()) for gr in graphs]
             # the single-stream figure (a caller with a dependency between steps) uses the latency form
             lat_graph = None
             if not distributed:
@@ -544,12 +569,14 @@ def main():
                 lat_graph.f_in.copy_(f)
         torch.cuda.synchronize()
         step_no = [0]
+        last = [None]                     # (features, H) the latest step returned
 
         def step():
             i = step_no[0] % S
             step_no[0] += 1
             with torch.cuda.stream(streams[i]):
-                out = runs[i]()
+                last[0] = runs[i]()
+                out = last[0][0]
                 if bg is not None:
                     bg.put(out if args.gather_full else out[..., block.h_dim:])
             return out
@@ -568,10 +595,15 @@ def main():
         timer = RegionTimer(fence, dist if distributed else None, dev)
         for _ in range(args.warmup):
             step()
-        # short regions are repeated (same K steps each) and the median is reported; every rank takes the same count
-        regions = timer.measure(args.steps, step)
+        # exactly K timed steps, one region (see the module docstring)
+        regions = timer.measure(args.steps, step, n_regions=1)
         n_regions = len(regions)
         elapsed = statistics.median(regions)
+        dumped = None
+        if args.dump_outputs and rank == 0:
+            # copied before any later leg replays the graphs (the outputs are their static buffers)
+            dumped = dump_outputs(args.dump_outputs, {k: t.cpu() for k, t in zip(("features", "H"), last[0])
+                                                      if t is not None})
 
         # ---- the same K steps on ONE stream, back to back (what a caller with a dependency between steps sees) ----
         def step1():
@@ -642,6 +674,7 @@ def main():
             "value_parity_mode": None if parity is None else parity["scenes_per_s"], "parity_mode": parity,
             "per_module_us": modules, "configs": {"c4": c4},
             "cpu_baseline": cpu,
+            "dumped_outputs": dumped,
         }
         print(json.dumps(line), flush=True)
     if distributed:

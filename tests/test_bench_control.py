@@ -110,3 +110,27 @@ def test_region_count_rule():
     assert RegionTimer.region_count(0.003) == 25
     c = RegionTimer.region_count(0.04)
     assert c % 2 == 1 and 3 <= c <= 25
+
+
+def test_dump_outputs_float32_within_budget_same_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files within the byte budget; above it the same seeded scene sample from every
+    array, and the same one on every run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    B = 200                      # 200 * (11*320 + 23*11) * 4 B = 3 MB > 1 MB; scene ids < 256 are exact in bf16
+    feats = torch.arange(B, dtype=torch.float32)[:, None, None].expand(B, 11, 320).to(torch.bfloat16)
+    H = torch.arange(B, dtype=torch.float32)[:, None, None].expand(B, 23, 11).contiguous()
+    runs = [bench.dump_outputs(str(tmp_path / d), {"features": feats, "H": H}) for d in ("a", "b")]
+    assert runs[0]["scenes"] == runs[1]["scenes"] < B
+    for d in ("a", "b"):
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["H.npy", "features.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 1 << 20
+    f, h = (np.load(tmp_path / "a" / n) for n in ("features.npy", "H.npy"))
+    assert f.dtype == h.dtype == np.float32 and f.shape == (runs[0]["scenes"], 11, 320)
+    assert np.array_equal(f[:, 0, 0], h[:, 0, 0]) and np.all(np.diff(h[:, 0, 0]) > 0)   # same scenes, in order
+    assert all(np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)) for n in ("features.npy", "H.npy"))
+    small = bench.dump_outputs(str(tmp_path / "c"), {"H": H[:4]})            # within budget: everything, as is
+    assert small["scenes"] == 4 and np.array_equal(np.load(tmp_path / "c" / "H.npy"), H[:4].numpy())
