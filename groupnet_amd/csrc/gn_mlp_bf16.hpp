@@ -637,7 +637,8 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
   const int gi = find_group(Tb, lwg);
   const gn_edge_group_t G = Tb.g[gi];
   const int rows = G.rows, K = G.K;
-  const int blk = (lwg - Tb.first_wg[gi]) * 4 + wave_id();
+  const bool sparse = hyper_unstaged(G, 128, PoolStage<T>::kPitch * sizeof(T), pool_bytes);   // one live row block
+  const int blk = sparse ? (wave_id() == 0 ? lwg - Tb.first_wg[gi] : (rows + 31) / 32) : (lwg - Tb.first_wg[gi]) * 4 + wave_id();
   const RowBlock rb = row_block(rows, blk);      // (a wave past the group's rows works on a clamped row, stores nothing)
   const int lane = rb.lane, h = rb.h;
   const int unit = lwg * 4 + wave_id();
@@ -647,12 +648,21 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
   if (G.edges != nullptr) {
     load_rows<2>(reinterpret_cast<const T*>(G.edges), GN_FEAT, rb.row_ld, h, in);
   } else {
-    // fused node -> edge pooling; unordered pairs: from the scenes' node rows staged in LDS when they fit
+    // fused node -> edge pooling, from the scenes' node rows staged in LDS when they fit (unordered pairs: x' and pq at
+    // once; hyper modules: pq, then x', through one buffer)
     const int nodes_max = G.pool_H == nullptr && G.sym_N > 0 ? pool_stage_nodes(128, gn_pair_count(G.pool_N), G.pool_N) : 0;
-    if (nodes_max > 0 && PoolStage<T>::bytes(nodes_max) <= (size_t)pool_bytes) {       // (block-uniform)
+    const int r0 = (lwg - Tb.first_wg[gi]) * 128;
+    if (G.pool_H != nullptr) {
+      if (pool_bytes < 0)
+        pooled_rows<T>(G, rb.row_ld, h, in);      // GN_POOL_STAGE = 0: the per-member reference form
+      else if ((size_t)hyper_stage_nodes(128, G.pool_E, G.pool_N) * PoolStage<T>::kPitch * sizeof(T) <= (size_t)pool_bytes) {
+        pooled_rows_hyper_staged<T, 1>(G, r0, min(rows - 1, r0 + 127), {rb.row_ld}, h, reinterpret_cast<T*>(pool_dyn),
+                                       [&](auto, f32x16 (&p)[2]) { in[0] = p[0], in[1] = p[1]; });
+      } else
+        pooled_rows_hyper<T>(G, rb.row_ld, h, in);
+    } else if (nodes_max > 0 && pool_bytes >= 0 && PoolStage<T>::bytes(nodes_max) <= (size_t)pool_bytes) {   // (block-uniform)
       T* s_xp = reinterpret_cast<T*>(pool_dyn);
       T* s_pq = s_xp + (size_t)nodes_max * PoolStage<T>::kPitch;
-      const int r0 = (lwg - Tb.first_wg[gi]) * 128;
       const int node0 = pool_stage_fill<T>(G, r0, min(rows - 1, r0 + 127), s_xp, s_pq);
       __syncthreads();
       pooled_rows_staged<T>(G, rb.row_ld, h, s_xp, s_pq, node0, in);
@@ -2215,29 +2225,40 @@ __global__ __launch_bounds__(256, 2) void edge_rb2_kernel(GroupTable<gn_edge_gro
   const float* bd1 = G.bias + 448;
   WS ws;
   ws.begin(G.Wx, wring, lane, wave, 80 / WS::CH);
-  // fused node -> edge pooling of unordered pairs: from the scenes' node rows staged in LDS when they fit
+  // fused node -> edge pooling, from the scenes' node rows staged in LDS when they fit (unordered pairs: x' and pq at
+  // once; hyper modules: pq, then x', through one buffer)
   const int nodes_max = G.edges == nullptr && G.pool_H == nullptr && G.sym_N > 0
                             ? pool_stage_nodes(128 * RB, gn_pair_count(G.pool_N), G.pool_N) : 0;
-  const bool staged = nodes_max > 0 && PoolStage<T>::bytes(nodes_max) <= (size_t)pool_bytes;   // (block-uniform)
+  const bool staged = nodes_max > 0 && pool_bytes >= 0 && PoolStage<T>::bytes(nodes_max) <= (size_t)pool_bytes;   // (block-uniform)
+  const bool hyper_staged = G.edges == nullptr && G.pool_H != nullptr && pool_bytes >= 0 &&
+                            (size_t)hyper_stage_nodes(128 * RB, G.pool_E, G.pool_N) * PoolStage<T>::kPitch * sizeof(T) <=
+                                (size_t)pool_bytes;
   T* s_xp = reinterpret_cast<T*>(pool_dyn);
   T* s_pq = s_xp + (size_t)nodes_max * PoolStage<T>::kPitch;
+  const int r0 = (lwg - Tb.first_wg[gi]) * (128 * RB);
   int node0 = 0;
   if (staged) {
-    const int r0 = (lwg - Tb.first_wg[gi]) * (128 * RB);
     node0 = pool_stage_fill<T>(G, r0, min(rows - 1, r0 + 128 * RB - 1), s_xp, s_pq);
     __syncthreads();
   }
   Parts<1> xi[RB][2][2];
+  if (hyper_staged) {
+    pooled_rows_hyper_staged<T, RB>(G, r0, min(rows - 1, r0 + 128 * RB - 1), {rb[0].row_ld, rb[1].row_ld}, h,
+                                    reinterpret_cast<T*>(pool_dyn),
+                                    [&](auto bc, f32x16 (&in)[2]) { make_parts_tiles<1, 2>(in, xi[decltype(bc)::value], ovf_unused); });
+  } else {
 #pragma unroll
-  for (int b = 0; b < RB; ++b) {
-    f32x16 in[2];
-    if (G.edges != nullptr)
-      load_rows<2>(reinterpret_cast<const T*>(G.edges), GN_FEAT, rb[b].row_ld, h, in);
-    else if (staged)
-      pooled_rows_staged<T>(G, rb[b].row_ld, h, s_xp, s_pq, node0, in);
-    else
-      pooled_rows<T>(G, rb[b].row_ld, h, in);  // fused node -> edge pooling
-    make_parts_tiles<1, 2>(in, xi[b], ovf_unused);
+    for (int b = 0; b < RB; ++b) {
+      f32x16 in[2];
+      if (G.edges != nullptr)
+        load_rows<2>(reinterpret_cast<const T*>(G.edges), GN_FEAT, rb[b].row_ld, h, in);
+      else if (staged)
+        pooled_rows_staged<T>(G, rb[b].row_ld, h, s_xp, s_pq, node0, in);
+      else
+        pooled_rows<T>(G, rb[b].row_ld, h, in);  // fused node -> edge pooling (hyper groups without a stage: the
+                                                 // per-member form; the batched one spills beside two row blocks)
+      make_parts_tiles<1, 2>(in, xi[b], ovf_unused);
+    }
   }
   f32x16 bias_n = load_bias_tile(bi0, h), bias_nn = load_bias_tile(bi0 + 32, h);
   f32x16 hidn[RB];

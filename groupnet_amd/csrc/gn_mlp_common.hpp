@@ -495,6 +495,228 @@ __device__ __forceinline__ void pooled_rows_staged(const gn_edge_group_t& G, int
   axpy_row(s_xp + rj, wj, h, in, false);
 }
 
+// ---- the hyper pooling (N <= 16) in three batched passes ---------------------------------------------------------
+// pooled_rows' hyper branch loads each member's rows inside a per-member branch: one memory latency per member and pass
+// (3 x 11 for a scale-N hyperedge).  Here a row's members are a 16-bit mask (walked in ascending node order, as there)
+// plus their H in registers, and each pass fetches the rows of a batch of members at once — unconditionally, a missing
+// member reading node 0 of the scene — and folds only the live ones in (selects, not branches).  Same members, same
+// order, same fmaf chains, max before sum, gn_nonmember_sum, weight v / sum * H: results identical to pooled_rows.  The
+// node rows come from `rowp(n)` (node n of the row's scene): the workgroup's LDS stage, or global memory for groups whose
+// scenes do not fit one.
+constexpr int kHyperMax = 16;
+// f(integral_constant<int, 0>), ..., f(integral_constant<int, N - 1>)
+template <int N, int I = 0, typename F>
+__device__ __forceinline__ void gn_static_for(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    gn_static_for<N, I + 1>(f);
+  }
+}
+struct HyperRow {
+  unsigned mask;              // members: nodes with H != 0
+  int cnt;
+  float hv[kHyperMax];        // H of the k-th member (0 past cnt); after hyper_weights: its pooling weight
+};
+// the next member of a mask walk (node 0 once the mask is empty)
+__device__ __forceinline__ int next_member(unsigned& m) {
+  const int n = m != 0u ? __builtin_ctz(m) : 0;
+  m &= m - 1u;                                              // (0 stays 0)
+  return n;
+}
+// the row's incidence (0 past N)
+__device__ __forceinline__ void hyper_load_h(const gn_edge_group_t& G, int row, float (&hr)[kHyperMax]) {
+  const int N = G.pool_N;
+  const float* Hrow = G.pool_H + (size_t)row * N;
+#pragma unroll
+  for (int n = 0; n < kHyperMax; ++n) hr[n] = n < N ? Hrow[n] : 0.f;
+}
+__device__ __forceinline__ void hyper_members(const float (&hr)[kHyperMax], HyperRow& R) {
+  unsigned mask = 0u;
+#pragma unroll
+  for (int n = 0; n < kHyperMax; ++n) mask |= (unsigned)(hr[n] != 0.f) << n;
+  R.mask = mask;
+  R.cnt = __popc(mask);
+  // compact the members' H to the front (k-th member at k): a prefix-count placement, no run-time register indexing
+#pragma unroll
+  for (int k = 0; k < kHyperMax; ++k) R.hv[k] = 0.f;
+#pragma unroll
+  for (int n = 0; n < kHyperMax; ++n) {
+    const int k = __popc(mask & ((1u << n) - 1u));
+#pragma unroll
+    for (int j = 0; j <= n; ++j) R.hv[j] = (hr[n] != 0.f && k == j) ? hr[n] : R.hv[j];
+  }
+}
+// Q = sum H Qn, the logits, their max and the softmax sum, from the members' pq rows; leaves the pooling weights in R.hv
+template <typename T, int BATCH = 4, typename RowP>
+__device__ __forceinline__ void hyper_weights(const gn_edge_group_t& G, RowP rowp, int h, HyperRow& R) {
+  const int N = G.pool_N, cnt = R.cnt;
+  float w2[16];
+  load16(G.w2 + 16 * h, w2);
+  const float b2v = *G.b2;
+  float Q[16];
+#pragma unroll
+  for (int c = 0; c < 16; ++c) Q[c] = 0.f;
+  unsigned m = R.mask;
+#pragma unroll
+  for (int k0 = 0; k0 < kHyperMax; k0 += BATCH) {
+    if (!__any(k0 < cnt)) break;
+    float Qn[BATCH][16];
+#pragma unroll
+    for (int u = 0; u < BATCH; ++u) load16(rowp(next_member(m)) + 32 + 16 * h, Qn[u]);
+#pragma unroll
+    for (int u = 0; u < BATCH; ++u)
+#pragma unroll
+      for (int c = 0; c < 16; ++c) Q[c] = k0 + u < cnt ? fmaf(R.hv[k0 + u], Qn[u][c], Q[c]) : Q[c];
+  }
+  float v[kHyperMax];
+  float mx = cnt < N ? 0.f : -INFINITY;
+  m = R.mask;
+#pragma unroll
+  for (int k0 = 0; k0 < kHyperMax; k0 += BATCH) {
+#pragma unroll
+    for (int u = 0; u < BATCH; ++u) v[k0 + u] = 0.f;
+    if (!__any(k0 < cnt)) continue;
+    float Pn[BATCH][16];
+#pragma unroll
+    for (int u = 0; u < BATCH; ++u) load16(rowp(next_member(m)) + 16 * h, Pn[u]);
+#pragma unroll
+    for (int u = 0; u < BATCH; ++u) {
+      float t = 0.f;
+#pragma unroll
+      for (int c = 0; c < 16; ++c) t = fmaf(w2[c], fmaxf(Pn[u][c] + Q[c], 0.f), t);
+      t += __shfl_xor(t, 32, GN_WAVE);     // (both lanes of a row have the same members)
+      if (k0 + u < cnt) {
+        v[k0 + u] = (t + b2v) * R.hv[k0 + u];
+        mx = fmaxf(mx, v[k0 + u]);
+      }
+    }
+  }
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < kHyperMax; ++k)
+    if (k < cnt) {
+      v[k] = expf(v[k] - mx);
+      sum += v[k];
+    }
+  sum += gn_nonmember_sum(N - cnt, mx);
+#pragma unroll
+  for (int k = 0; k < kHyperMax; ++k) R.hv[k] = k < cnt ? v[k] / sum * R.hv[k] : 0.f;
+}
+// in = sum over the members of weight * x'_n, from the members' x' rows
+template <typename T, int BATCH = 2, typename RowP>
+__device__ __forceinline__ void hyper_pool(RowP rowp, int h, const HyperRow& R, f32x16 (&in)[2]) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) in[t][r] = 0.f;
+  unsigned m = R.mask;
+#pragma unroll
+  for (int k0 = 0; k0 < kHyperMax; k0 += BATCH) {
+    if (!__any(k0 < R.cnt)) break;
+    f32x4 x[BATCH][8];
+#pragma unroll
+    for (int u = 0; u < BATCH; ++u) {
+      const T* p = rowp(next_member(m)) + 4 * h;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) x[u][i] = ld4(p + 32 * (i >> 2) + 8 * (i & 3));
+    }
+#pragma unroll
+    for (int u = 0; u < BATCH; ++u) {
+      const bool live = k0 + u < R.cnt;
+      const float w = R.hv[k0 + u];
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float a = in[i >> 2][4 * (i & 3) + c];
+          in[i >> 2][4 * (i & 3) + c] = live ? fmaf(w, x[u][i][c], a) : a;
+        }
+    }
+  }
+}
+// the whole hyper pooling of one row straight from global memory (groups whose scenes do not fit the LDS stage)
+template <typename T>
+__device__ __forceinline__ void pooled_rows_hyper(const gn_edge_group_t& G, int row, int h, f32x16 (&in)[2]) {
+  const size_t sb = (size_t)(row / G.pool_E) * G.pool_N;
+  const T* xp = reinterpret_cast<const T*>(G.xp) + sb * GN_FEAT;
+  const T* pq = reinterpret_cast<const T*>(G.pq) + sb * GN_FEAT;
+  float hr[kHyperMax];
+  hyper_load_h(G, row, hr);
+  HyperRow R;
+  hyper_members(hr, R);
+  hyper_weights<T>(G, [&](int n) { return pq + (size_t)n * GN_FEAT; }, h, R);
+  hyper_pool<T, sizeof(T) == 4 ? 4 : 2>([&](int n) { return xp + (size_t)n * GN_FEAT; }, h, R, in);
+}
+// copies `nodes` node rows from src into the stage at pitch PoolStage<T>::kPitch (all threads; the caller barriers)
+template <typename T>
+__device__ __forceinline__ void stage_node_rows(const T* __restrict__ src, int nodes, T* __restrict__ s) {
+  // kFill pieces per thread in flight before the first store: a stage of ~140 rows is two memory round trips, not the
+  // nine of a load-store-per-iteration loop
+  using PS = PoolStage<T>;
+  constexpr int kFill = 8;
+  const int total = nodes * PS::kRowPieces;
+  for (int i0 = threadIdx.x; i0 < total; i0 += kFill * (int)blockDim.x) {
+    f32x4 v[kFill];
+#pragma unroll
+    for (int u = 0; u < kFill; ++u) {
+      const int idx = i0 + u * (int)blockDim.x;
+      if (idx < total) v[u] = *reinterpret_cast<const f32x4*>(src + (size_t)idx * PS::kPiece);
+    }
+#pragma unroll
+    for (int u = 0; u < kFill; ++u) {
+      const int idx = i0 + u * (int)blockDim.x;
+      const int r = idx / PS::kRowPieces, c = idx - r * PS::kRowPieces;
+      if (idx < total) *reinterpret_cast<f32x4*>(s + r * PS::kPitch + c * PS::kPiece) = v[u];
+    }
+  }
+}
+__host__ __device__ inline int hyper_stage_nodes(int wg_rows, int E, int N) { return pool_stage_nodes(wg_rows, E, N); }
+// A hyper group whose scenes do not fit the stage of a `wg_rows`-row workgroup (scale = N: one hyperedge, one scene per
+// row) pools from global memory, where each load instruction touches one line per row: ~200 instructions x 32 lines per
+// row block at N = 11, and the L1 handles one line per clock.  Four such row blocks per CU made the group the long pole of
+// the launch (edge kernel 26 -> 47 us at B = 512); the launcher gives it ONE live row block per workgroup instead (the
+// other three waves run a clamped row that stores nothing).
+__host__ __device__ inline bool hyper_unstaged(const gn_edge_group_t& G, int wg_rows, size_t row_bytes, int pool_bytes) {
+  return G.edges == nullptr && G.pool_H != nullptr && pool_bytes >= 0 &&
+         (size_t)hyper_stage_nodes(wg_rows, G.pool_E, G.pool_N) * row_bytes > (size_t)pool_bytes;
+}
+// The hyper pooling of a workgroup's rows [r0, r1] through ONE stage buffer of hyper_stage_nodes() rows, in two phases:
+// the scenes' pq rows (member masks, Q, logits, softmax weights into registers), then their x' rows; emit(b, in) receives
+// row block b's pooled rows.  Block-uniform: every thread of the workgroup calls it (three barriers).  x' and pq staged
+// together would not fit beside the weight ring at two workgroups per CU (N = E = 11: 143 nodes x 2 x 272 B).
+template <typename T, int RB, int BATCH = 4, typename Emit>
+__device__ __forceinline__ void pooled_rows_hyper_staged(const gn_edge_group_t& G, int r0, int r1, const int (&row)[RB], int h,
+                                                         T* __restrict__ s, Emit emit) {
+  using PS = PoolStage<T>;
+  const int N = G.pool_N, E = G.pool_E;
+  const int node0 = (r0 / E) * N, nodes = (r1 / E - r0 / E + 1) * N;
+  HyperRow R[RB];
+  {
+    float hr[RB][kHyperMax];           // (requested before the stage's loads: its round trips hide this one)
+#pragma unroll
+    for (int b = 0; b < RB; ++b) hyper_load_h(G, row[b], hr[b]);
+    stage_node_rows(reinterpret_cast<const T*>(G.pq) + (size_t)node0 * GN_FEAT, nodes, s);
+#pragma unroll
+    for (int b = 0; b < RB; ++b) hyper_members(hr[b], R[b]);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int b = 0; b < RB; ++b) {
+    const T* sb = s + (size_t)((row[b] / E) * N - node0) * PS::kPitch;      // the row's scene in the stage
+    hyper_weights<T, BATCH>(G, [&](int n) { return sb + n * PS::kPitch; }, h, R[b]);
+  }
+  __syncthreads();
+  stage_node_rows(reinterpret_cast<const T*>(G.xp) + (size_t)node0 * GN_FEAT, nodes, s);
+  __syncthreads();
+  gn_static_for<RB>([&](auto bc) {
+    constexpr int b = decltype(bc)::value;
+    const T* sb = s + (size_t)((row[b] / E) * N - node0) * PS::kPitch;
+    f32x16 in[2];
+    hyper_pool<T>([&](int n) { return sb + n * PS::kPitch; }, h, R[b], in);
+    emit(bc, in);
+  });
+}
+
 // The 16 pre-activation values lane (j,h) needs of hidden tile t of type k for ONE node: A row + offset.
 struct PreTile {
   f32x4 v[4];

@@ -1008,6 +1008,12 @@ static long long rb2_min_pairs() {
 }
 
 // ---- edge MLP --------------------------------------------------------------------------------------------------
+constexpr size_t kEdgeCuLds = 160 * 1024;      // LDS per CU (gfx950)
+template <typename K>
+static size_t static_lds_of(K kernel) {
+  hipFuncAttributes a{};
+  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel)) == hipSuccess ? a.sharedSizeBytes : kEdgeCuLds / 2;
+}
 static int edge_launch(const gn_edge_group_t* groups, int n_groups, float tau, unsigned long long seed,
                        const unsigned long long* offset_dev, hipStream_t stream, bool twin) {
   GN_CHECK(check_groups(groups, n_groups));
@@ -1047,19 +1053,34 @@ static int edge_launch(const gn_edge_group_t* groups, int n_groups, float tau, u
     wg += row_grid(G.rows);
   }
   T.first_wg[n_groups] = wg;
-  // LDS for the staged node rows of the fused pairwise pooling (the largest any group wants, at most 48 KiB; a group
-  // that would need more pools straight from L2).  GN_POOL_STAGE = 0 switches the stage off.
+  // LDS for the staged node rows of the fused pooling: the largest stage any group wants, as long as the launch keeps two
+  // workgroups per CU (160 KiB of LDS less the kernel's static weight ring; edge_x_kernel<2, float>: 44 800 bytes).  A
+  // group that would need more pools straight from global memory.  GN_POOL_STAGE = 0 switches the stage off (pool_bytes
+  // = -1: every group in the per-member reference form).
   const bool no_pool_stage = getenv("GN_POOL_STAGE") != nullptr && atoi(getenv("GN_POOL_STAGE")) == 0;   // (per call: tests toggle it)
-  auto pool_bytes_for = [&](int wg_rows) {
+  auto pool_bytes_for = [&](int wg_rows, size_t static_lds) -> int {
+    if (no_pool_stage) return -1;
+    const size_t cap = kEdgeCuLds / 2 - min(static_lds, kEdgeCuLds / 2);
     size_t need = 0;
-    for (int g = 0; g < n_groups && !no_pool_stage; ++g) {
+    for (int g = 0; g < n_groups; ++g) {
       const gn_edge_group_t& G = groups[g];
-      if (G.edges != nullptr || G.pool_H != nullptr || G.sym_N <= 0) continue;
-      const int nodes = pool_stage_nodes(wg_rows, gn_pair_count(G.pool_N), G.pool_N);
-      const size_t b = twin ? PoolStage<__bf16>::bytes(nodes) : PoolStage<float>::bytes(nodes);
-      if (b <= 48 * 1024 && b > need) need = b;
+      if (G.edges != nullptr || (G.pool_H == nullptr && G.sym_N <= 0)) continue;
+      const size_t row_bytes = twin ? PoolStage<__bf16>::kPitch * sizeof(__bf16) : PoolStage<float>::kPitch * sizeof(float);
+      const size_t b = G.pool_H != nullptr ? (size_t)hyper_stage_nodes(wg_rows, G.pool_E, G.pool_N) * row_bytes   // pq, then x'
+                                           : 2 * (size_t)pool_stage_nodes(wg_rows, gn_pair_count(G.pool_N), G.pool_N) * row_bytes;
+      if (b <= cap && b > need) need = b;
     }
-    return need;
+    return (int)need;
+  };
+  auto launch_lds = [](int pb) { return (size_t)(pb > 0 ? pb : 0); };
+  // edge_x_kernel: hyper groups without a stage get one workgroup per 32-row block (hyper_unstaged)
+  auto sparse_grid = [&](int pb, size_t row_bytes) {
+    int w = 0;
+    for (int g = 0; g < n_groups; ++g) {
+      T.first_wg[g] = w;
+      w += hyper_unstaged(groups[g], 128, row_bytes, pb) ? (groups[g].rows + 31) / 32 : row_grid(groups[g].rows);
+    }
+    T.first_wg[n_groups] = w;
   };
   if (twin) {
     // a large launch: two row blocks per wave (edge_rb2_kernel); GN_EDGE_RB2 = 0 / 1 forces the choice (parity tests)
@@ -1074,25 +1095,30 @@ static int edge_launch(const gn_edge_group_t* groups, int n_groups, float tau, u
         wg += ((groups[g].rows + 31) / 32 + 7) / 8;
       }
       T.first_wg[n_groups] = wg;
-      const size_t pb = pool_bytes_for(256);
-      hipLaunchKernelGGL((edge_rb2_kernel<__bf16>), dim3(table_xcd_grid(T)), dim3(256), pb, stream, T, tau, seed, offset_dev,
-                         (int)pb);
+      static const size_t rb2_static = static_lds_of(edge_rb2_kernel<__bf16>);
+      const int pb = pool_bytes_for(256, rb2_static);
+      hipLaunchKernelGGL((edge_rb2_kernel<__bf16>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb), stream, T, tau, seed,
+                         offset_dev, pb);
       return gn_check_launch();
     }
-    const size_t pb = pool_bytes_for(128);
-    hipLaunchKernelGGL((edge_x_kernel<1, __bf16>), dim3(table_xcd_grid(T)), dim3(256), pb, stream, T, tau, seed, offset_dev,
-                       (int)pb);
+    static const size_t x1_static = static_lds_of(edge_x_kernel<1, __bf16>);
+    const int pb = pool_bytes_for(128, x1_static);
+    sparse_grid(pb, PoolStage<__bf16>::kPitch * sizeof(__bf16));
+    hipLaunchKernelGGL((edge_x_kernel<1, __bf16>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb), stream, T, tau, seed,
+                       offset_dev, pb);
   }
   else if (xm) {
     const int hm = x_mode(groups, n_groups, [](const gn_edge_group_t& G) { return G.Wh != nullptr; });
     if (hm < 0) return GN_ERR_SHAPE;
-    const size_t pb = pool_bytes_for(128);
+    static const size_t x2_static = static_lds_of(edge_x_kernel<2, float>), x3_static = static_lds_of(edge_x_kernel<3, float>);
+    const int pb = pool_bytes_for(128, hm ? x2_static : x3_static);
+    sparse_grid(pb, PoolStage<float>::kPitch * sizeof(float));
     if (hm)
-      hipLaunchKernelGGL((edge_x_kernel<2, float>), dim3(table_xcd_grid(T)), dim3(256), pb, stream, T, tau, seed, offset_dev,
-                         (int)pb);
+      hipLaunchKernelGGL((edge_x_kernel<2, float>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb), stream, T, tau, seed,
+                         offset_dev, pb);
     else
-      hipLaunchKernelGGL((edge_x_kernel<3, float>), dim3(table_xcd_grid(T)), dim3(256), pb, stream, T, tau, seed, offset_dev,
-                         (int)pb);
+      hipLaunchKernelGGL((edge_x_kernel<3, float>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb), stream, T, tau, seed,
+                         offset_dev, pb);
   }
   else
     hipLaunchKernelGGL(edge_mlp_gumbel_kernel, dim3(wg), dim3(256), 0, stream, T, tau, seed, offset_dev);

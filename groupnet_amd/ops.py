@@ -712,11 +712,12 @@ class PoolSpec:
 
 
 # Hyper modules: largest N whose pooling the edge kernel may form itself (the kernel's bound is 16: a row's incidence
-# stays in registers).  Default 0 = pairwise graph only: without an LDS stage the hyper form pays one L2 latency per
-# member and pass — measured at B=512, N=11: edge kernel +15.7 us against the ~10 us the hyper groups cost in the
-# node2edge launch; the pairwise form costs +3 us and removes 5.5 us (and, at N=50 / B=1024, 2 x 167 MB of traffic).
-POOL_MAX_N = int(os.environ.get("GN_POOL_MAX_N", "0"))
+# stays in registers).  Default: all of them, so that an inference forward at N <= 16 has no node2edge launch.  The edge
+# kernel stages a workgroup's scenes in LDS (pq, then x', through one buffer); groups that fit no stage (scale = N: one
+# hyperedge per scene) pool from global memory with one live row block per workgroup ("Edge-kernel
+# prologue").  GN_POOL_MAX_N=0: pairwise graph only, hyper modules through the node2edge launch.
 POOL_KERNEL_MAX_N = 16
+POOL_MAX_N = int(os.environ.get("GN_POOL_MAX_N", str(POOL_KERNEL_MAX_N)))
 
 
 def edge_mlp_gumbel_grouped(items: Sequence[tuple], tau: float = 0.5, keep: Optional[List[dict]] = None
