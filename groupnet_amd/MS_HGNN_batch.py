@@ -26,7 +26,6 @@ from __future__ import annotations
 import warnings
 from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple, Union
 
-import os
 import torch
 import torch.nn as nn
 
@@ -39,9 +38,10 @@ _GUMBEL_TAU = 0.5      # model/MS_HGNN_batch.py:45
 # a per-lane gather of N feature rows in the prologue of an MFMA kernel (latency-bound at 1-2 waves per SIMD; measured
 # again in round 2 at N = 50, B = 1024, bf16: typed MLP 390 -> 439 us against a 38-us gather launch, closing MLP
 # 54 -> 303 us against 71 + 56 us of scatter launches).
-_FUSED_GATHER_MAX_N = int(os.environ.get("GN_FUSED_GATHER_MAX_N", "16"))     # eo = H @ ori inside the typed MLP kernel
-_FUSED_SCATTER_MAX_N = int(os.environ.get("GN_FUSED_SCATTER_MAX_N", "16"))   # cat(H^T feat, ori)/N inside the closing MLP
-_FUSE_POOL = os.environ.get("GN_FUSE_POOL", "1") != "0"   # node->edge pooling inside the edge kernel (inference)
+_FUSED_GATHER_MAX_N = 16      # eo = H @ ori inside the typed MLP kernel
+_FUSED_SCATTER_MAX_N = 16     # cat(H^T feat, ori)/N inside the closing MLP
+# node->edge pooling inside the edge kernel (inference); the parity tests clear it to compare against the node2edge launch
+_FUSE_POOL = True
 
 
 # ---------------------------------------------------------------------------------------------
@@ -558,12 +558,6 @@ class _Closed(list):
     """Outputs of closing MLPs that the aggregation launch applied itself."""
 
 
-def _pair_form() -> bool:
-    """Pairwise module, fp32 entry points: first layer of the typed aggregation MLP per NODE in the node stage + pair
-    form (True), or both layers per unordered pair inside the aggregation kernel (False: no `A` tensor)."""
-    return os.environ.get("GN_PAIR_FORM", "1") != "0"
-
-
 def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor], Hs: Sequence[Optional[Tensor]],
                         noises: Sequence, outs: Sequence[Optional[Tensor]], traces=None, join=None, affinity=None,
                         fuse_closing: bool = False) -> List[Tuple[Tensor, Tensor]]:
@@ -618,7 +612,7 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
         # graph its first layer is linear in the two nodes (eo = ori_i + ori_j) and runs once per NODE, in this
         # same launch (fp32 path; the bf16 twin runs both layers per pair on the matrix cores instead)
         specs = [((m.edge_aggregation_list[idx]._packed(), m.edge_aggregation_list[idx].edge_types)
-                  if (sy and not twin and _pair_form()) else None) for m, sy in zip(mods, syms)]
+                  if (sy and not twin) else None) for m, sy in zip(mods, syms)]
         xpq, As = ops.node_stage_grouped([(x, pk) for x, pk in zip(xs, pks)], keep, specs,
                                          affinity if idx == 0 else None)
         pair_A[:] = As

@@ -329,10 +329,10 @@ __device__ __forceinline__ void gemm_body(const GemmDesc& D, float (&As)[BK][BM 
 }
 
 // C = beta*C + alpha*op(A)op(B) (+bias)(relu)(mask), or with GN_GEMM_ACCUM: C += alpha*op(A)op(B) by atomics
-// (K split over workgroups).  fp32 matrix cores (v_mfma_f32_32x32x2_f32), operands staged through LDS
-// k-major so that either storage order of A and B loads coalesced.  Two kernels so that each keeps its own
-// register budget: the vector-staging one (16-byte aligned operands, K a multiple of 32 — every large
-// problem of the backward) runs 4 workgroups per CU; the scalar one takes anything.
+// (K split over workgroups).  Operands staged through LDS k-major so that either storage order of A and B loads
+// coalesced.  Two kernels so that each keeps its own register budget: the vector-staging one (16-byte aligned
+// operands, K a multiple of 32 — every large problem of the backward) runs 3 workgroups per CU; the scalar one
+// (fp32 matrix cores, v_mfma_f32_32x32x2_f32) takes anything.
 template <bool FAST, bool X6>
 __device__ __forceinline__ void gemm_dispatch(const GemmTable& T, float (&As)[BK][BM + 4], float (&Bs)[BK][BN + 4]) {
   int g = 0;
@@ -347,14 +347,8 @@ __device__ __forceinline__ void gemm_dispatch(const GemmTable& T, float (&As)[BK
   else gemm_body<true, true, FAST, X6>(D, As, Bs);
 }
 
-__global__ __launch_bounds__(kB, 4) void gemm_mfma_kernel(const GemmTable T) {
-  __shared__ float As[BK][BM + 4];
-  __shared__ float Bs[BK][BN + 4];
-  gemm_dispatch<true, false>(T, As, Bs);
-}
-
-// the same tiles with the products formed on the bf16 matrix cores from three-part splits (fp32-accurate, like the
-// forward's P = 3 kernels): the default for the vector-staged problems; GN_GEMM_X6=0 selects the fp32-core kernel
+// vector staging, the products formed on the bf16 matrix cores from three-part splits (fp32-accurate, like the
+// forward's P = 3 kernels)
 __global__ __launch_bounds__(kB, 3) void gemm_x6_kernel(const GemmTable T) {
   __shared__ float As[BK][BM + 4];
   __shared__ float Bs[BK][BN + 4];
@@ -787,9 +781,7 @@ extern "C" int gn_gemm_grouped_f32(const gn_gemm_desc_t* descs, int n, gn_stream
   T[0].n = T[1].n = 0;
   auto flush = [&](int which) {
     if (T[which].n == 0) return;
-    static const bool x6 = !(getenv("GN_GEMM_X6") && atoi(getenv("GN_GEMM_X6")) == 0);
-    if (which == 0 && x6) hipLaunchKernelGGL(gemm_x6_kernel, dim3((unsigned)tiles[0]), dim3(kB), 0, s, T[0]);
-    else if (which == 0) hipLaunchKernelGGL(gemm_mfma_kernel, dim3((unsigned)tiles[0]), dim3(kB), 0, s, T[0]);
+    if (which == 0) hipLaunchKernelGGL(gemm_x6_kernel, dim3((unsigned)tiles[0]), dim3(kB), 0, s, T[0]);
     else hipLaunchKernelGGL(gemm_mfma_edge_kernel, dim3((unsigned)tiles[1]), dim3(kB), 0, s, T[1]);
     T[which].n = 0;
     tiles[which] = 0;

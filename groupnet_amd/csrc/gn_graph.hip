@@ -7,14 +7,11 @@
 #include "gn_mlp_common.hpp"
 #include "gn_affinity.hpp"
 
-// hyperedges per wave and band whose H rows the node->edge kernel holds in registers (band = 4 waves x this many)
-#ifndef GN_N2E_U
-#define GN_N2E_U 4
-#endif
-
 namespace {
 
 constexpr int kBlock = 256;
+// hyperedges per wave and band whose H rows the node->edge kernel holds in registers (band = 4 waves x this many)
+constexpr int kN2EU = 4;
 constexpr size_t kLdsBudget = 128 * 1024;  // per workgroup (of the CU's 160 KiB)
 
 // --------------------------------------------------------------------------------------------
@@ -192,7 +189,7 @@ __device__ __forceinline__ void node2edge_hyper_body(const WaveTable<gn_n2e_grou
   const int total = sg * E;
   // H rows ride one band ahead in registers (N <= 64: one value per lane and edge, up to U edges per wave and band):
   // a wave that loaded each row when it needed it paid one memory latency per hyperedge.
-  constexpr int U = GN_N2E_U;
+  constexpr int U = kN2EU;
   const bool pre = N <= 64 && EB <= U * (kBlock / 64);
   float hn[U];
   auto fetch = [&](int e0n) {
@@ -1224,9 +1221,9 @@ static int node2edge_launch(const gn_n2e_group_t* groups, int n_groups, int B, i
     // most edges any group's workgroup walks
     int maxE = 1;
     for (int g = 0; g < T.n; ++g) maxE = maxE > T.g[g].E ? maxE : T.g[g].E;
-    EBh = (int)((size_t)3072 * GN_N2E_U / ((size_t)12 * N + 144));
+    EBh = (int)((size_t)3072 * kN2EU / ((size_t)12 * N + 144));
     EBh = EBh < 4 ? 4 : EBh;
-    if (N <= 64 && EBh > 4 * GN_N2E_U) EBh = 4 * GN_N2E_U;        // (the band whose H rows a workgroup can hold in registers, see the kernel)
+    if (N <= 64 && EBh > 4 * kN2EU) EBh = 4 * kN2EU;        // (the band whose H rows a workgroup can hold in registers, see the kernel)
     EBh = EBh > SGh * maxE ? SGh * maxE : EBh;
     size_t scratch = n2e_hyper_scratch_floats(EBh, N) * sizeof(float);
     size_t stage = (size_t)SGh * per_scene;
@@ -1247,7 +1244,6 @@ static int node2edge_launch(const gn_n2e_group_t* groups, int n_groups, int B, i
       while ((SGh + 1) * maxE <= kBlock / 2 && (size_t)(SGh + 1) * row_scene <= 56 * 1024 &&
              (long long)((B + SGh) / (SGh + 1)) * T.n >= 1024)
         ++SGh;
-      if (const char* e = getenv("GN_N2E_ROWS_SG")) SGh = atoi(e) > 0 ? atoi(e) : SGh;     // (tuning)
       EBh = 0;
       scratch = 0;
       stage = (size_t)SGh * row_scene;
@@ -1286,13 +1282,10 @@ extern "C" int gn_node2edge_bf16(const gn_n2e_group_t* groups, int n_groups, int
   return node2edge_launch<__bf16>(groups, n_groups, B, N, (hipStream_t)stream);
 }
 
-// workgroups a gather / scatter launch keeps at least when it packs several scenes into one (GN_GS_MIN_WGS).  2048 = two
-// rounds of the chip at B = 4096, N = 11: the second round's loads overlap the first one's stores (3.90 -> 4.12 TB/s for
-// the pair; 4096 and 8192 measured the same as 2048)
-static int gs_min_wgs() {
-  static const int v = getenv("GN_GS_MIN_WGS") != nullptr ? atoi(getenv("GN_GS_MIN_WGS")) : 2048;
-  return v;
-}
+// workgroups a gather / scatter launch keeps at least when it packs several scenes into one.  2048 = two rounds of the
+// chip at B = 4096, N = 11: the second round's loads overlap the first one's stores (3.90 -> 4.12 TB/s for the pair;
+// 4096 and 8192 measured the same as 2048)
+constexpr int kGsMinWgs = 2048;
 
 template <typename TS>
 static int gather_launch(const gn_gather_group_t* groups, int n_groups, int B, int N, hipStream_t s) {
@@ -1333,7 +1326,7 @@ static int gather_launch(const gn_gather_group_t* groups, int n_groups, int B, i
     const size_t per_scene = ori_b + (size_t)Emax * N * sizeof(float);
     if (per_scene <= kLdsBudget) {
       // several scenes per workgroup while the tile stays <= 24 KiB and the grid stays >= 1024
-      while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= gs_min_wgs())
+      while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= kGsMinWgs)
         G *= 2;
     } else {
       TE = (int)((kLdsBudget - ori_b) / ((size_t)N * sizeof(float)));
@@ -1397,7 +1390,7 @@ static int scatter_launch(const gn_scatter_group_t* groups, int n_groups, int B,
   if (nh > 0) {
     const size_t per_scene = (size_t)Emax * (GN_FEAT + N) * sizeof(float);
     int G = 1;
-    while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= gs_min_wgs())
+    while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= kGsMinWgs)
       G *= 2;
     gn_allow_big_lds(agg_scatter_kernel<TS>);
     hipLaunchKernelGGL(agg_scatter_kernel<TS>, dim3((B + G - 1) / G, nh), dim3(kBlock), (size_t)G * per_scene, s, T, B,

@@ -41,29 +41,12 @@
 #include "gn_mlp_common.hpp"
 #include "gn_affinity.hpp"
 
-#ifdef GN_STAMPS
-// Diagnostic build only (never the product): per-wave cycle stamps, read back with gn_debug_read_stamps.
-__device__ unsigned long long gn_stamp_buf[1 << 17];
-#define GN_STAMP(unit, slot)                                                              \
-  do {                                                                                    \
-    if ((threadIdx.x & 63) == 0 && (unit) < (1 << 13))                                    \
-      gn_stamp_buf[(size_t)(unit) * 16 + (slot)] = ((slot) & 8) ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime(); \
-  } while (0)
-extern "C" int gn_debug_read_stamps(void* dst, size_t bytes) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(gn_stamp_buf), bytes);
-}
-#else
-#define GN_STAMP(unit, slot) do { (void)(unit); } while (0)
-#endif
-
-// workgroups per CU the bf16-storage (P = 1) edge / aggregation kernels are compiled for
-#ifndef GN_OCC_P1
-#define GN_OCC_P1 2
-#endif
-
 #include <type_traits>
 
 namespace {
+
+// workgroups per CU the bf16-storage (P = 1) edge / aggregation kernels are compiled for
+constexpr int kOccP1 = 2;
 
 template <int P>
 struct Parts {
@@ -95,13 +78,6 @@ struct ovf_t {
 };
 template <int P>
 __device__ __forceinline__ void make_parts(const f32x16& v, int hf, Parts<P>& x, ovf_t& ovf) {
-#ifdef GN_DIAG_NO_SPLIT      // diagnostic builds only: what the kernels take without the VALU splitting work
-  for (int p = 0; p < P; ++p) {
-    const f32x4 w = {v[8 * hf], v[8 * hf + 1], v[8 * hf + 2], v[8 * hf + 3]};
-    x.p[p] = __builtin_bit_cast(bf16x8, w);
-  }
-  return;
-#endif
   if constexpr (P == 3) {
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) {
@@ -131,9 +107,7 @@ __device__ __forceinline__ void make_parts(const f32x16& v, int hf, Parts<P>& x,
     }
     x.p[0] = __builtin_bit_cast(bf16x8, hi);
     x.p[1] = __builtin_bit_cast(bf16x8, lo);
-#ifndef GN_NO_OVF
     ovf.mask |= __builtin_amdgcn_ballot_w64(__builtin_fmaxf(__builtin_fmaxf(m[0], m[1]), __builtin_fmaxf(m[2], m[3])) > kF16Limit);
-#endif
   }
   if constexpr (P == 1) x.p[0] = cvt_half(v, hf);
 }
@@ -180,10 +154,8 @@ __device__ __forceinline__ void run_with_fallback(F body) {
   if constexpr (P == 2) {
     body(std::integral_constant<int, 2>{}, ovf);
     if (!__syncthreads_or(ovf.mask != 0ull || ovf.wf != 0)) return;
-#ifndef GN_NO_FALLBACK       // (diagnostic builds: the fp16 path alone)
     ovf = {0ull, 0};
     body(std::integral_constant<int, 3>{}, ovf);
-#endif
   } else {
     body(std::integral_constant<int, P>{}, ovf);
   }
@@ -200,10 +172,6 @@ __device__ __forceinline__ const void* pick_image(const void* x, const void* h) 
 // acc += W[sub-step] . x from the sub-step's P 16-byte operand pieces
 template <int P>
 __device__ __forceinline__ void mfma_substep(const f32x4 (&w)[P], const Parts<P>& x, f32x16& acc) {
-#ifdef GN_DIAG_NO_MFMA       // diagnostic builds only: everything but the matrix instructions
-  for (int p = 0; p < P; ++p) acc[p] += w[p][0] * __builtin_bit_cast(f32x4, x.p[p])[0];
-  return;
-#endif
   if constexpr (P == 3) {
     const bf16x8 w1 = __builtin_bit_cast(bf16x8, w[0]);
     const bf16x8 w2 = __builtin_bit_cast(bf16x8, w[1]);
@@ -249,14 +217,8 @@ struct XStream {
     const int u = s % D;
     mfma_substep<P>(q[u], x, acc);
     const f32x4* src = s + D < seg ? cur + (size_t)(s + D) * P * 64 : nxt + (size_t)(s + D - seg) * P * 64;
-#ifdef GN_DIAG_HALF_W        // diagnostic builds only (results are wrong): half of the ring's bytes from L2
-    q[u][0] = src[0];
-#pragma unroll
-    for (int p = 1; p < P; ++p) q[u][p] = q[u][0];
-#else
 #pragma unroll
     for (int p = 0; p < P; ++p) q[u][p] = src[p * 64];
-#endif
     // hipcc otherwise sinks the run-ahead loads down to their use and collapses the ring
     if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
   }
@@ -276,13 +238,7 @@ struct XStream {
 //                 chunk c+2+LOOK : global -> staging registers
 // Requirements: all 4 waves of the workgroup call begin / step / skip with identical arguments (no early exits);
 // segment lengths are multiples of CH * LOOK sub-steps wherever the chunk index is not a compile-time constant.
-#ifndef GN_LOOK2
-#define GN_LOOK2 2
-#endif
-#ifndef GN_QD2
-#define GN_QD2 2
-#endif
-template <int P, int LOOK_ = (P == 1 ? 4 : (P == 2 ? GN_LOOK2 : 2)), int QD_ = (P == 1 ? 4 : (P == 2 ? GN_QD2 : 2))>
+template <int P, int LOOK_ = (P == 1 ? 4 : 2), int QD_ = (P == 1 ? 4 : 2)>
 struct WStream {
   static constexpr int CH = P == 1 ? 8 : 4;      // sub-steps per chunk
   static constexpr int LOOK = LOOK_;             // chunks between a piece's global load and its LDS write (the kernels
@@ -315,13 +271,8 @@ struct WStream {
   // previous boundary are older than operand reads it has since waited for, so they have landed before it signals;
   // (2) the slot overwritten after the barrier held chunk c-1, whose last operand reads every wave consumed (waited
   // for) before its last MFMA of that chunk, i.e. before it arrived here.
-#ifdef GN_DIAG_NO_BARRIER    // diagnostic builds only (results are wrong)
-  __device__ __forceinline__ static void barrier_drain() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-  __device__ __forceinline__ static void barrier() { asm volatile("" ::: "memory"); }
-#else
   __device__ __forceinline__ static void barrier_drain() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
   __device__ __forceinline__ static void barrier() { asm volatile("s_barrier" ::: "memory"); }
-#endif
   __device__ __forceinline__ void load_stage(int j) {
 #pragma unroll
     for (int i = 0; i < PW; ++i) st[j][i] = ld[i * 64];
@@ -420,14 +371,9 @@ __device__ __forceinline__ void layer_pair(Stream& ws, int c0, int s0, const Par
                                            f32x16 (&out)[OT], ovf_t& ovf, PostFn post) {
   constexpr int NA = 2 * IT, NB = 2 * OT;
   constexpr int kMfma = NA * kMfmaPerSub<P>;                   // MFMAs of one A phase
-#ifndef GN_KVALU
-#define GN_KVALU 96
-#endif
-#ifndef GN_KVALU2
-#define GN_KVALU2 84
-#endif
-  // VALU slots per MFMA (V_t: ReLU / scale, the split into parts, the range maximum)
-  constexpr int kValu = ((P == 3 ? GN_KVALU : (P == 2 ? GN_KVALU2 : 40)) + kMfma - 1) / kMfma;
+  // VALU slots per MFMA (V_t: ReLU / scale, the split into parts, the range maximum), spread over one A phase
+  constexpr int kValuPerPhase = P == 3 ? 96 : (P == 2 ? 84 : 40);
+  constexpr int kValu = (kValuPerPhase + kMfma - 1) / kMfma;
   int pos = s0;
   f32x16 hidn = hid0;
   f32x16 bias_n;
@@ -506,10 +452,7 @@ struct NodeTable {
 };
 // output tiles of WA per "A" workgroup (a multiple of 4).  4: 264 workgroups of 16 sub-steps at B = 512 instead of 132 of
 // 32 — the A workgroups were the node stage's last to finish (same-session A/B: launch 22.1 -> 19.9 us).
-#ifndef GN_KATILES
-#define GN_KATILES 4
-#endif
-constexpr int kATiles = GN_KATILES;
+constexpr int kATiles = 4;
 
 template <int P, typename T>
 __device__ __forceinline__ void node_stage_body(const NodeTable& Tb, f32x4* wring, ovf_t& ovf) {
@@ -523,9 +466,6 @@ __device__ __forceinline__ void node_stage_body(const NodeTable& Tb, f32x4* wrin
     const int gi = gn_uniform(wg / Tb.wgs_per_group);
     const gn_node_group_t G = Tb.g[gi];
     const RowBlock rb = row_block(Tb.rows, (wg - gi * Tb.wgs_per_group) * 4 + wave);
-    const int unit = wg * 4 + wave;
-    GN_STAMP(unit, 0);
-    GN_STAMP(unit, 8);
     const float* b0 = G.bias;
     const float* b1 = G.bias + 256;
     const float* bpq = G.bias + 320;
@@ -540,7 +480,6 @@ __device__ __forceinline__ void node_stage_body(const NodeTable& Tb, f32x4* wrin
     xp[1] = load_bias_tile(b1 + 32, h);
     Parts<P> xi[2][2];
     make_parts_tiles<P, 2>(in, xi, ovf);
-    GN_STAMP(unit, 1);
     // image: the 64->256->64 pair in pipeline order (A_t = [W0(t,in0), W0(t,in1)], B_t = [W1(0,t), W1(1,t)]), then
     // [Wpq(0,in0), Wpq(0,in1), Wpq(1,in0), Wpq(1,in1)]
     layer_pair<P, 2, 2, 8, P == 1>(ws, 0, 0, xi, hid0, b0, h, xp, ovf, [&](int t, f32x16& hid) {
@@ -549,7 +488,6 @@ __device__ __forceinline__ void node_stage_body(const NodeTable& Tb, f32x4* wrin
         if (G.hid_out != nullptr && rb.live) store_tile(G.hid_out + (size_t)rb.row * 256 + 32 * t + 4 * h, hid);
       }
     });
-    GN_STAMP(unit, 2);
     pq[0] = load_bias_tile(bpq, h);         // (requested here: held across the layer pair they cost 32 registers)
     pq[1] = load_bias_tile(bpq + 32, h);
     store_rows<2>(reinterpret_cast<T*>(G.xp), GN_FEAT, rb.row, h, rb.live, xp);
@@ -559,10 +497,7 @@ __device__ __forceinline__ void node_stage_body(const NodeTable& Tb, f32x4* wrin
     for (int o = 0; o < 2; ++o)
 #pragma unroll
       for (int i = 0; i < 4; ++i) ws.step(0, 64 + 4 * o + i, xq[i >> 1][i & 1], pq[o]);
-    GN_STAMP(unit, 3);
     store_rows<2>(reinterpret_cast<T*>(G.pq), GN_FEAT, rb.row, h, rb.live, pq);
-    GN_STAMP(unit, 4);
-    GN_STAMP(unit, 9);
     return;
   }
   // ---- A workgroup: (output-tile chunk c, 4 row blocks) ----
@@ -575,9 +510,6 @@ __device__ __forceinline__ void node_stage_body(const NodeTable& Tb, f32x4* wrin
   const int local = v - Tb.a_first[gi];
   const int c = local / Tb.wgs_per_group, quad = local - c * Tb.wgs_per_group;
   const RowBlock rb = row_block(Tb.rows, quad * 4 + wave);
-  const int unit = wg * 4 + wave;
-  GN_STAMP(unit, 0);
-  GN_STAMP(unit, 8);
   const int o0 = c * kATiles;
   const int nt = min(kATiles, OTA - o0);                 // a multiple of 4
   // 4 sub-steps per output tile; the stream of this workgroup starts at tile o0 of the image
@@ -588,7 +520,6 @@ __device__ __forceinline__ void node_stage_body(const NodeTable& Tb, f32x4* wrin
   load_rows<2>(reinterpret_cast<const T*>(G.x), GN_FEAT, rb.row_ld, h, in);
   Parts<P> xi[2][2];
   make_parts_tiles<P, 2>(in, xi, ovf);
-  GN_STAMP(unit, 1);
   const size_t ldA = (size_t)OTA * 32;
   T* arow = reinterpret_cast<T*>(G.A) + (size_t)rb.row * ldA + 4 * h;
   f32x16 bn = load_bias_tile(G.bA + 32 * o0, h);          // bias rides one tile ahead (see layer_pair)
@@ -604,8 +535,6 @@ __device__ __forceinline__ void node_stage_body(const NodeTable& Tb, f32x4* wrin
       if (rb.live) store_tile(arow + 32 * o, acc);
     }
   }
-  GN_STAMP(unit, 4);
-  GN_STAMP(unit, 9);
 }
 // largest weight ring of the precisions a kernel instantiation may run (P = 2 falls back to 3)
 template <int P>
@@ -641,9 +570,6 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
   const int blk = sparse ? (wave_id() == 0 ? lwg - Tb.first_wg[gi] : (rows + 31) / 32) : (lwg - Tb.first_wg[gi]) * 4 + wave_id();
   const RowBlock rb = row_block(rows, blk);      // (a wave past the group's rows works on a clamped row, stores nothing)
   const int lane = rb.lane, h = rb.h;
-  const int unit = lwg * 4 + wave_id();
-  GN_STAMP(unit, 0);
-  GN_STAMP(unit, 8);
   f32x16 in[2], z[2], lg;
   if (G.edges != nullptr) {
     load_rows<2>(reinterpret_cast<const T*>(G.edges), GN_FEAT, rb.row_ld, h, in);
@@ -698,7 +624,6 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
   z[1] = load_bias_tile(bi1 + 32, h);
   Parts<P> xi[2][2];
   make_parts_tiles<P, 2>(in, xi, ovf);
-  GN_STAMP(unit, 1);
   // ---- pair A: 64 -> 128 -> 64, 4 hidden tiles x (4 + 4) sub-steps, pipeline order ----
   layer_pair<P, 2, 2, 4, P == 1>(ws, 0, 0, xi, hidA0, bi0, h, z, ovf, [&](int t, f32x16& hid) {
     if constexpr (P != 1) {
@@ -706,7 +631,6 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
       if (G.keep_z1 != nullptr && rb.live) store_tile(G.keep_z1 + (size_t)rb.row * 128 + 32 * t + 4 * h, hid);
     }
   });
-  GN_STAMP(unit, 2);
   if (G.keep_z != nullptr) store_rows<2>(G.keep_z, GN_FEAT, rb.row, h, rb.live, z);
   // (the bias tiles of pair B are requested here, not at the top: held across pair A they cost 32 registers — and scratch)
   const f32x16 hidB0 = load_bias_tile(bd0, h);
@@ -721,7 +645,6 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
     }
   });
   lg = lgv[0];
-  GN_STAMP(unit, 3);
   // uniforms: read from U or generated from the Philox stream — after the chains (nothing is in flight any more)
   fetch_uniforms(G.U, pbase, seed, o1, K, h, u1);
   if (G.sym_N > 0) fetch_uniforms(G.U, pbase, seed, o2, K, h, u2);
@@ -766,11 +689,9 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
       }
     }
   }
-  GN_STAMP(unit, 4);
-  GN_STAMP(unit, 9);
 }
 template <int P, typename T>
-__global__ __launch_bounds__(256, P == 1 ? GN_OCC_P1 : 2) void edge_x_kernel(GroupTable<gn_edge_group_t> Tb, float tau,
+__global__ __launch_bounds__(256, P == 1 ? kOccP1 : 2) void edge_x_kernel(GroupTable<gn_edge_group_t> Tb, float tau,
                                                         unsigned long long seed,
                                                         const unsigned long long* __restrict__ offset_dev, int pool_bytes) {
   __shared__ f32x4 wring[kRingF4For<P>];
@@ -899,12 +820,12 @@ template <int P>
 struct ClosingStream {
   const f32x4* segA;
   const f32x4* segB;
-#ifndef GN_CLOSING_DEPTH
-#define GN_CLOSING_DEPTH 4      // sub-steps in flight.  Four cover ~400 cycles of MFMA work against an L2 round trip of ~1 k
-#endif                          // beside a second workgroup: a row block's chain runs three round trips long (per-wave stamps:
-                                // ~8 k cycles per row block).  Five or more cost the kernel scratch (20 / 80 / 128 bytes per
-                                // lane at 5 / 6 / 8: measured +2 us) — the depth stays at what 254 registers allow.
-  PStream<P, 12, GN_CLOSING_DEPTH> ps;
+  // sub-steps in flight.  Four cover ~400 cycles of MFMA work against an L2 round trip of ~1 k beside a second
+  // workgroup: a row block's chain runs three round trips long (~8 k cycles per row block, measured in round 3).  Five or
+  // more cost the kernel scratch (20 / 80 / 128 bytes per lane at 5 / 6 / 8: measured +2 us) — the depth stays at what
+  // 254 registers allow.
+  static constexpr int kDepth = 4;
+  PStream<P, 12, kDepth> ps;
   __device__ __forceinline__ void init(const void* image, int wave, int lane, ovf_t& ovf) {
     if constexpr (P == 2) ovf.wf |= image_flag(image, 48);
     const f32x4* img = reinterpret_cast<const f32x4*>(image) + lane;
@@ -1012,12 +933,9 @@ __device__ __forceinline__ void closing_chain(ClosingStream<P>& cs, const float*
 // pair.  With s a power of two such that s * |a + b| < 1 for every staged value of the type, relu(a + b) =
 // clamp01(s b + s a) / s is ONE v_pk_fma_f32 with the clamp modifier, and 1/s goes into the type weight: two packed
 // instructions per value pair.  Scaling by powers of two commutes with rounding, so the result is bit-identical to the
-// max form (GN_NODE_CLAMP = 0 builds that one; a type whose largest pre-activation is beyond 2^72 takes it at run time).
+// max form (a type whose largest pre-activation is beyond 2^72 takes that one at run time).
 // s comes from the maximum |A| of the staged rows, which the waves record while they stage a type (one slot per wave and
 // buffer, read behind the barrier that publishes the buffer).
-#ifndef GN_NODE_CLAMP
-#define GN_NODE_CLAMP 1
-#endif
 constexpr int kNodeLoads = 8;                        // 16-byte pieces per thread and type of the stage (<= 64 nodes)
 __host__ __device__ __forceinline__ int node_stage_nodes(int N) { return (31 / N + 2) * N; }
 // floats of the launch's dynamic LDS the node form needs: stage buffer 1, efs, the waves' maxima
@@ -1031,7 +949,7 @@ __device__ __forceinline__ f32x2 pk_fma_clamp(f32x2 a, f32x2 b, f32x2 c) {      
 }
 template <int P, typename T>
 __device__ __forceinline__ void agg_node_body(const gn_agg_group_t& G, int wg, int wave, int lane, const void* img,
-                                              float* stage0, float* dyn, ovf_t& ovf, int unit) {
+                                              float* stage0, float* dyn, ovf_t& ovf) {
   const int N = G.N, E = G.E, K = G.K;
   const int rowsN = G.rows / E * N;                  // node rows of the group
   const int h = lane >> 5, r = lane & 31;
@@ -1066,27 +984,24 @@ __device__ __forceinline__ void agg_node_body(const gn_agg_group_t& G, int wg, i
       if (it * 256 < total4) {                       // (uniform; clamped loads repeat the last piece: harmless in the max)
         if (idx < total4)
           *reinterpret_cast<f32x4*>((buf ? stage1 : stage0) + (idx >> 5) * kStagePitch + (idx & 31) * 4) = pre[it];
-        if constexpr (GN_NODE_CLAMP != 0)
-          m = fmaxf(fmaxf(m, fmaxf(fabsf(pre[it][0]), fabsf(pre[it][1]))), fmaxf(fabsf(pre[it][2]), fabsf(pre[it][3])));
+        m = fmaxf(fmaxf(m, fmaxf(fabsf(pre[it][0]), fabsf(pre[it][1]))), fmaxf(fabsf(pre[it][2]), fabsf(pre[it][3])));
       }
     }
     // wave maximum on DPP moves (a __shfl butterfly is six dependent LDS round trips; LDS atomics on one word serialise
     // 256 lanes: both measured, thousands of cycles per type), one slot per wave
-    if constexpr (GN_NODE_CLAMP != 0) {
-      auto dpp_max = [&](auto ctrl) {
-        const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), decltype(ctrl)::value, 0xf, 0xf, false);
-        m = fmaxf(m, __builtin_bit_cast(float, o));
-      };
-      dpp_max(std::integral_constant<int, 0xb1>{});    // quad_perm [1,0,3,2]
-      dpp_max(std::integral_constant<int, 0x4e>{});    // quad_perm [2,3,0,1]
-      dpp_max(std::integral_constant<int, 0x141>{});   // row_half_mirror
-      dpp_max(std::integral_constant<int, 0x140>{});   // row_mirror: every lane holds its 16-lane row's maximum
-      const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 0));
-      const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 16));
-      const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 32));
-      const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 48));
-      if (lane == 0) wmax[(kk % 3) * 4 + wave] = __builtin_bit_cast(unsigned, fmaxf(fmaxf(r0, r1), fmaxf(r2, r3)));
-    }
+    auto dpp_max = [&](auto ctrl) {
+      const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), decltype(ctrl)::value, 0xf, 0xf, false);
+      m = fmaxf(m, __builtin_bit_cast(float, o));
+    };
+    dpp_max(std::integral_constant<int, 0xb1>{});    // quad_perm [1,0,3,2]
+    dpp_max(std::integral_constant<int, 0x4e>{});    // quad_perm [2,3,0,1]
+    dpp_max(std::integral_constant<int, 0x141>{});   // row_half_mirror
+    dpp_max(std::integral_constant<int, 0x140>{});   // row_mirror: every lane holds its 16-lane row's maximum
+    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 0));
+    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 16));
+    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 32));
+    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 48));
+    if (lane == 0) wmax[(kk % 3) * 4 + wave] = __builtin_bit_cast(unsigned, fmaxf(fmaxf(r0, r1), fmaxf(r2, r3)));
   };
   fetch(0);
   // type weights of the block's rows: efs[row * efp + k * 16 + j] = ef[pair(i_row, j), k], 0 for j >= N.  Eight threads
@@ -1114,7 +1029,6 @@ __device__ __forceinline__ void agg_node_body(const gn_agg_group_t& G, int wg, i
   commit(0, 0);
   if (K > 1) fetch(1);
   __syncthreads();
-  GN_STAMP(unit, 1);
   // (these waves end the launch — their instructions go first where a SIMD is shared — unless the closing stage is
   // fused: then the hyper groups' waves, with two row blocks to close, do)
   if (G.y == nullptr) __builtin_amdgcn_s_setprio(2);
@@ -1129,20 +1043,15 @@ __device__ __forceinline__ void agg_node_body(const gn_agg_group_t& G, int wg, i
 #pragma unroll 1
   for (int k = 0; k < K; ++k) {
     const float* cb = ((k & 1) ? stage1 : stage0) + 32 * wave;
-    if (k == 1) GN_STAMP(unit, 5);
     // scale of the clamp form for this type (uniform): s = 2^-(floor(log2 M) + 2) for M = max |A| staged, so that
-    // s |a + b| < 1; M below 2^-27 is treated as 2^-27, M beyond 2^72 (or not finite) takes the max form
-    float sc = 1.f, isc = 1.f;
-    bool clamp_form = false;
-    if constexpr (GN_NODE_CLAMP != 0) {
-      // slots k % 3 were filled while type k was staged (before the barrier that published it); they are next written
-      // while type k + 3 is staged, two barriers from here
-      const u32x4 wm = *reinterpret_cast<const u32x4*>(wmax + (k % 3) * 4);      // (non-negative floats order like their bits)
-      const int eb = max(gn_uniform((int)(max(max(wm[0], wm[1]), max(wm[2], wm[3])) >> 23)), 100);
-      clamp_form = eb <= 199;
-      sc = __builtin_bit_cast(float, (unsigned)(252 - min(eb, 199)) << 23);
-      isc = __builtin_bit_cast(float, (unsigned)(min(eb, 199) + 2) << 23);
-    }
+    // s |a + b| < 1; M below 2^-27 is treated as 2^-27, M beyond 2^72 (or not finite) takes the max form.
+    // The slots k % 3 were filled while type k was staged (before the barrier that published it); they are next written
+    // while type k + 3 is staged, two barriers from here
+    const u32x4 wm = *reinterpret_cast<const u32x4*>(wmax + (k % 3) * 4);      // (non-negative floats order like their bits)
+    const int eb = max(gn_uniform((int)(max(max(wm[0], wm[1]), max(wm[2], wm[3])) >> 23)), 100);
+    const bool clamp_form = eb <= 199;
+    const float sc = __builtin_bit_cast(float, (unsigned)(252 - min(eb, 199)) << 23);
+    const float isc = __builtin_bit_cast(float, (unsigned)(min(eb, 199) + 2) << 23);
     if (k + 1 < K) commit((k + 1) & 1, k + 1);       // (that buffer was last read before the barrier that closed type k - 1)
     if (k + 2 < K) fetch(k + 2);
     f32x4 w[4][P];                                   // [W2k(0,t) hf0, hf1, W2k(1,t) hf0, hf1] of hidden tile t = wave
@@ -1160,7 +1069,6 @@ __device__ __forceinline__ void agg_node_body(const gn_agg_group_t& G, int wg, i
     const float* b2k = G.b2 + k * 64 + r;
     const float bf0 = b2k[0], bf1 = b2k[32];
     const PreTile a = load_pre(cb + my * kStagePitch, h);
-    if (k == 1) GN_STAMP(unit, 6);
     f32x2 acc2[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) acc2[q] = f32x2{0.f, 0.f};
@@ -1229,7 +1137,6 @@ __device__ __forceinline__ void agg_node_body(const gn_agg_group_t& G, int wg, i
       acc[2 * q] = acc2[q][0];
       acc[2 * q + 1] = acc2[q][1];
     }
-    if (k == 1) GN_STAMP(unit, 7);
     Parts<P> xh[2];
     make_parts<P>(acc, 0, xh[0], ovf);
     make_parts<P>(acc, 1, xh[1], ovf);
@@ -1243,7 +1150,6 @@ __device__ __forceinline__ void agg_node_body(const gn_agg_group_t& G, int wg, i
     __syncthreads();                                 // type k + 1 is visible; every wave is past its reads of type k
   }
   // partial outputs of the four waves (one hidden tile each) meet in LDS; wave w finishes quads 2w, 2w + 1
-  GN_STAMP(unit, 2);
   f32x4* lds = reinterpret_cast<f32x4*>(dyn);          // (32 KiB; the launch's dynamic part is at least kAggPartBytes)
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
@@ -1296,9 +1202,6 @@ __device__ __forceinline__ void agg_node_body(const gn_agg_group_t& G, int wg, i
     __syncthreads();
     closing_chain<P, T>(cs, G.m2bias, reinterpret_cast<T*>(G.y), G.ldy, G.dout, g0, rowsN - g0, X,
                         reinterpret_cast<f32x4*>(dyn), wave, lane, ovf);
-    GN_STAMP(unit, 3);
-    GN_STAMP(unit, 4);
-    GN_STAMP(unit, 9);
     return;
   }
   if (g0 + r < rowsN) {
@@ -1318,9 +1221,6 @@ __device__ __forceinline__ void agg_node_body(const gn_agg_group_t& G, int wg, i
       st4(yrow + 32 * (q >> 2) + 8 * (q & 3) + 4 * h, v);
     }
   }
-  GN_STAMP(unit, 3);
-  GN_STAMP(unit, 4);
-  GN_STAMP(unit, 9);
 }
 
 // ---- node form, ONE SCENE per workgroup (bf16 twins, N <= 64): both layers of the pairwise typed MLP per NODE -------------
@@ -1333,9 +1233,7 @@ __device__ __forceinline__ void agg_node_body(const gn_agg_group_t& G, int wg, i
 //      min(f(j) + n, f(n) + j), f(m) = m (N - 1) - m (m - 1) / 2: no branch), clamp form as in agg_node_body,
 //   3. applies W2k to S (bf16 operand, as the twins do) — B*N rows of matrix work per layer instead of B*N(N+1)/2.
 // The weights are the two-layer image of the twins (pipeline order: A_w and B_w of each type), straight from L2.
-#ifndef GN_SCENE_OCC
-#define GN_SCENE_OCC 3          // workgroups per CU the scene-form kernel is compiled for (register budget 512 / occupancy)
-#endif
+constexpr int kSceneOcc = 3;           // workgroups per CU the scene-form kernel is compiled for (register budget 512 / occupancy)
 // floats of dynamic LDS: the stage (N rows), two columns of pair weights, the waves' maxima — and at least the 32 KiB the
 // partial outputs need at the end
 __host__ __device__ __forceinline__ int node_scene_lds_floats(int N) {
@@ -1345,11 +1243,11 @@ __host__ __device__ __forceinline__ int node_scene_lds_floats(int N) {
 }
 // One workgroup per (scene, 32-node row block): the VALU work of step 2 is what bounds this form, a wave issues an
 // instruction every ~5-10 cycles whatever its neighbours do, and the matrix-core kernels' 256 registers allow two waves
-// per SIMD — so the form has its own kernel, compiled for GN_SCENE_OCC workgroups per CU (measured inside
+// per SIMD — so the form has its own kernel, compiled for kSceneOcc workgroups per CU (measured inside
 // agg_rb2_kernel, two per CU: 250 us for the pairwise module of config 4).  Every workgroup of a scene forms A' for all
 // of the scene's nodes (matrix work, cheap) and S / layer 2 for its own row block.
 template <typename T>
-__global__ __launch_bounds__(256, GN_SCENE_OCC) void agg_scene_kernel(gn_agg_group_t G) {
+__global__ __launch_bounds__(256, kSceneOcc) void agg_scene_kernel(gn_agg_group_t G) {
   constexpr int P = 1;
   extern __shared__ __align__(16) float dyn[];
   ovf_t ovf_unused = {0ull, 0};
@@ -1495,7 +1393,7 @@ __global__ __launch_bounds__(256, GN_SCENE_OCC) void agg_scene_kernel(gn_agg_gro
             }
         }
       };
-      // (no explicit software pipeline: with GN_SCENE_OCC waves per SIMD the other waves cover a partner's LDS round trip)
+      // (no explicit software pipeline: with kSceneOcc waves per SIMD the other waves cover a partner's LDS round trip)
       if (clamp_form) {
 #pragma unroll 2
         for (int j = 0; j < N; ++j) partner(j, std::integral_constant<bool, true>{});
@@ -1608,9 +1506,6 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
   const float* b1 = G.b1;
   const float* b2 = G.b2;
   WS ws;
-  const int unit = lwg * 4 + wave;
-  GN_STAMP(unit, 0);
-  GN_STAMP(unit, 8);
 
   // hyper gather from the workgroup's scenes staged in LDS (block-uniform; the stage shares `part` with the partial
   // sums, which are exchanged behind a barrier at the end)
@@ -1631,7 +1526,7 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
   if constexpr (P == 2) ovf.wf |= image_flag(img, pair_form ? K * 16 : K * 32);
   if constexpr (P != 1) {
     if (pair_form && G.node_form) {      // (block-uniform; the workgroup's four waves share one 32-node row block)
-      agg_node_body<P, T>(G, wg, wave, threadIdx.x & 63, img, reinterpret_cast<float*>(wring), part_dyn, ovf, lwg * 4 + wave);
+      agg_node_body<P, T>(G, wg, wave, threadIdx.x & 63, img, reinterpret_cast<float*>(wring), part_dyn, ovf);
       return;
     }
   }
@@ -1826,7 +1721,6 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
     }
     Parts<P> xi[2][2];
     make_parts_tiles<P, 2>(in, xi, ovf);
-    GN_STAMP(unit, 1);
     ws.begin(img, wring, lane, wave, K * 32 / CH);
     f32x16 hid0 = load_bias_tile(b1, h);
     float efk = efrow[0];
@@ -1877,7 +1771,6 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
     }
     Parts<P> xi[2][2];
     make_parts_tiles<P, 2>(in, xi, ovf);
-    GN_STAMP(unit, 1);
     const f32x4* Wx = reinterpret_cast<const f32x4*>(img) + lane;      // sub-step s of type k: (k*32 + s)
     XStream<P> xs;
     xs.begin(Wx + (size_t)sub * 32 * P * 64);
@@ -1899,22 +1792,16 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
 #pragma unroll
           for (int r = 0; r < 16; ++r) out[o][r] = fmaf(efk, tmp[o][r], out[o][r]);
       } else {
-        if (k == sub + wpr) GN_STAMP(unit, 5);
         add_b2_regs(bf0, bf1, efk, h, out);
-        if (k == sub + wpr) GN_STAMP(unit, 6);
         layer_pair<P, 2, 2, 4>(xs, 0, 0, xi, hid0, b1 + k * 128, h, out, ovf, [&](int, f32x16& hid) { relu_scale16(hid, efk); });
-        if (k == sub + wpr) GN_STAMP(unit, 7);
       }
       hid0 = hid0_next;
       efk = efk_next, bf0 = bn0, bf1 = bn1;
     }
   }
   T* feat = reinterpret_cast<T*>(G.feat);
-  GN_STAMP(unit, 2);
   if (wpr == 1) {
     store_rows<2>(feat, GN_FEAT, rb.row, h, rb.live && any_rows, out);
-    GN_STAMP(unit, 4);
-    GN_STAMP(unit, 9);
     return;
   }
   __syncthreads();      // (the staged node rows share `part`; not used together with wpr > 1, but keep the order explicit)
@@ -1978,7 +1865,7 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
         const float* hcol = G.H + ((size_t)(scene0 + sl) * E) * N + n;
         f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
         // (the node's incidence column first, all of it in flight at once — E <= 16 here: a load per loop iteration cost
-        // one L2 round trip per hyperedge, 8 k cycles per row block in the per-wave stamps)
+        // one L2 round trip per hyperedge, 8 k cycles per row block, measured in round 3)
         float hw[16];
 #pragma unroll
         for (int e = 0; e < 16; ++e) hw[e] = e < E ? hcol[(size_t)e * N] : 0.f;
@@ -2011,8 +1898,6 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
         closing_chain<P, T>(cs, G.m2bias, reinterpret_cast<T*>(G.y), G.ldy, G.dout, scene0 * N + nb * 32, nodes - nb * 32, X,
                             wring, wave, lane, ovf);
       }
-      GN_STAMP(unit, 4);
-      GN_STAMP(unit, 9);
       return;
     }
   }
@@ -2033,11 +1918,9 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
       st4(p + 32 * o + 8 * q, v);
     }
   }
-  GN_STAMP(unit, 4);
-  GN_STAMP(unit, 9);
 }
 template <int P, typename T, bool PAIRF>
-__global__ __launch_bounds__(256, P == 1 ? GN_OCC_P1 : 2) void agg_x_kernel(GroupTable<AggGroup> Tb) {
+__global__ __launch_bounds__(256, P == 1 ? kOccP1 : 2) void agg_x_kernel(GroupTable<AggGroup> Tb) {
   __shared__ f32x4 wring[kRingF4For<P>];
   run_with_fallback<P>([&](auto pc, ovf_t& ovf) { agg_x_body<decltype(pc)::value, T, PAIRF>(Tb, wring, ovf); });
 }
@@ -2463,9 +2346,6 @@ __device__ __forceinline__ void mlp2_x_body(const GroupTable<gn_mlp2_group_t>& T
   const gn_mlp2_group_t G = Tb.g[gi];
   const RowBlock rb = row_block(rows, blk);      // (a wave past the rows works on a clamped row, stores nothing)
   const int lane = rb.lane, h = rb.h;
-  const int unit = lwg * 4 + wave_id();
-  GN_STAMP(unit, 0);
-  GN_STAMP(unit, 8);
   constexpr int kSub = HT * (2 * IT + 2 * OT);
   static_assert(kSub % WS::CH == 0, "the image must be a whole number of chunks");
   const float* b0 = G.bias;
@@ -2487,20 +2367,16 @@ __device__ __forceinline__ void mlp2_x_body(const GroupTable<gn_mlp2_group_t>& T
     if (G.in_out != nullptr) store_rows<IT>(G.in_out, 32 * IT, rb.row, h, rb.live, in);   // kept for the backward
     make_parts_tiles<P, IT>(in, xi, ovf);
   }
-  GN_STAMP(unit, 1);
   layer_pair<P, IT, OT, HT, P == 1>(ws, 0, 0, xi, hid0, b0, h, out, ovf, [&](int t, f32x16& hid) {
     if constexpr (P != 1) {
       relu16(hid);
       if (G.hid_out != nullptr && rb.live) store_tile(G.hid_out + (size_t)rb.row * (32 * HT) + 32 * t + 4 * h, hid);
     }
   });
-  GN_STAMP(unit, 2);
   if (rb.live) {
 #pragma unroll
     for (int o = 0; o < OT; ++o) store_out_tile(reinterpret_cast<T*>(G.y), rb.row, ldy, dout, o, h, out[o]);
   }
-  GN_STAMP(unit, 4);
-  GN_STAMP(unit, 9);
 }
 template <int P, typename T, int IT, int HT, int OT>
 __global__ __launch_bounds__(256, P == 1 ? (IT == 4 ? 2 : 3) : (IT == 4 ? 1 : 2)) void mlp2_x_kernel(GroupTable<gn_mlp2_group_t> Tb, int rows, int dout, int ldy,
@@ -2691,9 +2567,6 @@ __device__ __forceinline__ void mlp2_xs_body(const GroupTable<gn_mlp2_group_t>& 
   const int wave = wave_id();
   const RowBlock rb = row_block(rows, lwg - Tb.first_wg[gi]);
   const int lane = rb.lane, h = rb.h;
-  const int unit = lwg * 4 + wave;
-  GN_STAMP(unit, 0);
-  GN_STAMP(unit, 8);
   const float* b0 = G.bias;
   const float* b1 = G.bias + 32 * HT;
   const void* image = pick_image<P>(G.Wx, G.Wh);
@@ -2745,7 +2618,6 @@ __device__ __forceinline__ void mlp2_xs_body(const GroupTable<gn_mlp2_group_t>& 
   };
   Parts<P> xa[2];
   xop(0, xa[0]);
-  GN_STAMP(unit, 1);
   // accumulators start at zero and the bias tiles — requested before a phase, added behind it — arrive in its shadow
   // (held from the start they would be live across the gather and cost the third workgroup per CU)
   f32x16 hid[TPW], bt[TPW];
@@ -2798,13 +2670,9 @@ __device__ __forceinline__ void mlp2_xs_body(const GroupTable<gn_mlp2_group_t>& 
 #pragma unroll
       for (int r = 0; r < 16; ++r) out[o][r] += bo[o][r];
   }
-  GN_STAMP(unit, 2);
   __syncthreads();                                // every wave is past its reads of the exchanged operands
   put_partial<OT>(lds, wave, lane, out);
   __syncthreads();
-  GN_STAMP(unit, 3);
-  GN_STAMP(unit, 4);
-  GN_STAMP(unit, 9);
   if (!rb.live) return;
   T* yrow = reinterpret_cast<T*>(G.y) + (size_t)rb.row * ldy;
   const bool vec = ((dout | ldy) & 3) == 0;

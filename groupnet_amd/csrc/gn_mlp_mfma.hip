@@ -1197,15 +1197,11 @@ static int agg_launch(const gn_agg_group_t* groups_in, int n_groups_in, hipStrea
     GN_CHECK(need(G.b2, false));
     if (G.rows <= 0 || G.K < 1 || G.K > GN_MAX_TYPES) return GN_ERR_SHAPE;
     const int blocks32 = (G.rows + 31) / 32;
-    // waves per row block (measured on MI355X at B = 512, N = 11, scripts in DESIGN.md): a group that
+    // waves per row block (measured on MI355X at B = 512, N = 11): a group that
     // alone covers most of the 1024 SIMDs runs one wave per block; a mid-sized group halves its units
     // (4 waves of a workgroup sit on ONE CU, so 4-way splitting 176..700 blocks stacks two workgroups on
     // some CUs and idles others); only small groups split 4 ways
     int wpr = blocks32 >= 768 ? 1 : (blocks32 >= 128 && G.K >= 2 ? 2 : (G.K >= 4 ? 4 : 1));
-    if (const char* e = getenv(G.A != nullptr ? "GN_AGG_WPR_PAIR" : "GN_AGG_WPR")) {  // tuning knobs: force 1, 2 or 4
-      const int v = atoi(e);
-      if (v == 1 || v == 2 || v == 4) wpr = v;
-    }
     if (G.node_form) wpr = 1;
     T.g[g].a = G;
     T.g[g].wpr = wpr;
@@ -1235,24 +1231,20 @@ static int agg_launch(const gn_agg_group_t* groups_in, int n_groups_in, hipStrea
       }
     }
     // pair form with one wave per row block: stage the scenes' node rows in LDS when they fit
-    const bool no_stage = getenv("GN_AGG_NO_STAGE") != nullptr;
-    T.g[g].stage = (!no_stage && G.A != nullptr && wpr == 1 && !G.node_form &&
+    T.g[g].stage = (G.A != nullptr && wpr == 1 && !G.node_form &&
                     (127 / G.E + 2) * G.N <= (xm ? kStageMaxNodesX : kStageMaxNodes)) ? 1 : 0;
   }
   // Workgroups are dispatched in index order: give the low indices to the group whose waves run longest
   // (types x layers per wave), so the long waves start first and the short ones fill the tail.
-  const bool as_given = getenv("GN_AGG_ORDER_AS_GIVEN") != nullptr;
-  if (!as_given) {
-    auto cost = [](const AggGroup& a) {
-      return a.a.node_form ? 1ll : (long long)a.a.K * (a.a.A != nullptr ? 1 : 2) * 4 / a.wpr;
-    };
-    for (int i = 1; i < n_groups; ++i)        // insertion sort, stable, n <= GN_MAX_GROUPS
-      for (int j = i; j > 0 && cost(T.g[j]) > cost(T.g[j - 1]); --j) {
-        const AggGroup tmp = T.g[j];
-        T.g[j] = T.g[j - 1];
-        T.g[j - 1] = tmp;
-      }
-  }
+  auto cost = [](const AggGroup& a) {
+    return a.a.node_form ? 1ll : (long long)a.a.K * (a.a.A != nullptr ? 1 : 2) * 4 / a.wpr;
+  };
+  for (int i = 1; i < n_groups; ++i)        // insertion sort, stable, n <= GN_MAX_GROUPS
+    for (int j = i; j > 0 && cost(T.g[j]) > cost(T.g[j - 1]); --j) {
+      const AggGroup tmp = T.g[j];
+      T.g[j] = T.g[j - 1];
+      T.g[j - 1] = tmp;
+    }
   for (int g = 0; g < n_groups; ++g) {
     T.first_wg[g] = wg;
     const gn_agg_group_t& a = T.g[g].a;
@@ -1449,11 +1441,8 @@ static int mlp2_launch(const gn_mlp2_group_t* groups, int n_groups, int rows, in
   bool fused = false;   // (also set when activations are to be kept: only the whole-chain kernel writes them)
   for (int g = 0; g < n_groups; ++g)
     fused = fused || groups[g].x == nullptr || groups[g].in_out != nullptr || groups[g].hid_out != nullptr;
-  int use_split = (dh == 128 && dout <= 64 && (long long)blocks32 * n_groups <= 1024 && (din == 64 || din == 128) &&
-                   !fused)   // the fused-scatter prologue would be repeated by all 4 waves of a row block
-                      ? 1
-                      : 0;
-  if (const char* e = getenv("GN_MLP2_SPLIT")) use_split = atoi(e) != 0 && dh == 128 && dout <= 64 && !fused;
+  const bool use_split = dh == 128 && dout <= 64 && (long long)blocks32 * n_groups <= 1024 && (din == 64 || din == 128) &&
+                         !fused;   // the fused-scatter prologue would be repeated by all 4 waves of a row block
   if (use_split) {
     const dim3 grid(blocks32, n_groups);
     if (din == 64)

@@ -17,7 +17,6 @@ from __future__ import annotations
 from typing import List, Optional, Sequence, Tuple
 
 import contextlib
-import os
 import torch
 import torch.nn as nn
 
@@ -188,7 +187,7 @@ class MultiScaleHGNN(nn.Module):
             # (latency form — `affinity_tail` — also folds the closing MLPs into the aggregation launch: 4 launches)
             run_message_passing(mods, [f] * (1 + S), [None, *Hs], list(noise_u), cols, join=join,
                                 affinity=tail if (S and ops.fused_affinity_fits(N, D)) else None,
-                                fuse_closing=self.affinity_tail or os.environ.get("GN_FUSE_CLOSING") == "2")
+                                fuse_closing=self.affinity_tail)
         else:
             for m, H, u, c in zip(mods, [None, *Hs], noise_u, cols):
                 run_message_passing([m], [f], [H], [u], [c])

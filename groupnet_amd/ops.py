@@ -58,10 +58,14 @@ def _ptr(t: Optional[Tensor]) -> ctypes.c_void_p:
 launch_probe = None
 
 
-BF16X6 = os.environ.get("GN_BF16X6", "1") != "0"   # fp32 entry points: fp32-accurate products on the bf16 cores
-# ... and, on top of it, the two-part fp16 path ("f16x3": three part-products per product instead of six, bf16x6 as the
-# in-kernel fallback for operands beyond the fp16 range).  GN_PRECISION = bf16x6 keeps the six-product path.
-F16X3 = BF16X6 and os.environ.get("GN_PRECISION", "f16x3").lower() != "bf16x6"
+# Matrix path of the fp32 entry points, chosen at import by GN_PRECISION (set_precision changes it later):
+#   f16x3 (default): two fp16 parts per operand, three part-products per product, bf16x6 as the in-kernel fallback for
+#                    operands beyond the fp16 range;
+#   bf16x6: fp32-accurate products on the bf16 cores (three parts, six products);
+#   fp32: the fp32 matrix cores.
+_PRECISION = os.environ.get("GN_PRECISION", "f16x3").lower()
+BF16X6 = _PRECISION != "fp32"      # fp32-accurate products on the 16-bit cores ...
+F16X3 = _PRECISION not in ("bf16x6", "fp32")      # ... from fp16 parts
 
 
 # the fused affinity + top-k launch as the tail workgroups of the first node stage (GN_AFFINITY_TAIL = 0: its own launch)
@@ -712,12 +716,13 @@ class PoolSpec:
 
 
 # Hyper modules: largest N whose pooling the edge kernel may form itself (the kernel's bound is 16: a row's incidence
-# stays in registers).  Default: all of them, so that an inference forward at N <= 16 has no node2edge launch.  The edge
-# kernel stages a workgroup's scenes in LDS (pq, then x', through one buffer); groups that fit no stage (scale = N: one
-# hyperedge per scene) pool from global memory with one live row block per workgroup ("Edge-kernel
-# prologue").  GN_POOL_MAX_N=0: pairwise graph only, hyper modules through the node2edge launch.
+# stays in registers), so that an inference forward at N <= 16 has no node2edge launch.  The edge kernel stages a
+# workgroup's scenes in LDS (pq, then x', through one buffer); groups that fit no stage (scale = N: one hyperedge per
+# scene) pool from global memory with one live row block per workgroup ("Edge-kernel prologue").
 POOL_KERNEL_MAX_N = 16
-POOL_MAX_N = int(os.environ.get("GN_POOL_MAX_N", str(POOL_KERNEL_MAX_N)))
+# the hyper modules' limit run_message_passing applies: all the kernel covers (the parity tests lower it to 0 to compare
+# against the node2edge launch)
+POOL_MAX_N = POOL_KERNEL_MAX_N
 
 
 def edge_mlp_gumbel_grouped(items: Sequence[tuple], tau: float = 0.5, keep: Optional[List[dict]] = None
@@ -906,7 +911,7 @@ def closing_fusable(items: Sequence[Tuple[object, Tensor, dict, int]], pks2: Seq
     if not (BF16X6 and closing_fusion_enabled()):
         return False
     if os.environ.get("GN_AGG_HSTAGE", "1") == "0" or os.environ.get("GN_AGG_LINES", "1") == "0":
-        return False      # (diagnostic gathers: the fused stage reads its scenes' rows from the LDS stage)
+        return False      # (the fused stage reads its scenes' rows from the LDS stage)
     for (src, ef, pk, K), pk2 in zip(items, pks2):
         if (pk2["din"], pk2["dh"]) != (2 * FEAT, 128) or not (32 < pk2["dout"] <= 64) or _ximg(pk2, "mlp2", torch.float32) == 0:
             return False
