@@ -24,12 +24,13 @@ Differences from the reference that a caller can observe
 from __future__ import annotations
 
 import warnings
-from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple, Union
+from typing import Iterator, List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, weights
+from .weights import _param_key, _volatile, training_call  # noqa: F401  (cache policy, re-exported)
 
 Tensor = torch.Tensor
 _HDIM_EXTEND = 64      # model/MS_HGNN_batch.py:72,292
@@ -178,83 +179,11 @@ class MLP_dict_softmax(nn.Module):
         self.MLP_distribution = MLP(input_dim=input_dim, output_dim=edge_types, hidden_size=hidden_size)
         self.MLP_factor = MLP(input_dim=input_dim, output_dim=1, hidden_size=hidden_size)
         self.init_MLP = MLP(input_dim=input_dim, output_dim=input_dim, hidden_size=hidden_size)
-        self._pk: Optional[dict] = None
-        self._pk_key = None
-        self._plan = None
 
     def _packed(self) -> dict:
-        """Weight stream of the edge-MLP kernel (layout: `ops.edge_stream`) and its biases, refreshed from the
-        parameters by one `PackPlan` launch whenever they changed."""
-        params = _plist(self)
-        if self._plan is None or self._plan[0] != tuple(p.data_ptr() for p in params):
-            K = self.bottleneck_dim
-            i0, i1 = _two_layer(self.init_MLP)
-            d0, d1 = _two_layer(self.MLP_distribution)
-            f0, f1 = _two_layer(self.MLP_factor)
-            plan, T = ops.PackPlan(params[0].device), ops.PackPlan.TILE
-            w0 = plan.alloc(0)
-            a0 = lambda o: plan.block(plan.alloc(2 * T), i0.weight, 2, r0=32 * o, rows=32)         # hidden tile o of layer 0
-            b0 = lambda o: plan.block(plan.alloc(2 * T), (d0 if o < 4 else f0).weight, 2, r0=32 * (o % 4), rows=32)
-
-            def sa(t):      # both output tiles of init_MLP layer 1 over hidden tile t
-                off = plan.alloc(2 * T)
-                for o in range(2):
-                    plan.block(off + o * T, i1.weight, 1, r0=32 * o, c0=32 * t, rows=32, cols=32)
-
-            def sb(t):      # (logits | factor) head over hidden tile t: d1 rows 0..K-1, f1 row K
-                off = plan.alloc(T)
-                if t < 4:
-                    plan.block(off, d1.weight, 1, c0=32 * t, cols=32)
-                else:
-                    plan.block(off, f1.weight, 1, c0=32 * (t - 4), cols=32, place_r=K)
-            # pair A: T0 T1 S0 T2 S1 T3 S2 S3; pair B: T0 T1 S0 T2 S1 ... T7 S6 S7; then the ring's 8-step run-out
-            a0(0), a0(1), sa(0), a0(2), sa(1), a0(3), sa(2), sa(3)
-            b0(0), b0(1)
-            for t in range(8):
-                sb(t)
-                if t < 6:
-                    b0(t + 2)
-            plan.alloc(2 * T)
-            w_len = plan.size - w0
-            # the same four layers in the pipeline order of the bf16-core kernel (source of its image): 40 tiles
-            wh = plan.alloc(40 * T)
-            off = wh
-            for kind, t in ops.pipeline_order(4):
-                if kind == "A":
-                    plan.block(off, i0.weight, 2, r0=32 * t, rows=32)
-                else:
-                    plan.block(off, i1.weight, 1, r0=0, c0=32 * t, rows=32, cols=32)
-                    plan.block(off + T, i1.weight, 1, r0=32, c0=32 * t, rows=32, cols=32)
-                off += 2 * T
-            for kind, t in ops.pipeline_order(8):
-                if kind == "A":
-                    plan.block(off, (d0 if t < 4 else f0).weight, 2, r0=32 * (t % 4), rows=32)
-                    off += 2 * T
-                else:
-                    if t < 4:
-                        plan.block(off, d1.weight, 1, c0=32 * t, cols=32)
-                    else:
-                        plan.block(off, f1.weight, 1, c0=32 * (t - 4), cols=32, place_r=K)
-                    off += T
-            bo = plan.alloc(128 + 64 + 256 + 32)
-            plan.vector(bo, i0.bias)
-            plan.vector(bo + 128, i1.bias)
-            plan.vector(bo + 192, d0.bias)
-            plan.vector(bo + 320, f0.bias)
-            plan.vector(bo + 448, d1.bias)
-            plan.vector(bo + 448, f1.bias, place=K)
-            plan.finish()
-            self._plan = (plan.sources[:0] + tuple(p.data_ptr() for p in params), plan)
-            xi = ops.XImages()
-            xi.add("edge", plan.view(wh, 40 * T))
-            self._pk = dict(W=plan.view(w0, w_len), bias=plan.view(bo, 480), xi=xi)
-            self._pk_key = None
-        key = _param_key(params)
-        if key != self._pk_key or _volatile(params):
-            self._plan[1].refresh()
-            self._pk["xi"].bump()
-            self._pk_key = key
-        return self._pk
+        """Weight stream of the edge-MLP kernel (layout: `weights.edge_mlp`) and its biases."""
+        return weights.cache(self, "edge").get(_plist(self), lambda plan: weights.edge_mlp(
+            plan, _two_layer(self.init_MLP), _two_layer(self.MLP_distribution), _two_layer(self.MLP_factor)))
 
     def forward(self, x, noise_u: Optional[Tensor] = None):
         _check_forward_only(x)
@@ -279,61 +208,11 @@ class edge_aggregation(nn.Module):
         self.agg_mlp = nn.ModuleList(MLP(input_dim=input_dim, output_dim=input_dim, hidden_size=(128,))
                                      for _ in range(edge_types))
         self.mlp = MLP(input_dim=input_dim, output_dim=input_dim, hidden_size=(128,))  # unused, kept for state_dict
-        self._pk: Optional[dict] = None
-        self._pk_key = None
-        self._plan = None
 
     def _packed(self) -> dict:
-        """Packed images of the K typed MLPs, refreshed by one `PackPlan` launch whenever they changed:
-        W (both layers, type by type), b1 / b2, and for the pairwise form layer 1 of all types as one
-        (K*128 x 64) matrix applied per node (half the bias rides with each of the two nodes of a pair) and
-        layer 2 re-ordered hidden-tile-major."""
-        params = _plist(self.agg_mlp)
-        if self._plan is None or self._plan[0] != tuple(p.data_ptr() for p in params):
-            K = self.edge_types
-            l0 = [m.layers[0] for m in self.agg_mlp]
-            l1 = [m.layers[1] for m in self.agg_mlp]
-            plan, T = ops.PackPlan(params[0].device), ops.PackPlan.TILE
-            w0 = plan.alloc(0)
-            for a, b in zip(l0, l1):
-                plan.matrix(a.weight)
-                plan.matrix(b.weight)
-            w_len = plan.size - w0
-            b1o, b2o, bho = plan.alloc(K * 128), plan.alloc(K * 64), plan.alloc(K * 128)
-            w1c, w2t, w12 = plan.alloc(K * 8 * T), plan.alloc(K * 8 * T), plan.alloc(K * 16 * T)
-            for k in range(K):
-                off = w12 + k * 16 * T  # both layers in the pipeline order of the bf16-core kernel (its image's source)
-                for kind, o in ops.pipeline_order(4):
-                    if kind == "A":
-                        plan.block(off, l0[k].weight, 2, r0=32 * o, rows=32)
-                    else:
-                        plan.block(off, l1[k].weight, 1, r0=0, c0=32 * o, rows=32, cols=32)
-                        plan.block(off + T, l1[k].weight, 1, r0=32, c0=32 * o, rows=32, cols=32)
-                    off += 2 * T
-                plan.vector(b1o + 128 * k, l0[k].bias)
-                plan.vector(b2o + 64 * k, l1[k].bias)
-                plan.vector(bho + 128 * k, l0[k].bias, scale=0.5)
-                plan.block(w1c + k * 8 * T, l0[k].weight, 2)
-                for t in range(4):
-                    for o in range(2):
-                        plan.block(w2t + (k * 8 + t * 2 + o) * T, l1[k].weight, 1, r0=32 * o, c0=32 * t, rows=32, cols=32)
-            plan.finish()
-            self._plan = (tuple(p.data_ptr() for p in params), plan)
-            self._pk = dict(W=plan.view(w0, w_len), b1=plan.view(b1o, K * 128).view(K, 128),
-                            b2=plan.view(b2o, K * 64).view(K, 64), W1cat=plan.view(w1c, K * 8 * T),
-                            b1half=plan.view(bho, K * 128), W2t=plan.view(w2t, K * 8 * T))
-            xi = ops.XImages()
-            xi.add("W2t", self._pk["W2t"])                   # layer 2 per hidden tile (pair form)
-            xi.add("W12", plan.view(w12, K * 16 * T))        # both layers, hidden-tile-major (two-layer form)
-            xi.add("W1cat", self._pk["W1cat"])               # layer 1 of all types per node (node stage)
-            self._pk["xi"] = xi
-            self._pk_key = None
-        key = _param_key(params)
-        if key != self._pk_key or _volatile(params):
-            self._plan[1].refresh()
-            self._pk["xi"].bump()
-            self._pk_key = key
-        return self._pk
+        """Packed images of the K typed MLPs (layout: `weights.typed_agg`)."""
+        return weights.cache(self, "agg").get(_plist(self.agg_mlp), lambda plan: weights.typed_agg(
+            plan, [m.layers[0] for m in self.agg_mlp], [m.layers[1] for m in self.agg_mlp]))
 
     def forward(self, edge_distribution, H, ori):
         """Returns cat(H^T feat, ori) WITHOUT the division by N (that is edge2node's,
@@ -348,36 +227,6 @@ class edge_aggregation(nn.Module):
         return ops.agg_scatter(feat, H, ori, divisor)
 
 
-def _param_key(params: Iterable[nn.Parameter]):
-    """Cheap fingerprint of a parameter set: storage address + in-place version counter."""
-    return tuple((p.data_ptr(), p._version) for p in params)
-
-
-def _volatile(params: Iterable[nn.Parameter]) -> bool:
-    """Whether the packed-image cache must not be trusted for this call.  The fingerprint above misses writes
-    made through ``p.data`` / raw pointers (they do not bump ``_version``) — the idiom of hand-written
-    optimizers, EMA updates, weight clamping and the reference's own ``m.bias.data.fill_`` re-initialisation.
-    While autograd is recording for these parameters (a training step) every call therefore re-runs the one
-    refresh launch of its pack plan; only inference (no-grad / frozen parameters) trusts the cache, and code
-    that rewrites weights there behind autograd's back calls `invalidate_weight_caches`."""
-    return _TRAINING_CALL[0] or (torch.is_grad_enabled() and any(p.requires_grad for p in params))
-
-
-_TRAINING_CALL = [False]
-
-
-class training_call:
-    """Context of a forward that belongs to a training step (`backward.MSHGNNFunction.forward` runs under
-    no_grad, so `_volatile` cannot see it from the grad mode)."""
-
-    def __enter__(self):
-        self.prev, _TRAINING_CALL[0] = _TRAINING_CALL[0], True
-
-    def __exit__(self, *exc):
-        _TRAINING_CALL[0] = self.prev
-        return False
-
-
 def invalidate_weight_caches(module: nn.Module) -> None:
     """Mark every packed / concatenated weight image below `module` stale.  They are keyed on the parameters'
     (address, in-place version); anything that rewrites parameters behind autograd's back — a replayed
@@ -386,11 +235,8 @@ def invalidate_weight_caches(module: nn.Module) -> None:
     for m in module.modules():
         d = m.__dict__
         d.pop("_gn_plist", None)
-        if "_pk_key" in d:
-            m._pk_key = None
-        for name in ("_pk_n2e", "_pk_mlp", "_bwd_cat"):
-            for hit in d.get(name, {}).values():
-                hit[3] = None
+        for c in weights.caches(m):
+            c.invalidate()
         if "_affine" in d:
             m._affine = None
 
@@ -424,103 +270,15 @@ class _MessagePassing(nn.Module):
         self.edge_aggregation_list = nn.ModuleList(
             edge_aggregation(input_dim=h_dim, output_dim=bottleneck_dim, hidden_size=(128,), edge_types=K)
             for _ in range(nmp_layers))
-        self._pk_n2e: Dict[int, list] = {}      # idx -> [param addresses, packed dict, PackPlan, version key]
-        self._pk_mlp: Dict[int, list] = {}
 
     # -- packed weights ------------------------------------------------------------------------
     def _packed_n2e(self, idx: int) -> dict:
         start, att = self.node2edge_start_mlp[idx], self.attention_mlp[idx]
-        params = _plist(start) + _plist(att)
-        ptrs = tuple(p.data_ptr() for p in params)
-        hit = self._pk_n2e.get(idx)
-        if hit is None or hit[0] != ptrs:
-            s0, s1 = _two_layer(start)
-            a0, a1 = _two_layer(att)
-            D = _HDIM_EXTEND
-            plan = ops.PackPlan(params[0].device)
-            w0 = plan.matrix(s0.weight)
-            plan.matrix(s1.weight)
-            # attention layer 0 acts on cat(x'_n, e0_e): split it into the node half (with the bias) and the
-            # edge half, which by linearity is applied to x' before the H-pooling: Wpq = [W[:, :D]; W[:, D:]]
-            wpq = plan.alloc(4 * plan.TILE)
-            plan.block(wpq, a0.weight, 2, c0=0, cols=D)
-            plan.block(wpq, a0.weight, 2, c0=D, cols=D, place_r=32)
-            w_len = plan.size - w0
-            # the same chain in the pipeline order of the bf16-core kernel (source of its image): A_t = [W0(t,in0),
-            # W0(t,in1)], B_t = [W1(0,t), W1(1,t)], then Wpq as above: 36 tiles = 72 sub-steps
-            T = plan.TILE
-            wc = plan.alloc(36 * T)
-            off = wc
-            for kind, t in ops.pipeline_order(8):
-                if kind == "A":
-                    plan.block(off, s0.weight, 2, r0=32 * t, rows=32)
-                else:
-                    plan.block(off, s1.weight, 1, r0=0, c0=32 * t, rows=32, cols=32)
-                    plan.block(off + T, s1.weight, 1, r0=32, c0=32 * t, rows=32, cols=32)
-                off += 2 * T
-            plan.block(wc + 32 * T, a0.weight, 2, c0=0, cols=D)
-            plan.block(wc + 32 * T, a0.weight, 2, c0=D, cols=D, place_r=32)
-            bo = plan.alloc(256 + 64 + 64)
-            plan.vector(bo, s0.bias)
-            plan.vector(bo + 256, s1.bias)
-            plan.vector(bo + 320, a0.bias)
-            plan.finish()
-            xi = ops.XImages()
-            xi.add("chain", plan.view(wc, 36 * T))
-            pk = dict(W=plan.view(w0, w_len), bias=plan.view(bo, 384), xi=xi,
-                      w2=a1.weight.detach()[0], b2=a1.bias.detach())    # views of the parameters: no host sync
-            hit = self._pk_n2e[idx] = [ptrs, pk, plan, None]
-        key = _param_key(params)
-        if key != hit[3] or _volatile(params):
-            hit[2].refresh()
-            hit[1]["xi"].bump()
-            hit[3] = key
-        return hit[1]
+        return weights.cache(self, ("n2e", idx)).get(_plist(start) + _plist(att), lambda plan: weights.node_chain(
+            plan, _two_layer(start), _two_layer(att)))
 
     def _packed_mlp2(self, mlp: MLP) -> dict:
-        params = _plist(mlp)
-        ptrs = tuple(p.data_ptr() for p in params)
-        hit = self._pk_mlp.get(id(mlp))
-        if hit is None or hit[0] != ptrs:
-            l0, l1 = _two_layer(mlp)
-            plan = ops.PackPlan(params[0].device)
-            w0 = plan.matrix(l0.weight)
-            plan.matrix(l1.weight)
-            w_len = plan.size - w0
-            pad = lambda n: (n + 31) // 32 * 32
-            din, dh, dout = l0.in_features, l0.out_features, l1.out_features
-            xi = ops.XImages()
-            wh = n_t = 0
-            if dout <= 64 and din % 32 == 0 and dh % 32 == 0:
-                # pipeline order of the bf16-core kernel (source of its image): A_t = W0(t, in *), B_t = W1(*, t)
-                T, IT, HT, OT = plan.TILE, din // 32, dh // 32, (dout + 31) // 32
-                n_t = HT * (IT + OT)
-                wh = plan.alloc(n_t * T)
-                off = wh
-                for kind, t in ops.pipeline_order(HT):
-                    if kind == "A":
-                        plan.block(off, l0.weight, IT, r0=32 * t, rows=32)
-                        off += IT * T
-                    else:
-                        for o in range(OT):
-                            plan.block(off + o * T, l1.weight, 1, r0=32 * o, c0=32 * t, rows=min(32, dout - 32 * o),
-                                       cols=32)
-                        off += OT * T
-            bo = plan.alloc(pad(dh) + pad(dout))
-            plan.vector(bo, l0.bias)
-            plan.vector(bo + pad(dh), l1.bias)
-            plan.finish()
-            if n_t:
-                xi.add("mlp2", plan.view(wh, n_t * plan.TILE))
-            pk = dict(W=plan.view(w0, w_len), bias=plan.view(bo, pad(dh) + pad(dout)), xi=xi,
-                      din=din, dh=dh, dout=dout)
-            hit = self._pk_mlp[id(mlp)] = [ptrs, pk, plan, None]
-        key = _param_key(params)
-        if key != hit[3] or _volatile(params):
-            hit[2].refresh()
-            hit[1]["xi"].bump()
-            hit[3] = key
-        return hit[1]
+        return weights.cache(mlp, "mlp2").get(_plist(mlp), lambda plan: weights.closing_mlp(plan, *_two_layer(mlp)))
 
     # -- stages (single-module faces of the grouped engine below) -----------------------------------
     def _node2edge(self, x: Tensor, H: Optional[Tensor], idx: int) -> Tensor:

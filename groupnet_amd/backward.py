@@ -21,19 +21,17 @@ the same two blocks repeated, walked backwards.
 """
 from __future__ import annotations
 
-import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, ops, weights
 from ._lib import _P, check, load, stream_handle
+from .weights import _HID, _LGF_LD
 
 Tensor = torch.Tensor
 _TAU = 0.5
-_HID = 128           # hidden width of the typed aggregation MLPs (model/MS_HGNN_batch.py:253-255)
-_LGF_LD = 32         # leading dimension of the (logits | factor pre-activation) buffer
 
 
 def _p(t: Optional[Tensor]):
@@ -175,53 +173,17 @@ def _round_layers(mod, j: int):
 
 
 def _bwd_weights(mod, j: int) -> dict:
-    """The concatenated weight matrices round j's backward GEMMs read — the K typed MLPs as one wide layer,
-    MLP_distribution | MLP_factor side by side, the split attention layer 0 — assembled from the parameters
-    by ONE `PackPlan` launch (no torch.cat, capturable).  A backward is by definition part of a training
-    step, where parameters may have been rewritten through `.data` without a version bump: the plan (arena and
-    segment table) is cached per parameter addresses, its one refresh launch runs on every call."""
-    from .MS_HGNN_batch import _param_key
-    cache = mod.__dict__.setdefault("_bwd_cat", {})
-    hit = cache.get(j)
-    (s0, s1), (a0, a1), st, agg, _ = _round_layers(mod, j)
-    d0, d1 = st.MLP_distribution.layers
-    f0, f1 = st.MLP_factor.layers
+    """The concatenated weight matrices round j's backward GEMMs read (layout: `weights.backward_cat`), assembled
+    from the parameters by ONE `PackPlan` launch (no torch.cat, capturable).  A backward is by definition part of a
+    training step, where parameters may have been rewritten through `.data` without a version bump: the cache
+    refreshes on every call."""
+    _, (a0, _), st, agg, _ = _round_layers(mod, j)
+    d, f = st.MLP_distribution.layers, st.MLP_factor.layers
     l0 = [m.layers[0] for m in agg.agg_mlp]
     l1 = [m.layers[1] for m in agg.agg_mlp]
-    params = [a0.weight, a0.bias, d0.weight, d0.bias, d1.weight, d1.bias, f0.weight, f0.bias, f1.weight, f1.bias]
-    params += [p for l in l0 + l1 for p in (l.weight, l.bias)]
-    ptrs = tuple(p.data_ptr() for p in params)
-    if hit is None or hit[0] != ptrs:
-        K, D = mod.edge_types, ops.FEAT
-        plan = ops.PackPlan(params[0].device)
-        off = dict(W1cat=plan.alloc(K * _HID * D), b1cat=plan.alloc(K * _HID), W2cat=plan.alloc(D * K * _HID),
-                   b2mat=plan.alloc(K * D), Wd0=plan.alloc(256 * D), bd0=plan.alloc(256), Wd1=plan.alloc(_LGF_LD * 256),
-                   bd1=plan.alloc(_LGF_LD), Wpq=plan.alloc(D * D), bpq=plan.alloc(D))
-        for k in range(K):
-            plan.place(off["W1cat"], D, l0[k].weight, place_r=k * _HID)           # (K*128, 64)
-            plan.place(off["b1cat"], 0, l0[k].bias, place_c=k * _HID)
-            plan.place(off["W2cat"], K * _HID, l1[k].weight, place_c=k * _HID)     # (64, K*128)
-            plan.place(off["b2mat"], 0, l1[k].bias, place_c=k * D)                 # (K, 64)
-        plan.place(off["Wd0"], D, d0.weight)                                       # hidden layers side by side
-        plan.place(off["Wd0"], D, f0.weight, place_r=128)
-        plan.place(off["bd0"], 0, d0.bias)
-        plan.place(off["bd0"], 0, f0.bias, place_c=128)
-        plan.place(off["Wd1"], 256, d1.weight)                                     # rows 0..K-1: logits over hidden[:128]
-        plan.place(off["Wd1"], 256, f1.weight, place_r=K, place_c=128)             # row K: factor over hidden[128:]
-        plan.place(off["bd1"], 0, d1.bias)
-        plan.place(off["bd1"], 0, f1.bias, place_c=K)
-        plan.place(off["Wpq"], D, a0.weight[:, :D])                                # P = W[:, :64] x' + b
-        plan.place(off["Wpq"], D, a0.weight[:, D:], place_r=32)                    # Qn = W[:, 64:] x'
-        plan.place(off["bpq"], 0, a0.bias)
-        plan.finish()
-        shapes = dict(W1cat=(K * _HID, D), b1cat=(K * _HID,), W2cat=(D, K * _HID), b2mat=(K, D), Wd0=(256, D), bd0=(256,),
-                      Wd1=(_LGF_LD, 256), bd1=(_LGF_LD,), Wpq=(D, D), bpq=(D,))
-        cat = {n: plan.view(off[n], math.prod(shp)).view(*shp) for n, shp in shapes.items()}
-        hit = cache[j] = [ptrs, cat, plan, None, params]
-    hit[4] = params
-    hit[2].refresh()
-    hit[3] = _param_key(params)
-    return hit[1]
+    params = [a0.weight, a0.bias] + [p for l in (*d, *f, *l0, *l1) for p in (l.weight, l.bias)]
+    return weights.cache(mod, ("bwd", j), always=True).get(params, lambda plan: weights.backward_cat(
+        plan, a0, d, f, l0, l1))
 
 
 def round_backward(traces: Sequence[ModuleTrace], j: int, g_ys: Sequence[Optional[Tensor]],

@@ -102,13 +102,10 @@ class XImages:
     parts (3: the fp32-accurate path of the fp32 entry points, 1: the bf16 twins) from hidden-tile-major fp32
     tile streams of a `PackPlan` arena, and rebuilt whenever the owner bumps `version` after a refresh."""
 
-    def __init__(self):
-        self.src = {}
+    def __init__(self, **src: Tensor):
+        self.src = src
         self.img = {}
         self.version = 0
-
-    def add(self, name: str, tiles: Tensor) -> None:
-        self.src[name] = tiles
 
     def bump(self) -> None:
         self.version += 1
@@ -394,7 +391,7 @@ def bias_stream(biases: Sequence[Tensor]) -> Tensor:
 class PackPlan:
     """All packed weight images of one module as ONE arena refreshed by ONE launch.
 
-    Built once (per module and parameter addresses): `matrix` / `block` / `vector` record segments of
+    Built once (per module and parameter addresses): `block` / `place` / `vector` record segments of
     `gn_pack_segments_f32` and hand out arena offsets; `finish()` uploads the segment table to the device.
     `refresh()` = one kernel launch, reading the parameters in place — what has to happen after every
     optimizer step, capturable in a hipGraph."""
@@ -440,13 +437,6 @@ class PackPlan:
         self._segs.append((W.data_ptr(), dst_off, W.stride(0), W.shape[0], W.shape[1], place_r, place_c, 0, scale, dst_ld))
         self.max_elems = max(self.max_elems, W.numel())
 
-    def matrix(self, W: Tensor) -> int:
-        """The whole (out x in) weight as a standard packed image; returns its arena offset."""
-        OT, IT = (W.shape[0] + 31) // 32, (W.shape[1] + 31) // 32
-        off = self.alloc(OT * IT * self.TILE)
-        self.block(off, W, IT)
-        return off
-
     def vector(self, dst_off: int, v: Tensor, place=0, scale=1.0) -> None:
         v = v.detach().reshape(1, -1)
         if v.stride(1) != 1 or v.dtype != torch.float32 or v.device != self.device:
@@ -463,7 +453,6 @@ class PackPlan:
             arr[i] = _lib.PackSeg(src, base + 4 * off, ld, rows, cols, pr, pc, IT, float(scale), dst_ld)
         raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
         self.table = raw.to(self.device)
-        self.sources = tuple(t.data_ptr() for t in self._keep)
         return self
 
     def view(self, off: int, numel: int) -> Tensor:

@@ -801,10 +801,21 @@ def test_hyper_module_with_listall_builder():
 def test_pack_plan_equals_matrix_by_matrix_packing():
     """The one-launch refresh of a module's packed weights (`ops.PackPlan`, gn_pack_segments_f32) writes
     bit for bit what packing matrix by matrix (gn_pack_linear_f32 + concatenation) produces — for the node,
-    edge, typed-aggregation and closing MLP streams — and follows in-place parameter updates."""
+    edge, typed-aggregation and closing MLP streams and every source of their bf16-core images (the layers' packed
+    tiles in `ops.pipeline_order`, a ragged closing MLP included) — and follows in-place parameter updates."""
+    import groupnet_amd as G
     from groupnet_amd import ops
     torch.manual_seed(17)
     pair, hyper = build_modules(2)
+    ragged = G.MLP(128, 40, hidden_size=(128,)).to(dev())
+
+    def pipeline(first, second):
+        """Both layers packed matrix by matrix, re-ordered into A_t (rows of hidden tile t) / B_t (its columns)."""
+        HT = (first.shape[0] + 31) // 32
+        a = ops.pack_linear(first.detach().contiguous()).view(HT, -1)
+        b = ops.pack_linear(second.detach().contiguous()).view(-1, HT, 1024)
+        return torch.cat([a[t] if kind == "A" else b[:, t].reshape(-1) for kind, t in ops.pipeline_order(HT)])
+
     for m in (pair.to(dev()), hyper.to(dev())):
         K = m.edge_types
         for rnd in range(2):
@@ -815,6 +826,8 @@ def test_pack_plan_equals_matrix_by_matrix_packing():
             bpq = torch.cat((a0.bias, torch.zeros_like(a0.bias)), 0).detach()
             assert torch.equal(pk["W"], ops.pack_stream([s0.weight, s1.weight, Wpq]))
             assert torch.equal(pk["bias"], ops.bias_stream([s0.bias, s1.bias, bpq]))
+            assert set(pk["xi"].src) == {"chain"}
+            assert torch.equal(pk["xi"].src["chain"], torch.cat((pipeline(s0.weight, s1.weight), ops.pack_linear(Wpq))))
             st = m.nmp_mlps[1]
             i0, i1 = st.init_MLP.layers
             d0, d1 = st.MLP_distribution.layers
@@ -828,6 +841,9 @@ def test_pack_plan_equals_matrix_by_matrix_packing():
             pk = st._packed()
             assert torch.equal(pk["W"], ops.edge_stream(i0.weight, i1.weight, torch.cat((d0.weight, f0.weight), 0).detach(), Wd1))
             assert torch.equal(pk["bias"], ops.bias_stream([i0.bias, i1.bias, torch.cat((d0.bias, f0.bias), 0), bd1]))
+            assert set(pk["xi"].src) == {"edge"}
+            assert torch.equal(pk["xi"].src["edge"], torch.cat((pipeline(i0.weight, i1.weight),
+                                                                pipeline(torch.cat((d0.weight, f0.weight), 0), Wd1))))
             agg = m.edge_aggregation_list[0]
             l0 = [x.layers[0] for x in agg.agg_mlp]
             l1 = [x.layers[1] for x in agg.agg_mlp]
@@ -839,12 +855,22 @@ def test_pack_plan_equals_matrix_by_matrix_packing():
             assert torch.equal(pk["b1half"], torch.cat([l.bias.detach() for l in l0]) * 0.5)
             w2t = [ops.pack_linear(l.weight.detach().contiguous()).view(2, 4, 4, 256).permute(1, 0, 2, 3).reshape(-1) for l in l1]
             assert torch.equal(pk["W2t"], torch.cat(w2t))
+            assert set(pk["xi"].src) == {"W2t", "W12", "W1cat"}
+            assert torch.equal(pk["xi"].src["W2t"], torch.cat(w2t))
+            assert torch.equal(pk["xi"].src["W1cat"], pk["W1cat"])
+            assert torch.equal(pk["xi"].src["W12"], torch.cat([pipeline(a.weight, b.weight) for a, b in zip(l0, l1)]))
             e0, e1 = m.nmp_mlp_end.layers
             pk = m._packed_mlp2(m.nmp_mlp_end)
             assert torch.equal(pk["W"], ops.pack_stream([e0.weight, e1.weight]))
             assert torch.equal(pk["bias"], ops.bias_stream([e0.bias, e1.bias]))
+            assert set(pk["xi"].src) == {"mlp2"}
+            assert torch.equal(pk["xi"].src["mlp2"], pipeline(e0.weight, e1.weight))
+            r0, r1 = ragged.layers
+            pk = m._packed_mlp2(ragged)
+            assert torch.equal(pk["W"], ops.pack_stream([r0.weight, r1.weight]))
+            assert torch.equal(pk["xi"].src["mlp2"], pipeline(r0.weight, r1.weight))
             with torch.no_grad():          # in-place update (an optimizer step): the next access re-packs
-                for p in m.parameters():
+                for p in list(m.parameters()) + list(ragged.parameters()):
                     p.add_(torch.randn_like(p) * 0.1)
 
 
