@@ -1238,6 +1238,7 @@ static int node2edge_launch(const gn_n2e_group_t* groups, int n_groups, int B, i
     // (few short scenes cannot fill the 128 lane pairs of a workgroup AND the chip.  Measured, banded vs rows, us —
     // N = 11: B = 512 10.6 / 21.0, 1024 15.3 / 19.1, 2048 25.0 / 24.3, 4096 42.1 / 39.1;
     // N = 50: B = 32 23.7 / 14.8, 128 25.9 / 18.4, 256 32.1 / 31.9, 1024 104 / 79)
+    // (restated in tests/launch_forms.py expected_forms: keep in step)
     if (N <= 64 && !no_rows && (maxE >= 24 || hyper_rows >= 49152 || force_rows)) {
       const size_t row_scene = (size_t)2 * N * kRowPitch * sizeof(float);
       SGh = 1;
@@ -1325,7 +1326,8 @@ static int gather_launch(const gn_gather_group_t* groups, int n_groups, int B, i
     int G = 1, TE = Emax;
     const size_t per_scene = ori_b + (size_t)Emax * N * sizeof(float);
     if (per_scene <= kLdsBudget) {
-      // several scenes per workgroup while the tile stays <= 24 KiB and the grid stays >= 1024
+      // several scenes per workgroup while the tile stays <= 24 KiB and the grid stays >= 1024 (restated in
+      // tests/launch_forms.py expected_forms)
       while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= kGsMinWgs)
         G *= 2;
     } else {

@@ -1201,6 +1201,7 @@ static int agg_launch(const gn_agg_group_t* groups_in, int n_groups_in, hipStrea
     // alone covers most of the 1024 SIMDs runs one wave per block; a mid-sized group halves its units
     // (4 waves of a workgroup sit on ONE CU, so 4-way splitting 176..700 blocks stacks two workgroups on
     // some CUs and idles others); only small groups split 4 ways
+    // (this rule, spw below, the scene form and rb2 are restated in tests/launch_forms.py expected_forms: keep in step)
     int wpr = blocks32 >= 768 ? 1 : (blocks32 >= 128 && G.K >= 2 ? 2 : (G.K >= 4 ? 4 : 1));
     if (G.node_form) wpr = 1;
     T.g[g].a = G;
@@ -1358,7 +1359,7 @@ static int mlp2_x_launch(GroupTable<gn_mlp2_group_t>& T_, int n_groups, int rows
   // a small launch: 4 waves per row block (mlp2_xs_kernel; its fused scatter reads every hyperedge of the scene, so
   // hyper groups need E <= 16).  GN_MLP2_XS = 0 / 1 forces the choice (parity tests run both)
   const int blocks32 = (rows + 31) / 32;
-  bool xs = (long long)blocks32 * n_groups <= 1536;
+  bool xs = (long long)blocks32 * n_groups <= 1536;      // (restated in tests/launch_forms.py expected_forms)
   if (const char* e = getenv("GN_MLP2_XS")) xs = atoi(e) != 0;
   for (int g = 0; g < n_groups; ++g)
     if (T_.g[g].x == nullptr && T_.g[g].H != nullptr && T_.g[g].E > 16) xs = false;

@@ -896,7 +896,8 @@ def split_bf16(packed: Tensor, out: Optional[Tensor] = None, parts: int = 3) -> 
 def closing_fusable(items: Sequence[Tuple[object, Tensor, dict, int]], pks2: Sequence[dict]) -> bool:
     """Can gn_agg_mlp_f32 apply the closing MLPs itself (gn_agg_group_t.y)?  Mirrors the launcher's rules: fp32
     results on the 16-bit matrix cores, N <= 16, every group the node form of the pairwise graph or a hyper module with
-    the fused gather whose edge rows run more than one wave per row block (< 768 row blocks), a 128 -> 128 -> dout <= 64 MLP."""
+    the fused gather whose edge rows run more than one wave per row block (< 768 row blocks), a 128 -> 128 -> dout <= 64 MLP.
+    (tests/launch_forms.py expected_forms restates these rules.)"""
     if not (BF16X6 and closing_fusion_enabled()):
         return False
     if os.environ.get("GN_AGG_HSTAGE", "1") == "0" or os.environ.get("GN_AGG_LINES", "1") == "0":

@@ -1,0 +1,317 @@
+"""Test helper: which kernel forms the launchers pick at a given launch size, a scene sampler that aims at the
+boundaries of those forms, and a float64 oracle evaluated on the sampled scenes only.
+
+Why.  The launchers choose a work shape by launch size (waves per row block, scenes per workgroup, fused or unfused
+closing stage, ...).  A full CPU oracle of a batch large enough to select the large-launch forms costs seconds to
+minutes; scenes are independent, so the oracle runs on a sample of ~32-64 scenes while the HIP path runs the whole
+batch, and the sampled rows are compared.  `expected_forms` states the launchers' rules in plain Python so that a test
+can say which form a case reaches (tests/test_launch_forms_cpu.py checks that the case table reaches every value) and
+a kernel trace can confirm it (the aggregation kernel's grid).
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence
+
+import torch
+
+from oracle import ms_hgnn_oracle as O
+
+K_PAIR, K_HYPER = 6, 10          # edge types (MS_HGNN_batch.py: MS_HGNN_oridinary / MS_HGNN_hyper)
+NODE_FORM_MAX_N, NODE_FORM_MAX_K = 16, 12      # ops.NODE_FORM_MAX_N / NODE_FORM_MAX_K
+SCENE_FORM_MAX_N = 64                          # ops.SCENE_FORM_MAX_N
+FUSED_MAX_N = 16                 # MS_HGNN_batch._FUSED_GATHER_MAX_N / _FUSED_SCATTER_MAX_N / ops.POOL_MAX_N
+RB2_MIN_PAIRS = 2048             # gn_mlp_mfma.hip rb2_min_pairs() without the test knob
+GS_MIN_WGS = 2048                # gn_graph.hip kGsMinWgs
+GS_LDS_BUDGET = 128 * 1024       # gn_graph.hip kLdsBudget
+
+
+def pair_count(N: int) -> int:
+    return N * (N + 1) // 2
+
+
+def cdiv(a: int, b: int) -> int:
+    return (a + b - 1) // b
+
+
+def xcd_grid(counts: Sequence[int]) -> int:
+    """Workgroups of a launch whose groups are dealt over the 8 XCDs in sections (gn_common.hpp gn_xcd_grid)."""
+    total = sum(counts)
+    if len(counts) > 16 or total < 64:      # (GN_MAX_SECTIONS = 16)
+        return total
+    worst = 0
+    for x in range(8):
+        worst = max(worst, sum((W * (x + 1) >> 3) - (W * x >> 3) for W in counts))
+    return 8 * worst
+
+
+def agg_wpr(rows: int, K: int) -> int:
+    """Waves per 32-row block of the typed aggregation (gn_mlp_mfma.hip agg_launch: `wpr = blocks32 >= 768 ? 1 : ...`)."""
+    b32 = cdiv(rows, 32)
+    return 1 if b32 >= 768 else (2 if b32 >= 128 and K >= 2 else (4 if K >= 4 else 1))
+
+
+def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x3", dtype: str = "fp32",
+                   training: bool = False, block: bool = True, with_pair: bool = True) -> Dict:
+    """The forms the launchers pick for one forward of the multiscale block (`block=True`, latency form: closing fused
+    where allowed) or of the same modules launched one by one through the module API (`block=False`: no fused closing).
+    precision: ops.precision() of the fp32 entry points ('f16x3' | 'bf16x6' | 'fp32'); dtype: 'fp32' | 'bf16' storage.
+
+    Returns {"groups": [per module: {"name", "E", "K", "rows", "node_form", "wpr", "spw"}], "fused_closing",
+    "agg_kernel", "agg_wgs", "agg_grid" (of the launch of the groups that are not in the twins' scene form), "scene_grid",
+    "mlp2", "n2e", "gather_spw"}; "scene_grid" / "mlp2" / "n2e" / "gather_spw" are None where that launch does not run.
+    with_pair=False: the hyper modules alone (one MS_HGNN_hyper through the module API).
+
+    These rules restate the launchers' C code; the comment above each rule in the launchers points back here, and a
+    kernel trace of tests/test_launch_forms_gpu.py's forward cases shows the aggregation grid `agg_grid` (and the scene
+    form's `scene_grid`) for every case."""
+    twin = dtype == "bf16"
+    xm = twin or precision != "fp32"            # bf16-core images (ops.BF16X6) or the twins
+    mods = ([("pair", None)] if with_pair else []) + [(f"hyper{s}", s) for s in scales]
+    groups = []
+    for name, s in mods:
+        if s is None:
+            E, K = pair_count(N), K_PAIR
+            # run_message_passing.edge2node: PairSpec(node=BF16X6 and N <= NODE_FORM_MAX_N ...) on fp32 storage,
+            # GatherSpec(node=N <= SCENE_FORM_MAX_N) on the twins (ops.node_form_enabled() is on by default)
+            node = (N <= SCENE_FORM_MAX_N) if twin else (xm and N <= NODE_FORM_MAX_N and K <= NODE_FORM_MAX_K)
+        else:
+            E, K, node = (1 if s == N else N), K_HYPER, False
+        rows = B * E
+        groups.append(dict(name=name, E=E, K=K, rows=rows, node_form=node, wpr=1 if node else agg_wpr(rows, K), spw=0))
+    hyp = [g for g in groups if g["name"] != "pair"]
+    # ops.closing_fusable + run_message_passing.edge2node (and agg_launch's own checks): fp32 results on the 16-bit cores,
+    # N <= 16, the pairwise group in its node form, every hyper group with E <= 16 below 768 row blocks
+    fused = (block and with_pair and not training and not twin and xm and N <= FUSED_MAX_N and groups[0]["node_form"]
+             and all(g["E"] <= 16 and cdiv(g["rows"], 32) < 768 and not (cdiv(g["rows"], 32) < 128 and g["K"] < 4)
+                     for g in hyp))
+    if fused:
+        for g in hyp:       # agg_launch: `spw = (128 / wpr) / E`, capped at node_cap / N nodes
+            g["spw"] = min((128 // g["wpr"]) // g["E"], (160 if g["E"] == 1 else 64) // N)
+    # the twins' scene form (node form without the per-node first layer) runs in a launch of its own, one workgroup per
+    # 32 nodes of a scene (agg_launch: agg_scene_kernel), ahead of the launch of the other groups
+    scene_grid = None
+    main = groups
+    if twin and groups[0]["node_form"]:
+        scene_grid, main = B * cdiv(N, 32), groups[1:]
+    wgs = []
+    for g in main:
+        if g["node_form"]:
+            wgs.append(cdiv(B * N, 32))
+        elif g["spw"]:
+            wgs.append(cdiv(B, g["spw"]))
+        else:
+            wgs.append(cdiv(cdiv(g["rows"], 32) * g["wpr"], 4))
+    if twin and sum(cdiv(cdiv(g["rows"], 32), 2) for g in main) >= RB2_MIN_PAIRS:
+        agg_kernel = "agg_rb2_kernel"
+        wgs = [cdiv(cdiv(g["rows"], 32), 8) for g in main]
+        grid = xcd_grid(wgs)
+    elif xm:
+        agg_kernel, grid = "agg_x_kernel", xcd_grid(wgs)
+    else:
+        agg_kernel, grid = "agg_mlp_kernel", sum(wgs)
+    # closing MLP launch (gn_mlp_mfma.hip mlp2_launch / mlp2_x_launch); din = 128, dh = 128, dout = 64
+    mlp2 = None
+    if not fused:
+        n = len(groups)
+        b32 = cdiv(B * N, 32)
+        if xm:
+            mlp2 = "mlp2_xs_kernel" if b32 * n <= 1536 else "mlp2_x_kernel"
+        else:
+            # the fp32 kernels: the 4-waves-per-block split kernel only without a fused scatter (N > 16)
+            mlp2 = "mlp2_split_kernel" if (b32 * n <= 1024 and N > FUSED_MAX_N) else "mlp2_kernel"
+    # node -> edge pooling of the hyper modules (gn_graph.hip node2edge_launch): launched for training, the fp32 cores and
+    # N > POOL_MAX_N (run_message_passing.node2edge `fuse`); row form when `maxE >= 24 || hyper_rows >= 49152`
+    n2e = None
+    if hyp and (training or not xm or N > FUSED_MAX_N):
+        hyper_rows = sum(g["rows"] for g in hyp)
+        n2e = "rows" if N <= 64 and (max(g["E"] for g in hyp) >= 24 or hyper_rows >= 49152) else "banded"
+    # stand-alone gather of the hyper modules for N > 16 (gn_graph.hip gather_launch): scenes per workgroup
+    gather_spw = None
+    if hyp and N > FUSED_MAX_N:
+        Emax, nh = max(g["E"] for g in hyp), len(hyp)
+        per_scene = N * 64 * 4 + Emax * N * 4
+        G = 1
+        if per_scene <= GS_LDS_BUDGET:
+            while G < 16 and 2 * G * per_scene <= 24 * 1024 and cdiv(B, 2 * G) * nh >= GS_MIN_WGS:
+                G *= 2
+        gather_spw = G
+    return dict(groups=groups, fused_closing=fused, agg_kernel=agg_kernel, agg_wgs=sum(wgs), agg_grid=grid,
+                scene_grid=scene_grid, mlp2=mlp2, n2e=n2e, gather_spw=gather_spw)
+
+
+def describe(forms: Dict) -> str:
+    g = ", ".join(f"{x['name']}:{'node' if x['node_form'] else 'wpr%d' % x['wpr']}{'/spw%d' % x['spw'] if x['spw'] else ''}"
+                  for x in forms["groups"])
+    return (f"[{g}] {'fused' if forms['fused_closing'] else 'unfused'} closing, {forms['agg_kernel']} grid "
+            f"{forms['agg_grid']}, scene form grid {forms['scene_grid']}, mlp2 {forms['mlp2']}, n2e {forms['n2e']}, gather G {forms['gather_spw']}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# scene sampler
+# ---------------------------------------------------------------------------------------------------------------------
+def _spread(cands: Sequence[int], k: int) -> List[int]:
+    """k members of the sorted candidate list, evenly spread from its first to its last."""
+    c = sorted(set(cands))
+    if len(c) <= k:
+        return c
+    return [c[round(i * (len(c) - 1) / (k - 1))] for i in range(k)] if k > 1 else [c[0]]
+
+
+def _straddling(B: int, rows_per_scene: int, block: int) -> List[int]:
+    """Scenes whose rows [b*r, (b+1)*r) cross a multiple of `block` rows, or start / end one."""
+    out = []
+    r = rows_per_scene
+    for b in range(B):
+        lo, hi = b * r, (b + 1) * r - 1
+        if lo // block != hi // block or lo % block == 0 or (hi + 1) % block == 0:
+            out.append(b)
+    return out
+
+
+def sample_scenes(B: int, N: int, forms: Dict, n: int = 48, seed: int = 0, per_rule: int = 4) -> torch.Tensor:
+    """Sorted scene indices (int64): the first and last scene; per rule `per_rule` scenes spread over the batch that
+    straddle a 32-row block of every group's rows (edge rows and node rows), a workgroup of the selected form (128/wpr
+    edge rows, or `spw` whole scenes), and a seeded random remainder up to n."""
+    if B <= n:
+        return torch.arange(B)
+    pick = {0, B - 1}
+    rules = [_straddling(B, N, 32)]                              # node rows: node stage, closing MLP
+    for g in forms["groups"]:
+        rules.append(_straddling(B, g["E"], 32))                  # the group's 32-row blocks
+        if g["spw"]:
+            rules.append([b for b in range(B) if b % g["spw"] in (0, g["spw"] - 1)])
+        elif not g["node_form"]:
+            rules.append(_straddling(B, g["E"], 128 // g["wpr"]))   # one workgroup's row blocks
+    for c in rules:
+        pick.update(_spread(c, per_rule))
+    rest = [b for b in range(B) if b not in pick]
+    gen = torch.Generator().manual_seed(seed)
+    need = max(0, n - len(pick))
+    if need:
+        pick.update(rest[i] for i in torch.randperm(len(rest), generator=gen)[:need].tolist())
+    return torch.tensor(sorted(pick), dtype=torch.long)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# float64 oracle on sampled scenes
+# ---------------------------------------------------------------------------------------------------------------------
+def state64(state: Dict[str, torch.Tensor], requires_grad: bool = False) -> Dict[str, torch.Tensor]:
+    return {k: v.detach().double().requires_grad_(requires_grad) for k, v in state.items()}
+
+
+def _noise(U, scenes):
+    return [u[scenes].double() for u in (U if isinstance(U, (list, tuple)) else [U])]
+
+
+def _chunks(m: int, chunk: Optional[int]):
+    step = m if not chunk else chunk
+    return [slice(i, min(m, i + step)) for i in range(0, m, step)]
+
+
+def pairwise64(state, h, U, scenes, nmp: int = 1, chunk: Optional[int] = None):
+    """Pairwise module (MS_HGNN_oridinary.forward) in float64 on h[scenes] -> (node_feat, factors) of those scenes.
+    `state` may be a float64 state (e.g. leaves that require grad); chunk: scenes per oracle call (memory at large N)."""
+    st = state if all(v.dtype == torch.float64 for v in state.values()) else state64(state)
+    hs, Us = h[scenes].double(), _noise(U, scenes)
+    nf, fac = [], []
+    for c in _chunks(len(scenes), chunk):
+        a, b = O.ms_hgnn_pairwise_forward(st, hs[c], [u[c] for u in Us], nmp, decomposed=True)
+        nf.append(a)
+        fac.append(b)
+    return torch.cat(nf), torch.cat(fac)
+
+
+def hyper_incidence(h, scenes, scale: int) -> torch.Tensor:
+    """H of the sampled scenes from the fp32 affinity, lowest index winning ties (the HIP kernel's rule)."""
+    return O.topk_incidence_ranked(O.affinity(h[scenes].float()), scale)
+
+
+def hyper64(state, h, H, U, scenes, nmp: int = 1, chunk: Optional[int] = None):
+    """Hyper module (MS_HGNN_hyper.forward) in float64 on h[scenes] with the incidence H of those scenes (as given:
+    (len(scenes), E, N)) -> (node_feat, factors)."""
+    st = state if all(v.dtype == torch.float64 for v in state.values()) else state64(state)
+    hs, Us, Hd = h[scenes].double(), _noise(U, scenes), H.double()
+    nf, fac = [], []
+    for c in _chunks(len(scenes), chunk):
+        a, b = O._message_passing(st, hs[c], Hd[c], [u[c] for u in Us], nmp, True, None)
+        nf.append(a)
+        fac.append(b)
+    return torch.cat(nf), torch.cat(fac)
+
+
+def clean_scenes(state_pair, states_hyper, scales, h, Hs, U_pair, U_hyper, scenes, with_pair: bool = True,
+                 chunk: int = 16) -> torch.Tensor:
+    """(len(scenes),) bool: the scenes none of whose oracle ReLU inputs lies within relu_probe.WINDOW of zero.
+    The probe counts only ReLU inputs whose batch is its own, so every chunk of scenes gets one probe of its own and one
+    unchunked oracle call.  Hs: per scale the incidence of `scenes` (or None)."""
+    from relu_probe import relu_probe
+    out = []
+    for c in _chunks(len(scenes), chunk):
+        with torch.no_grad(), relu_probe(c.stop - c.start) as probe:
+            block64(state_pair, states_hyper, scales, h, None if Hs is None else [H[c] for H in Hs], U_pair, U_hyper,
+                    scenes[c], with_pair=with_pair)
+        assert probe.units > 0, "the probe saw no ReLU input"
+        out.append(probe.clean())
+    return torch.cat(out)
+
+
+def block64(state_pair, states_hyper, scales, h, Hs, U_pair, U_hyper, scenes, nmp: int = 1,
+            chunk: Optional[int] = None, with_pair: bool = True, with_hyper: bool = True):
+    """Multiscale block (PastEncoder.forward around the path) in float64 on h[scenes]: cat(f, pairwise, hyper_s...) and
+    the factors of every module.  Hs: per scale the incidence of the sampled scenes (None: built here from the fp32
+    affinity).  with_pair=False / with_hyper=False leave the pairwise / hyper columns zero and their factors None (a
+    loss that does not read them)."""
+    hs = h[scenes].double()
+    feats, facs = [hs], []
+    if with_pair:
+        nf, fac = pairwise64(state_pair, h, U_pair, scenes, nmp, chunk)
+    else:
+        nf, fac = torch.zeros_like(hs), None
+    feats.append(nf)
+    facs.append(fac)
+    for i, (st, s) in enumerate(zip(states_hyper, scales)):
+        if not with_hyper:
+            feats.append(torch.zeros_like(hs))
+            facs.append(None)
+            continue
+        H = hyper_incidence(h, scenes, s) if Hs is None or Hs[i] is None else Hs[i]
+        nf, fac = hyper64(st, h, H, U_hyper[i], scenes, nmp, chunk)
+        feats.append(nf)
+        facs.append(fac)
+    return torch.cat(feats, dim=-1), facs
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the cases of tests/test_launch_forms_gpu.py (shared with the CPU test that checks they reach every form)
+# ---------------------------------------------------------------------------------------------------------------------
+def _case(kind, B, N, scales, precision="f16x3", dtype="fp32"):
+    return dict(id=f"{kind}-B{B}-N{N}-s{'.'.join(map(str, scales))}-{precision if dtype == 'fp32' else dtype}",
+                kind=kind, B=B, N=N, scales=list(scales), precision=precision, dtype=dtype)
+
+
+FORWARD_CASES = (
+    # N = 11, scales {2,5,11}: E = 11 switches wpr 4 -> 2 at B = 370 and 2 -> 1 (closing unfused) at B = 2232; B = 64 is
+    # the anchor (the forms the small-size tests already trust); B = 512 packs 5 scenes per workgroup
+    [_case("block", B, 11, [2, 5, 11], p) for p in ("f16x3", "bf16x6", "fp32")
+     for B in (64, 369, 370, 512, 2231, 2232, 4096)]
+    # one scale = N module (E = 1): wpr 4 -> 2 at B = 4065, 2 -> 1 at B = 24545
+    + [_case("hyper", B, 11, [11]) for B in (4064, 4065, 24576)]
+    # the N <= 16 limit of the fused gather / scatter / pooling / closing stage; N = 17 at B = 2736 packs 4 scenes per
+    # gather workgroup and takes the row form of node -> edge
+    + [_case("block", 512, 16, [2, 5, 16]), _case("block", 512, 17, [2, 5, 17]), _case("block", 2736, 17, [2, 5, 17])]
+    # bf16 storage: config 4, and the twins' scene form of the pairwise aggregation on both sides of N = 64
+    + [_case("block", 1024, 50, [2, 4, 8, 16], dtype="bf16"), _case("block", 256, 64, [2, 16, 64], dtype="bf16"),
+       _case("block", 256, 65, [2, 16, 65], dtype="bf16")]
+)
+
+# training forward + backward of the block (fp32): node -> edge banded (B = 512) and row form (B = 2232, config 4 at its
+# own batch, B = 1024: at N = 50 only ~4 % of the scenes are clean in the hyper modules, so the clean scenes are drawn
+# from the whole batch)
+BACKWARD_CASES = [_case("train", 512, 11, [2, 5, 11]), _case("train", 2232, 11, [2, 5, 11]),
+                  _case("train", 1024, 50, [2, 4, 8, 16])]
+
+
+def case_forms(case: Dict) -> Dict:
+    return expected_forms(case["B"], case["N"], case["scales"], case["precision"], case["dtype"],
+                          training=case["kind"] == "train", block=case["kind"] != "hyper",
+                          with_pair=case["kind"] != "hyper")
