@@ -25,72 +25,108 @@ _F = ctypes.c_float
 _SZ = ctypes.c_size_t
 _U64 = ctypes.c_ulonglong
 
-class NodeGroup(ctypes.Structure):      # gn_node_group_t
+
+def addr(t) -> int:
+    """Device address of a tensor for a descriptor field or pointer argument, 0 (NULL) for None."""
+    return 0 if t is None else t.data_ptr()
+
+
+# Descriptor mirrors, filled by field name (fields left out are 0 / NULL; C's `def` is `def_`).  `c_name`: the header struct
+# (a CPU test compares the layouts); the empty `__slots__` make the constructor refuse a misspelt field name.
+class NodeGroup(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_node_group_t"
     _fields_ = [("x", _P), ("W", _P), ("bias", _P), ("xp", _P), ("pq", _P), ("hid_out", _P), ("Wx", _P),
                 ("WAx", _P), ("bA", _P), ("A", _P), ("KA", _I), ("Wh", _P), ("WAh", _P)]
 
 
-class N2EGroup(ctypes.Structure):       # gn_n2e_group_t
+class N2EGroup(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_n2e_group_t"
     _fields_ = [("xp", _P), ("pq", _P), ("H", _P), ("w2", _P), ("edges", _P), ("b2", _P), ("E", _I), ("sym", _I)]
 
 
-class EdgeGroup(ctypes.Structure):      # gn_edge_group_t
+class EdgeGroup(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_edge_group_t"
     _fields_ = [("edges", _P), ("U", _P), ("W", _P), ("bias", _P), ("edge_feat", _P), ("dist", _P),
                 ("philox_offset", _U64), ("rows", _I), ("K", _I), ("sym_N", _I), ("keep_z1", _P), ("keep_z", _P),
                 ("keep_dh1", _P), ("keep_lgf", _P), ("Wx", _P), ("xp", _P), ("pq", _P), ("pool_H", _P), ("w2", _P),
                 ("b2", _P), ("pool_N", _I), ("pool_E", _I), ("Wh", _P)]
 
 
-class GatherGroup(ctypes.Structure):    # gn_gather_group_t
+class GatherGroup(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_gather_group_t"
     _fields_ = [("ori", _P), ("H", _P), ("eo", _P), ("E", _I), ("sym", _I)]
 
 
-class AggGroup(ctypes.Structure):       # gn_agg_group_t
+class AggGroup(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_agg_group_t"
     _fields_ = [("eo", _P), ("edge_feat", _P), ("W", _P), ("b1", _P), ("b2", _P), ("feat", _P), ("rows", _I),
                 ("K", _I), ("ori", _P), ("H", _P), ("E", _I), ("N", _I), ("sym", _I), ("A", _P), ("W2x", _P), ("W12x", _P),
                 ("W2h", _P), ("W12h", _P), ("node_form", _I), ("m2x", _P), ("m2h", _P), ("m2bias", _P), ("y", _P), ("ldy", _I),
                 ("dout", _I), ("divisor", _F)]
 
 
-class ScatterGroup(ctypes.Structure):   # gn_scatter_group_t
+class ScatterGroup(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_scatter_group_t"
     _fields_ = [("feat", _P), ("H", _P), ("ori", _P), ("out", _P), ("E", _I), ("sym", _I)]
 
 
-class Mlp2Group(ctypes.Structure):      # gn_mlp2_group_t
+class Mlp2Group(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_mlp2_group_t"
     _fields_ = [("x", _P), ("W", _P), ("bias", _P), ("y", _P), ("feat", _P), ("H", _P), ("ori", _P), ("E", _I),
                 ("sym", _I), ("in_out", _P), ("hid_out", _P), ("Wx", _P), ("Wh", _P)]
 
 
-class BlockExtras(ctypes.Structure):    # gn_block_extras_t
+class BlockExtras(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_block_extras_t"
     _fields_ = [("f_out", _P), ("f_out_ld", _I), ("H_cat", _P), ("counter", _P), ("counter_add", _U64),
                 ("x_raw", _P), ("x_dim", _I), ("M", _P), ("c", _P), ("f_contig", _P)]
 
 
-class AffinityJob(ctypes.Structure):   # gn_affinity_job_t
+class AffinityJob(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_affinity_job_t"
     _fields_ = [("f", _P), ("corr", _P), ("H_list", ctypes.POINTER(_P)), ("k_list", ctypes.POINTER(_I)), ("n_scales", _I),
                 ("B", _I), ("N", _I), ("D", _I), ("extras", ctypes.POINTER(BlockExtras))]
 
 
-class PackSeg(ctypes.Structure):       # gn_pack_seg_t
+class PackSeg(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_pack_seg_t"
     _fields_ = [("src", _P), ("dst", _P), ("ld", _I), ("rows", _I), ("cols", _I), ("place_r", _I), ("place_c", _I),
                 ("IT", _I), ("scale", _F), ("dst_ld", _I)]
 
 
-class SplitJob(ctypes.Structure):      # gn_split_job_t
+class SplitJob(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_split_job_t"
     _fields_ = [("packed", _P), ("out", _P), ("n_tiles", _I), ("reserved", _I)]
 
 
-class GumbelBwdGroup(ctypes.Structure):  # gn_gumbel_bwd_group_t
+class GumbelBwdGroup(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_gumbel_bwd_group_t"
     _fields_ = [("dist", _P), ("lgf", _P), ("def_", _P), ("gdist", _P), ("dlgf", _P), ("rows", ctypes.c_longlong),
                 ("K", _I), ("sym_N", _I)]
 
 
-class N2EBwdGroup(ctypes.Structure):     # gn_n2e_bwd_group_t
+class N2EBwdGroup(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_n2e_bwd_group_t"
     _fields_ = [("xp", _P), ("pq", _P), ("H", _P), ("w2", _P), ("b2", _P), ("dedges", _P), ("dxp", _P), ("dpq", _P),
                 ("dw2", _P), ("db2", _P), ("E", _I), ("sym", _I)]
 
 
-class GemmDesc(ctypes.Structure):      # gn_gemm_desc_t
+class GemmDesc(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_gemm_desc_t"
     _fields_ = [("A", _P), ("B", _P), ("C", _P), ("bias", _P), ("mask", _P), ("rs", _P), ("colsum", _P),
                 ("M", _I), ("N", _I), ("K", _I), ("lda", _I), ("ldb", _I), ("ldc", _I), ("ldmask", _I), ("rs_ld", _I),
                 ("flags", _I), ("alpha", _F), ("beta", _F)]

@@ -27,15 +27,11 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops, weights
-from ._lib import _P, check, load, stream_handle
+from ._lib import addr, check, load, stream_handle
 from .weights import _HID, _LGF_LD
 
 Tensor = torch.Tensor
 _TAU = 0.5
-
-
-def _p(t: Optional[Tensor]):
-    return _P(0 if t is None else t.data_ptr())
 
 
 class GemmBatch:
@@ -64,10 +60,10 @@ class GemmBatch:
         if tC and not accum:
             raise ValueError("gemm: tC (write the product transposed) exists for accumulate mode only")
         ld = lambda t: max(t.stride(0), t.shape[1])
-        self.descs.append(_lib.GemmDesc(A.data_ptr(), Bm.data_ptr(), C.data_ptr(), _p(bias).value, _p(mask).value,
-                                        _p(rs).value, _p(colsum).value, M, N, K, ld(A), ld(Bm), ld(C),
-                                        0 if mask is None else ld(mask), 0 if rs is None else rs.stride(0), flags,
-                                        float(alpha), float(beta)))
+        self.descs.append(_lib.GemmDesc(A=A.data_ptr(), B=Bm.data_ptr(), C=C.data_ptr(), bias=addr(bias), mask=addr(mask),
+                                        rs=addr(rs), colsum=addr(colsum), M=M, N=N, K=K, lda=ld(A), ldb=ld(Bm), ldc=ld(C),
+                                        ldmask=0 if mask is None else ld(mask), rs_ld=0 if rs is None else rs.stride(0),
+                                        flags=flags, alpha=float(alpha), beta=float(beta)))
         self.keep += [t for t in (A, Bm, C, bias, mask, rs, colsum) if t is not None]
         self.device = A.device
         return C
@@ -98,7 +94,7 @@ def axpby(out: Tensor, a: Tensor, alpha=1.0, beta=0.0) -> Tensor:
     """out = alpha*a + beta*out on 2-D (possibly column-sliced) views."""
     assert out.shape == a.shape and out.stride(1) == 1 and a.stride(1) == 1
     with torch.cuda.device(a.device):
-        check(load().gn_axpby2d_f32(_p(out), out.stride(0), _p(a), a.stride(0), a.shape[0], a.shape[1], float(alpha),
+        check(load().gn_axpby2d_f32(addr(out), out.stride(0), addr(a), a.stride(0), a.shape[0], a.shape[1], float(alpha),
                                     float(beta), stream_handle()), "gn_axpby2d_f32")
     return out
 
@@ -273,7 +269,7 @@ def round_backward(traces: Sequence[ModuleTrace], j: int, g_ys: Sequence[Optiona
             c["Kp"] = (c["K"] + 3) // 4 * 4
             c["ef"] = c["pool"].take(c["R"], c["Kp"])
             with torch.cuda.device(dev):
-                check(load().gn_gumbel_ef_f32(_p(c["dist"]), _p(c["lgf"]), _p(c["ef"]), c["R"], c["K"], _LGF_LD,
+                check(load().gn_gumbel_ef_f32(addr(c["dist"]), addr(c["lgf"]), addr(c["ef"]), c["R"], c["K"], _LGF_LD,
                                               c["N"] if c["sym"] else 0, 1.0, c["Kp"], stream_handle()), "gn_gumbel_ef_f32")
             c["def"] = c["pool"].take(c["R"], c["K"])
             c["dx"] = None
@@ -304,8 +300,9 @@ def round_backward(traces: Sequence[ModuleTrace], j: int, g_ys: Sequence[Optiona
             stage(lambda c: c.update(T=gb.add(c["dfeat"], c["tw"]["W2cat"], new(c["R"], c["K"] * _HID))))
             for c in S:
                 with torch.cuda.device(dev):
-                    check(load().gn_typed_bwd_f32(_p(c["T"]), _p(c["Hc"]), _p(c["ef"]), c["Kp"], _p(c["dfeat"]), _p(c["tw"]["b2mat"]),
-                                                  _p(c["def"]), c["R"], c["K"], _HID, stream_handle()), "gn_typed_bwd_f32")
+                    check(load().gn_typed_bwd_f32(addr(c["T"]), addr(c["Hc"]), addr(c["ef"]), c["Kp"], addr(c["dfeat"]),
+                                                  addr(c["tw"]["b2mat"]), addr(c["def"]), c["R"], c["K"], _HID, stream_handle()),
+                          "gn_typed_bwd_f32")
             # (pair rows: the self-loop's eo = 2 ori, and the pair-form scatter below weighs every row once)
             # (K = K_types*128 is long and the output has few tiles: split K over workgroups, atomic accumulate)
             stage(lambda c: c.update(deo=gb.add(c["T"], c["tw"]["W1cat"], c["pool"].take(c["R"], D), accum=True,
@@ -339,8 +336,9 @@ def round_backward(traces: Sequence[ModuleTrace], j: int, g_ys: Sequence[Optiona
         arr = (_lib.GumbelBwdGroup * len(S))()
         for i, c in enumerate(S):
             c["dlgf"] = new(c["R"], _LGF_LD)
-            arr[i] = _lib.GumbelBwdGroup(_p(c["dist"]), _p(c["lgf"]), _p(c["def"]), _p(c["g_d"]), _p(c["dlgf"]), c["R"], c["K"],
-                                         c["N"] if c["sym"] else 0)
+            arr[i] = _lib.GumbelBwdGroup(dist=c["dist"].data_ptr(), lgf=c["lgf"].data_ptr(), def_=c["def"].data_ptr(),
+                                         gdist=addr(c["g_d"]), dlgf=c["dlgf"].data_ptr(), rows=c["R"], K=c["K"],
+                                         sym_N=c["N"] if c["sym"] else 0)
         with torch.cuda.device(dev):
             check(load().gn_gumbel_bwd_grouped_f32(arr, len(S), _LGF_LD, _TAU, stream_handle()), "gn_gumbel_bwd_grouped_f32")
 
@@ -360,19 +358,20 @@ def round_backward(traces: Sequence[ModuleTrace], j: int, g_ys: Sequence[Optiona
             # side by side instead of end to end
             arr = (_lib.N2EBwdGroup * len(S))()
             for i, c in enumerate(S):
-                arr[i] = _lib.N2EBwdGroup(_p(c["xp"]), _p(c["pq"]), _p(c["H"]), _p(c["w2"]), _p(c["b2"]), _p(c["dedges"]),
-                                          _p(c["dxp"]), _p(c["dpq"]), _p(grads[c["a1"].weight]), _p(grads[c["a1"].bias]),
-                                          c["E"], int(c["sym"]))
+                arr[i] = _lib.N2EBwdGroup(xp=c["xp"].data_ptr(), pq=c["pq"].data_ptr(), H=addr(c["H"]), w2=c["w2"].data_ptr(),
+                                          b2=c["b2"].data_ptr(), dedges=c["dedges"].data_ptr(), dxp=c["dxp"].data_ptr(),
+                                          dpq=c["dpq"].data_ptr(), dw2=grads[c["a1"].weight].data_ptr(),
+                                          db2=grads[c["a1"].bias].data_ptr(), E=c["E"], sym=int(c["sym"]))
             with torch.cuda.device(dev):
                 check(load().gn_node2edge_bwd_grouped_f32(arr, len(S), S[0]["B"], N0, stream_handle()),
                       "gn_node2edge_bwd_grouped_f32")
         else:
             for c in S:
                 with torch.cuda.device(dev):
-                    check(load().gn_node2edge_bwd_f32(_p(c["xp"]), _p(c["pq"]), _p(c["H"]), _p(c["w2"]), _p(c["b2"]),
-                                                      _p(c["dedges"]), _p(c["dxp"]), _p(c["dpq"]), _p(grads[c["a1"].weight]),
-                                                      _p(grads[c["a1"].bias]), c["B"], c["N"], c["E"], int(c["sym"]),
-                                                      stream_handle()),
+                    check(load().gn_node2edge_bwd_f32(addr(c["xp"]), addr(c["pq"]), addr(c["H"]), addr(c["w2"]),
+                                                      addr(c["b2"]), addr(c["dedges"]), addr(c["dxp"]), addr(c["dpq"]),
+                                                      addr(grads[c["a1"].weight]), addr(grads[c["a1"].bias]), c["B"],
+                                                      c["N"], c["E"], int(c["sym"]), stream_handle()),
                           "gn_node2edge_bwd_f32")
         stage(lambda c: gb.add(c["dpq"], c["tw"]["Wpq"], c["dxp"], beta=1.0))
         stage(lambda c: c.update(dx1=gb.add(c["dxp"], W(c["s1"]), new(c["B"] * c["N"], 256), mask=c["x1"])))

@@ -34,7 +34,7 @@
 //
 // Weight image: a "sub-step" = the (32 outputs x 16 k) operand of one MFMA position, P pieces of 64 lanes x 16 B:
 // piece p of sub-step s sits at ((s*P + p)*64 + lane) * 16 B.  Images are laid out in CONSUMPTION order (built by
-// ops.PackPlan as fp32 tiles, two sub-steps per 32x32 tile, then split), so a kernel walks its image linearly
+// weights.PackPlan as fp32 tiles, two sub-steps per 32x32 tile, then split), so a kernel walks its image linearly
 // through a register ring that runs D sub-steps ahead of the matrix pipe (D = 4 for P = 3: 24 MFMAs; D = 16 for
 // P = 1: 16 MFMAs).
 #pragma once

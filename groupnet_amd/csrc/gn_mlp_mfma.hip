@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256, 2) void edge_mlp_gumbel_kernel(GroupTable<gn_e
   // (8 steps) is produced, and while tile t+1 is being produced its ReLU runs in the MFMA shadow; then the
   // second layer's slice over tile t (4 steps per output tile) is accumulated.  Only two hidden tiles are
   // ever live (32 registers instead of 128), which is what lets 2-3 waves share a SIMD.  The weight stream
-  // was packed in exactly this order (edge_stream_order in ops.py):
+  // was packed in exactly this order (edge_stream in weights.py):
   //   A: T0 T1 S0 T2 S1 T3 S2 S3        (T = Wi0 tile, S = the two Wi1 slices over it: 8 steps each)
   //   B: T0 T1 S0 T2 S1 ... T7 S6 S7    (T = Wd0 tile: 8 steps, S = the Wd1 slice over it: 4 steps)
   // followed by 8 steps of padding, because the ring always reads 8 steps ahead.

@@ -16,7 +16,7 @@ from typing import Callable, Optional, Sequence, Tuple
 import torch
 
 from . import MS_HGNN_batch as _mods
-from . import ops
+from . import weights
 from .multiscale import MultiScaleHGNN
 
 Tensor = torch.Tensor
@@ -182,9 +182,9 @@ class GraphedTrainStep:
     def _step(self) -> Tensor:
         _mods.set_noise_mode("device", seed=self.seed, offset=0, counter=self.counter)
         self.optimizer.zero_grad(set_to_none=True)
-        # every packed weight image of the step from TWO launches at its head (ops.repack_scope: the first warm-up step
+        # every packed weight image of the step from TWO launches at its head (weights.repack_scope: the first warm-up step
         # records which plans / images a step touches)
-        with ops.repack_scope(self._repack):
+        with weights.repack_scope(self._repack):
             with torch.enable_grad():
                 out, H = self.block(self.f_in, advance=(self.counter, self.draws_per_step))
                 loss = self.loss_fn(out, H, *self.targets)

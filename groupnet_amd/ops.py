@@ -8,13 +8,14 @@ CPU oracle or falls back to torch math.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib
-from ._lib import _P, check, load, stream_handle
+from ._lib import _P, addr, check, load, stream_handle
 
 Tensor = torch.Tensor
 FEAT = 64
@@ -45,10 +46,6 @@ def _same_device(*ts: Tensor) -> None:
     for t in ts[1:]:
         if t is not None and t.device != dev:
             raise ValueError(f"tensors on different devices: {dev} vs {t.device}")
-
-
-def _ptr(t: Optional[Tensor]) -> ctypes.c_void_p:
-    return _P(0 if t is None else t.data_ptr())
 
 
 # ---- optional instrumentation ----------------------------------------------------------------------
@@ -95,34 +92,6 @@ def _twin(dtype: torch.dtype) -> bool:
 def _fn(stem: str, dtype: torch.dtype):
     """The C entry point of a stage for a storage type: `<stem>_f32` or its `<stem>_bf16` twin."""
     return getattr(load(), stem + ("_bf16" if _twin(dtype) else "_f32"))
-
-
-class XImages:
-    """bf16-core weight images of one packed-weight set (`gn_split_bf16_f32`), built on demand per number of
-    parts (3: the fp32-accurate path of the fp32 entry points, 1: the bf16 twins) from hidden-tile-major fp32
-    tile streams of a `PackPlan` arena, and rebuilt whenever the owner bumps `version` after a refresh."""
-
-    def __init__(self, **src: Tensor):
-        self.src = src
-        self.img = {}
-        self.version = 0
-
-    def bump(self) -> None:
-        self.version += 1
-
-    def get(self, name: str, parts: int) -> Tensor:
-        hit = self.img.get((name, parts))
-        src = self.src[name]
-        if hit is None:
-            n = src.numel() // 1024 * 2 * parts * 64 * 8
-            # (two fp16 parts: + the 16-byte flag word behind the image, zero-initialised once)
-            buf = (torch.zeros(n + 8, dtype=torch.int16, device=src.device) if parts == 2 else
-                   torch.empty(n, dtype=torch.int16, device=src.device))
-            hit = self.img[(name, parts)] = [buf, -1]
-        if hit[1] != self.version:
-            split_bf16(src, hit[0], parts)
-            hit[1] = self.version
-        return hit[0]
 
 
 def _ximg(pk: dict, name: str, dtype: torch.dtype) -> int:
@@ -172,7 +141,7 @@ def affinity(f: Tensor) -> Tensor:
     B, N, D = f.shape
     corr = torch.empty((B, N, N), dtype=f.dtype, device=f.device)
     with torch.cuda.device(f.device):
-        check(load().gn_affinity_f32(_ptr(f), _ptr(corr), B, N, D, stream_handle()), "gn_affinity_f32")
+        check(load().gn_affinity_f32(addr(f), addr(corr), B, N, D, stream_handle()), "gn_affinity_f32")
     return corr
 
 
@@ -205,7 +174,7 @@ def topk_incidence(corr: Tensor, scales: Sequence[int]) -> List[Tensor]:
     Hs = _alloc_incidence(B, N, scales, corr.device)
     Hl, kl, n = _scale_args(Hs, scales)
     with torch.cuda.device(corr.device):
-        check(load().gn_topk_incidence_f32(_ptr(corr), Hl, kl, n, B, N, stream_handle()), "gn_topk_incidence_f32")
+        check(load().gn_topk_incidence_f32(addr(corr), Hl, kl, n, B, N, stream_handle()), "gn_topk_incidence_f32")
     return Hs
 
 
@@ -224,7 +193,7 @@ def listall_incidence(corr: Tensor, scale: int) -> Tensor:
     if B == 0:
         return H
     with torch.cuda.device(corr.device):
-        check(load().gn_listall_incidence_f32(_ptr(corr), _ptr(H), B, N, scale, stream_handle()),
+        check(load().gn_listall_incidence_f32(addr(corr), addr(H), B, N, scale, stream_handle()),
               "gn_listall_incidence_f32")
     return H
 
@@ -243,8 +212,8 @@ def affinity_topk(f: Optional[Tensor], scales: Sequence[int], want_corr: bool = 
     (B, N, D) of a wider contiguous tensor that also receives f; ``want_H_cat`` — also build
     cat(H_s, dim=1); ``counter``/``counter_add`` — advance the device Philox position.
     ``embed`` = (x_raw (B,N,xd), M (D,xd), c (N,D)): f itself is computed in the launch as M x + c[n]
-    (pass f=None); a fourth return value then carries f (B,N,D)."""
-    f_contig = None
+    (pass f=None, fp32 only); a fourth return value then carries f (B,N,D)."""
+    front = None
     if embed is not None:
         x_raw, M, c = embed
         _req(x_raw, "x_raw", (None, None, None))
@@ -253,71 +222,46 @@ def affinity_topk(f: Optional[Tensor], scales: Sequence[int], want_corr: bool = 
         D = M.shape[0]
         _req(c, "c", (N, D))
         _same_device(x_raw, M, c)
-        f_contig = torch.empty((B, N, D), dtype=x_raw.dtype, device=x_raw.device)
-        f = f_contig          # shapes / device for the allocations below; the kernel ignores its contents
-    _req(f, "f", (None, None, None), _ACT_DTYPES)
-    if _twin(f.dtype) and embed is not None:
-        raise ValueError("the embedding front-end is fp32 only")
-    B, N, D = f.shape
-    corr = torch.empty((B, N, N), dtype=torch.float32, device=f.device) if want_corr else None
-    Hs = _alloc_incidence(B, N, scales, f.device)
-    Hl, kl, n = _scale_args(Hs, scales)
-    ex = _lib.BlockExtras()
-    H_cat = None
-    if f_out is not None:
-        if not (f_out.is_cuda and f_out.dtype == f.dtype and tuple(f_out.shape) == (B, N, D)
-                and f_out.stride(2) == 1 and f_out.stride(0) == N * f_out.stride(1)):
-            raise ValueError("f_out: a (B,N,D) last-dim slice of a contiguous GPU tensor of f's dtype")
-        ex.f_out, ex.f_out_ld = f_out.data_ptr(), f_out.stride(1)
-    if want_H_cat:
-        H_cat = torch.empty((B, sum(h.shape[1] for h in Hs), N), dtype=f.dtype, device=f.device)
-        ex.H_cat = H_cat.data_ptr()
-    if counter is not None:
-        if not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
-            raise ValueError("counter: a 1-element int64 GPU tensor")
-        ex.counter, ex.counter_add = counter.data_ptr(), int(counter_add) & (2**64 - 1)
-    if embed is not None:
-        ex.x_raw, ex.x_dim, ex.M, ex.c, ex.f_contig = (embed[0].data_ptr(), embed[0].shape[2], embed[1].data_ptr(),
-                                                      embed[2].data_ptr(), f_contig.data_ptr())
-    with torch.cuda.device(f.device):
-        check(_fn("gn_affinity_topk", f.dtype)(_ptr(f), _ptr(corr), Hl, kl, n, B, N, D, ctypes.byref(ex),
-                                               stream_handle()), "gn_affinity_topk")
-    if embed is not None:
-        return corr, Hs, H_cat, f_contig
-    return corr, Hs, H_cat
+        f = torch.empty((B, N, D), dtype=x_raw.dtype, device=x_raw.device)   # the launch writes it (f_contig)
+        front = dict(x_raw=x_raw.data_ptr(), x_dim=xd, M=M.data_ptr(), c=c.data_ptr(), f_contig=f.data_ptr())
+    job = AffinityTail(f, scales, want_corr, f_out, want_H_cat, counter, counter_add, _front_end=front)
+    job.launch()
+    return (job.corr, job.Hs, job.H_cat) + ((f,) if embed is not None else ())
 
 
 class AffinityTail:
     """The fused affinity + top-k launch of a forward, DEFERRED: outputs are allocated now, the work is issued as the tail
     workgroups of the first node-stage launch (`node_stage_grouped(..., affinity=job)` -> gn_node_mlp_affinity_*), or —
     when nothing picks it up — by `launch()` as the stand-alone launch.  Same arguments as `affinity_topk` (without the
-    embedding front-end)."""
+    embedding front-end, whose extras fields only `affinity_topk` passes in ``_front_end``)."""
 
     def __init__(self, f: Tensor, scales: Sequence[int], want_corr: bool = False, f_out: Optional[Tensor] = None,
-                 want_H_cat: bool = False, counter: Optional[Tensor] = None, counter_add: int = 0):
+                 want_H_cat: bool = False, counter: Optional[Tensor] = None, counter_add: int = 0,
+                 _front_end: Optional[dict] = None):
         _req(f, "f", (None, None, None), _ACT_DTYPES)
         self.f, self.scales = f, [int(s) for s in scales]
         B, N, D = f.shape
         self.corr = torch.empty((B, N, N), dtype=torch.float32, device=f.device) if want_corr else None
         self.Hs = _alloc_incidence(B, N, self.scales, f.device)
         self._Hl, self._kl, n = _scale_args(self.Hs, self.scales)
-        self._ex = _lib.BlockExtras()
+        ex = dict(_front_end or {})
         self.H_cat = None
         if f_out is not None:
             if not (f_out.is_cuda and f_out.dtype == f.dtype and tuple(f_out.shape) == (B, N, D)
                     and f_out.stride(2) == 1 and f_out.stride(0) == N * f_out.stride(1)):
                 raise ValueError("f_out: a (B,N,D) last-dim slice of a contiguous GPU tensor of f's dtype")
-            self._ex.f_out, self._ex.f_out_ld = f_out.data_ptr(), f_out.stride(1)
+            ex.update(f_out=f_out.data_ptr(), f_out_ld=f_out.stride(1))
         if want_H_cat:
             self.H_cat = torch.empty((B, sum(h.shape[1] for h in self.Hs), N), dtype=f.dtype, device=f.device)
-            self._ex.H_cat = self.H_cat.data_ptr()
+            ex.update(H_cat=self.H_cat.data_ptr())
         if counter is not None:
             if not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
                 raise ValueError("counter: a 1-element int64 GPU tensor")
-            self._ex.counter, self._ex.counter_add = counter.data_ptr(), int(counter_add) & (2**64 - 1)
+            ex.update(counter=counter.data_ptr(), counter_add=int(counter_add) & (2**64 - 1))
+        self._ex = _lib.BlockExtras(**ex)
         self._keep = (f_out, counter)
-        self.job = _lib.AffinityJob(f.data_ptr(), 0 if self.corr is None else self.corr.data_ptr(), self._Hl, self._kl, n,
-                                    B, N, D, ctypes.pointer(self._ex))
+        self.job = _lib.AffinityJob(f=f.data_ptr(), corr=addr(self.corr), H_list=self._Hl, k_list=self._kl, n_scales=n,
+                                    B=B, N=N, D=D, extras=ctypes.pointer(self._ex))
         self.done = False
 
     def fits_tail(self) -> bool:
@@ -330,235 +274,12 @@ class AffinityTail:
             return
         B, N, D = self.f.shape
         with torch.cuda.device(self.f.device):
-            check(_fn("gn_affinity_topk", self.f.dtype)(_ptr(self.f), _ptr(self.corr), self._Hl, self._kl, len(self.Hs), B, N, D,
+            check(_fn("gn_affinity_topk", self.f.dtype)(addr(self.f), addr(self.corr), self._Hl, self._kl, len(self.Hs), B, N, D,
                                                         ctypes.byref(self._ex), stream_handle()), "gn_affinity_topk")
         self.done = True
 
 
-# ---- weight packing ------------------------------------------------------------------------------
-def pack_linear(W: Tensor, col_offset: int = 0, in_features: Optional[int] = None) -> Tensor:
-    """Packed image of an nn.Linear weight (out x in), or of the column block
-    [col_offset, col_offset + in_features) of it."""
-    _req(W, "W", (None, None))
-    out_f, ld = W.shape
-    in_f = ld - col_offset if in_features is None else in_features
-    lib = load()
-    Wp = torch.empty(lib.gn_packed_elems(out_f, in_f), dtype=W.dtype, device=W.device)
-    with torch.cuda.device(W.device):
-        check(lib.gn_pack_linear_f32(_ptr(W), _ptr(Wp), out_f, in_f, ld, col_offset, stream_handle()),
-              "gn_pack_linear_f32")
-    return Wp
-
-
 # ---- A3 ------------------------------------------------------------------------------------------
-def pack_stream(weights: Sequence[Tensor]) -> Tensor:
-    """One weight stream: the packed images of `weights` (nn.Linear layout, out x in) back to back, in
-    the order a kernel consumes them."""
-    return torch.cat([pack_linear(w.detach().contiguous()) for w in weights])
-
-
-def edge_stream(Wi0: Tensor, Wi1: Tensor, Wd0: Tensor, Wd1: Tensor) -> Tensor:
-    """Weight stream of the edge-MLP kernel: the packed images of its four layers cut into hidden tiles
-    (T, 8 steps) and second-layer slices (S) and laid out in the order the kernel consumes them —
-    pair A: T0 T1 S0 T2 S1 T3 S2 S3 (S = both output tiles over one hidden tile, 8 steps);
-    pair B: T0 T1 S0 T2 S1 ... T7 S6 S7 (S = 4 steps).  One step = 256 floats."""
-    a0 = pack_linear(Wi0.detach().contiguous()).view(4, 8, 256)          # (128 x 64): 4 tiles x 8 steps
-    a1 = pack_linear(Wi1.detach().contiguous()).view(2, 4, 4, 256)       # (64 x 128): (o, t) x 4 steps
-    b0 = pack_linear(Wd0.detach().contiguous()).view(8, 8, 256)          # (256 x 64): 8 tiles x 8 steps
-    b1 = pack_linear(Wd1.detach().contiguous()).view(1, 8, 4, 256)       # (32 x 256): (0, t) x 4 steps
-    sa = lambda t: a1[:, t].reshape(8, 256)                               # slices (0,t), (1,t)
-    sb = lambda t: b1[0, t]
-    parts = [a0[0], a0[1], sa(0), a0[2], sa(1), a0[3], sa(2), sa(3)]
-    parts += [b0[0], b0[1]]
-    for t in range(8):
-        parts.append(sb(t))
-        if t < 6:
-            parts.append(b0[t + 2])
-    parts.append(a0.new_zeros(8, 256))      # the kernel's ring reads 8 steps ahead of the last one it uses
-    return torch.cat([p.reshape(-1) for p in parts]).contiguous()
-
-
-def bias_stream(biases: Sequence[Tensor]) -> Tensor:
-    """Biases back to back, each zero-padded to a multiple of 32 (one 32-float tile per output tile)."""
-    parts = []
-    for b in biases:
-        b = b.detach().reshape(-1)
-        pad = (-b.numel()) % 32
-        parts.append(torch.cat((b, b.new_zeros(pad))) if pad else b)
-    return torch.cat(parts).contiguous()
-
-
-class PackPlan:
-    """All packed weight images of one module as ONE arena refreshed by ONE launch.
-
-    Built once (per module and parameter addresses): `block` / `place` / `vector` record segments of
-    `gn_pack_segments_f32` and hand out arena offsets; `finish()` uploads the segment table to the device.
-    `refresh()` = one kernel launch, reading the parameters in place — what has to happen after every
-    optimizer step, capturable in a hipGraph."""
-
-    TILE = 1024
-
-    def __init__(self, device: torch.device):
-        self.device = device
-        self.size = 0
-        self._segs: List[tuple] = []
-        self._keep: List[Tensor] = []
-        self.arena: Optional[Tensor] = None
-        self.table: Optional[Tensor] = None
-        self.max_elems = 1
-
-    def alloc(self, numel: int) -> int:
-        off = self.size
-        self.size += (numel + 63) // 64 * 64          # keeps every image 256-byte aligned
-        return off
-
-    def block(self, dst_off: int, W: Tensor, IT: int, r0=0, c0=0, rows=None, cols=None, place_r=0, place_c=0,
-              scale=1.0) -> None:
-        """W[r0:r0+rows, c0:c0+cols] -> the packed image at arena offset dst_off (IT tiles per packed row),
-        at (place_r, place_c) of its virtual matrix."""
-        W = W.detach()
-        if W.dim() != 2 or W.stride(1) != 1 or W.dtype != torch.float32 or W.device != self.device:
-            raise ValueError("PackPlan.block: 2-D fp32 row-major matrix on the plan's device")
-        rows = W.shape[0] - r0 if rows is None else rows
-        cols = W.shape[1] - c0 if cols is None else cols
-        self._keep.append(W)
-        self._segs.append((W.data_ptr() + 4 * (r0 * W.stride(0) + c0), dst_off, W.stride(0), rows, cols, place_r, place_c,
-                           IT, scale, 0))
-        self.max_elems = max(self.max_elems, rows * cols)
-
-    def place(self, dst_off: int, dst_ld: int, W: Tensor, place_r=0, place_c=0, scale=1.0) -> None:
-        """W (2-D, or a vector as one row) -> rows [place_r, ...) x columns [place_c, ...) of the plain row-major
-        (.., dst_ld) matrix at arena offset dst_off: concatenations without torch.cat."""
-        W = W.detach()
-        W = W.reshape(1, -1) if W.dim() == 1 else W
-        if W.dim() != 2 or W.stride(1) != 1 or W.dtype != torch.float32 or W.device != self.device:
-            raise ValueError("PackPlan.place: fp32 row-major matrix or vector on the plan's device")
-        self._keep.append(W)
-        self._segs.append((W.data_ptr(), dst_off, W.stride(0), W.shape[0], W.shape[1], place_r, place_c, 0, scale, dst_ld))
-        self.max_elems = max(self.max_elems, W.numel())
-
-    def vector(self, dst_off: int, v: Tensor, place=0, scale=1.0) -> None:
-        v = v.detach().reshape(1, -1)
-        if v.stride(1) != 1 or v.dtype != torch.float32 or v.device != self.device:
-            raise ValueError("PackPlan.vector: contiguous fp32 vector on the plan's device")
-        self._keep.append(v)
-        self._segs.append((v.data_ptr(), dst_off, v.shape[1], 1, v.shape[1], 0, place, 0, scale, 0))
-        self.max_elems = max(self.max_elems, v.shape[1])
-
-    def finish(self) -> "PackPlan":
-        self.arena = torch.zeros(max(self.size, 64), dtype=torch.float32, device=self.device)
-        base = self.arena.data_ptr()
-        arr = (_lib.PackSeg * len(self._segs))()
-        for i, (src, off, ld, rows, cols, pr, pc, IT, scale, dst_ld) in enumerate(self._segs):
-            arr[i] = _lib.PackSeg(src, base + 4 * off, ld, rows, cols, pr, pc, IT, float(scale), dst_ld)
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-        self.table = raw.to(self.device)
-        return self
-
-    def view(self, off: int, numel: int) -> Tensor:
-        return self.arena[off:off + numel]
-
-    def refresh(self) -> None:
-        # (segments always write the same positions: the padding zeroed in finish() stays zero)
-        if _REPACK["rec"] is not None:
-            _REPACK["rec"][0].append(self)
-        elif _REPACK["done_plans"] is not None and id(self) in _REPACK["done_plans"]:
-            return      # this step's RepackBatch refreshed it already
-        with torch.cuda.device(self.device):
-            check(load().gn_pack_segments_f32(_ptr(self.table), len(self._segs), self.max_elems, stream_handle()),
-                  "gn_pack_segments_f32")
-
-
-# ---- one re-pack per training step -----------------------------------------------------------------------------
-# A training step re-derives every packed weight image from the parameters (the optimizer just rewrote them): one
-# `refresh` launch per pack plan and one `split_bf16` launch per bf16-core image — 21 + 17 launches of ~4.6 us per step
-# of the multiscale block, 9 % of the graphed step.  All of them read only the parameters, so they can run first and
-# together: `repack_scope` RECORDS which plans / images one step touches (first use), then runs them as TWO launches —
-# `gn_pack_segments_f32` over the concatenated segment tables, `gn_split_bf16_batch_f32` over all images — at the head
-# of every later step and turns the recorded per-plan / per-image launches of that step into no-ops.  A plan or image
-# that is not in the batch (rebuilt because parameter storage moved) simply takes its own launch as before.
-_REPACK = {"rec": None, "done_plans": None, "done_splits": None}
-
-
-class RepackBatch:
-    def __init__(self, plans: Sequence["PackPlan"], splits: Sequence[Tuple[Tensor, Tensor, int]]):
-        self.plans, self.splits = list(plans), list(splits)          # (keeps arenas, tables and images alive)
-        dev = self.plans[0].device
-        self.device = dev
-        self.table = torch.cat([p.table for p in self.plans])
-        self.n_segs = sum(len(p._segs) for p in self.plans)
-        self.max_elems = max(p.max_elems for p in self.plans)
-        if self.n_segs > 65535:
-            raise ValueError("RepackBatch: too many segments for one launch")
-        self.parts = sorted({pt for _, _, pt in self.splits})
-        self.jobs = {}
-        for pt in self.parts:
-            js = [(a, b) for a, b, q in self.splits if q == pt]
-            arr = (_lib.SplitJob * len(js))()
-            for i, (a, b) in enumerate(js):
-                arr[i] = _lib.SplitJob(a.data_ptr(), b.data_ptr(), a.numel() // 1024, 0)
-            raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-            self.jobs[pt] = (raw, len(js), max(a.numel() // 1024 for a, _ in js))
-        self.plan_ids = {id(p) for p in self.plans}
-        self.split_keys = {(a.data_ptr(), b.data_ptr(), q) for a, b, q in self.splits}
-
-    def run(self) -> None:
-        with torch.cuda.device(self.device):
-            check(load().gn_pack_segments_f32(_ptr(self.table), self.n_segs, self.max_elems, stream_handle()),
-                  "gn_pack_segments_f32")
-            for pt, (raw, n, mx) in self.jobs.items():
-                check(load().gn_split_bf16_batch_f32(_ptr(raw), n, mx, pt, stream_handle()), "gn_split_bf16_batch_f32")
-
-
-class repack_scope:
-    """``with repack_scope(holder):`` around ONE whole training step (forward and backward).  `holder` is a dict owned by
-    the caller; its first use records, later uses replay the batch (see above).  Not re-entrant."""
-
-    def __init__(self, holder: dict):
-        self.h = holder
-
-    def __enter__(self):
-        if _REPACK["rec"] is not None or _REPACK["done_plans"] is not None:
-            raise RuntimeError("repack_scope is not re-entrant")
-        batch = self.h.get("batch")
-        if batch is None:
-            _REPACK["rec"] = ([], [])
-        else:
-            batch.run()
-            _REPACK["done_plans"], _REPACK["done_splits"] = batch.plan_ids, batch.split_keys
-        return self
-
-    def __exit__(self, et, ev, tb):
-        rec = _REPACK["rec"]
-        _REPACK["rec"] = _REPACK["done_plans"] = _REPACK["done_splits"] = None
-        if rec is not None and et is None:
-            plans, seen = [], set()
-            for p in rec[0]:
-                if id(p) not in seen:
-                    seen.add(id(p))
-                    plans.append(p)
-            splits, seen2 = [], set()
-            for a, b, q in rec[1]:
-                k = (a.data_ptr(), b.data_ptr(), q)
-                if k not in seen2:
-                    seen2.add(k)
-                    splits.append((a, b, q))
-            self.h["batch"] = RepackBatch(plans, splits) if plans else None
-        return False
-
-
-def pipeline_order(HT: int) -> List[Tuple[str, int]]:
-    """Order in which the bf16-core kernels consume the tiles of one layer pair with HT hidden tiles
-    (gn_mlp_bf16.hpp, layer_pair): A_t = the first-layer tiles producing hidden tile t, B_t = the second-layer
-    tiles consuming it;  A0 A1 B0 A2 B1 ... A(HT-1) B(HT-2) B(HT-1)."""
-    out = [("A", 0)]
-    for t in range(HT):
-        if t + 1 < HT:
-            out.append(("A", t + 1))
-        out.append(("B", t))
-    return out
-
-
 def _groups(n: int) -> None:
     if not 1 <= n <= _lib.MAX_GROUPS:
         raise ValueError(f"1..{_lib.MAX_GROUPS} groups per launch, got {n}")
@@ -583,16 +304,14 @@ def node_stage_grouped(items: Sequence[Tuple[Tensor, dict]], keep: Optional[List
         _req(x, "x", tuple(x0.shape), dt)
         _same_device(x0, x)
         xp, pq = torch.empty_like(x), torch.empty_like(x)
-        hid_ptr = 0
+        hid = None
         if keep is not None:
             if _twin(dt):
                 raise ValueError("the bf16 twins are forward-only")
-            keep.append(dict(hid=torch.empty((rows, 256), dtype=x.dtype, device=x.device)))
-            hid_ptr = keep[-1]["hid"].data_ptr()
+            hid = torch.empty((rows, 256), dtype=x.dtype, device=x.device)
+            keep.append(dict(hid=hid))
         wx = _ximg(pk, "chain", dt)
-        a_fields = (0, 0, 0, 0)
-        A = None
-        wah = 0
+        A, a_fields = None, {}
         spec = a_specs[g] if a_specs is not None else None
         if spec is not None:
             if _twin(dt):
@@ -600,13 +319,14 @@ def node_stage_grouped(items: Sequence[Tuple[Tensor, dict]], keep: Optional[List
             apk, K = spec
             if wx:
                 A = torch.empty(tuple(x.shape[:-1]) + (K * 128,), dtype=x.dtype, device=x.device)
-                a_fields = (_ximg(apk, "W1cat", dt), apk["b1half"].data_ptr(), A.data_ptr(), K)
-                wah = _himg(apk, "W1cat", dt)
+                a_fields = dict(WAx=_ximg(apk, "W1cat", dt), bA=apk["b1half"].data_ptr(), A=A.data_ptr(), KA=K,
+                                WAh=_himg(apk, "W1cat", dt))
             else:
                 late.append((g, x, apk, K))
         As.append(A)
-        arr[g] = _lib.NodeGroup(x.data_ptr(), pk["W"].data_ptr(), pk["bias"].data_ptr(), xp.data_ptr(), pq.data_ptr(),
-                                hid_ptr, wx, *a_fields, _himg(pk, "chain", dt) if wx else 0, wah)
+        arr[g] = _lib.NodeGroup(x=x.data_ptr(), W=pk["W"].data_ptr(), bias=pk["bias"].data_ptr(), xp=xp.data_ptr(),
+                                pq=pq.data_ptr(), hid_out=addr(hid), Wx=wx, Wh=_himg(pk, "chain", dt) if wx else 0,
+                                **a_fields)
         outs.append((xp, pq))
     flops = sum(rows * 2 * (64 * 256 + 256 * 64 + 64 * 64 + (64 * 128 * int(a.KA) if a.A else 0)) for a in arr)
     # ``affinity``: a deferred fused affinity + top-k launch rides as this launch's tail workgroups (bf16-/fp16-core
@@ -627,14 +347,9 @@ def node_stage_grouped(items: Sequence[Tuple[Tensor, dict]], keep: Optional[List
     return outs, As
 
 
-def node_mlp_grouped(items: Sequence[Tuple[Tensor, dict]], keep: Optional[List[dict]] = None
-                     ) -> List[Tuple[Tensor, Tensor]]:
-    return node_stage_grouped(items, keep)[0]
-
-
 def node_mlp(x: Tensor, pk: dict) -> Tuple[Tensor, Tensor]:
     """x (B,N,64) -> x' = MLP_{64->256->64}(x), pq = x' Wpq^T + bpq.  pk: {"W": stream, "bias": stream}."""
-    return node_mlp_grouped([(x, pk)])[0]
+    return node_stage_grouped([(x, pk)])[0][0]
 
 
 def pair_count(N: int) -> int:
@@ -669,8 +384,8 @@ def node2edge_grouped(items: Sequence[tuple]) -> List[Tensor]:
         _req(b2, "b2", (1,))
         _same_device(xp0, xp, pq, H, w2, b2)
         edges = torch.empty((B, E, FEAT), dtype=xp.dtype, device=xp.device)
-        arr[g] = _lib.N2EGroup(xp.data_ptr(), pq.data_ptr(), 0 if H is None else H.data_ptr(), w2.data_ptr(),
-                               edges.data_ptr(), b2.data_ptr(), E, int(sym))
+        arr[g] = _lib.N2EGroup(xp=xp.data_ptr(), pq=pq.data_ptr(), H=addr(H), w2=w2.data_ptr(), edges=edges.data_ptr(),
+                               b2=b2.data_ptr(), E=E, sym=int(sym))
         outs.append(edges)
     with torch.cuda.device(xp0.device):
         check(_fn("gn_node2edge", dt)(arr, len(items), B, N, stream_handle()), "gn_node2edge")
@@ -774,23 +489,24 @@ def edge_mlp_gumbel_grouped(items: Sequence[tuple], tau: float = 0.5, keep: Opti
             u_ptr, off = U.data_ptr(), 0
         edge_feat = torch.empty((B, E, K), dtype=torch.float32, device=edges.device)    # always fp32: a VALU scale
         dist = torch.empty((B, Eo, K), dtype=dt, device=edges.device) if (want_dist or not sym_N) else None
-        kp = (0, 0, 0, 0)
+        opt = {}        # the training outputs keep_*, or the fused pooling's fields
         if keep is not None:
             if _twin(dt):
                 raise ValueError("the bf16 twins are forward-only")
             mk = lambda w: torch.empty((B * E, w), dtype=edges.dtype, device=edges.device)
             keep.append(dict(z1=mk(128), z=mk(64), dh1=mk(256), lgf=mk(32)))
-            kp = tuple(keep[-1][n].data_ptr() for n in ("z1", "z", "dh1", "lgf"))
-        pool_args = (0, 0, 0, 0, 0, 0, 0) if pool is None else (
-            pool.xp.data_ptr(), pool.pq.data_ptr(), 0 if pool.H is None else pool.H.data_ptr(), pool.w2.data_ptr(),
-            pool.b2.data_ptr(), pool.xp.shape[1], 0 if pool.H is None else pool.H.shape[1])
-        arr[g] = _lib.EdgeGroup(0 if pool is not None else edges.data_ptr(), u_ptr, pk["W"].data_ptr(),
-                                pk["bias"].data_ptr(), edge_feat.data_ptr(), 0 if dist is None else dist.data_ptr(), off,
-                                B * E, K, sym_N, *kp, _ximg(pk, "edge", dt), *pool_args, _himg(pk, "edge", dt))
+            opt = {"keep_" + n: t.data_ptr() for n, t in keep[-1].items()}
+        if pool is not None:
+            opt.update(xp=pool.xp.data_ptr(), pq=pool.pq.data_ptr(), pool_H=addr(pool.H), w2=pool.w2.data_ptr(),
+                       b2=pool.b2.data_ptr(), pool_N=pool.xp.shape[1], pool_E=0 if pool.H is None else pool.H.shape[1])
+        arr[g] = _lib.EdgeGroup(edges=0 if pool is not None else edges.data_ptr(), U=u_ptr, W=pk["W"].data_ptr(),
+                                bias=pk["bias"].data_ptr(), edge_feat=edge_feat.data_ptr(), dist=addr(dist),
+                                philox_offset=off, rows=B * E, K=K, sym_N=sym_N, Wx=_ximg(pk, "edge", dt),
+                                Wh=_himg(pk, "edge", dt), **opt)
         outs.append((edge_feat, dist))
     flops = sum(int(a.rows) for a in arr) * 2 * (64 * 128 + 128 * 64 + 64 * 256 + 256 * 32)
     with torch.cuda.device(e0.device), _Probed("edge_mlp_gumbel_kernel", flops):
-        check(_fn("gn_edge_mlp_gumbel", dt)(arr, len(items), float(tau), seed or 0, _ptr(ctr), stream_handle()),
+        check(_fn("gn_edge_mlp_gumbel", dt)(arr, len(items), float(tau), seed or 0, addr(ctr), stream_handle()),
               "gn_edge_mlp_gumbel")
     return outs
 
@@ -825,7 +541,7 @@ def agg_gather_grouped(items: Sequence[tuple]) -> List[Tensor]:
         E = _edge_count(H, B, N, sym)
         _same_device(o0, ori, H)
         eo = torch.empty((B, E, FEAT), dtype=ori.dtype, device=ori.device)
-        arr[g] = _lib.GatherGroup(ori.data_ptr(), 0 if H is None else H.data_ptr(), eo.data_ptr(), E, int(sym))
+        arr[g] = _lib.GatherGroup(ori=ori.data_ptr(), H=addr(H), eo=eo.data_ptr(), E=E, sym=int(sym))
         outs.append(eo)
     with torch.cuda.device(o0.device):
         check(_fn("gn_agg_gather", dt)(arr, len(items), B, N, stream_handle()), "gn_agg_gather")
@@ -871,26 +587,6 @@ NODE_FORM_MAX_K = 12
 def node_form_enabled() -> bool:
     """GN_NODE_FORM=0 keeps the per-pair form (A/B switch, read per call)."""
     return os.environ.get("GN_NODE_FORM", "1") != "0"
-
-
-def split_bf16(packed: Tensor, out: Optional[Tensor] = None, parts: int = 3) -> Tensor:
-    """bf16-core image (16-bit words, as int16) of packed fp32 32x32 weight tiles: `gn_split_bf16_f32`
-    (parts = 3: x = p1 + p2 + p3, the fp32-accurate path; parts = 1: x rounded to bf16, the twins; parts = 2: two fp16
-    parts x = hi + lo — the f16x3 path — followed by the 16-byte range flag)."""
-    _req(packed, "packed")
-    n_tiles = packed.numel() // 1024
-    if out is None:
-        n = n_tiles * 2 * parts * 64 * 8
-        out = (torch.zeros(n + 8, dtype=torch.int16, device=packed.device) if parts == 2 else     # (+ the flag word)
-               torch.empty(n, dtype=torch.int16, device=packed.device))
-    if _REPACK["rec"] is not None:
-        _REPACK["rec"][1].append((packed, out, int(parts)))
-    elif _REPACK["done_splits"] is not None and (packed.data_ptr(), out.data_ptr(), int(parts)) in _REPACK["done_splits"]:
-        return out      # this step's RepackBatch built it already
-    with torch.cuda.device(packed.device):
-        check(load().gn_split_bf16_f32(_ptr(packed), ctypes.c_void_p(out.data_ptr()), n_tiles, int(parts),
-                                       stream_handle()), "gn_split_bf16_f32")
-    return out
 
 
 def closing_fusable(items: Sequence[Tuple[object, Tensor, dict, int]], pks2: Sequence[dict]) -> bool:
@@ -945,10 +641,10 @@ def agg_mlp_grouped(items: Sequence[Tuple[object, Tensor, dict, int]],
             B, N = A.shape[0], A.shape[1]
             E = pair_count(N)
             _same_device(A, edge_feat)
-            like, eo_ptr, wkey = A, 0, "W2t"
-            extra = (0, 0, E, N, 1, A.data_ptr(), _ximg(pk, "W2t", A.dtype), 0, _himg(pk, "W2t", A.dtype), 0,
-                     1 if eo.node else 0)
-            if eo.node and (N > NODE_FORM_MAX_N or K > NODE_FORM_MAX_K or not extra[6]):
+            like, wkey = A, "W2t"
+            fields = dict(E=E, N=N, sym=1, A=A.data_ptr(), W2x=_ximg(pk, "W2t", A.dtype), W2h=_himg(pk, "W2t", A.dtype),
+                          node_form=int(eo.node))
+            if eo.node and (N > NODE_FORM_MAX_N or K > NODE_FORM_MAX_K or not fields["W2x"]):
                 raise ValueError("PairSpec(node=True): needs N <= 16, K <= 12 and the bf16-core weight images")
         elif isinstance(eo, GatherSpec):
             ori, H = eo.ori, eo.H
@@ -956,17 +652,17 @@ def agg_mlp_grouped(items: Sequence[Tuple[object, Tensor, dict, int]],
             B, N, _ = ori.shape
             E = _edge_count(H, B, N, eo.sym)
             _same_device(ori, H, edge_feat)
-            like, eo_ptr = ori, 0
+            like = ori
             if eo.node and not (_twin(ori.dtype) and H is None and eo.sym and N <= SCENE_FORM_MAX_N):
                 raise ValueError("GatherSpec(node=True): bf16 storage, the pairwise graph's unordered pairs and N <= 64")
-            extra = (ori.data_ptr(), 0 if H is None else H.data_ptr(), E, N, int(eo.sym), 0, 0,
-                     _ximg(pk, "W12", ori.dtype), 0, _himg(pk, "W12", ori.dtype), 1 if eo.node else 0)
+            fields = dict(ori=ori.data_ptr(), H=addr(H), E=E, N=N, sym=int(eo.sym), W12x=_ximg(pk, "W12", ori.dtype),
+                          W12h=_himg(pk, "W12", ori.dtype), node_form=int(eo.node))
         else:
             _req(eo, "eo", (None, None, FEAT), _ACT_DTYPES)
             B, E, _ = eo.shape
             _same_device(eo, edge_feat)
-            like, eo_ptr = eo, eo.data_ptr()
-            extra = (0, 0, 0, 0, 0, 0, 0, _ximg(pk, "W12", eo.dtype), 0, _himg(pk, "W12", eo.dtype))
+            like = eo
+            fields = dict(eo=eo.data_ptr(), W12x=_ximg(pk, "W12", eo.dtype), W12h=_himg(pk, "W12", eo.dtype))
         dev0, dt = dev0 or like.device, dt or like.dtype
         if like.device != dev0 or like.dtype != dt:
             raise ValueError("grouped launch: every group must be on the same device and of the same storage type")
@@ -976,20 +672,17 @@ def agg_mlp_grouped(items: Sequence[Tuple[object, Tensor, dict, int]],
             pk2, out2, ori2 = closing[g]
             _req(ori2, "ori", (B, N, FEAT))
             y, ldy = _mlp2_out((B, N), pk2["dout"], out2, ori2)
-            if len(extra) == 10:
-                extra = extra + (0,)
-            # (ori: the pairwise group's extra[0] is unused by its node form — the fused stage reads it from there)
-            extra = (ori2.data_ptr(),) + tuple(extra[1:]) + (_ximg(pk2, "mlp2", like.dtype), _himg(pk2, "mlp2", like.dtype),
-                                                             pk2["bias"].data_ptr(), y.data_ptr(), ldy, pk2["dout"], float(N))
-            arr[g] = _lib.AggGroup(eo_ptr, edge_feat.data_ptr(), pk[wkey].data_ptr(), pk["b1"].data_ptr(),
-                                   pk["b2"].data_ptr(), 0, B * E, K, *extra)
+            # (ori: the pairwise group's node form does not read it — the fused stage reads it from there)
+            fields.update(ori=ori2.data_ptr(), m2x=_ximg(pk2, "mlp2", like.dtype), m2h=_himg(pk2, "mlp2", like.dtype),
+                          m2bias=pk2["bias"].data_ptr(), y=y.data_ptr(), ldy=ldy, dout=pk2["dout"], divisor=float(N))
             outs.append(y)
             flops2 += B * N * 2 * (128 * 128 + 128 * (((pk2["dout"] + 31) // 32) * 32))
         else:
             feat = torch.empty((B, N if node else E, FEAT), dtype=like.dtype, device=like.device)
-            arr[g] = _lib.AggGroup(eo_ptr, edge_feat.data_ptr(), pk[wkey].data_ptr(), pk["b1"].data_ptr(),
-                                   pk["b2"].data_ptr(), feat.data_ptr(), B * E, K, *extra)
+            fields.update(feat=feat.data_ptr())
             outs.append(feat)
+        arr[g] = _lib.AggGroup(edge_feat=edge_feat.data_ptr(), W=pk[wkey].data_ptr(), b1=pk["b1"].data_ptr(),
+                               b2=pk["b2"].data_ptr(), rows=B * E, K=K, **fields)
         # executed FLOPs: both layers, or the second layer only in the pair form; node form: layer 2 per node plus the
         # 3 flops (add, max, fma) per pair-member and hidden value that form S
         if node:
@@ -1022,7 +715,7 @@ def node_linear(x: Tensor, W: Tensor, bias: Tensor, dout: int) -> Tensor:
     rows = x.numel() // FEAT
     y = torch.empty(tuple(x.shape[:-1]) + (dout,), dtype=x.dtype, device=x.device)
     with torch.cuda.device(x.device), _Probed("node_linear_kernel", rows * 2 * 64 * dout):
-        check(load().gn_node_linear_f32(_ptr(x), _ptr(W), _ptr(bias), _ptr(y), rows, dout, stream_handle()),
+        check(load().gn_node_linear_f32(addr(x), addr(W), addr(bias), addr(y), rows, dout, stream_handle()),
               "gn_node_linear_f32")
     return y
 
@@ -1044,8 +737,8 @@ def agg_scatter_grouped(items: Sequence[tuple], divisor: Optional[float] = None)
         _req(feat, "feat", (B, E, FEAT), dt)
         _same_device(o0, feat, ori, H)
         out = torch.empty((B, N, 2 * FEAT), dtype=ori.dtype, device=ori.device)
-        arr[g] = _lib.ScatterGroup(feat.data_ptr(), 0 if H is None else H.data_ptr(), ori.data_ptr(), out.data_ptr(), E,
-                                   int(sym))
+        arr[g] = _lib.ScatterGroup(feat=feat.data_ptr(), H=addr(H), ori=ori.data_ptr(), out=out.data_ptr(), E=E,
+                                   sym=int(sym))
         outs.append(out)
     with torch.cuda.device(o0.device):
         check(_fn("gn_agg_scatter", dt)(arr, len(items), B, N, float(N if divisor is None else divisor),
@@ -1107,40 +800,31 @@ def mlp2_grouped(items: Sequence[Tuple[object, dict, Optional[Tensor]]], keep: O
     for g, (x, pk, out) in enumerate(items):
         if (pk["din"], pk["dh"], pk["dout"]) != (din, dh, dout):
             raise ValueError("grouped mlp2: every group must have the same layer widths")
-        if isinstance(x, NodeAggSpec):
+        if isinstance(x, (NodeAggSpec, ScatterSpec)):      # the input rows cat(., ori) / divisor formed in the kernel
             if din != 2 * FEAT:
-                raise ValueError("NodeAggSpec feeds a 128-wide MLP")
+                raise ValueError(f"{type(x).__name__} feeds a 128-wide MLP")
             _req(x.ori, "ori", (None, None, FEAT), _ACT_DTYPES)
             B, Nn, _ = x.ori.shape
-            _req(x.agg, "agg", (B, Nn, FEAT), x.ori.dtype)
-            _same_device(x.ori, x.agg)
+            if isinstance(x, NodeAggSpec):
+                _req(x.agg, "agg", (B, Nn, FEAT), x.ori.dtype)
+                _same_device(x.ori, x.agg)
+                fields = dict(feat=x.agg.data_ptr(), ori=x.ori.data_ptr())
+            else:
+                E = _edge_count(x.H, B, Nn, x.sym)
+                _req(x.feat, "feat", (B, E, FEAT), x.ori.dtype)
+                _same_device(x.ori, x.feat, x.H)
+                fields = dict(feat=x.feat.data_ptr(), H=addr(x.H), ori=x.ori.data_ptr(), E=E, sym=int(x.sym))
             d = float(Nn if x.divisor is None else x.divisor)
             if N and (N, divisor) != (Nn, d):
                 raise ValueError("grouped mlp2: every fused-scatter group must share N and divisor")
             N, divisor = Nn, d
             lead, like = (B, Nn), x.ori
-            fields = (0, pk["W"].data_ptr(), pk["bias"].data_ptr(), None, x.agg.data_ptr(), 0, x.ori.data_ptr(), 0, 0)
-        elif isinstance(x, ScatterSpec):
-            if din != 2 * FEAT:
-                raise ValueError("ScatterSpec feeds a 128-wide MLP")
-            _req(x.ori, "ori", (None, None, FEAT), _ACT_DTYPES)
-            B, Nn, _ = x.ori.shape
-            E = _edge_count(x.H, B, Nn, x.sym)
-            _req(x.feat, "feat", (B, E, FEAT), x.ori.dtype)
-            _same_device(x.ori, x.feat, x.H)
-            d = float(Nn if x.divisor is None else x.divisor)
-            if N and (N, divisor) != (Nn, d):
-                raise ValueError("grouped mlp2: every fused-scatter group must share N and divisor")
-            N, divisor = Nn, d
-            lead, like = (B, Nn), x.ori
-            fields = (0, pk["W"].data_ptr(), pk["bias"].data_ptr(), None, x.feat.data_ptr(),
-                      0 if x.H is None else x.H.data_ptr(), x.ori.data_ptr(), E, int(x.sym))
         else:
             _req(x, "x", None, _ACT_DTYPES)
             if x.shape[-1] != din:
                 raise ValueError(f"x: last dim {x.shape[-1]} != {din}")
             lead, like = tuple(x.shape[:-1]), x
-            fields = (x.data_ptr(), pk["W"].data_ptr(), pk["bias"].data_ptr(), None, 0, 0, 0, 0, 0)
+            fields = dict(x=x.data_ptr())
         if shape0 is None:
             shape0, dev0, dt = lead, like.device, like.dtype
         elif lead != shape0 or like.device != dev0 or like.dtype != dt:
@@ -1150,23 +834,18 @@ def mlp2_grouped(items: Sequence[Tuple[object, dict, Optional[Tensor]]], keep: O
             ld0 = ldy
         elif ldy != ld0:
             raise ValueError("grouped mlp2: every group must have the same output row stride")
-        kp = (0, 0)
         if keep is not None:
             if _twin(dt):
                 raise ValueError("the bf16 twins are forward-only")
-            nrow = 1
-            for d_ in lead:
-                nrow *= int(d_)
-            kd = dict(x=torch.empty((nrow, din), dtype=like.dtype, device=like.device),
-                      hid=torch.empty((nrow, dh), dtype=like.dtype, device=like.device))
+            kd = dict(x=torch.empty((math.prod(lead), din), dtype=like.dtype, device=like.device),
+                      hid=torch.empty((math.prod(lead), dh), dtype=like.dtype, device=like.device))
             keep.append(kd)
-            kp = (kd["x"].data_ptr(), kd["hid"].data_ptr())
-        arr[g] = _lib.Mlp2Group(fields[0], fields[1], fields[2], y.data_ptr(), *fields[4:], *kp,
-                                _ximg(pk, "mlp2", dt) if dout <= 64 else 0, _himg(pk, "mlp2", dt) if dout <= 64 else 0)
+            fields.update(in_out=kd["x"].data_ptr(), hid_out=kd["hid"].data_ptr())
+        arr[g] = _lib.Mlp2Group(W=pk["W"].data_ptr(), bias=pk["bias"].data_ptr(), y=y.data_ptr(),
+                                Wx=_ximg(pk, "mlp2", dt) if dout <= 64 else 0, Wh=_himg(pk, "mlp2", dt) if dout <= 64 else 0,
+                                **fields)
         outs.append(y)
-    rows = 1
-    for d_ in shape0:
-        rows *= int(d_)
+    rows = math.prod(shape0)
     flops = len(items) * rows * 2 * (din * dh + dh * (((dout + 31) // 32) * 32))
     with torch.cuda.device(dev0), _Probed("mlp2_kernel", flops):
         check(_fn("gn_mlp2", dt)(arr, len(items), rows, din, dh, dout, ld0, N, divisor, stream_handle()),
@@ -1189,7 +868,7 @@ def philox_uniform(shape: Sequence[int], seed: int, offset: int, device, offset_
     if offset_dev is not None and not (offset_dev.is_cuda and offset_dev.dtype == torch.int64 and offset_dev.numel() == 1):
         raise ValueError("offset_dev: a 1-element int64 GPU tensor")
     with torch.cuda.device(U.device):
-        check(load().gn_philox_uniform_f32(_ptr(U), U.numel(), int(seed) & (2**64 - 1), int(offset), _ptr(offset_dev),
+        check(load().gn_philox_uniform_f32(addr(U), U.numel(), int(seed) & (2**64 - 1), int(offset), addr(offset_dev),
                                            stream_handle()), "gn_philox_uniform_f32")
     return U
 
@@ -1199,7 +878,7 @@ def counter_add(counter: Tensor, add: int) -> None:
     if not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
         raise ValueError("counter: a 1-element int64 GPU tensor")
     with torch.cuda.device(counter.device):
-        check(load().gn_counter_add_u64(_ptr(counter), int(add), stream_handle()), "gn_counter_add_u64")
+        check(load().gn_counter_add_u64(addr(counter), int(add), stream_handle()), "gn_counter_add_u64")
 
 
 

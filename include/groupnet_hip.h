@@ -37,7 +37,7 @@
  *     the same launch.  Either all groups of a launch carry `Wh` or none.  The image is followed by a 16-byte FLAG
  *     word the caller zero-initialises once (the split raises it when a weight does not fit fp16).
  *   - Order of the tiles in every bf16-/fp16-core image of a LAYER PAIR  out += W1 act(W0 x)  ("pipeline order", the
- *     order the kernels consume them; ops.pipeline_order): with A_t = the first-layer tiles [W0(t, in 0..IT-1)] that
+ *     order the kernels consume them; weights.pipeline_order): with A_t = the first-layer tiles [W0(t, in 0..IT-1)] that
  *     produce hidden tile t and B_t = the second-layer tiles [W1(0..OT-1, t)] that consume it:
  *         A0 A1 B0 A2 B1 ... A(HT-1) B(HT-2) B(HT-1)
  *     (NOT hidden-tile-major [A_t B_t]: A_{t+1} is issued between A_t and B_t so that the splitting of hidden tile t

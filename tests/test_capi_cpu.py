@@ -4,6 +4,7 @@ imports the oracle.  No kernel is launched."""
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 import torch
@@ -17,6 +18,16 @@ def declared_symbols():
     src = open(HEADER).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return sorted(set(re.findall(r"\b(gn_[a-z0-9_]+)\s*\(", src)))
+
+
+def declared_structs():
+    """{typedef name: field names in declaration order} of every struct the header declares."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    out = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S):
+        # "const float* const* H_list;", "int ld, rows, cols, place_r;": the last word of every declarator
+        out[name] = [re.findall(r"\w+", d)[-1] for decl in body.split(";") if decl.strip() for d in decl.split(",")]
+    return out
 
 
 def test_library_exports_every_declared_symbol():
@@ -45,7 +56,7 @@ def test_null_and_shape_errors_do_not_launch():
     ks = (ctypes.c_int * 1)(12)
     assert lib.gn_topk_incidence_f32(P(16), Hs, ks, 1, 2, 11, P(0)) == -3      # k > N
     # grouped stages: descriptors are validated on the host too
-    g = (_lib.Mlp2Group * 1)(_lib.Mlp2Group(16, 16, 16, 16))
+    g = (_lib.Mlp2Group * 1)(_lib.Mlp2Group(x=16, W=16, bias=16, y=16))
     assert lib.gn_mlp2_f32(g, 1, 5, 96, 128, 64, 64, 0, 1.0, P(0)) == -2    # unsupported widths
     assert lib.gn_mlp2_f32(g, 0, 5, 128, 128, 64, 64, 0, 1.0, P(0)) == -2   # no groups
     assert lib.gn_mlp2_f32(g, 11, 5, 128, 128, 64, 64, 0, 1.0, P(0)) == -2  # > GN_MAX_GROUPS
@@ -53,16 +64,16 @@ def test_null_and_shape_errors_do_not_launch():
     g[0].x = 0                                                               # fused scatter needs din=128, N, divisor
     assert lib.gn_mlp2_f32(g, 1, 22, 64, 128, 64, 64, 11, 11.0, P(0)) == -2
     assert lib.gn_mlp2_f32(g, 1, 22, 128, 128, 64, 64, 11, 0.0, P(0)) == -2
-    a = (_lib.AggGroup * 1)(_lib.AggGroup(16, 16, 16, 16, 16, 16, 5, 17))
+    a = (_lib.AggGroup * 1)(_lib.AggGroup(eo=16, edge_feat=16, W=16, b1=16, b2=16, feat=16, rows=5, K=17))
     assert lib.gn_agg_mlp_f32(a, 1, P(0)) == -2                             # K > GN_MAX_TYPES
     a[0].K, a[0].W = 6, 8
     assert lib.gn_agg_mlp_f32(a, 1, P(0)) == -4                             # misaligned weight stream
-    n = (_lib.N2EGroup * 1)(_lib.N2EGroup(16, 16, 0, 16, 16, 16, 8))
+    n = (_lib.N2EGroup * 1)(_lib.N2EGroup(xp=16, pq=16, w2=16, edges=16, b2=16, E=8))
     assert lib.gn_node2edge_f32(n, 1, 2, 3, P(0)) == -2                     # pairwise needs E == N*N
     n[0].b2 = 0
     assert lib.gn_node2edge_f32(n, 1, 2, 3, P(0)) == -1                     # the bias is a device pointer
     # backward blocks validate on the host as well
-    d = (_lib.GemmDesc * 1)(_lib.GemmDesc(16, 16, 16, 0, 0, 0, 0, 4, 4, 4, 4, 4, 3, 0, 0, 0, 1.0, 0.0))
+    d = (_lib.GemmDesc * 1)(_lib.GemmDesc(A=16, B=16, C=16, M=4, N=4, K=4, lda=4, ldb=4, ldc=3, alpha=1.0))
     assert lib.gn_gemm_grouped_f32(d, 1, P(0)) == -2                        # ldc < N
     d[0].ldc, d[0].colsum = 4, 16
     assert lib.gn_gemm_grouped_f32(d, 1, P(0)) == -2                        # colsum needs GN_GEMM_TRANS_A
@@ -70,10 +81,44 @@ def test_null_and_shape_errors_do_not_launch():
     assert lib.gn_node2edge_bwd_f32(P(16), P(16), P(0), P(16), P(16), P(16), P(16), P(16), P(16), P(16), 2, 3, 8, 0,
                                     P(0)) == -2                             # pairwise: E == N*N
     assert lib.gn_gumbel_bwd_f32(P(16), P(16), P(16), P(0), P(16), 7, 6, 32, 0.5, 3, P(0)) == -2   # rows % pairs
-    e = (_lib.EdgeGroup * 1)(_lib.EdgeGroup(16, 0, 16, 16, 16, 16, 0, 10, 16))
+    e = (_lib.EdgeGroup * 1)(_lib.EdgeGroup(edges=16, W=16, bias=16, edge_feat=16, dist=16, rows=10, K=16))
     assert lib.gn_edge_mlp_gumbel_f32(e, 1, 0.5, 0, P(0), P(0)) == -2       # K > 15
     e[0].K = 10
     assert lib.gn_edge_mlp_gumbel_f32(e, 1, 0.0, 0, P(0), P(0)) == -2       # tau must be > 0
+
+
+def test_descriptor_mirrors_match_the_header(tmp_path):
+    """Every ctypes.Structure of `_lib` mirrors the header struct its `c_name` names: the same field names in the same
+    order (C's `def` is `def_`), and the offsets, sizes and total size a C compiler gives them.  Every header struct has
+    a mirror, and a misspelt field name in a keyword construction raises instead of leaving the real field at 0."""
+    from groupnet_amd import _lib
+    mirrors = [c for c in vars(_lib).values()
+               if isinstance(c, type) and issubclass(c, ctypes.Structure) and c.__module__ == _lib.__name__]
+    structs = declared_structs()
+    for cls in mirrors:
+        assert "c_name" in vars(cls) and vars(cls).get("__slots__") == (), cls.__name__
+    assert sorted(c.c_name for c in mirrors) == sorted(structs)
+    c_field = lambda n: "def" if n == "def_" else n
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "groupnet_hip.h"', "int main(void) {"]
+    for cls in mirrors:
+        t = cls.c_name
+        assert [c_field(n) for n, _ in cls._fields_] == structs[t], t
+        lines.append(f'  printf("{t} %zu\\n", sizeof({t}));')
+        lines += [f'  printf("{t}.{f} %zu %zu\\n", offsetof({t}, {f}), sizeof((({t}*)0)->{f}));' for f in structs[t]]
+    (tmp_path / "layout.c").write_text("\n".join(lines + ["  return 0;", "}"]) + "\n")
+    exe = str(tmp_path / "layout")
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.dirname(HEADER), "-o", exe,
+                    str(tmp_path / "layout.c")], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
+    got = dict(line.split(" ", 1) for line in out.splitlines())
+    for cls in mirrors:
+        assert got[cls.c_name] == str(ctypes.sizeof(cls)), cls.c_name
+        for n, _ in cls._fields_:
+            assert got[f"{cls.c_name}.{c_field(n)}"] == f"{getattr(cls, n).offset} {getattr(cls, n).size}", (cls.c_name, n)
+        with pytest.raises(AttributeError):
+            cls(no_such_field=1)
+    with pytest.raises(AttributeError):
+        _lib.AggGroup(WH=16)
 
 
 def test_state_dict_layout_matches_reference_checkpoints():

@@ -243,24 +243,6 @@ def test_topk_large_n_banded():
         assert torch.equal(H.cpu(), O.topk_incidence(cc, s))
 
 
-def test_mlp2_shapes_and_pack():
-    from groupnet_amd import MLP, ops
-    torch.manual_seed(3)
-    for din, dh, dout, rows in [(128, 128, 64, 300), (64, 256, 64, 33), (128, 128, 1024, 70), (64, 128, 10, 129),
-                                (128, 256, 7, 1)]:
-        m = MLP(din, dout, hidden_size=(dh,))
-        x = torch.randn(rows, din)
-        l0, l1 = m.layers
-        with torch.no_grad():      # plain torch fp32 layer math on the CPU as the reference of this op
-            y_ref = torch.nn.functional.linear(torch.relu(torch.nn.functional.linear(x, l0.weight, l0.bias)),
-                                               l1.weight, l1.bias)
-        pk = dict(W=ops.pack_stream([l0.weight.detach().to(dev()), l1.weight.detach().to(dev())]),
-                  bias=ops.bias_stream([l0.bias.detach().to(dev()), l1.bias.detach().to(dev())]),
-                  din=din, dh=dh, dout=dout)
-        y = ops.mlp2(x.to(dev()), pk)
-        assert maxerr(y, y_ref) <= TOL, (din, dh, dout, rows)
-
-
 def test_philox_matches_oracle_bit_exact():
     from groupnet_amd import ops
     for n, seed, off in [(4, 0, 0), (1000, 12345, 0), (777, 2**40 + 17, 3), (10, 5, 2**33 + 1)]:
@@ -798,82 +780,6 @@ def test_hyper_module_with_listall_builder():
         ops.listall_incidence(corr.to(dev()), 12)
 
 
-def test_pack_plan_equals_matrix_by_matrix_packing():
-    """The one-launch refresh of a module's packed weights (`ops.PackPlan`, gn_pack_segments_f32) writes
-    bit for bit what packing matrix by matrix (gn_pack_linear_f32 + concatenation) produces — for the node,
-    edge, typed-aggregation and closing MLP streams and every source of their bf16-core images (the layers' packed
-    tiles in `ops.pipeline_order`, a ragged closing MLP included) — and follows in-place parameter updates."""
-    import groupnet_amd as G
-    from groupnet_amd import ops
-    torch.manual_seed(17)
-    pair, hyper = build_modules(2)
-    ragged = G.MLP(128, 40, hidden_size=(128,)).to(dev())
-
-    def pipeline(first, second):
-        """Both layers packed matrix by matrix, re-ordered into A_t (rows of hidden tile t) / B_t (its columns)."""
-        HT = (first.shape[0] + 31) // 32
-        a = ops.pack_linear(first.detach().contiguous()).view(HT, -1)
-        b = ops.pack_linear(second.detach().contiguous()).view(-1, HT, 1024)
-        return torch.cat([a[t] if kind == "A" else b[:, t].reshape(-1) for kind, t in ops.pipeline_order(HT)])
-
-    for m in (pair.to(dev()), hyper.to(dev())):
-        K = m.edge_types
-        for rnd in range(2):
-            s0, s1 = m.node2edge_start_mlp[1].layers
-            a0, a1 = m.attention_mlp[1].layers
-            pk = m._packed_n2e(1)
-            Wpq = torch.cat((a0.weight[:, :64], a0.weight[:, 64:]), 0).detach().contiguous()
-            bpq = torch.cat((a0.bias, torch.zeros_like(a0.bias)), 0).detach()
-            assert torch.equal(pk["W"], ops.pack_stream([s0.weight, s1.weight, Wpq]))
-            assert torch.equal(pk["bias"], ops.bias_stream([s0.bias, s1.bias, bpq]))
-            assert set(pk["xi"].src) == {"chain"}
-            assert torch.equal(pk["xi"].src["chain"], torch.cat((pipeline(s0.weight, s1.weight), ops.pack_linear(Wpq))))
-            st = m.nmp_mlps[1]
-            i0, i1 = st.init_MLP.layers
-            d0, d1 = st.MLP_distribution.layers
-            f0, f1 = st.MLP_factor.layers
-            Wd1 = torch.zeros(32, 256, device=dev())
-            Wd1[:K, :128] = d1.weight.detach()
-            Wd1[K, 128:] = f1.weight.detach()[0]
-            bd1 = torch.zeros(32, device=dev())
-            bd1[:K] = d1.bias.detach()
-            bd1[K] = f1.bias.detach()[0]
-            pk = st._packed()
-            assert torch.equal(pk["W"], ops.edge_stream(i0.weight, i1.weight, torch.cat((d0.weight, f0.weight), 0).detach(), Wd1))
-            assert torch.equal(pk["bias"], ops.bias_stream([i0.bias, i1.bias, torch.cat((d0.bias, f0.bias), 0), bd1]))
-            assert set(pk["xi"].src) == {"edge"}
-            assert torch.equal(pk["xi"].src["edge"], torch.cat((pipeline(i0.weight, i1.weight),
-                                                                pipeline(torch.cat((d0.weight, f0.weight), 0), Wd1))))
-            agg = m.edge_aggregation_list[0]
-            l0 = [x.layers[0] for x in agg.agg_mlp]
-            l1 = [x.layers[1] for x in agg.agg_mlp]
-            pk = agg._packed()
-            assert torch.equal(pk["W"], ops.pack_stream([w for a, b in zip(l0, l1) for w in (a.weight, b.weight)]))
-            assert torch.equal(pk["b1"], torch.stack([l.bias.detach() for l in l0]))
-            assert torch.equal(pk["b2"], torch.stack([l.bias.detach() for l in l1]))
-            assert torch.equal(pk["W1cat"], ops.pack_linear(torch.cat([l.weight.detach() for l in l0], 0).contiguous()))
-            assert torch.equal(pk["b1half"], torch.cat([l.bias.detach() for l in l0]) * 0.5)
-            w2t = [ops.pack_linear(l.weight.detach().contiguous()).view(2, 4, 4, 256).permute(1, 0, 2, 3).reshape(-1) for l in l1]
-            assert torch.equal(pk["W2t"], torch.cat(w2t))
-            assert set(pk["xi"].src) == {"W2t", "W12", "W1cat"}
-            assert torch.equal(pk["xi"].src["W2t"], torch.cat(w2t))
-            assert torch.equal(pk["xi"].src["W1cat"], pk["W1cat"])
-            assert torch.equal(pk["xi"].src["W12"], torch.cat([pipeline(a.weight, b.weight) for a, b in zip(l0, l1)]))
-            e0, e1 = m.nmp_mlp_end.layers
-            pk = m._packed_mlp2(m.nmp_mlp_end)
-            assert torch.equal(pk["W"], ops.pack_stream([e0.weight, e1.weight]))
-            assert torch.equal(pk["bias"], ops.bias_stream([e0.bias, e1.bias]))
-            assert set(pk["xi"].src) == {"mlp2"}
-            assert torch.equal(pk["xi"].src["mlp2"], pipeline(e0.weight, e1.weight))
-            r0, r1 = ragged.layers
-            pk = m._packed_mlp2(ragged)
-            assert torch.equal(pk["W"], ops.pack_stream([r0.weight, r1.weight]))
-            assert torch.equal(pk["xi"].src["mlp2"], pipeline(r0.weight, r1.weight))
-            with torch.no_grad():          # in-place update (an optimizer step): the next access re-packs
-                for p in list(m.parameters()) + list(ragged.parameters()):
-                    p.add_(torch.randn_like(p) * 0.1)
-
-
 def test_mlp_standalone_on_the_hip_gemm():
     """`MLP.forward` on its own (model/MS_HGNN_batch.py:220-229: Linear, activation between layers, optional
     final sigmoid) against plain torch fp32 layer math on the same device, forward and gradients; odd widths
@@ -1322,27 +1228,6 @@ def test_f16x3_flagged_weight_image_falls_back():
     assert maxerr(fast[0], nf_p.numpy()) <= 2e-5 * max(1.0, float(nf_p.abs().max()))
     assert maxerr(fast[2], nf_h.numpy()) <= 2e-5 * max(1.0, float(nf_h.abs().max()))
     assert maxerr(fast[1], fac_p.numpy()) <= 1e-4 and maxerr(fast[3], fac_h.numpy()) <= 1e-4
-
-
-def test_split_fp16_image_layout_and_flag():
-    """gn_split_bf16_f32 with parts = 2: hi + lo reproduces every weight to 2^-22 relative (2^-25 absolute below the
-    fp16 normal range), pieces in the (sub-step, part, lane, j) order of the bf16 images, flag word zero unless a
-    weight exceeds the fp16 range."""
-    from groupnet_amd import ops
-    torch.manual_seed(5)
-    packed = (torch.randn(6 * 1024, device=dev()) * torch.logspace(-6, 2, 6 * 1024, device=dev())).contiguous()
-    img = ops.split_bf16(packed, parts=2)
-    n = 6 * 2 * 2 * 64 * 8
-    assert img.numel() == n + 8 and int(img[n:].abs().sum()) == 0
-    parts = img[:n].view(torch.float16).view(6, 2, 2, 64, 8).float()          # (tile, half, part, lane, j)
-    ref = ops.split_bf16(packed, parts=3).view(torch.bfloat16).view(6, 2, 3, 64, 8).float().sum(2)   # same element order
-    got = parts.sum(2)
-    err = (got - ref).abs()
-    assert float((err / ref.abs().clamp_min(2.0 ** -3)).max()) <= 2.0 ** -21
-    bad = packed.clone()
-    bad[100] = 7.0e4
-    img2 = ops.split_bf16(bad, parts=2)
-    assert int(img2[n:].view(torch.int32)[0]) != 0
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
