@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must be imported before the .so is loaded)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GROUPNET_HIP_LIB") or os.path.join(_HERE, "libgroupnet_hip.so")  # env: tuning builds
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 GN_OK = 0
 GN_ERR_K_RANGE = -3
@@ -156,10 +156,13 @@ SIGNATURES = {
     "gn_node_mlp_affinity_f32": (_I, [ctypes.POINTER(NodeGroup), _I, _I, ctypes.POINTER(AffinityJob), _P]),
     "gn_node_mlp_affinity_bf16": (_I, [ctypes.POINTER(NodeGroup), _I, _I, ctypes.POINTER(AffinityJob), _P]),
     "gn_affinity_tail_lds_limit": (_SZ, []),
+    "gn_node_mlp_affinity_launch_info_f32": (_I, [ctypes.POINTER(NodeGroup), _I, _I, ctypes.POINTER(AffinityJob),
+                                                  ctypes.POINTER(_SZ), ctypes.POINTER(_I)]),
     "gn_node2edge_f32": (_I, [ctypes.POINTER(N2EGroup), _I, _I, _I, _P]),
     "gn_node2edge_bf16": (_I, [ctypes.POINTER(N2EGroup), _I, _I, _I, _P]),
     "gn_edge_mlp_gumbel_f32": (_I, [ctypes.POINTER(EdgeGroup), _I, _F, _U64, _P, _P]),
     "gn_edge_mlp_gumbel_bf16": (_I, [ctypes.POINTER(EdgeGroup), _I, _F, _U64, _P, _P]),
+    "gn_edge_mlp_gumbel_launch_info_f32": (_I, [ctypes.POINTER(EdgeGroup), _I, ctypes.POINTER(_SZ), ctypes.POINTER(_I)]),
     "gn_agg_gather_f32": (_I, [ctypes.POINTER(GatherGroup), _I, _I, _I, _P]),
     "gn_agg_gather_bf16": (_I, [ctypes.POINTER(GatherGroup), _I, _I, _I, _P]),
     "gn_agg_mlp_f32": (_I, [ctypes.POINTER(AggGroup), _I, _P]),

@@ -27,6 +27,12 @@ static inline int gn_check_launch() { return hipGetLastError() == hipSuccess ? G
 
 // Wave-uniform value → SGPR, so that addresses derived from it use the scalar path.
 __device__ __forceinline__ int gn_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// *p of a wave-uniform address whose target no launch in flight writes, through the scalar cache (constant address
+// space: s_load), into SGPRs
+template <typename T>
+__device__ __forceinline__ T gn_uniform_load(const T* p) {
+  return *(const __attribute__((address_space(4))) T*)p;
+}
 
 // Reductions over the 32 lanes of one half-wave (lanes 0..31 and 32..63 separately).
 __device__ __forceinline__ float gn_half_sum(float v) {

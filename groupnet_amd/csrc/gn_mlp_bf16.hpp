@@ -47,6 +47,12 @@ namespace {
 
 // workgroups per CU the bf16-storage (P = 1) edge / aggregation kernels are compiled for
 constexpr int kOccP1 = 2;
+// ... the node stage and the edge kernel: the f16x3 instantiations (P = 2) at THREE — their hot path fits 168 registers,
+// the bf16x6 fallback body behind the range vote takes the spills — bf16x6 itself at two
+template <int P>
+constexpr int kNodeOcc = P == 2 ? 3 : 2;
+template <int P>
+constexpr int kEdgeOcc = P == 1 ? kOccP1 : (P == 2 ? 3 : 2);
 
 template <int P>
 struct Parts {
@@ -162,8 +168,10 @@ __device__ __forceinline__ void run_with_fallback(F body) {
 }
 // The flag word behind an fp16 weight image of `substeps` sub-steps (gn_split_f16_f32 sets it when a weight does not
 // fit fp16): nonzero sends the workgroup to the bf16x6 path.
+// (A scalar load: the word sits in an SGPR until the vote.  In a vector register it is live across the whole chain, and
+// at three waves per SIMD the allocator spilled exactly that register — with a full wait in the prologue.)
 __device__ __forceinline__ int image_flag(const void* image, int substeps) {
-  return *reinterpret_cast<const int*>(reinterpret_cast<const char*>(image) + (size_t)substeps * 2 * 1024);
+  return gn_uniform_load(reinterpret_cast<const int*>(reinterpret_cast<const char*>(image) + (size_t)substeps * 2 * 1024));
 }
 // the image a group's chain walks with P parts (f16x3: `h`, bf16x6 / twins: `x`)
 template <int P>
@@ -365,7 +373,7 @@ struct WStream {
 //   hid0: bias tile 0 (loaded early by the caller).
 //   PACKED_RELU (P = 1 only): the hidden layer's ReLU is applied on the packed bf16 operands (make_parts_relu);
 //   `post` then must not apply it.
-template <int P, int IT, int OT, int HT, bool PACKED_RELU = false, typename Stream, typename PostFn>
+template <int P, int IT, int OT, int HT, bool PACKED_RELU = false, bool LATE_BIAS = false, typename Stream, typename PostFn>
 __device__ __forceinline__ void layer_pair(Stream& ws, int c0, int s0, const Parts<P> (&xi)[IT][2],
                                            const f32x16& hid0, const float* __restrict__ b0, int h,
                                            f32x16 (&out)[OT], ovf_t& ovf, PostFn post) {
@@ -388,7 +396,7 @@ __device__ __forceinline__ void layer_pair(Stream& ws, int c0, int s0, const Par
     f32x16 cur = hidn;
     if (t + 1 < HT) {
       hidn = bias_n;
-      if (t + 2 < HT) bias_n = load_bias_tile(b0 + 32 * (t + 2), h);
+      if (!LATE_BIAS && t + 2 < HT) bias_n = load_bias_tile(b0 + 32 * (t + 2), h);
     }
     post(t, cur);
     Parts<P> xh[2];
@@ -414,6 +422,7 @@ __device__ __forceinline__ void layer_pair(Stream& ws, int c0, int s0, const Par
       }
     }
     __builtin_amdgcn_sched_barrier(0);
+    if (LATE_BIAS && t + 2 < HT) bias_n = load_bias_tile(b0 + 32 * (t + 2), h);
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
       ws.step(c0, pos, xh[u & 1], out[u >> 1]);
@@ -541,7 +550,7 @@ template <int P>
 constexpr int kRingF4For = WStream<P == 2 ? 3 : P>::kRingF4;
 
 template <int P, typename T>
-__global__ __launch_bounds__(256, 2) void node_stage_kernel(NodeTable Tb) {
+__global__ __launch_bounds__(256, kNodeOcc<P>) void node_stage_kernel(NodeTable Tb) {
   __shared__ f32x4 wring[kRingF4For<P>];
   if (Tb.aff_scenes > 0 && (int)blockIdx.x >= Tb.node_grid) {       // (block-uniform)
     extern __shared__ __align__(16) float aff_lds[];
@@ -560,7 +569,10 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
                                             const unsigned long long* __restrict__ offset_dev, int pool_bytes,
                                             f32x4* wring, ovf_t& ovf) {
   using WS = WStream<P>;
-  extern __shared__ __align__(16) unsigned char pool_dyn[];      // staged x' / pq rows of the pairwise pooling
+  // The staged x' / pq rows of the fused pooling live in the SAME LDS region as the weight ring: the pooling is over
+  // before ws.begin() writes the ring's first chunks (one workgroup barrier in between), so only the part of a stage that
+  // exceeds the ring costs LDS of its own (pool_bytes = ring + that part; the launcher sizes the region).
+  unsigned char* pool_dyn = reinterpret_cast<unsigned char*>(wring);
   const int lwg = gn_uniform(gn_xcd_logical(Tb.xs, blockIdx.x));
   if (lwg < 0) return;
   const int gi = find_group(Tb, lwg);
@@ -584,6 +596,7 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
       else if ((size_t)hyper_stage_nodes(128, G.pool_E, G.pool_N) * PoolStage<T>::kPitch * sizeof(T) <= (size_t)pool_bytes) {
         pooled_rows_hyper_staged<T, 1>(G, r0, min(rows - 1, r0 + 127), {rb.row_ld}, h, reinterpret_cast<T*>(pool_dyn),
                                        [&](auto, f32x16 (&p)[2]) { in[0] = p[0], in[1] = p[1]; });
+        __syncthreads();                          // last read of the stage | first write of the ring (ws.begin)
       } else
         pooled_rows_hyper<T>(G, rb.row_ld, h, in);
     } else if (nodes_max > 0 && pool_bytes >= 0 && PoolStage<T>::bytes(nodes_max) <= (size_t)pool_bytes) {   // (block-uniform)
@@ -592,25 +605,13 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
       const int node0 = pool_stage_fill<T>(G, r0, min(rows - 1, r0 + 127), s_xp, s_pq);
       __syncthreads();
       pooled_rows_staged<T>(G, rb.row_ld, h, s_xp, s_pq, node0, in);
+      __syncthreads();                            // (as above)
     } else {
       pooled_rows<T>(G, rb.row_ld, h, in);
     }
   }
-  // ordered edge rows whose uniforms this row consumes: itself, or — symmetric pairwise form — the two ordered
-  // edges (i,j) and (j,i) of its unordered pair
-  long long o1 = rb.row_ld, o2 = rb.row_ld;
-  bool diag = true;
-  if (G.sym_N > 0) {
-    const int N = G.sym_N, Pn = gn_pair_count(N);
-    const int b = rb.row_ld / Pn, p = rb.row_ld - b * Pn;
-    int i, j;
-    gn_pair_decode(p, N, i, j);
-    o1 = (long long)b * N * N + i * N + j;
-    o2 = (long long)b * N * N + j * N + i;
-    diag = i == j;
-  }
   float u1[8], u2[8];
-  const unsigned long long pbase = G.philox_offset + (offset_dev ? *offset_dev : 0ull);
+  const unsigned long long pbase = G.philox_offset + (offset_dev ? gn_uniform_load(offset_dev) : 0ull);   // (SGPRs)
   const float* bi0 = G.bias;
   const float* bi1 = G.bias + 128;
   const float* bd0 = G.bias + 192;
@@ -625,13 +626,19 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
   Parts<P> xi[2][2];
   make_parts_tiles<P, 2>(in, xi, ovf);
   // ---- pair A: 64 -> 128 -> 64, 4 hidden tiles x (4 + 4) sub-steps, pipeline order ----
-  layer_pair<P, 2, 2, 4, P == 1>(ws, 0, 0, xi, hidA0, bi0, h, z, ovf, [&](int t, f32x16& hid) {
+  layer_pair<P, 2, 2, 4, P == 1, P == 2>(ws, 0, 0, xi, hidA0, bi0, h, z, ovf, [&](int t, f32x16& hid) {
     if constexpr (P != 1) {
       relu16(hid);
-      if (G.keep_z1 != nullptr && rb.live) store_tile(G.keep_z1 + (size_t)rb.row * 128 + 32 * t + 4 * h, hid);
+      if (G.keep_z1 != nullptr) {
+        const RowBlock rk = row_block_again(rows, blk);
+        if (rk.live) store_tile(G.keep_z1 + (size_t)rk.row * 128 + 32 * t + 4 * h, hid);
+      }
     }
   });
-  if (G.keep_z != nullptr) store_rows<2>(G.keep_z, GN_FEAT, rb.row, h, rb.live, z);
+  if (G.keep_z != nullptr) {
+    const RowBlock rk = row_block_again(rows, blk);
+    store_rows<2>(G.keep_z, GN_FEAT, rk.row, h, rk.live, z);
+  }
   // (the bias tiles of pair B are requested here, not at the top: held across pair A they cost 32 registers — and scratch)
   const f32x16 hidB0 = load_bias_tile(bd0, h);
   f32x16 lgv[1];
@@ -641,14 +648,32 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
   layer_pair<P, 2, 1, 8, P == 1>(ws, 0, 32, xi, hidB0, bd0, h, lgv, ovf, [&](int t, f32x16& hid) {
     if constexpr (P != 1) {
       relu16(hid);
-      if (G.keep_dh1 != nullptr && rb.live) store_tile(G.keep_dh1 + (size_t)rb.row * 256 + 32 * t + 4 * h, hid);
+      if (G.keep_dh1 != nullptr) {
+        const RowBlock rk = row_block_again(rows, blk);
+        if (rk.live) store_tile(G.keep_dh1 + (size_t)rk.row * 256 + 32 * t + 4 * h, hid);
+      }
     }
   });
   lg = lgv[0];
+  // (the row block afresh: of the first one nothing but `h` is live across the two chains)
+  const RowBlock re = row_block_again(rows, blk);
+  // ordered edge rows whose uniforms this row consumes: itself, or — symmetric pairwise form — the two ordered
+  // edges (i,j) and (j,i) of its unordered pair (worked out behind the chains: nothing of it is live across them)
+  long long o1 = re.row_ld, o2 = re.row_ld;
+  bool diag = true;
+  if (G.sym_N > 0) {
+    const int N = G.sym_N, Pn = gn_pair_count(N);
+    const int b = re.row_ld / Pn, p = re.row_ld - b * Pn;
+    int i, j;
+    gn_pair_decode(p, N, i, j);
+    o1 = (long long)b * N * N + i * N + j;
+    o2 = (long long)b * N * N + j * N + i;
+    diag = i == j;
+  }
   // uniforms: read from U or generated from the Philox stream — after the chains (nothing is in flight any more)
   fetch_uniforms(G.U, pbase, seed, o1, K, h, u1);
   if (G.sym_N > 0) fetch_uniforms(G.U, pbase, seed, o2, K, h, u2);
-  if (G.keep_lgf != nullptr && rb.live) store_tile(G.keep_lgf + (size_t)rb.row * 32 + 4 * h, lg);
+  if (G.keep_lgf != nullptr && re.live) store_tile(G.keep_lgf + (size_t)re.row * 32 + 4 * h, lg);
 
   // Epilogue.  Features 0..K-1 of `lg` are the logits of this lane's row, feature K the factor pre-activation; a
   // row's features are split over its two lanes (j, h=0) and (j, h=1).
@@ -661,11 +686,11 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
   float d1[8], d2[8];
   gumbel_softmax_row<P == 1>(lg, u1, K, tau, h, d1);
   if (G.sym_N > 0) gumbel_softmax_row<P == 1>(lg, u2, K, tau, h, d2);
-  if (rb.live) {
-    float* frow = G.edge_feat + (size_t)rb.row * K;
+  if (re.live) {
+    float* frow = G.edge_feat + (size_t)re.row * K;
     T* dist = reinterpret_cast<T*>(G.dist);
     if (G.sym_N == 0) {
-      T* drow = dist + (size_t)rb.row * K;
+      T* drow = dist + (size_t)re.row * K;
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
         const int f = feat_of(r, h);
@@ -690,11 +715,14 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
     }
   }
 }
+// The launch's dynamic LDS is ONE region of at least kRingF4For<P> f32x4 (a static ring and a dynamic stage would not be
+// guaranteed adjacent): first the pool stage, then the weight ring (edge_x_body).
 template <int P, typename T>
-__global__ __launch_bounds__(256, P == 1 ? kOccP1 : 2) void edge_x_kernel(GroupTable<gn_edge_group_t> Tb, float tau,
+__global__ __launch_bounds__(256, kEdgeOcc<P>) void edge_x_kernel(GroupTable<gn_edge_group_t> Tb, float tau,
                                                         unsigned long long seed,
                                                         const unsigned long long* __restrict__ offset_dev, int pool_bytes) {
-  __shared__ f32x4 wring[kRingF4For<P>];
+  extern __shared__ __align__(16) unsigned char ring_and_stage[];
+  f32x4* wring = reinterpret_cast<f32x4*>(ring_and_stage);
   run_with_fallback<P>([&](auto pc, ovf_t& ovf) {
     edge_x_body<decltype(pc)::value, T>(Tb, tau, seed, offset_dev, pool_bytes, wring, ovf);
   });

@@ -103,6 +103,20 @@ __device__ __forceinline__ RowBlock row_block(int rows, int block_index) {
   rb.row_ld = rb.live ? rb.row : rows - 1;
   return rb;
 }
+// The same row block worked out AGAIN, from an opaque copy of the work-item id: nothing lane-dependent of an earlier
+// row_block() (row, row_ld, lane, h, live: five registers) has to stay alive across the code in between — what a kernel
+// compiled for three waves per SIMD would otherwise spill around its chain.
+__device__ __forceinline__ RowBlock row_block_again(int rows, int block_index) {
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  RowBlock rb;
+  rb.lane = t & 63;
+  rb.h = rb.lane >> 5;
+  rb.row = block_index * 32 + (rb.lane & 31);
+  rb.live = rb.row < rows;
+  rb.row_ld = rb.live ? rb.row : rows - 1;
+  return rb;
+}
 __device__ __forceinline__ int wave_id() { return gn_uniform((int)(threadIdx.x >> 6)); }
 
 // ---- group tables (kernel arguments, by value) -------------------------------------------------

@@ -874,13 +874,27 @@ static int x_mode(const G* groups, int n, F has) {
   return cnt == 0 ? 0 : (cnt == n ? 1 : -1);
 }
 
+// A launcher asked for its launch's resources instead of the launch (gn_*_launch_info_f32): the dynamic LDS it would pass
+// and the workgroups per CU the runtime grants the kernel with it.
+struct LaunchQuery {
+  size_t* dyn_lds;
+  int* wgs_per_cu;
+  template <typename K>
+  int fill(K kernel, size_t lds) const {
+    *dyn_lds = lds;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(wgs_per_cu, reinterpret_cast<const void*>(kernel), 256, lds) == hipSuccess
+               ? GN_OK
+               : GN_ERR_LAUNCH;
+  }
+};
+
 // ---- node stage ----------------------------------------------------------------------------------------------
 // largest LDS a scene of the fused affinity tail may ask for: beside the node stage's 36 KiB weight ring two workgroups
-// per CU must still fit
+// per CU must still fit (the f16x3 kernel keeps its three up to 17 408 bytes: N = 11, D = 64 asks for 3 968)
 constexpr size_t kAffTailLds = 24 * 1024;
 template <int P, typename T>
 static int node_stage_launch(const gn_node_group_t* groups, int n_groups, int rows, hipStream_t s,
-                             const gn_affinity_job_t* job = nullptr) {
+                             const gn_affinity_job_t* job = nullptr, LaunchQuery* query = nullptr) {
   NodeTable Tb{};
   Tb.n = n_groups;
   Tb.rows = rows;
@@ -937,6 +951,7 @@ static int node_stage_launch(const gn_node_group_t* groups, int n_groups, int ro
     Tb.aff_f = job->f;
     Tb.aff_corr = job->corr;
   }
+  if (query != nullptr) return query->fill(node_stage_kernel<P, T>, aff_lds);
   hipLaunchKernelGGL((node_stage_kernel<P, T>), dim3(node_grid + Tb.aff_scenes), dim3(256), aff_lds, s, Tb);
   return gn_check_launch();
 }
@@ -995,6 +1010,18 @@ extern "C" int gn_node_mlp_affinity_bf16(const gn_node_group_t* groups, int n_gr
   return node_stage_launch<1, __bf16>(groups, n_groups, rows, (hipStream_t)stream, job);
 }
 extern "C" size_t gn_affinity_tail_lds_limit(void) { return kAffTailLds; }
+extern "C" int gn_node_mlp_affinity_launch_info_f32(const gn_node_group_t* groups, int n_groups, int rows,
+                                                    const gn_affinity_job_t* job, size_t* dyn_lds, int* wgs_per_cu) {
+  GN_CHECK(check_groups(groups, n_groups));
+  if (dyn_lds == nullptr || wgs_per_cu == nullptr) return GN_ERR_NULL;
+  if (rows <= 0 || job == nullptr) return GN_ERR_SHAPE;
+  if (x_mode(groups, n_groups, [](const gn_node_group_t& G) { return G.Wx != nullptr; }) != 1) return GN_ERR_SHAPE;
+  const int hm = x_mode(groups, n_groups, [](const gn_node_group_t& G) { return G.Wh != nullptr; });
+  if (hm < 0) return GN_ERR_SHAPE;
+  LaunchQuery q{dyn_lds, wgs_per_cu};
+  return hm ? node_stage_launch<2, float>(groups, n_groups, rows, nullptr, job, &q)
+            : node_stage_launch<3, float>(groups, n_groups, rows, nullptr, job, &q);
+}
 
 // Row-block pairs from which the bf16-storage edge / aggregation launches run two row blocks per wave (the chip must
 // still be filled: >= 2048 waves).  GN_RB2_MIN_PAIRS is a TEST knob: the parity suite lowers it so that the launcher's
@@ -1009,13 +1036,16 @@ static long long rb2_min_pairs() {
 
 // ---- edge MLP --------------------------------------------------------------------------------------------------
 constexpr size_t kEdgeCuLds = 160 * 1024;      // LDS per CU (gfx950)
+constexpr size_t kLdsGranule = 1280;           // ... is allocated to a workgroup in granules of 320 dwords
+template <int P>
+constexpr size_t kEdgeRing = kRingF4For<P> * sizeof(f32x4);   // weight ring of edge_x_kernel<P> (head of its dynamic LDS)
 template <typename K>
 static size_t static_lds_of(K kernel) {
   hipFuncAttributes a{};
   return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel)) == hipSuccess ? a.sharedSizeBytes : kEdgeCuLds / 2;
 }
 static int edge_launch(const gn_edge_group_t* groups, int n_groups, float tau, unsigned long long seed,
-                       const unsigned long long* offset_dev, hipStream_t stream, bool twin) {
+                       const unsigned long long* offset_dev, hipStream_t stream, bool twin, const LaunchQuery* query = nullptr) {
   GN_CHECK(check_groups(groups, n_groups));
   if (!(tau > 0.f)) return GN_ERR_SHAPE;
   const int xm = x_mode(groups, n_groups, [](const gn_edge_group_t& G) { return G.Wx != nullptr; });
@@ -1053,15 +1083,19 @@ static int edge_launch(const gn_edge_group_t* groups, int n_groups, float tau, u
     wg += row_grid(G.rows);
   }
   T.first_wg[n_groups] = wg;
-  // LDS for the staged node rows of the fused pooling: the largest stage any group wants, as long as the launch keeps two
-  // workgroups per CU (160 KiB of LDS less the kernel's static weight ring; edge_x_kernel<2, float>: 44 800 bytes).  A
-  // group that would need more pools straight from global memory.  GN_POOL_STAGE = 0 switches the stage off (pool_bytes
-  // = -1: every group in the per-member reference form).
+  // LDS for the staged node rows of the fused pooling: the largest stage any group wants, as long as the launch keeps the
+  // `occ` workgroups per CU its kernel is compiled for (a workgroup's share of the CU's LDS, in whole allocation granules,
+  // less the kernel's static LDS).  edge_x_kernel stages into the region of its weight ring (`ring` bytes, part of the
+  // dynamic LDS: the stage capacity is the ring plus what the largest stage needs beyond it; f16x3 at three workgroups per
+  // CU: 53 504 bytes); edge_rb2_kernel keeps a static ring and a stage of its own (ring = 0).  A group that would need
+  // more pools straight from global memory.  GN_POOL_STAGE = 0 switches the stage off (pool_bytes = -1: every group in the
+  // per-member reference form).
   const bool no_pool_stage = getenv("GN_POOL_STAGE") != nullptr && atoi(getenv("GN_POOL_STAGE")) == 0;   // (per call: tests toggle it)
-  auto pool_bytes_for = [&](int wg_rows, size_t static_lds) -> int {
+  auto pool_bytes_for = [&](int wg_rows, size_t static_lds, int occ, size_t ring) -> int {
     if (no_pool_stage) return -1;
-    const size_t cap = kEdgeCuLds / 2 - min(static_lds, kEdgeCuLds / 2);
-    size_t need = 0;
+    const size_t share = kEdgeCuLds / occ / kLdsGranule * kLdsGranule;
+    const size_t cap = min(share - min(static_lds, share), (size_t)64 * 1024);   // (dynamic LDS of a launch: at most 64 KiB)
+    size_t need = ring;
     for (int g = 0; g < n_groups; ++g) {
       const gn_edge_group_t& G = groups[g];
       if (G.edges != nullptr || (G.pool_H == nullptr && G.sym_N <= 0)) continue;
@@ -1072,7 +1106,7 @@ static int edge_launch(const gn_edge_group_t* groups, int n_groups, float tau, u
     }
     return (int)need;
   };
-  auto launch_lds = [](int pb) { return (size_t)(pb > 0 ? pb : 0); };
+  auto launch_lds = [](int pb, size_t ring) { return pb > 0 ? (size_t)pb : ring; };
   // edge_x_kernel: hyper groups without a stage get one workgroup per 32-row block (hyper_unstaged)
   auto sparse_grid = [&](int pb, size_t row_bytes) {
     int w = 0;
@@ -1096,29 +1130,31 @@ static int edge_launch(const gn_edge_group_t* groups, int n_groups, float tau, u
       }
       T.first_wg[n_groups] = wg;
       static const size_t rb2_static = static_lds_of(edge_rb2_kernel<__bf16>);
-      const int pb = pool_bytes_for(256, rb2_static);
-      hipLaunchKernelGGL((edge_rb2_kernel<__bf16>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb), stream, T, tau, seed,
+      const int pb = pool_bytes_for(256, rb2_static, 2, 0);
+      hipLaunchKernelGGL((edge_rb2_kernel<__bf16>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb, 0), stream, T, tau, seed,
                          offset_dev, pb);
       return gn_check_launch();
     }
     static const size_t x1_static = static_lds_of(edge_x_kernel<1, __bf16>);
-    const int pb = pool_bytes_for(128, x1_static);
+    const int pb = pool_bytes_for(128, x1_static, kEdgeOcc<1>, kEdgeRing<1>);
     sparse_grid(pb, PoolStage<__bf16>::kPitch * sizeof(__bf16));
-    hipLaunchKernelGGL((edge_x_kernel<1, __bf16>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb), stream, T, tau, seed,
+    hipLaunchKernelGGL((edge_x_kernel<1, __bf16>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb, kEdgeRing<1>), stream, T, tau, seed,
                        offset_dev, pb);
   }
   else if (xm) {
     const int hm = x_mode(groups, n_groups, [](const gn_edge_group_t& G) { return G.Wh != nullptr; });
     if (hm < 0) return GN_ERR_SHAPE;
     static const size_t x2_static = static_lds_of(edge_x_kernel<2, float>), x3_static = static_lds_of(edge_x_kernel<3, float>);
-    const int pb = pool_bytes_for(128, hm ? x2_static : x3_static);
+    const int pb = hm ? pool_bytes_for(128, x2_static, kEdgeOcc<2>, kEdgeRing<2>) : pool_bytes_for(128, x3_static, kEdgeOcc<3>, kEdgeRing<3>);
     sparse_grid(pb, PoolStage<float>::kPitch * sizeof(float));
+    if (query != nullptr)
+      return hm ? query->fill(edge_x_kernel<2, float>, launch_lds(pb, kEdgeRing<2>)) : query->fill(edge_x_kernel<3, float>, launch_lds(pb, kEdgeRing<3>));
     if (hm)
-      hipLaunchKernelGGL((edge_x_kernel<2, float>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb), stream, T, tau, seed,
-                         offset_dev, pb);
+      hipLaunchKernelGGL((edge_x_kernel<2, float>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb, kEdgeRing<2>), stream, T, tau,
+                         seed, offset_dev, pb);
     else
-      hipLaunchKernelGGL((edge_x_kernel<3, float>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb), stream, T, tau, seed,
-                         offset_dev, pb);
+      hipLaunchKernelGGL((edge_x_kernel<3, float>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb, kEdgeRing<3>), stream, T, tau,
+                         seed, offset_dev, pb);
   }
   else
     hipLaunchKernelGGL(edge_mlp_gumbel_kernel, dim3(wg), dim3(256), 0, stream, T, tau, seed, offset_dev);
@@ -1128,6 +1164,13 @@ extern "C" int gn_edge_mlp_gumbel_f32(const gn_edge_group_t* groups, int n_group
                                       unsigned long long seed, const unsigned long long* offset_dev,
                                       gn_stream_t stream) {
   return edge_launch(groups, n_groups, tau, seed, offset_dev, (hipStream_t)stream, false);
+}
+extern "C" int gn_edge_mlp_gumbel_launch_info_f32(const gn_edge_group_t* groups, int n_groups, size_t* dyn_lds, int* wgs_per_cu) {
+  GN_CHECK(check_groups(groups, n_groups));
+  if (dyn_lds == nullptr || wgs_per_cu == nullptr) return GN_ERR_NULL;
+  if (x_mode(groups, n_groups, [](const gn_edge_group_t& G) { return G.Wx != nullptr; }) != 1) return GN_ERR_SHAPE;
+  const LaunchQuery q{dyn_lds, wgs_per_cu};
+  return edge_launch(groups, n_groups, 1.f, 0ull, nullptr, nullptr, false, &q);
 }
 extern "C" int gn_edge_mlp_gumbel_bf16(const gn_edge_group_t* groups, int n_groups, float tau,
                                        unsigned long long seed, const unsigned long long* offset_dev,

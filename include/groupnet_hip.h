@@ -231,6 +231,12 @@ int gn_node_mlp_affinity_f32(const gn_node_group_t* groups, int n_groups, int ro
 int gn_node_mlp_affinity_bf16(const gn_node_group_t* groups, int n_groups, int rows, const gn_affinity_job_t* job,
                               gn_stream_t stream);
 size_t gn_affinity_tail_lds_limit(void);
+/* Resources of a launch instead of the launch (ABI 35; a host can check the residency it budgets for, the test suite
+ * does): what gn_node_mlp_affinity_f32 would pass as dynamic LDS for these arguments (the scene tile of the affinity
+ * tail), and the workgroups per CU the HIP runtime grants the kernel with it (hipOccupancyMaxActiveBlocksPerMultiprocessor).
+ * Same argument checks as the launcher; nothing is launched. */
+int gn_node_mlp_affinity_launch_info_f32(const gn_node_group_t* groups, int n_groups, int rows, const gn_affinity_job_t* job,
+                                         size_t* dyn_lds, int* wgs_per_cu);
 
 /* ---- A3 (second half): attention-weighted node -> edge pooling ---------------------------
  * Replaces the rest of node2edge, MS_HGNN_batch.py:127-141 / 359-370:
@@ -317,6 +323,10 @@ int gn_edge_mlp_gumbel_f32(const gn_edge_group_t* groups, int n_groups, float ta
                            const unsigned long long* offset_dev, gn_stream_t stream);
 int gn_edge_mlp_gumbel_bf16(const gn_edge_group_t* groups, int n_groups, float tau, unsigned long long seed,
                             const unsigned long long* offset_dev, gn_stream_t stream);
+/* Resources of gn_edge_mlp_gumbel_f32's launch for groups with the `Wx` image (ABI 35; as
+ * gn_node_mlp_affinity_launch_info_f32): dynamic LDS = the kernel's weight ring and the pool stage of the fused pooling,
+ * which share one region (GN_POOL_STAGE is honoured). */
+int gn_edge_mlp_gumbel_launch_info_f32(const gn_edge_group_t* groups, int n_groups, size_t* dyn_lds, int* wgs_per_cu);
 
 /* ---- A5: hyperedge aggregation --------------------------------------------------------------
  * gather: eo = H ori            (edge_aggregation.forward, MS_HGNN_batch.py:263)
