@@ -4,15 +4,17 @@
 // GENERIC blocks, correctness first (train_hyper_nba.py:116 back-propagates through these modules, but
 // training throughput is not the path's headline):
 //   gn_gemm[_grouped]_f32  C = beta*C + op(A) op(B) (+ bias) (relu) (masked by another tensor's sign), many
-//                          problems per launch; LDS-staged 128x64x32 tiles on the fp32 matrix cores with
-//                          optional split-K (atomic) — used for the re-computation of hidden activations,
-//                          for input gradients dX = dY W and for weight gradients dW = dY^T X (K = rows,
-//                          split over workgroups, bias gradient as a side output);
-//   gn_typed_bwd_f32       the per-type scalings / dot products of the typed aggregation;
-//   gn_typed_scale/dot     the per-row, per-type scalings of the typed aggregation;
+//                          problems per launch; LDS-staged 128x64x32 tiles (bf16 matrix cores on three-part
+//                          splits for aligned operands, fp32 matrix cores otherwise) with optional split-K
+//                          (atomic) — used for the re-computation of hidden activations, for input gradients
+//                          dX = dY W and for weight gradients dW = dY^T X (K = rows, split over workgroups,
+//                          bias gradient as a side output);
+//   gn_axpby2d_f32         slices, scalings and sums of gradients;
+//   gn_typed_bwd_f32       the per-row, per-type scalings / dot products of the typed aggregation;
+//   gn_gumbel_ef_f32       edge_feat = sigmoid(f) * dist from its saved pieces;
 //   gn_gumbel_bwd_f32      back through fac * softmax((logits + g) / tau) and the sigmoid;
-//   gn_node2edge_bwd_f32   back through the attention-weighted pooling (one wave per hyperedge, like the
-//                          forward; node rows are shared by edges, so their gradients are atomic adds).
+//   gn_node2edge_bwd_f32   back through the attention-weighted pooling (one workgroup per scene with its rows
+//                          in LDS; beyond that one wave per hyperedge with atomic adds into the node rows).
 // Gather and scatter are each other's adjoints and reuse the forward kernels.
 #include <stdlib.h>
 

@@ -44,6 +44,19 @@ def _check(grads_hip, grads_ref, names, tol=TOL_ANY):
     return worst, where
 
 
+def _attention_layer1_errors(grads_hip, grads_ref):
+    """db2 / dw2 of the attention MLP (sums over all scenes with heavy cancellation) relative to their OWN max|ref| —
+    _check divides by at least 1 % of the model's largest gradient, which hides them.  Printed, not gated here:
+    tests/test_backward_kernels_gpu.py gates the kernel that forms them against their absolute-term sums."""
+    parts = []
+    for name, ref in grads_ref.items():
+        if "attention_mlp" in name and ".layers.1." in name and ref is not None and grads_hip.get(name) is not None:
+            own = float(ref.abs().max())
+            err = float((grads_hip[name].cpu() - ref).abs().max())
+            parts.append(f"{name} {err / own:.1e} of its own max {own:.1e}" if own > 0 else f"{name} |err| {err:.1e}, ref 0")
+    return "; ".join(parts)
+
+
 def _grad_compare(tag, module, oracle_fwd, hip_fwd, h, noise, min_used):
     """Gradients of L = <node_feat, R1> + <factors, R2> w.r.t. h and every used parameter, HIP vs torch autograd on
     the CPU oracle — on the whole batch (gate TOL_ANY) and on its clean scenes alone (gate TOL_CLEAN); prints the
@@ -54,9 +67,10 @@ def _grad_compare(tag, module, oracle_fwd, hip_fwd, h, noise, min_used):
     state0 = {k: v.detach().clone() for k, v in module.state_dict().items()}
     module.to(dev).train()
     R2 = None
+    att1 = ""
 
     def both(rows, tol):
-        nonlocal R2
+        nonlocal R2, att1
         state = {k: v.clone().requires_grad_(True) for k, v in state0.items()}
         hh = h[rows].clone().requires_grad_(True)
         nz = [u[rows].contiguous() for u in noise]
@@ -77,11 +91,13 @@ def _grad_compare(tag, module, oracle_fwd, hip_fwd, h, noise, min_used):
         assert len(used) >= min_used
         ew, where = _check({k: p.grad for k, p in module.named_parameters()}, {k: v.grad for k, v in state.items()}, used,
                            tol)
+        att1 = _attention_layer1_errors({k: p.grad for k, p in module.named_parameters()}, {k: v.grad for k, v in state.items()})
         return probe, eh, ew, where, {k: p.grad for k, p in module.named_parameters()}
 
     rows_all = torch.arange(B)
     probe, eh, ew, where, hip_grads = both(rows_all, TOL_ANY)
     clean = probe.clean()
+    print(f"\n{tag}: attention layer 1, whole batch: {att1}")
     msg = (f"\n{tag}: whole batch dL/dh {eh:.1e}, worst parameter {ew:.1e} ({where}); {int(clean.sum())}/{B} scenes clean "
            f"({probe.units} ReLU units per scene, window {WINDOW:g})")
     if bool(clean.any()) and not bool(clean.all()):
