@@ -333,7 +333,7 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     `affinity`: an `ops.AffinityTail` — the deferred affinity + top-k launch that produces Hs; it rides in the first
     node-stage launch (its tail workgroups), or is issued beside it when that launch cannot take it.
     `fuse_closing`: let the typed-aggregation launch apply the closing MLP of every stage itself where its launch shape
-    allows (`ops.closing_fusable`): one launch fewer per stage, bit-identical rows.  At B = 512, N = 11 the chain costs
+    allows (`ops.agg_mlp_closing`: the launcher's plan decides): one launch fewer per stage, bit-identical rows.  At B = 512, N = 11 the chain costs
     inside that launch what the closing launch cost on its own (single-stream forward 0.104 -> 0.103 ms, 4-stream
     throughput -2 %): the block asks for it in its latency form only."""
     n = len(mods)
@@ -432,9 +432,10 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
                 src = eos[i]
             items.append((src, edge_feats[i], pk, K))
         if (fuse_closing and closing is not None and traces is None and not twin and N <= _FUSED_SCATTER_MAX_N
-                and len({(-1 if o is None else o.stride(-2)) for _, o in closing}) == 1
-                and ops.closing_fusable(items, [pk2 for pk2, _ in closing])):
-            return _Closed(ops.agg_mlp_grouped(items, [(pk2, o, ori) for (pk2, o), ori in zip(closing, oris)]))
+                and len({(-1 if o is None else o.stride(-2)) for _, o in closing}) == 1):
+            closed = ops.agg_mlp_closing(items, [(pk2, o, ori) for (pk2, o), ori in zip(closing, oris)])
+            if closed is not None:
+                return _Closed(closed)
         feats = ops.agg_mlp_grouped(items)
 
         def node_item(it) -> bool:

@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must be imported before the .so is loaded)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GROUPNET_HIP_LIB") or os.path.join(_HERE, "libgroupnet_hip.so")  # env: tuning builds
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 GN_OK = 0
 GN_ERR_K_RANGE = -3
@@ -132,6 +132,17 @@ class GemmDesc(ctypes.Structure):
                 ("flags", _I), ("alpha", _F), ("beta", _F)]
 
 
+class LaunchPlan(ctypes.Structure):
+    """What a forward launcher would launch (gn_*_plan_*): per-group arrays in the caller's group order."""
+    __slots__ = ()
+    c_name = "gn_launch_plan_t"
+    _G = _I * 10      # GN_MAX_GROUPS
+    _fields_ = [("kernel", _I), ("precision", _I), ("variant", _I), ("tiles", _I * 3), ("grid", _I * 3), ("dyn_lds", _I),
+                ("stage_bytes", _I), ("xcd", _I), ("closing", _I), ("n_groups", _I), ("wgs", _G), ("wpr", _G), ("spw", _G),
+                ("stage", _G), ("lines", _G), ("node_form", _G), ("unstaged", _G), ("pos", _G), ("pre_grid", _G),
+                ("pre_lds", _G), ("SGh", _I), ("EBh", _I), ("G", _I), ("TE", _I)]
+
+
 GEMM_TRANS_A, GEMM_TRANS_B, GEMM_RELU, GEMM_ACCUM, GEMM_TRANS_C = 1, 2, 4, 8, 16
 MAX_GROUPS = 10
 
@@ -172,6 +183,21 @@ SIGNATURES = {
     "gn_agg_scatter_bf16": (_I, [ctypes.POINTER(ScatterGroup), _I, _I, _I, _F, _P]),
     "gn_mlp2_f32": (_I, [ctypes.POINTER(Mlp2Group), _I, _I, _I, _I, _I, _I, _I, _F, _P]),
     "gn_mlp2_bf16": (_I, [ctypes.POINTER(Mlp2Group), _I, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "gn_kernel_name": (ctypes.c_char_p, [_I]),
+    "gn_node_mlp_plan_f32": (_I, [ctypes.POINTER(NodeGroup), _I, _I, ctypes.POINTER(AffinityJob), ctypes.POINTER(LaunchPlan)]),
+    "gn_node_mlp_plan_bf16": (_I, [ctypes.POINTER(NodeGroup), _I, _I, ctypes.POINTER(AffinityJob), ctypes.POINTER(LaunchPlan)]),
+    "gn_edge_mlp_gumbel_plan_f32": (_I, [ctypes.POINTER(EdgeGroup), _I, _F, _U64, _P, ctypes.c_longlong,
+                                         ctypes.POINTER(LaunchPlan)]),
+    "gn_edge_mlp_gumbel_plan_bf16": (_I, [ctypes.POINTER(EdgeGroup), _I, _F, _U64, _P, ctypes.c_longlong,
+                                          ctypes.POINTER(LaunchPlan)]),
+    "gn_agg_mlp_plan_f32": (_I, [ctypes.POINTER(AggGroup), _I, ctypes.POINTER(LaunchPlan)]),
+    "gn_agg_mlp_plan_bf16": (_I, [ctypes.POINTER(AggGroup), _I, ctypes.POINTER(LaunchPlan)]),
+    "gn_mlp2_plan_f32": (_I, [ctypes.POINTER(Mlp2Group), _I, _I, _I, _I, _I, _I, _I, _F, ctypes.POINTER(LaunchPlan)]),
+    "gn_mlp2_plan_bf16": (_I, [ctypes.POINTER(Mlp2Group), _I, _I, _I, _I, _I, _I, _I, _F, ctypes.POINTER(LaunchPlan)]),
+    "gn_node2edge_plan_f32": (_I, [ctypes.POINTER(N2EGroup), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
+    "gn_node2edge_plan_bf16": (_I, [ctypes.POINTER(N2EGroup), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
+    "gn_agg_gather_plan_f32": (_I, [ctypes.POINTER(GatherGroup), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
+    "gn_agg_gather_plan_bf16": (_I, [ctypes.POINTER(GatherGroup), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
     "gn_gemm_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _F, _F, _P]),
     "gn_gemm_grouped_f32": (_I, [ctypes.POINTER(GemmDesc), _I, _P]),
     "gn_typed_bwd_f32": (_I, [_P, _P, _P, _I, _P, _P, _P, ctypes.c_longlong, _I, _I, _P]),

@@ -104,6 +104,41 @@ __device__ __forceinline__ float gn_philox_uniform_at(unsigned long long idx, un
   return gn_philox_to_uniform(x);
 }
 
+// ---- per-call switches -------------------------------------------------------------------------------------------
+// Every environment switch of the launchers (A/B and test knobs; -1 = unset, the launcher's own rule decides).  Read once
+// at the top of each extern "C" entry point, never cached: the parity tests toggle them inside one process.  The plan
+// functions take the struct and read no environment themselves.
+struct GnSwitches {
+  bool xcd;                  // GN_XCD = 0: plain workgroup order
+  bool pool_stage;           // GN_POOL_STAGE = 0: no LDS stage for the fused pooling / the rb2 pairwise gather
+  bool agg_lines;            // GN_AGG_LINES = 0: per-lane fused hyper gather
+  bool agg_hstage;           // GN_AGG_HSTAGE = 0: line-layout gather instead of the staged ori rows
+  bool scatter_pairs;        // GN_SCATTER_PAIRS = 0: the direct scatter kernel for the unordered pairs
+  int edge_rb2, agg_rb2;     // GN_EDGE_RB2 / GN_AGG_RB2 = 0 / 1: force the choice of the two-row-block kernels
+  int mlp2_xs;               // GN_MLP2_XS = 0 / 1: force mlp2_x_kernel / mlp2_xs_kernel
+  int n2e_rows;              // GN_N2E_ROWS = 0: never the row form, 1: whenever N <= 64
+  long long rb2_min_pairs;   // GN_RB2_MIN_PAIRS > 0: row-block pairs from which rb2 is chosen (0: the launcher's default)
+};
+static inline GnSwitches gn_read_switches() {
+  auto tri = [](const char* name) {
+    const char* e = getenv(name);
+    return e == nullptr ? -1 : (atoi(e) != 0 ? 1 : 0);
+  };
+  GnSwitches sw{};
+  sw.xcd = tri("GN_XCD") != 0;
+  sw.pool_stage = tri("GN_POOL_STAGE") != 0;
+  sw.agg_lines = tri("GN_AGG_LINES") != 0;
+  sw.agg_hstage = tri("GN_AGG_HSTAGE") != 0;
+  sw.scatter_pairs = tri("GN_SCATTER_PAIRS") != 0;
+  sw.edge_rb2 = tri("GN_EDGE_RB2");
+  sw.agg_rb2 = tri("GN_AGG_RB2");
+  sw.mlp2_xs = tri("GN_MLP2_XS");
+  sw.n2e_rows = tri("GN_N2E_ROWS");
+  const char* e = getenv("GN_RB2_MIN_PAIRS");
+  sw.rb2_min_pairs = e != nullptr && atoll(e) > 0 ? atoll(e) : 0;
+  return sw;
+}
+
 // ---- XCD-aware workgroup order ---------------------------------------------------------------------------------
 // The hardware deals the workgroups of a launch round-robin over the 8 XCDs (block p runs on the XCD of p % 8), and
 // every XCD has its own 4 MiB L2.  Every stage of the forward is a set of SECTIONS (one per module, or per module and
@@ -130,11 +165,10 @@ __device__ __forceinline__ int gn_xcd_logical(const XcdSections& S, int p) {
   }
   return -1;
 }
-// host: finish a table whose first[0..n] is filled; returns the grid size
-static inline int gn_xcd_grid(XcdSections& S) {
-  const bool off = getenv("GN_XCD") != nullptr && atoi(getenv("GN_XCD")) == 0;      // (per call: tests toggle it)
+// host: finish a table whose first[0..n] is filled; returns the grid size (`on`: GnSwitches::xcd)
+static inline int gn_xcd_grid(XcdSections& S, bool on) {
   const int total = S.first[S.n];
-  S.enabled = (!off && S.n <= GN_MAX_SECTIONS && total >= 64) ? 1 : 0;
+  S.enabled = (on && S.n <= GN_MAX_SECTIONS && total >= 64) ? 1 : 0;
   if (!S.enabled) return total;
   int worst = 0;
   for (int x = 0; x < 8; ++x) {

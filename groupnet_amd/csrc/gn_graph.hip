@@ -1049,7 +1049,27 @@ inline int capped_grid(long long work_items, int per_block, int cap = 256 * 16) 
 
 }  // namespace
 
-extern "C" int gn_abi_version(void) { return 35; }
+extern "C" int gn_abi_version(void) { return 36; }
+
+extern "C" const char* gn_kernel_name(int kernel) {
+  static const char* const names[] = {"",
+                                      "node_stage_kernel",
+                                      "node_mlp_split_kernel",
+                                      "node_mlp_kernel",
+                                      "edge_x_kernel",
+                                      "edge_rb2_kernel",
+                                      "edge_mlp_gumbel_kernel",
+                                      "agg_x_kernel",
+                                      "agg_rb2_kernel",
+                                      "agg_mlp_kernel",
+                                      "mlp2_xs_kernel",
+                                      "mlp2_x_kernel",
+                                      "mlp2_split_kernel",
+                                      "mlp2_kernel",
+                                      "node2edge_kernel",
+                                      "agg_gather_kernel"};
+  return kernel >= 0 && kernel <= GN_K_AGG_GATHER ? names[kernel] : nullptr;
+}
 
 extern "C" const char* gn_strerror(int code) {
   switch (code) {
@@ -1169,15 +1189,31 @@ extern "C" int gn_affinity_topk_bf16(const void* f, float* corr, float* const* H
                                       extras, (hipStream_t)stream);
 }
 
-template <typename TS>
-static int node2edge_launch(const gn_n2e_group_t* groups, int n_groups, int B, int N, hipStream_t s) {
+// ---- node -> edge and gather: plan, then launch (see the launch-plan comment in gn_mlp_mfma.hip) ------------------
+// pairwise groups: scenes per workgroup so that the staged rows stay <= 32 KiB; edge bands when one
+// scene alone has many more edges than a workgroup should walk
+static void n2e_pair_shape(int B, int N, int E, int& SG, int& bands) {
+  const size_t per_scene = (size_t)N * (GN_FEAT + GN_FEAT + 1) * sizeof(float);
+  SG = 1;
+  while (SG < 8 && (size_t)(2 * SG) * per_scene <= 32 * 1024 && (B + 2 * SG - 1) / (2 * SG) >= 512) SG *= 2;
+  const long long edges_per_wg = (long long)SG * E;
+  bands = 1;
+  while (bands < 64 && edges_per_wg / (bands * 2) >= 2048 && (long long)((B + SG - 1) / SG) * bands < 2048)
+    bands *= 2;
+}
+static int node2edge_plan(const gn_n2e_group_t* groups, int n_groups, int B, int N, bool twin, const GnSwitches& sw,
+                          gn_launch_plan_t& p) {
   int rc = check_groups(groups, n_groups);
   if (rc != GN_OK) return rc;
   if (B <= 0 || N <= 0) return GN_ERR_SHAPE;
-  WaveTable<gn_n2e_group_t> T{};
-  PairTable P{};
-  long long waves = 0;
-  int pair_wgs = 0;
+  p = gn_launch_plan_t{};
+  p.n_groups = n_groups;
+  p.kernel = GN_K_NODE2EDGE;
+  p.precision = twin ? 1 : 0;
+  p.grid[1] = p.grid[2] = 1;
+  const size_t per_scene = (size_t)N * (GN_FEAT + GN_FEAT + 1) * sizeof(float);
+  int nh = 0, maxE = 1, pair_wgs = 0;
+  long long hyper_rows = 0;
   size_t lds = 0;
   for (int g = 0; g < n_groups; ++g) {
     const gn_n2e_group_t& G = groups[g];
@@ -1186,41 +1222,28 @@ static int node2edge_launch(const gn_n2e_group_t* groups, int n_groups, int B, i
     if (!gn_aligned16(G.xp) || !gn_aligned16(G.pq) || !gn_aligned16(G.edges)) return GN_ERR_ALIGN;
     if (G.H == nullptr) {
       if ((long long)G.E != (G.sym ? (long long)gn_pair_count(N) : (long long)N * N)) return GN_ERR_SHAPE;
-      // pairwise groups: scenes per workgroup so that the staged rows stay <= 32 KiB; edge bands when one
-      // scene alone has many more edges than a workgroup should walk
-      const size_t per_scene = (size_t)N * (GN_FEAT + GN_FEAT + 1) * sizeof(float);
       const size_t fixed = (3 * kBlock + 32) * sizeof(float);
       if (per_scene + fixed > 158 * 1024 || N > 32767) return GN_ERR_LDS;   // one workgroup may take the CU's 160 KiB
-      int SG = 1;
-      while (SG < 8 && (size_t)(2 * SG) * per_scene <= 32 * 1024 && (B + 2 * SG - 1) / (2 * SG) >= 512) SG *= 2;
-      const long long edges_per_wg = (long long)SG * G.E;
-      int bands = 1;
-      while (bands < 64 && edges_per_wg / (bands * 2) >= 2048 && (long long)((B + SG - 1) / SG) * bands < 2048)
-        bands *= 2;
-      P.g[P.n] = G;
-      P.SG[P.n] = SG;
-      P.bands[P.n] = bands;
-      P.first_wg[P.n] = pair_wgs;
-      pair_wgs += ((B + SG - 1) / SG) * bands;
-      ++P.n;
+      int SG, bands;
+      n2e_pair_shape(B, N, G.E, SG, bands);
+      p.spw[g] = SG;
+      p.wgs[g] = ((B + SG - 1) / SG) * bands;
+      pair_wgs += p.wgs[g];
       lds = lds > (size_t)SG * per_scene + fixed ? lds : (size_t)SG * per_scene + fixed;
       continue;
     }
     if (G.sym) return GN_ERR_SHAPE;  // the symmetric form exists for the pairwise graph only
-    T.g[T.n] = G;
-    ++T.n;
+    ++nh;
+    maxE = maxE > G.E ? maxE : G.E;
+    hyper_rows += (long long)B * G.E;
   }
-  P.first_wg[P.n] = pair_wgs;
   // hyper groups: scenes per workgroup so that the staged rows stay <= 32 KiB while the grid keeps >= ~1024 workgroups
   int SGh = 1, EBh = 1;
-  if (T.n > 0) {
-    const size_t per_scene = (size_t)N * (GN_FEAT + GN_FEAT + 1) * sizeof(float);
-    while (SGh < 8 && (size_t)(2 * SGh) * per_scene <= 32 * 1024 && (long long)((B + 2 * SGh - 1) / (2 * SGh)) * T.n >= 1024)
+  if (nh > 0) {
+    while (SGh < 8 && (size_t)(2 * SGh) * per_scene <= 32 * 1024 && (long long)((B + 2 * SGh - 1) / (2 * SGh)) * nh >= 1024)
       SGh *= 2;
     // hyperedges per band: ~12 KiB of member lists (3 words per (edge, node) slot), at least 4 edges, at most the
     // most edges any group's workgroup walks
-    int maxE = 1;
-    for (int g = 0; g < T.n; ++g) maxE = maxE > T.g[g].E ? maxE : T.g[g].E;
     EBh = (int)((size_t)3072 * kN2EU / ((size_t)12 * N + 144));
     EBh = EBh < 4 ? 4 : EBh;
     if (N <= 64 && EBh > 4 * kN2EU) EBh = 4 * kN2EU;        // (the band whose H rows a workgroup can hold in registers, see the kernel)
@@ -1229,58 +1252,101 @@ static int node2edge_launch(const gn_n2e_group_t* groups, int n_groups, int B, i
     size_t stage = (size_t)SGh * per_scene;
     // N <= 64: one lane pair per hyperedge (no scratch, no barriers after the stage); scenes per workgroup so that
     // ~100 of the 128 pairs have a row, the stage stays <= 56 KiB and the grid keeps >= 1024 workgroups.
-    // GN_N2E_ROWS = 0 keeps the banded form, 1 forces this one (parity tests).
-    const char* rows_env = getenv("GN_N2E_ROWS");                 // 0: never, 1: whenever N <= 64, unset: by launch size
-    const bool no_rows = rows_env != nullptr && atoi(rows_env) == 0;
-    const bool force_rows = rows_env != nullptr && atoi(rows_env) != 0;
-    long long hyper_rows = 0;
-    for (int g = 0; g < T.n; ++g) hyper_rows += (long long)B * T.g[g].E;
+    // GN_N2E_ROWS = 0 keeps the banded form, 1 forces this one (parity tests); unset: by launch size
     // (few short scenes cannot fill the 128 lane pairs of a workgroup AND the chip.  Measured, banded vs rows, us —
     // N = 11: B = 512 10.6 / 21.0, 1024 15.3 / 19.1, 2048 25.0 / 24.3, 4096 42.1 / 39.1;
     // N = 50: B = 32 23.7 / 14.8, 128 25.9 / 18.4, 256 32.1 / 31.9, 1024 104 / 79)
-    // (restated in tests/launch_forms.py expected_forms: keep in step)
-    if (N <= 64 && !no_rows && (maxE >= 24 || hyper_rows >= 49152 || force_rows)) {
+    if (N <= 64 && sw.n2e_rows != 0 && (maxE >= 24 || hyper_rows >= 49152 || sw.n2e_rows == 1)) {
       const size_t row_scene = (size_t)2 * N * kRowPitch * sizeof(float);
       SGh = 1;
       while ((SGh + 1) * maxE <= kBlock / 2 && (size_t)(SGh + 1) * row_scene <= 56 * 1024 &&
-             (long long)((B + SGh) / (SGh + 1)) * T.n >= 1024)
+             (long long)((B + SGh) / (SGh + 1)) * nh >= 1024)
         ++SGh;
       EBh = 0;
       scratch = 0;
       stage = (size_t)SGh * row_scene;
+      p.variant = 1;
     }
     if (stage + scratch > 158 * 1024) return GN_ERR_LDS;
     const size_t l = stage + scratch;
     lds = lds > l ? lds : l;
-    for (int g = 0; g < T.n; ++g) {
-      T.first[g] = waves;
-      waves += (B + SGh - 1) / SGh;                    // (`waves` counts workgroups here)
+  }
+  p.SGh = SGh;
+  p.EBh = EBh;
+  p.dyn_lds = (int)lds;
+  // sections: the pairwise groups, then the hyper groups, each in the caller's order
+  // (pairwise workgroups are (scene chunk, band) with the band fastest: scene order, like every other stage)
+  XcdSections xs{};
+  long long grid = 0;
+  for (int hyper = 0; hyper < 2; ++hyper)
+    for (int g = 0; g < n_groups; ++g) {
+      if ((groups[g].H != nullptr) != (hyper != 0)) continue;
+      if (hyper) p.wgs[g] = (B + SGh - 1) / SGh, p.spw[g] = SGh;
+      p.pos[g] = xs.n;
+      grid += p.wgs[g];
+      if (grid > 0x3fffffffLL) return GN_ERR_SHAPE;
+      xs.first[++xs.n] = (int)grid;
     }
+  p.grid[0] = gn_xcd_grid(xs, sw.xcd);
+  p.xcd = xs.enabled;
+  return GN_OK;
+}
+template <typename TS>
+static int node2edge_launch(const gn_launch_plan_t& p, const gn_n2e_group_t* groups, int B, int N, hipStream_t s) {
+  WaveTable<gn_n2e_group_t> T{};
+  PairTable P{};
+  XcdSections xs{};
+  int pair_wgs = 0;
+  for (int g = 0; g < p.n_groups; ++g) {
+    if (groups[g].H != nullptr) continue;
+    int SG, bands;
+    n2e_pair_shape(B, N, groups[g].E, SG, bands);
+    P.g[P.n] = groups[g];
+    P.SG[P.n] = SG;
+    P.bands[P.n] = bands;
+    P.first_wg[P.n] = pair_wgs;
+    xs.first[xs.n++] = pair_wgs;
+    pair_wgs += p.wgs[g];
+    ++P.n;
+  }
+  P.first_wg[P.n] = pair_wgs;
+  long long waves = 0;                                 // (`waves` counts workgroups here)
+  for (int g = 0; g < p.n_groups; ++g) {
+    if (groups[g].H == nullptr) continue;
+    T.g[T.n] = groups[g];
+    T.first[T.n++] = waves;
+    xs.first[xs.n++] = pair_wgs + (int)waves;
+    waves += p.wgs[g];
   }
   T.first[T.n] = waves;
-  const long long grid = pair_wgs + waves;
-  if (grid > 0x3fffffffLL) return GN_ERR_SHAPE;
-  XcdSections xs{};
-  for (int g = 0; g < P.n; ++g) xs.first[xs.n++] = P.first_wg[g];
-  for (int g = 0; g < T.n; ++g) xs.first[xs.n++] = pair_wgs + (int)T.first[g];
-  xs.first[xs.n] = (int)grid;
-  // (pairwise workgroups are (scene chunk, band) with the band fastest: scene order, like every other stage)
-  if (T.n > 0 && EBh == 0) {
-    gn_allow_big_lds(node2edge_kernel<TS, true>);
-    hipLaunchKernelGGL((node2edge_kernel<TS, true>), dim3((unsigned)gn_xcd_grid(xs)), dim3(kBlock), lds, s, T, P, B, N, SGh,
-                       EBh, xs);
-  } else {
-    gn_allow_big_lds(node2edge_kernel<TS, false>);
-    hipLaunchKernelGGL((node2edge_kernel<TS, false>), dim3((unsigned)gn_xcd_grid(xs)), dim3(kBlock), lds, s, T, P, B, N, SGh,
-                       EBh, xs);
-  }
-  return gn_check_launch();
+  xs.first[xs.n] = pair_wgs + (int)waves;
+  gn_xcd_grid(xs, p.xcd != 0);
+  auto launch = [&](auto k) {
+    gn_allow_big_lds(k);
+    hipLaunchKernelGGL(k, dim3((unsigned)p.grid[0]), dim3(kBlock), (size_t)p.dyn_lds, s, T, P, B, N, p.SGh, p.EBh, xs);
+    return gn_check_launch();
+  };
+  return p.variant ? launch(node2edge_kernel<TS, true>) : launch(node2edge_kernel<TS, false>);
+}
+template <typename TS>
+static int node2edge_entry(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_stream_t stream,
+                           gn_launch_plan_t* plan) {
+  gn_launch_plan_t p;
+  int rc = node2edge_plan(groups, n_groups, B, N, sizeof(TS) != sizeof(float), gn_read_switches(), plan != nullptr ? *plan : p);
+  if (rc != GN_OK || plan != nullptr) return rc;
+  return node2edge_launch<TS>(p, groups, B, N, (hipStream_t)stream);
 }
 extern "C" int gn_node2edge_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_stream_t stream) {
-  return node2edge_launch<float>(groups, n_groups, B, N, (hipStream_t)stream);
+  return node2edge_entry<float>(groups, n_groups, B, N, stream, nullptr);
 }
 extern "C" int gn_node2edge_bf16(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_stream_t stream) {
-  return node2edge_launch<__bf16>(groups, n_groups, B, N, (hipStream_t)stream);
+  return node2edge_entry<__bf16>(groups, n_groups, B, N, stream, nullptr);
+}
+extern "C" int gn_node2edge_plan_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : node2edge_entry<float>(groups, n_groups, B, N, nullptr, plan);
+}
+extern "C" int gn_node2edge_plan_bf16(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : node2edge_entry<__bf16>(groups, n_groups, B, N, nullptr, plan);
 }
 
 // workgroups a gather / scatter launch keeps at least when it packs several scenes into one.  2048 = two rounds of the
@@ -1288,12 +1354,14 @@ extern "C" int gn_node2edge_bf16(const gn_n2e_group_t* groups, int n_groups, int
 // 4096 and 8192 measured the same as 2048)
 constexpr int kGsMinWgs = 2048;
 
-template <typename TS>
-static int gather_launch(const gn_gather_group_t* groups, int n_groups, int B, int N, hipStream_t s) {
+static int gather_plan(const gn_gather_group_t* groups, int n_groups, int B, int N, bool twin, gn_launch_plan_t& p) {
   int rc = check_groups(groups, n_groups);
   if (rc != GN_OK) return rc;
   if (B <= 0 || N <= 0) return GN_ERR_SHAPE;
-  GatherTable T{};
+  p = gn_launch_plan_t{};
+  p.n_groups = n_groups;
+  p.precision = twin ? 1 : 0;
+  p.grid[1] = p.grid[2] = 1;
   int nh = 0, Emax = 0;
   for (int g = 0; g < n_groups; ++g) {
     const gn_gather_group_t& G = groups[g];
@@ -1302,17 +1370,49 @@ static int gather_launch(const gn_gather_group_t* groups, int n_groups, int B, i
     if (G.E <= 0) return GN_ERR_SHAPE;
     if (G.H == nullptr) {
       if ((long long)G.E != (G.sym ? (long long)gn_pair_count(N) : (long long)N * N)) return GN_ERR_SHAPE;
+      p.pos[g] = -1;      // agg_gather_pairwise_kernel, a launch of its own
+      p.pre_grid[g] = capped_grid((long long)B * G.E * 16, kBlock * 4);
     } else {
       if (G.sym) return GN_ERR_SHAPE;
-      T.g[nh++] = G;
+      p.pos[g] = nh++;
       Emax = G.E > Emax ? G.E : Emax;
     }
   }
-  for (int g = 0; g < n_groups; ++g) {
+  if (nh == 0) return GN_OK;
+  const size_t ori_b = (size_t)N * GN_FEAT * sizeof(float);
+  if (ori_b + (size_t)N * sizeof(float) > kLdsBudget) return GN_ERR_LDS;
+  int G = 1, TE = Emax;
+  const size_t per_scene = ori_b + (size_t)Emax * N * sizeof(float);
+  if (per_scene <= kLdsBudget) {
+    // several scenes per workgroup while the tile stays <= 24 KiB and the grid stays >= kGsMinWgs
+    while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= kGsMinWgs)
+      G *= 2;
+  } else {
+    TE = (int)((kLdsBudget - ori_b) / ((size_t)N * sizeof(float)));
+    if (TE < 1) return GN_ERR_LDS;
+  }
+  p.kernel = GN_K_AGG_GATHER;
+  p.G = G;
+  p.TE = TE;
+  p.dyn_lds = (int)((size_t)G * ori_b + (size_t)G * TE * N * sizeof(float));
+  p.grid[0] = (B + G - 1) / G;
+  p.grid[1] = (Emax + TE - 1) / TE;
+  p.grid[2] = nh;
+  for (int g = 0; g < n_groups; ++g)
+    if (groups[g].H != nullptr) p.wgs[g] = p.grid[0] * p.grid[1], p.spw[g] = G;
+  return GN_OK;
+}
+template <typename TS>
+static int gather_launch(const gn_launch_plan_t& p, const gn_gather_group_t* groups, int B, int N, hipStream_t s) {
+  GatherTable T{};
+  for (int g = 0; g < p.n_groups; ++g) {
     const gn_gather_group_t& G = groups[g];
-    if (G.H != nullptr) continue;
+    if (G.H != nullptr) {
+      T.g[p.pos[g]] = G;
+      continue;
+    }
     const long long total4 = (long long)B * G.E * 16;
-    const dim3 grid(capped_grid(total4, kBlock * 4));
+    const dim3 grid(p.pre_grid[g]);
     const TS* ori = reinterpret_cast<const TS*>(G.ori);
     TS* eo = reinterpret_cast<TS*>(G.eo);
     if (G.sym)
@@ -1320,36 +1420,36 @@ static int gather_launch(const gn_gather_group_t* groups, int n_groups, int B, i
     else
       hipLaunchKernelGGL((agg_gather_pairwise_kernel<false, TS>), grid, dim3(kBlock), 0, s, ori, eo, N, total4);
   }
-  if (nh > 0) {
-    const size_t ori_b = (size_t)N * GN_FEAT * sizeof(float);
-    if (ori_b + (size_t)N * sizeof(float) > kLdsBudget) return GN_ERR_LDS;
-    int G = 1, TE = Emax;
-    const size_t per_scene = ori_b + (size_t)Emax * N * sizeof(float);
-    if (per_scene <= kLdsBudget) {
-      // several scenes per workgroup while the tile stays <= 24 KiB and the grid stays >= 1024 (restated in
-      // tests/launch_forms.py expected_forms)
-      while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= kGsMinWgs)
-        G *= 2;
-    } else {
-      TE = (int)((kLdsBudget - ori_b) / ((size_t)N * sizeof(float)));
-      if (TE < 1) return GN_ERR_LDS;
-    }
-    const size_t lds = (size_t)G * ori_b + (size_t)G * TE * N * sizeof(float);
+  if (p.kernel == GN_K_AGG_GATHER) {
     gn_allow_big_lds(agg_gather_kernel<TS>);
-    hipLaunchKernelGGL(agg_gather_kernel<TS>, dim3((B + G - 1) / G, (Emax + TE - 1) / TE, nh), dim3(kBlock), lds, s, T,
-                       B, N, G, TE);
+    hipLaunchKernelGGL(agg_gather_kernel<TS>, dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(kBlock), (size_t)p.dyn_lds, s, T,
+                       B, N, p.G, p.TE);
   }
   return gn_check_launch();
 }
+template <typename TS>
+static int gather_entry(const gn_gather_group_t* groups, int n_groups, int B, int N, gn_stream_t stream, gn_launch_plan_t* plan) {
+  gn_launch_plan_t p;
+  int rc = gather_plan(groups, n_groups, B, N, sizeof(TS) != sizeof(float), plan != nullptr ? *plan : p);
+  if (rc != GN_OK || plan != nullptr) return rc;
+  return gather_launch<TS>(p, groups, B, N, (hipStream_t)stream);
+}
 extern "C" int gn_agg_gather_f32(const gn_gather_group_t* groups, int n_groups, int B, int N, gn_stream_t stream) {
-  return gather_launch<float>(groups, n_groups, B, N, (hipStream_t)stream);
+  return gather_entry<float>(groups, n_groups, B, N, stream, nullptr);
 }
 extern "C" int gn_agg_gather_bf16(const gn_gather_group_t* groups, int n_groups, int B, int N, gn_stream_t stream) {
-  return gather_launch<__bf16>(groups, n_groups, B, N, (hipStream_t)stream);
+  return gather_entry<__bf16>(groups, n_groups, B, N, stream, nullptr);
+}
+extern "C" int gn_agg_gather_plan_f32(const gn_gather_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : gather_entry<float>(groups, n_groups, B, N, nullptr, plan);
+}
+extern "C" int gn_agg_gather_plan_bf16(const gn_gather_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : gather_entry<__bf16>(groups, n_groups, B, N, nullptr, plan);
 }
 
 template <typename TS>
-static int scatter_launch(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor, hipStream_t s) {
+static int scatter_launch(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor, hipStream_t s,
+                          const GnSwitches& sw) {
   int rc = check_groups(groups, n_groups);
   if (rc != GN_OK) return rc;
   if (B <= 0 || N <= 0 || !(divisor != 0.f)) return GN_ERR_SHAPE;
@@ -1370,8 +1470,7 @@ static int scatter_launch(const gn_scatter_group_t* groups, int n_groups, int B,
     const TS* feat = reinterpret_cast<const TS*>(G.feat);
     const TS* ori = reinterpret_cast<const TS*>(G.ori);
     TS* out = reinterpret_cast<TS*>(G.out);
-    if (G.H == nullptr && G.sym && N * 16 <= kBlock * kPairItems && B >= 256 &&
-        !(getenv("GN_SCATTER_PAIRS") && atoi(getenv("GN_SCATTER_PAIRS")) == 0)) {
+    if (G.H == nullptr && G.sym && N * 16 <= kBlock * kPairItems && B >= 256 && sw.scatter_pairs) {
       // one workgroup per scene, every pair row read once (enough scenes to fill the chip; GN_SCATTER_PAIRS = 0 keeps
       // the direct kernel: parity tests run both)
       hipLaunchKernelGGL((agg_scatter_pairs_kernel<TS>), dim3(B), dim3(kBlock), 0, s, feat, ori, out, N, divisor);
@@ -1402,11 +1501,11 @@ static int scatter_launch(const gn_scatter_group_t* groups, int n_groups, int B,
 }
 extern "C" int gn_agg_scatter_f32(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
                                   gn_stream_t stream) {
-  return scatter_launch<float>(groups, n_groups, B, N, divisor, (hipStream_t)stream);
+  return scatter_launch<float>(groups, n_groups, B, N, divisor, (hipStream_t)stream, gn_read_switches());
 }
 extern "C" int gn_agg_scatter_bf16(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
                                    gn_stream_t stream) {
-  return scatter_launch<__bf16>(groups, n_groups, B, N, divisor, (hipStream_t)stream);
+  return scatter_launch<__bf16>(groups, n_groups, B, N, divisor, (hipStream_t)stream, gn_read_switches());
 }
 
 // Pitched copy (rows x width bytes, 16-byte pieces): the column block of the feature tensor that a rank ships into its

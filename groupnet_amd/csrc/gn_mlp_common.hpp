@@ -130,10 +130,10 @@ struct GroupTable {
   XcdSections xs;     // bf16-core kernels: XCD-aware order of the logical workgroups (sections = groups)
 };
 template <typename G>
-inline int table_xcd_grid(GroupTable<G>& T) {
+inline int table_xcd_grid(GroupTable<G>& T, bool on) {
   T.xs.n = T.n;
   for (int g = 0; g <= T.n; ++g) T.xs.first[g] = T.first_wg[g];
-  return gn_xcd_grid(T.xs);
+  return gn_xcd_grid(T.xs, on);
 }
 template <typename G>
 __device__ __forceinline__ int find_group(const GroupTable<G>& t, int wg) {

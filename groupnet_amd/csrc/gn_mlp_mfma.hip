@@ -23,6 +23,8 @@
 // GEMMs only by summation order (~1e-7 relative).
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "gn_mlp_common.hpp"
 #include "gn_mlp_bf16.hpp"
 
@@ -866,6 +868,15 @@ extern "C" int gn_pack_segments_f32(const gn_pack_seg_t* segs_dev, int n_segs, i
   return gn_check_launch();
 }
 
+// ---- launch plans ----------------------------------------------------------------------------------------------------
+// Every forward launcher below is two functions.  Its PLAN is pure host code: it validates the descriptors and decides
+// the kernel instantiation, grid, LDS and per-group work shapes from the descriptors, the scalar arguments, the storage
+// type and the switches (GnSwitches, read once per extern "C" call) — no HIP call, no environment, no device pointer
+// dereferenced.  Its LAUNCH turns a plan into the kernel table and issues it; one dispatch per launcher maps the planned
+// instantiation to the kernel symbol, for the launch and for the occupancy query of gn_*_launch_info_f32 alike.
+// gn_*_plan_* export the plans (include/groupnet_hip.h); tests/test_launch_plan_cpu.py holds them, without a GPU, against
+// the rules as the tests state them (tests/launch_forms.py expected_forms).
+
 // How many groups of a launch carry the bf16-core image: all (returns 1), none (0), or a mix (-1, an error).
 template <typename G, typename F>
 static int x_mode(const G* groups, int n, F has) {
@@ -874,74 +885,156 @@ static int x_mode(const G* groups, int n, F has) {
   return cnt == 0 ? 0 : (cnt == n ? 1 : -1);
 }
 
-// A launcher asked for its launch's resources instead of the launch (gn_*_launch_info_f32): the dynamic LDS it would pass
-// and the workgroups per CU the runtime grants the kernel with it.
-struct LaunchQuery {
-  size_t* dyn_lds;
-  int* wgs_per_cu;
-  template <typename K>
-  int fill(K kernel, size_t lds) const {
-    *dyn_lds = lds;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(wgs_per_cu, reinterpret_cast<const void*>(kernel), 256, lds) == hipSuccess
-               ? GN_OK
-               : GN_ERR_LAUNCH;
-  }
-};
+static void plan_begin(gn_launch_plan_t& p, int n_groups) {
+  p = gn_launch_plan_t{};
+  p.n_groups = n_groups;
+  p.grid[1] = p.grid[2] = 1;
+}
+// the launch's grid from the groups' workgroups in launch order `order` (nullptr: the caller's), XCD-aware when `xcd`
+static void plan_grid(gn_launch_plan_t& p, int n, const int* order, bool xcd, const GnSwitches& sw) {
+  XcdSections xs{};
+  xs.n = n;
+  for (int i = 0; i < n; ++i) xs.first[i + 1] = xs.first[i] + p.wgs[order != nullptr ? order[i] : i];
+  p.grid[0] = xcd ? gn_xcd_grid(xs, sw.xcd) : xs.first[n];
+  p.xcd = xs.enabled;
+}
+// first_wg of a table whose groups are filled in launch order, from the plan's workgroups
+template <typename G>
+static void table_first_wg(GroupTable<G>& T, const gn_launch_plan_t& p, const int* order) {
+  for (int i = 0; i < T.n; ++i) T.first_wg[i + 1] = T.first_wg[i] + p.wgs[order != nullptr ? order[i] : i];
+}
+// workgroups per CU the runtime grants `kernel` with the plan's dynamic LDS (gn_*_launch_info_f32)
+template <typename K>
+static int occupancy_of(K kernel, const gn_launch_plan_t& p, int* wgs_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(wgs_per_cu, reinterpret_cast<const void*>(kernel), 256, (size_t)p.dyn_lds) == hipSuccess
+             ? GN_OK
+             : GN_ERR_LAUNCH;
+}
 
 // ---- node stage ----------------------------------------------------------------------------------------------
 // largest LDS a scene of the fused affinity tail may ask for: beside the node stage's 36 KiB weight ring two workgroups
 // per CU must still fit (the f16x3 kernel keeps its three up to 17 408 bytes: N = 11, D = 64 asks for 3 968)
 constexpr size_t kAffTailLds = 24 * 1024;
-template <int P, typename T>
-static int node_stage_launch(const gn_node_group_t* groups, int n_groups, int rows, hipStream_t s,
-                             const gn_affinity_job_t* job = nullptr, LaunchQuery* query = nullptr) {
-  NodeTable Tb{};
+// the workgroup layout of node_stage_kernel: every group's chain, then the A workgroups; returns the node stage's grid
+static int node_layout(NodeTable& Tb, const gn_node_group_t* groups, int n_groups, int rows, bool xcd) {
   Tb.n = n_groups;
   Tb.rows = rows;
   Tb.wgs_per_group = (rows + 127) / 128;          // 4 row blocks of one group per workgroup
   Tb.chain_wgs = n_groups * Tb.wgs_per_group;
   int a_wgs = 0;
   for (int g = 0; g < n_groups; ++g) {
-    const gn_node_group_t& G = groups[g];
-    const void* ptrs[] = {G.x, G.Wx, G.bias, G.xp, G.pq};
-    for (const void* p : ptrs) GN_CHECK(need(p, true));
-    if (P == 1 && G.hid_out != nullptr) return GN_ERR_SHAPE;   // the twins are forward-only
-    if (P == 2) GN_CHECK(need(G.Wh, true));
     Tb.a_first[g] = a_wgs;
-    if (G.A != nullptr) {
-      GN_CHECK(need(G.WAx, true));
-      if (P == 2) GN_CHECK(need(G.WAh, true));
-      GN_CHECK(need(G.bA, true));
-      GN_CHECK(need(G.A, true));
-      if (G.KA < 1 || G.KA > GN_MAX_TYPES) return GN_ERR_SHAPE;
-      a_wgs += Tb.wgs_per_group * ((4 * G.KA + kATiles - 1) / kATiles);
-    }
-    Tb.g[g] = G;
+    if (groups[g].A != nullptr) a_wgs += Tb.wgs_per_group * ((4 * groups[g].KA + kATiles - 1) / kATiles);
+    Tb.g[g] = groups[g];
   }
   Tb.a_first[n_groups] = a_wgs;
   // sections of equal size: every group's chain, then every (group, chunk) of WA
   const int n_sec = (Tb.chain_wgs + a_wgs) / Tb.wgs_per_group;
   Tb.xs.n = n_sec <= GN_MAX_SECTIONS ? n_sec : 1;
   for (int i = 0; i <= Tb.xs.n; ++i) Tb.xs.first[i] = n_sec <= GN_MAX_SECTIONS ? i * Tb.wgs_per_group : i * (Tb.chain_wgs + a_wgs);
-  const int node_grid = gn_xcd_grid(Tb.xs);
-  size_t aff_lds = 0;
+  return gn_xcd_grid(Tb.xs, xcd);
+}
+// job: the affinity + top-k launch as the tail workgroups (bf16-/fp16-core kernels only: every group must carry `Wx`)
+static int node_plan(const gn_node_group_t* groups, int n_groups, int rows, const gn_affinity_job_t* job, bool twin,
+                     const GnSwitches& sw, gn_launch_plan_t& p) {
+  GN_CHECK(check_groups(groups, n_groups));
+  if (rows <= 0) return GN_ERR_SHAPE;
+  plan_begin(p, n_groups);
+  int P = 1;
+  if (!twin) {
+    const int xm = x_mode(groups, n_groups, [](const gn_node_group_t& G) { return G.Wx != nullptr; });
+    if (xm < 0 || (job != nullptr && xm != 1)) return GN_ERR_SHAPE;
+    // f16x3 (two fp16 parts, bf16x6 fallback inside the launch) when every group carries the fp16 image too
+    const int hm = xm ? x_mode(groups, n_groups, [](const gn_node_group_t& G) { return G.Wh != nullptr; }) : 0;
+    if (hm < 0) return GN_ERR_SHAPE;
+    P = xm ? (hm ? 2 : 3) : 0;
+  }
+  p.precision = P;
+  if (P == 0) {
+    for (int g = 0; g < n_groups; ++g) {
+      const gn_node_group_t& G = groups[g];
+      const void* ptrs[] = {G.x, G.W, G.bias, G.xp, G.pq};
+      for (const void* q : ptrs) GN_CHECK(need(q, true));
+      if (G.A != nullptr) return GN_ERR_SHAPE;   // the fused per-node layer exists on the bf16-core path only
+    }
+    const int blocks32 = (rows + 31) / 32;
+    const bool split = (long long)blocks32 * n_groups <= 1024;   // fewer row blocks than SIMDs: 4 waves per row block
+    p.kernel = split ? GN_K_NODE_MLP_SPLIT : GN_K_NODE_MLP;
+    p.grid[0] = split ? blocks32 : row_grid(rows);
+    p.grid[1] = n_groups;
+    for (int g = 0; g < n_groups; ++g) p.wgs[g] = p.grid[0], p.pos[g] = g;
+    return GN_OK;
+  }
+  for (int g = 0; g < n_groups; ++g) {
+    const gn_node_group_t& G = groups[g];
+    const void* ptrs[] = {G.x, G.Wx, G.bias, G.xp, G.pq};
+    for (const void* q : ptrs) GN_CHECK(need(q, true));
+    if (P == 1 && G.hid_out != nullptr) return GN_ERR_SHAPE;   // the twins are forward-only
+    if (P == 2) GN_CHECK(need(G.Wh, true));
+    if (G.A != nullptr) {
+      GN_CHECK(need(G.WAx, true));
+      if (P == 2) GN_CHECK(need(G.WAh, true));
+      GN_CHECK(need(G.bA, true));
+      GN_CHECK(need(G.A, true));
+      if (G.KA < 1 || G.KA > GN_MAX_TYPES) return GN_ERR_SHAPE;
+    }
+  }
+  NodeTable Tb{};
+  p.grid[0] = node_layout(Tb, groups, n_groups, rows, sw.xcd);
+  p.xcd = Tb.xs.enabled;
+  p.kernel = GN_K_NODE_STAGE;
+  for (int g = 0; g < n_groups; ++g) p.wgs[g] = Tb.wgs_per_group + Tb.a_first[g + 1] - Tb.a_first[g], p.pos[g] = g;
   if (job != nullptr) {
     // the affinity + top-k of job->B scenes as the launch's tail workgroups (same checks as gn_affinity_topk_*)
     const bool embed = job->extras != nullptr && job->extras->x_raw != nullptr;
-    if (embed && sizeof(T) != sizeof(float)) return GN_ERR_SHAPE;
+    if (embed && twin) return GN_ERR_SHAPE;
     if (!embed) GN_CHECK(need(job->f, true));
     if (job->B <= 0 || job->N <= 0 || job->D <= 0 || (job->D & 3) || job->D > 1024) return GN_ERR_SHAPE;
-    GN_CHECK(fill_scales(Tb.aff_sl, job->H_list, job->k_list, job->n_scales, job->N));
+    ScaleList sl;
+    GN_CHECK(fill_scales(sl, job->H_list, job->k_list, job->n_scales, job->N));
     if (embed) {
       if (job->extras->x_dim <= 0 || !job->extras->M || !job->extras->c || !job->extras->f_contig) return GN_ERR_NULL;
       if (!gn_aligned16(job->extras->c) || !gn_aligned16(job->extras->f_contig)) return GN_ERR_ALIGN;
     }
-    aff_lds = affinity_fused_lds(job->N, job->D, embed ? job->extras->x_dim : 0);
+    const size_t aff_lds = affinity_fused_lds(job->N, job->D, embed ? job->extras->x_dim : 0);
     if (aff_lds > kAffTailLds) return GN_ERR_LDS;
     if (job->extras != nullptr) {
+      const gn_block_extras_t& ex = *job->extras;
+      if (ex.f_out != nullptr && (!gn_aligned16(ex.f_out) || ex.f_out_ld < job->D || (ex.f_out_ld & 3))) return GN_ERR_ALIGN;
+    }
+    p.dyn_lds = (int)aff_lds;
+    p.grid[0] += job->B;
+  }
+  return GN_OK;
+}
+template <typename F>
+static int node_dispatch(const gn_launch_plan_t& p, F&& f) {
+  switch (p.kernel == GN_K_NODE_STAGE ? p.precision : -p.kernel) {
+    case 1: return f(node_stage_kernel<1, __bf16>);
+    case 2: return f(node_stage_kernel<2, float>);
+    case 3: return f(node_stage_kernel<3, float>);
+    case -GN_K_NODE_MLP_SPLIT: return f(node_mlp_split_kernel);
+    default: return f(node_mlp_kernel);
+  }
+}
+static int node_launch(const gn_launch_plan_t& p, const gn_node_group_t* groups, int rows, const gn_affinity_job_t* job,
+                       hipStream_t s) {
+  const dim3 grid(p.grid[0], p.grid[1]);
+  if (p.kernel != GN_K_NODE_STAGE) {
+    GroupTable<gn_node_group_t> T{};
+    T.n = p.n_groups;
+    for (int g = 0; g < T.n; ++g) T.g[g] = groups[g];
+    return node_dispatch(p, [&](auto k) {
+      if constexpr (std::is_invocable_v<decltype(k), GroupTable<gn_node_group_t>, int>) hipLaunchKernelGGL(k, grid, dim3(256), 0, s, T, rows);
+      return gn_check_launch();
+    });
+  }
+  NodeTable Tb{};
+  const int node_grid = node_layout(Tb, groups, p.n_groups, rows, p.xcd != 0);
+  if (job != nullptr) {
+    (void)fill_scales(Tb.aff_sl, job->H_list, job->k_list, job->n_scales, job->N);
+    if (job->extras != nullptr) {
       Tb.aff_ex = *job->extras;
-      if (Tb.aff_ex.f_out != nullptr && (!gn_aligned16(Tb.aff_ex.f_out) || Tb.aff_ex.f_out_ld < job->D || (Tb.aff_ex.f_out_ld & 3)))
-        return GN_ERR_ALIGN;
       Tb.aff_sl.H_cat = Tb.aff_ex.H_cat;
     }
     Tb.node_grid = node_grid;
@@ -951,108 +1044,97 @@ static int node_stage_launch(const gn_node_group_t* groups, int n_groups, int ro
     Tb.aff_f = job->f;
     Tb.aff_corr = job->corr;
   }
-  if (query != nullptr) return query->fill(node_stage_kernel<P, T>, aff_lds);
-  hipLaunchKernelGGL((node_stage_kernel<P, T>), dim3(node_grid + Tb.aff_scenes), dim3(256), aff_lds, s, Tb);
-  return gn_check_launch();
+  return node_dispatch(p, [&](auto k) {
+    if constexpr (std::is_invocable_v<decltype(k), NodeTable>) hipLaunchKernelGGL(k, grid, dim3(256), (size_t)p.dyn_lds, s, Tb);
+    return gn_check_launch();
+  });
+}
+static int node_entry(const gn_node_group_t* groups, int n_groups, int rows, const gn_affinity_job_t* job, bool twin,
+                      gn_stream_t stream) {
+  gn_launch_plan_t p;
+  GN_CHECK(node_plan(groups, n_groups, rows, job, twin, gn_read_switches(), p));
+  return node_launch(p, groups, rows, job, (hipStream_t)stream);
 }
 
 extern "C" int gn_node_mlp_f32(const gn_node_group_t* groups, int n_groups, int rows, gn_stream_t stream) {
-  GN_CHECK(check_groups(groups, n_groups));
-  if (rows <= 0) return GN_ERR_SHAPE;
-  const int xm = x_mode(groups, n_groups, [](const gn_node_group_t& G) { return G.Wx != nullptr; });
-  if (xm < 0) return GN_ERR_SHAPE;
-  if (xm == 1) {
-    // f16x3 (two fp16 parts, bf16x6 fallback inside the launch) when every group carries the fp16 image too
-    const int hm = x_mode(groups, n_groups, [](const gn_node_group_t& G) { return G.Wh != nullptr; });
-    if (hm < 0) return GN_ERR_SHAPE;
-    return hm ? node_stage_launch<2, float>(groups, n_groups, rows, (hipStream_t)stream)
-              : node_stage_launch<3, float>(groups, n_groups, rows, (hipStream_t)stream);
-  }
-  GroupTable<gn_node_group_t> T{};
-  T.n = n_groups;
-  for (int g = 0; g < n_groups; ++g) {
-    const gn_node_group_t& G = groups[g];
-    const void* ptrs[] = {G.x, G.W, G.bias, G.xp, G.pq};
-    for (const void* p : ptrs) GN_CHECK(need(p, true));
-    if (G.A != nullptr) return GN_ERR_SHAPE;   // the fused per-node layer exists on the bf16-core path only
-    T.g[g] = G;
-  }
-  const int blocks32 = (rows + 31) / 32;
-  if ((long long)blocks32 * n_groups <= 1024)   // fewer row blocks than SIMDs: 4 waves per row block
-    hipLaunchKernelGGL(node_mlp_split_kernel, dim3(blocks32, n_groups), dim3(256), 0, (hipStream_t)stream, T, rows);
-  else
-    hipLaunchKernelGGL(node_mlp_kernel, dim3(row_grid(rows), n_groups), dim3(256), 0, (hipStream_t)stream, T, rows);
-  return gn_check_launch();
+  return node_entry(groups, n_groups, rows, nullptr, false, stream);
 }
-
 extern "C" int gn_node_mlp_bf16(const gn_node_group_t* groups, int n_groups, int rows, gn_stream_t stream) {
-  GN_CHECK(check_groups(groups, n_groups));
-  if (rows <= 0) return GN_ERR_SHAPE;
-  return node_stage_launch<1, __bf16>(groups, n_groups, rows, (hipStream_t)stream);
+  return node_entry(groups, n_groups, rows, nullptr, true, stream);
 }
-
 // The node stage with the fused affinity + top-k launch as its tail workgroups (bf16-/fp16-core kernels only: every group
 // must carry its `Wx` image).
 extern "C" int gn_node_mlp_affinity_f32(const gn_node_group_t* groups, int n_groups, int rows, const gn_affinity_job_t* job,
                                         gn_stream_t stream) {
   GN_CHECK(check_groups(groups, n_groups));
-  if (rows <= 0 || job == nullptr) return GN_ERR_SHAPE;
-  if (x_mode(groups, n_groups, [](const gn_node_group_t& G) { return G.Wx != nullptr; }) != 1) return GN_ERR_SHAPE;
-  const int hm = x_mode(groups, n_groups, [](const gn_node_group_t& G) { return G.Wh != nullptr; });
-  if (hm < 0) return GN_ERR_SHAPE;
-  return hm ? node_stage_launch<2, float>(groups, n_groups, rows, (hipStream_t)stream, job)
-            : node_stage_launch<3, float>(groups, n_groups, rows, (hipStream_t)stream, job);
+  if (job == nullptr) return GN_ERR_SHAPE;
+  return node_entry(groups, n_groups, rows, job, false, stream);
 }
 extern "C" int gn_node_mlp_affinity_bf16(const gn_node_group_t* groups, int n_groups, int rows, const gn_affinity_job_t* job,
                                          gn_stream_t stream) {
   GN_CHECK(check_groups(groups, n_groups));
-  if (rows <= 0 || job == nullptr) return GN_ERR_SHAPE;
-  return node_stage_launch<1, __bf16>(groups, n_groups, rows, (hipStream_t)stream, job);
+  if (job == nullptr) return GN_ERR_SHAPE;
+  return node_entry(groups, n_groups, rows, job, true, stream);
 }
 extern "C" size_t gn_affinity_tail_lds_limit(void) { return kAffTailLds; }
+extern "C" int gn_node_mlp_plan_f32(const gn_node_group_t* groups, int n_groups, int rows, const gn_affinity_job_t* job,
+                                    gn_launch_plan_t* plan) {
+  GN_REQUIRE_PTR(plan);
+  return node_plan(groups, n_groups, rows, job, false, gn_read_switches(), *plan);
+}
+extern "C" int gn_node_mlp_plan_bf16(const gn_node_group_t* groups, int n_groups, int rows, const gn_affinity_job_t* job,
+                                     gn_launch_plan_t* plan) {
+  GN_REQUIRE_PTR(plan);
+  return node_plan(groups, n_groups, rows, job, true, gn_read_switches(), *plan);
+}
 extern "C" int gn_node_mlp_affinity_launch_info_f32(const gn_node_group_t* groups, int n_groups, int rows,
                                                     const gn_affinity_job_t* job, size_t* dyn_lds, int* wgs_per_cu) {
   GN_CHECK(check_groups(groups, n_groups));
   if (dyn_lds == nullptr || wgs_per_cu == nullptr) return GN_ERR_NULL;
-  if (rows <= 0 || job == nullptr) return GN_ERR_SHAPE;
-  if (x_mode(groups, n_groups, [](const gn_node_group_t& G) { return G.Wx != nullptr; }) != 1) return GN_ERR_SHAPE;
-  const int hm = x_mode(groups, n_groups, [](const gn_node_group_t& G) { return G.Wh != nullptr; });
-  if (hm < 0) return GN_ERR_SHAPE;
-  LaunchQuery q{dyn_lds, wgs_per_cu};
-  return hm ? node_stage_launch<2, float>(groups, n_groups, rows, nullptr, job, &q)
-            : node_stage_launch<3, float>(groups, n_groups, rows, nullptr, job, &q);
+  if (job == nullptr) return GN_ERR_SHAPE;
+  gn_launch_plan_t p;
+  GN_CHECK(node_plan(groups, n_groups, rows, job, false, gn_read_switches(), p));
+  *dyn_lds = (size_t)p.dyn_lds;
+  return node_dispatch(p, [&](auto k) { return occupancy_of(k, p, wgs_per_cu); });
 }
 
 // Row-block pairs from which the bf16-storage edge / aggregation launches run two row blocks per wave (the chip must
 // still be filled: >= 2048 waves).  GN_RB2_MIN_PAIRS is a TEST knob: the parity suite lowers it so that the launcher's
 // own choice falls on those kernels at sizes the CPU oracle can follow (tests/test_bf16_gpu.py).
-static long long rb2_min_pairs() {
-  if (const char* e = getenv("GN_RB2_MIN_PAIRS")) {
-    const long long v = atoll(e);
-    if (v > 0) return v;
-  }
-  return 2048;
-}
+static long long rb2_min_pairs(const GnSwitches& sw) { return sw.rb2_min_pairs > 0 ? sw.rb2_min_pairs : 2048; }
 
 // ---- edge MLP --------------------------------------------------------------------------------------------------
 constexpr size_t kEdgeCuLds = 160 * 1024;      // LDS per CU (gfx950)
 constexpr size_t kLdsGranule = 1280;           // ... is allocated to a workgroup in granules of 320 dwords
 template <int P>
 constexpr size_t kEdgeRing = kRingF4For<P> * sizeof(f32x4);   // weight ring of edge_x_kernel<P> (head of its dynamic LDS)
+// static LDS of edge_rb2_kernel and of edge_x_kernel<P>: what only the runtime knows, an input of the plan
+struct EdgeStaticLds {
+  size_t rb2, x[4];
+};
 template <typename K>
 static size_t static_lds_of(K kernel) {
   hipFuncAttributes a{};
   return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel)) == hipSuccess ? a.sharedSizeBytes : kEdgeCuLds / 2;
 }
-static int edge_launch(const gn_edge_group_t* groups, int n_groups, float tau, unsigned long long seed,
-                       const unsigned long long* offset_dev, hipStream_t stream, bool twin, const LaunchQuery* query = nullptr) {
+// given >= 0: the value itself (plan query); else the runtime's, asked only when the launch can stage at all (its groups
+// carry the bf16-core image)
+static EdgeStaticLds edge_static_lds(long long given, const gn_edge_group_t* groups, int n_groups) {
+  const size_t v = (size_t)given;
+  if (given >= 0) return EdgeStaticLds{v, {0, v, v, v}};
+  if (check_groups(groups, n_groups) != GN_OK || groups[0].Wx == nullptr) return EdgeStaticLds{};
+  static const EdgeStaticLds rt{static_lds_of(edge_rb2_kernel<__bf16>),
+                                {0, static_lds_of(edge_x_kernel<1, __bf16>), static_lds_of(edge_x_kernel<2, float>),
+                                 static_lds_of(edge_x_kernel<3, float>)}};
+  return rt;
+}
+static int edge_plan(const gn_edge_group_t* groups, int n_groups, float tau, bool twin, const EdgeStaticLds& st,
+                     const GnSwitches& sw, gn_launch_plan_t& p) {
   GN_CHECK(check_groups(groups, n_groups));
   if (!(tau > 0.f)) return GN_ERR_SHAPE;
   const int xm = x_mode(groups, n_groups, [](const gn_edge_group_t& G) { return G.Wx != nullptr; });
   if (xm < 0 || (twin && xm != 1)) return GN_ERR_SHAPE;
-  GroupTable<gn_edge_group_t> T{};
-  T.n = n_groups;
-  int wg = 0;
+  plan_begin(p, n_groups);
   for (int g = 0; g < n_groups; ++g) {
     const gn_edge_group_t& G = groups[g];
     if (G.edges != nullptr) {
@@ -1078,11 +1160,27 @@ static int edge_launch(const gn_edge_group_t* groups, int n_groups, float tau, u
     if (G.rows <= 0 || G.K < 1 || G.K > 15 || G.sym_N < 0) return GN_ERR_SHAPE;
     if (G.sym_N > 0 && G.rows % gn_pair_count(G.sym_N) != 0) return GN_ERR_SHAPE;
     if (twin && (G.keep_z1 || G.keep_z || G.keep_dh1 || G.keep_lgf)) return GN_ERR_SHAPE;
-    T.g[g] = G;
-    T.first_wg[g] = wg;
-    wg += row_grid(G.rows);
+    p.pos[g] = g;
   }
-  T.first_wg[n_groups] = wg;
+  if (!xm) {
+    p.kernel = GN_K_EDGE_MLP_GUMBEL;
+    for (int g = 0; g < n_groups; ++g) p.wgs[g] = row_grid(groups[g].rows);
+    plan_grid(p, n_groups, nullptr, false, sw);
+    return GN_OK;
+  }
+  // a large launch of the twins: two row blocks per wave (edge_rb2_kernel); GN_EDGE_RB2 = 0 / 1 forces the choice
+  bool rb2 = false;
+  if (twin) {
+    long long pairs = 0;
+    for (int g = 0; g < n_groups; ++g) pairs += ((groups[g].rows + 31) / 32 + 1) / 2;
+    rb2 = sw.edge_rb2 >= 0 ? sw.edge_rb2 != 0 : pairs >= rb2_min_pairs(sw);
+  } else {
+    const int hm = x_mode(groups, n_groups, [](const gn_edge_group_t& G) { return G.Wh != nullptr; });
+    if (hm < 0) return GN_ERR_SHAPE;
+    p.precision = hm ? 2 : 3;
+  }
+  if (twin) p.precision = 1;
+  p.kernel = rb2 ? GN_K_EDGE_RB2 : GN_K_EDGE_X;
   // LDS for the staged node rows of the fused pooling: the largest stage any group wants, as long as the launch keeps the
   // `occ` workgroups per CU its kernel is compiled for (a workgroup's share of the CU's LDS, in whole allocation granules,
   // less the kernel's static LDS).  edge_x_kernel stages into the region of its weight ring (`ring` bytes, part of the
@@ -1090,105 +1188,113 @@ static int edge_launch(const gn_edge_group_t* groups, int n_groups, float tau, u
   // CU: 53 504 bytes); edge_rb2_kernel keeps a static ring and a stage of its own (ring = 0).  A group that would need
   // more pools straight from global memory.  GN_POOL_STAGE = 0 switches the stage off (pool_bytes = -1: every group in the
   // per-member reference form).
-  const bool no_pool_stage = getenv("GN_POOL_STAGE") != nullptr && atoi(getenv("GN_POOL_STAGE")) == 0;   // (per call: tests toggle it)
-  auto pool_bytes_for = [&](int wg_rows, size_t static_lds, int occ, size_t ring) -> int {
-    if (no_pool_stage) return -1;
+  const int occs[4] = {0, kEdgeOcc<1>, kEdgeOcc<2>, kEdgeOcc<3>};
+  const size_t rings[4] = {0, kEdgeRing<1>, kEdgeRing<2>, kEdgeRing<3>};
+  const int wg_rows = rb2 ? 256 : 128, occ = rb2 ? 2 : occs[p.precision];
+  const size_t ring = rb2 ? 0 : rings[p.precision], static_lds = rb2 ? st.rb2 : st.x[p.precision];
+  const size_t row_bytes = twin ? PoolStage<__bf16>::kPitch * sizeof(__bf16) : PoolStage<float>::kPitch * sizeof(float);
+  int pb = -1;
+  if (sw.pool_stage) {
     const size_t share = kEdgeCuLds / occ / kLdsGranule * kLdsGranule;
     const size_t cap = min(share - min(static_lds, share), (size_t)64 * 1024);   // (dynamic LDS of a launch: at most 64 KiB)
     size_t need = ring;
     for (int g = 0; g < n_groups; ++g) {
       const gn_edge_group_t& G = groups[g];
       if (G.edges != nullptr || (G.pool_H == nullptr && G.sym_N <= 0)) continue;
-      const size_t row_bytes = twin ? PoolStage<__bf16>::kPitch * sizeof(__bf16) : PoolStage<float>::kPitch * sizeof(float);
       const size_t b = G.pool_H != nullptr ? (size_t)hyper_stage_nodes(wg_rows, G.pool_E, G.pool_N) * row_bytes   // pq, then x'
                                            : 2 * (size_t)pool_stage_nodes(wg_rows, gn_pair_count(G.pool_N), G.pool_N) * row_bytes;
       if (b <= cap && b > need) need = b;
     }
-    return (int)need;
-  };
-  auto launch_lds = [](int pb, size_t ring) { return pb > 0 ? (size_t)pb : ring; };
-  // edge_x_kernel: hyper groups without a stage get one workgroup per 32-row block (hyper_unstaged)
-  auto sparse_grid = [&](int pb, size_t row_bytes) {
-    int w = 0;
-    for (int g = 0; g < n_groups; ++g) {
-      T.first_wg[g] = w;
-      w += hyper_unstaged(groups[g], 128, row_bytes, pb) ? (groups[g].rows + 31) / 32 : row_grid(groups[g].rows);
-    }
-    T.first_wg[n_groups] = w;
-  };
-  if (twin) {
-    // a large launch: two row blocks per wave (edge_rb2_kernel); GN_EDGE_RB2 = 0 / 1 forces the choice (parity tests)
-    long long pairs = 0;
-    for (int g = 0; g < n_groups; ++g) pairs += ((groups[g].rows + 31) / 32 + 1) / 2;
-    bool rb2 = pairs >= rb2_min_pairs();
-    if (const char* e = getenv("GN_EDGE_RB2")) rb2 = atoi(e) != 0;
-    if (rb2) {
-      wg = 0;
-      for (int g = 0; g < n_groups; ++g) {
-        T.first_wg[g] = wg;
-        wg += ((groups[g].rows + 31) / 32 + 7) / 8;
-      }
-      T.first_wg[n_groups] = wg;
-      static const size_t rb2_static = static_lds_of(edge_rb2_kernel<__bf16>);
-      const int pb = pool_bytes_for(256, rb2_static, 2, 0);
-      hipLaunchKernelGGL((edge_rb2_kernel<__bf16>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb, 0), stream, T, tau, seed,
-                         offset_dev, pb);
-      return gn_check_launch();
-    }
-    static const size_t x1_static = static_lds_of(edge_x_kernel<1, __bf16>);
-    const int pb = pool_bytes_for(128, x1_static, kEdgeOcc<1>, kEdgeRing<1>);
-    sparse_grid(pb, PoolStage<__bf16>::kPitch * sizeof(__bf16));
-    hipLaunchKernelGGL((edge_x_kernel<1, __bf16>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb, kEdgeRing<1>), stream, T, tau, seed,
-                       offset_dev, pb);
+    pb = (int)need;
   }
-  else if (xm) {
-    const int hm = x_mode(groups, n_groups, [](const gn_edge_group_t& G) { return G.Wh != nullptr; });
-    if (hm < 0) return GN_ERR_SHAPE;
-    static const size_t x2_static = static_lds_of(edge_x_kernel<2, float>), x3_static = static_lds_of(edge_x_kernel<3, float>);
-    const int pb = hm ? pool_bytes_for(128, x2_static, kEdgeOcc<2>, kEdgeRing<2>) : pool_bytes_for(128, x3_static, kEdgeOcc<3>, kEdgeRing<3>);
-    sparse_grid(pb, PoolStage<float>::kPitch * sizeof(float));
-    if (query != nullptr)
-      return hm ? query->fill(edge_x_kernel<2, float>, launch_lds(pb, kEdgeRing<2>)) : query->fill(edge_x_kernel<3, float>, launch_lds(pb, kEdgeRing<3>));
-    if (hm)
-      hipLaunchKernelGGL((edge_x_kernel<2, float>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb, kEdgeRing<2>), stream, T, tau,
-                         seed, offset_dev, pb);
+  p.stage_bytes = pb;
+  p.dyn_lds = (int)(pb > 0 ? (size_t)pb : ring);
+  for (int g = 0; g < n_groups; ++g) {
+    const int blocks32 = (groups[g].rows + 31) / 32;
+    // edge_x_kernel: hyper groups without a stage get one workgroup per 32-row block (hyper_unstaged)
+    p.unstaged[g] = !rb2 && hyper_unstaged(groups[g], 128, row_bytes, pb) ? 1 : 0;
+    p.wgs[g] = rb2 ? (blocks32 + 7) / 8 : (p.unstaged[g] ? blocks32 : row_grid(groups[g].rows));
+  }
+  plan_grid(p, n_groups, nullptr, true, sw);
+  return GN_OK;
+}
+template <typename F>
+static int edge_dispatch(const gn_launch_plan_t& p, F&& f) {
+  switch (p.kernel == GN_K_EDGE_X ? p.precision : -p.kernel) {
+    case 1: return f(edge_x_kernel<1, __bf16>);
+    case 2: return f(edge_x_kernel<2, float>);
+    case 3: return f(edge_x_kernel<3, float>);
+    case -GN_K_EDGE_RB2: return f(edge_rb2_kernel<__bf16>);
+    default: return f(edge_mlp_gumbel_kernel);
+  }
+}
+static int edge_launch(const gn_launch_plan_t& p, const gn_edge_group_t* groups, float tau, unsigned long long seed,
+                       const unsigned long long* offset_dev, hipStream_t stream) {
+  GroupTable<gn_edge_group_t> T{};
+  T.n = p.n_groups;
+  for (int g = 0; g < T.n; ++g) T.g[g] = groups[g];
+  table_first_wg(T, p, nullptr);
+  if (p.kernel != GN_K_EDGE_MLP_GUMBEL) table_xcd_grid(T, p.xcd != 0);
+  return edge_dispatch(p, [&](auto k) {
+    if constexpr (std::is_invocable_v<decltype(k), decltype(T), float, unsigned long long, const unsigned long long*, int>)
+      hipLaunchKernelGGL(k, dim3(p.grid[0]), dim3(256), (size_t)p.dyn_lds, stream, T, tau, seed, offset_dev, p.stage_bytes);
     else
-      hipLaunchKernelGGL((edge_x_kernel<3, float>), dim3(table_xcd_grid(T)), dim3(256), launch_lds(pb, kEdgeRing<3>), stream, T, tau,
-                         seed, offset_dev, pb);
-  }
-  else
-    hipLaunchKernelGGL(edge_mlp_gumbel_kernel, dim3(wg), dim3(256), 0, stream, T, tau, seed, offset_dev);
-  return gn_check_launch();
+      hipLaunchKernelGGL(k, dim3(p.grid[0]), dim3(256), 0, stream, T, tau, seed, offset_dev);
+    return gn_check_launch();
+  });
+}
+static int edge_entry(const gn_edge_group_t* groups, int n_groups, float tau, unsigned long long seed,
+                      const unsigned long long* offset_dev, gn_stream_t stream, bool twin) {
+  gn_launch_plan_t p;
+  GN_CHECK(edge_plan(groups, n_groups, tau, twin, edge_static_lds(-1, groups, n_groups), gn_read_switches(), p));
+  return edge_launch(p, groups, tau, seed, offset_dev, (hipStream_t)stream);
 }
 extern "C" int gn_edge_mlp_gumbel_f32(const gn_edge_group_t* groups, int n_groups, float tau,
                                       unsigned long long seed, const unsigned long long* offset_dev,
                                       gn_stream_t stream) {
-  return edge_launch(groups, n_groups, tau, seed, offset_dev, (hipStream_t)stream, false);
+  return edge_entry(groups, n_groups, tau, seed, offset_dev, stream, false);
+}
+extern "C" int gn_edge_mlp_gumbel_bf16(const gn_edge_group_t* groups, int n_groups, float tau,
+                                       unsigned long long seed, const unsigned long long* offset_dev,
+                                       gn_stream_t stream) {
+  return edge_entry(groups, n_groups, tau, seed, offset_dev, stream, true);
+}
+static int edge_plan_query(const gn_edge_group_t* groups, int n_groups, float tau, long long static_lds, bool twin,
+                           gn_launch_plan_t* plan) {
+  GN_REQUIRE_PTR(plan);
+  return edge_plan(groups, n_groups, tau, twin, edge_static_lds(static_lds, groups, n_groups), gn_read_switches(), *plan);
+}
+extern "C" int gn_edge_mlp_gumbel_plan_f32(const gn_edge_group_t* groups, int n_groups, float tau, unsigned long long,
+                                           const unsigned long long*, long long static_lds, gn_launch_plan_t* plan) {
+  return edge_plan_query(groups, n_groups, tau, static_lds, false, plan);
+}
+extern "C" int gn_edge_mlp_gumbel_plan_bf16(const gn_edge_group_t* groups, int n_groups, float tau, unsigned long long,
+                                            const unsigned long long*, long long static_lds, gn_launch_plan_t* plan) {
+  return edge_plan_query(groups, n_groups, tau, static_lds, true, plan);
 }
 extern "C" int gn_edge_mlp_gumbel_launch_info_f32(const gn_edge_group_t* groups, int n_groups, size_t* dyn_lds, int* wgs_per_cu) {
   GN_CHECK(check_groups(groups, n_groups));
   if (dyn_lds == nullptr || wgs_per_cu == nullptr) return GN_ERR_NULL;
   if (x_mode(groups, n_groups, [](const gn_edge_group_t& G) { return G.Wx != nullptr; }) != 1) return GN_ERR_SHAPE;
-  const LaunchQuery q{dyn_lds, wgs_per_cu};
-  return edge_launch(groups, n_groups, 1.f, 0ull, nullptr, nullptr, false, &q);
-}
-extern "C" int gn_edge_mlp_gumbel_bf16(const gn_edge_group_t* groups, int n_groups, float tau,
-                                       unsigned long long seed, const unsigned long long* offset_dev,
-                                       gn_stream_t stream) {
-  return edge_launch(groups, n_groups, tau, seed, offset_dev, (hipStream_t)stream, true);
+  gn_launch_plan_t p;
+  GN_CHECK(edge_plan(groups, n_groups, 1.f, false, edge_static_lds(-1, groups, n_groups), gn_read_switches(), p));
+  *dyn_lds = (size_t)p.dyn_lds;
+  return edge_dispatch(p, [&](auto k) { return occupancy_of(k, p, wgs_per_cu); });
 }
 
 // ---- typed aggregation MLP ---------------------------------------------------------------------------------------
-static int agg_launch(const gn_agg_group_t* groups_in, int n_groups_in, hipStream_t stream, bool twin) {
-  GN_CHECK(check_groups(groups_in, n_groups_in));
+// order[0..n): the caller's indices of the groups of the main launch, in launch order (returned n: their number)
+static int agg_plan(const gn_agg_group_t* groups, int n_groups_in, bool twin, const GnSwitches& sw, gn_launch_plan_t& p,
+                    int (&order)[GN_MAX_GROUPS], int& n_main) {
+  GN_CHECK(check_groups(groups, n_groups_in));
+  plan_begin(p, n_groups_in);
   // twins: scene-form groups (node form without A) run in their own kernel (agg_scene_kernel: VALU-bound, compiled for
   // more waves per SIMD than the matrix-core kernels), ahead of the launch of the remaining groups
-  gn_agg_group_t rest[GN_MAX_GROUPS];
-  int n_groups = 0;
+  int n = 0;
   for (int g = 0; g < n_groups_in; ++g) {
-    const gn_agg_group_t& G = groups_in[g];
+    const gn_agg_group_t& G = groups[g];
     if (!(G.node_form && G.A == nullptr)) {
-      rest[n_groups++] = G;
+      order[n++] = g;
       continue;
     }
     if (!twin || G.eo != nullptr || G.H != nullptr || !G.sym || G.N <= 0 || G.N > 64 || G.E != gn_pair_count(G.N) ||
@@ -1200,22 +1306,21 @@ static int agg_launch(const gn_agg_group_t* groups_in, int n_groups_in, hipStrea
     GN_CHECK(need(G.b2, false));
     GN_CHECK(need(G.edge_feat, false));
     GN_CHECK(need(G.feat, true));
-    const int B = G.rows / G.E, RBN = (G.N + 31) / 32;
-    hipLaunchKernelGGL((agg_scene_kernel<__bf16>), dim3(B * RBN), dim3(256), (size_t)node_scene_lds_floats(G.N) * sizeof(float),
-                       stream, G);
-    GN_CHECK(gn_check_launch());
+    p.pos[g] = -1;
+    p.node_form[g] = p.wpr[g] = 1;
+    p.pre_grid[g] = G.rows / G.E * ((G.N + 31) / 32);
+    p.pre_lds[g] = (int)((size_t)node_scene_lds_floats(G.N) * sizeof(float));
   }
-  if (n_groups == 0) return GN_OK;
-  const gn_agg_group_t* groups = rest;
-  const int xm = x_mode(groups, n_groups, [](const gn_agg_group_t& G) {
-    return (G.A != nullptr ? G.W2x : G.W12x) != nullptr;
-  });
+  n_main = n;
+  if (n == 0) return GN_OK;
+  auto has_x = [](const gn_agg_group_t& G) { return (G.A != nullptr ? G.W2x : G.W12x) != nullptr; };
+  int cnt = 0;
+  for (int i = 0; i < n; ++i) cnt += has_x(groups[order[i]]) ? 1 : 0;
+  const int xm = cnt == 0 ? 0 : (cnt == n ? 1 : -1);
   if (xm < 0 || (twin && xm != 1)) return GN_ERR_SHAPE;
-  GroupTable<AggGroup> T{};
-  T.n = n_groups;
-  int wg = 0;
   int n_fused = 0;
-  for (int g = 0; g < n_groups; ++g) {
+  for (int i = 0; i < n; ++i) {
+    const int g = order[i];
     const gn_agg_group_t& G = groups[g];
     if (G.A != nullptr) {
       if (twin) return GN_ERR_SHAPE;
@@ -1244,12 +1349,10 @@ static int agg_launch(const gn_agg_group_t* groups_in, int n_groups_in, hipStrea
     // alone covers most of the 1024 SIMDs runs one wave per block; a mid-sized group halves its units
     // (4 waves of a workgroup sit on ONE CU, so 4-way splitting 176..700 blocks stacks two workgroups on
     // some CUs and idles others); only small groups split 4 ways
-    // (this rule, spw below, the scene form and rb2 are restated in tests/launch_forms.py expected_forms: keep in step)
     int wpr = blocks32 >= 768 ? 1 : (blocks32 >= 128 && G.K >= 2 ? 2 : (G.K >= 4 ? 4 : 1));
     if (G.node_form) wpr = 1;
-    T.g[g].a = G;
-    T.g[g].wpr = wpr;
-    T.g[g].spw = 0;
+    p.wpr[g] = wpr;
+    p.node_form[g] = G.node_form ? 1 : 0;
     if (G.y != nullptr) {      // fused closing stage
       ++n_fused;
       // (the chain is built for two output tiles: 32 < dout <= 64, the image gn_mlp2's kernels take for that width)
@@ -1271,118 +1374,162 @@ static int agg_launch(const gn_agg_group_t* groups_in, int n_groups_in, hipStrea
         int spw = (128 / wpr) / G.E;
         if (node_cap / G.N < spw) spw = node_cap / G.N;
         if (spw < 1) return GN_ERR_SHAPE;
-        T.g[g].spw = spw;
+        p.spw[g] = spw;
       }
     }
     // pair form with one wave per row block: stage the scenes' node rows in LDS when they fit
-    T.g[g].stage = (G.A != nullptr && wpr == 1 && !G.node_form &&
-                    (127 / G.E + 2) * G.N <= (xm ? kStageMaxNodesX : kStageMaxNodes)) ? 1 : 0;
+    p.stage[g] = (G.A != nullptr && wpr == 1 && !G.node_form &&
+                  (127 / G.E + 2) * G.N <= (xm ? kStageMaxNodesX : kStageMaxNodes)) ? 1 : 0;
   }
   // Workgroups are dispatched in index order: give the low indices to the group whose waves run longest
   // (types x layers per wave), so the long waves start first and the short ones fill the tail.
-  auto cost = [](const AggGroup& a) {
-    return a.a.node_form ? 1ll : (long long)a.a.K * (a.a.A != nullptr ? 1 : 2) * 4 / a.wpr;
+  auto cost = [&](int g) {
+    const gn_agg_group_t& a = groups[g];
+    return a.node_form ? 1ll : (long long)a.K * (a.A != nullptr ? 1 : 2) * 4 / p.wpr[g];
   };
-  for (int i = 1; i < n_groups; ++i)        // insertion sort, stable, n <= GN_MAX_GROUPS
-    for (int j = i; j > 0 && cost(T.g[j]) > cost(T.g[j - 1]); --j) {
-      const AggGroup tmp = T.g[j];
-      T.g[j] = T.g[j - 1];
-      T.g[j - 1] = tmp;
+  for (int i = 1; i < n; ++i)        // insertion sort, stable, n <= GN_MAX_GROUPS
+    for (int j = i; j > 0 && cost(order[j]) > cost(order[j - 1]); --j) {
+      const int tmp = order[j];
+      order[j] = order[j - 1];
+      order[j - 1] = tmp;
     }
-  for (int g = 0; g < n_groups; ++g) {
-    T.first_wg[g] = wg;
-    const gn_agg_group_t& a = T.g[g].a;
-    wg += a.node_form ? (a.rows / a.E * a.N + 31) / 32      // one workgroup per 32-NODE row block
-          : T.g[g].spw > 0 ? (a.rows / a.E + T.g[g].spw - 1) / T.g[g].spw      // fused closing stage: whole scenes
-                           : ((a.rows + 31) / 32 * T.g[g].wpr + 3) / 4;
+  for (int i = 0; i < n; ++i) {
+    const int g = order[i];
+    const gn_agg_group_t& a = groups[g];
+    p.pos[g] = i;
+    p.wgs[g] = a.node_form ? (a.rows / a.E * a.N + 31) / 32      // one workgroup per 32-NODE row block
+               : p.spw[g] > 0 ? (a.rows / a.E + p.spw[g] - 1) / p.spw[g]      // fused closing stage: whole scenes
+                              : ((a.rows + 31) / 32 * p.wpr[g] + 3) / 4;
   }
-  T.first_wg[n_groups] = wg;
-  if (n_fused != 0 && n_fused != n_groups) return GN_ERR_SHAPE;      // every group of a launch or none
+  if (n_fused != 0 && n_fused != n) return GN_ERR_SHAPE;      // every group of a launch or none
+  p.closing = n_fused != 0;
   // bf16 storage, a large launch: two row blocks per wave (agg_rb2_kernel)
   if (twin) {
     // (pairs of row blocks must still fill the chip: >= 2048 waves in all.  GN_AGG_RB2 = 0 / 1 forces the choice —
     // the parity tests run small cases through both kernels)
     long long pairs = 0;
-    for (int g = 0; g < n_groups; ++g) pairs += ((groups[g].rows + 31) / 32 + 1) / 2;
-    bool rb2 = pairs >= rb2_min_pairs();
-    if (const char* e = getenv("GN_AGG_RB2")) rb2 = atoi(e) != 0;
-    if (rb2) {
-      wg = 0;
-      for (int g = 0; g < n_groups; ++g) {
-        T.first_wg[g] = wg;
-        wg += ((T.g[g].a.rows + 31) / 32 + 7) / 8;
-      }
-      T.first_wg[n_groups] = wg;
+    for (int i = 0; i < n; ++i) pairs += ((groups[order[i]].rows + 31) / 32 + 1) / 2;
+    if (sw.agg_rb2 >= 0 ? sw.agg_rb2 != 0 : pairs >= rb2_min_pairs(sw)) {
       // LDS for the staged ori rows of the pairwise gather (GN_POOL_STAGE = 0 switches it off)
-      const bool no_stage = getenv("GN_POOL_STAGE") != nullptr && atoi(getenv("GN_POOL_STAGE")) == 0;   // (per call)
       size_t sb = 0;
-      for (int g = 0; g < n_groups && !no_stage; ++g) {
-        const gn_agg_group_t& a = T.g[g].a;
-        if (a.eo != nullptr || a.H != nullptr || !a.sym) continue;
+      for (int i = 0; i < n; ++i) {
+        const gn_agg_group_t& a = groups[order[i]];
+        p.wgs[order[i]] = ((a.rows + 31) / 32 + 7) / 8;
+        if (!sw.pool_stage || a.eo != nullptr || a.H != nullptr || !a.sym) continue;
         const size_t b = (size_t)pool_stage_nodes(256, a.E, a.N) * PoolStage<__bf16>::kPitch * sizeof(__bf16);
         if (b <= 48 * 1024 && b > sb) sb = b;
       }
-      hipLaunchKernelGGL((agg_rb2_kernel<__bf16>), dim3(table_xcd_grid(T)), dim3(256), sb, stream, T, (int)sb);
-      return gn_check_launch();
+      p.kernel = GN_K_AGG_RB2;
+      p.precision = 1;
+      p.dyn_lds = p.stage_bytes = (int)sb;
+      plan_grid(p, n, order, true, sw);
+      return GN_OK;
     }
   }
   // fused hyper gather in line layout (bf16-core kernels; GN_AGG_LINES = 0 keeps the per-lane gather): needs the LDS too
-  const bool no_lines = getenv("GN_AGG_LINES") != nullptr && atoi(getenv("GN_AGG_LINES")) == 0;
   // ... or, when the scenes of a workgroup's rows fit the LDS, from their ori rows staged there (GN_AGG_HSTAGE = 0
   // keeps the line-layout gather): lines = 2
-  const bool no_hstage = getenv("GN_AGG_HSTAGE") != nullptr && atoi(getenv("GN_AGG_HSTAGE")) == 0;
   size_t stage_need = 0;
-  for (int g = 0; g < n_groups; ++g) {
-    const gn_agg_group_t& a = T.g[g].a;
-    T.g[g].lines = (xm && !no_lines && a.A == nullptr && a.eo == nullptr && a.H != nullptr && a.N <= 64) ? 1 : 0;
-    if (T.g[g].lines && !no_hstage) {
-      const int nodes = T.g[g].spw > 0 ? T.g[g].spw * a.N : pool_stage_nodes(128 / T.g[g].wpr, a.E, a.N);
+  for (int i = 0; i < n; ++i) {
+    const int g = order[i];
+    const gn_agg_group_t& a = groups[g];
+    p.lines[g] = (xm && sw.agg_lines && a.A == nullptr && a.eo == nullptr && a.H != nullptr && a.N <= 64) ? 1 : 0;
+    if (p.lines[g] && sw.agg_hstage) {
+      const int nodes = p.spw[g] > 0 ? p.spw[g] * a.N : pool_stage_nodes(128 / p.wpr[g], a.E, a.N);
       const size_t b = (size_t)nodes * (twin ? PoolStage<__bf16>::kPitch * sizeof(__bf16) : PoolStage<float>::kPitch * sizeof(float));
       if (b <= 44 * 1024) {
-        T.g[g].lines = 2;
+        p.lines[g] = 2;
         stage_need = b > stage_need ? b : stage_need;
       }
     }
   }
-  for (int g = 0; g < n_groups; ++g)      // the fused closing stage of a hyper group reads its scenes' rows from the stage
-    if (T.g[g].spw > 0 && T.g[g].lines != 2) return GN_ERR_SHAPE;
+  for (int i = 0; i < n; ++i)      // the fused closing stage of a hyper group reads its scenes' rows from the stage
+    if (p.spw[order[i]] > 0 && p.lines[order[i]] != 2) return GN_ERR_SHAPE;
   bool need_part = false;       // LDS for partial sums (wpr > 1), the staged node rows or the line-layout gather
-  for (int g = 0; g < n_groups; ++g) {
-    need_part = need_part || T.g[g].wpr > 1 || T.g[g].stage != 0 || T.g[g].lines != 0;
-    if (T.g[g].a.node_form) {   // second stage buffer of the row block's scenes + the block's type weights / scene form
-      const size_t b = (size_t)node_form_lds_floats(T.g[g].a.N, T.g[g].a.K) * sizeof(float);
+  bool any_pair = false;        // a per-pair form of the pairwise graph in this launch: the instantiation that has them
+  for (int i = 0; i < n; ++i) {
+    const int g = order[i];
+    need_part = need_part || p.wpr[g] > 1 || p.stage[g] != 0 || p.lines[g] != 0;
+    any_pair = any_pair || (groups[g].A != nullptr && !groups[g].node_form);
+    if (groups[g].node_form) {   // second stage buffer of the row block's scenes + the block's type weights / scene form
+      const size_t b = (size_t)node_form_lds_floats(groups[g].N, groups[g].K) * sizeof(float);
       need_part = true;
       stage_need = b > stage_need ? b : stage_need;
     }
   }
-  const size_t part_bytes = need_part ? (stage_need > kAggPartBytes ? stage_need : (size_t)kAggPartBytes) : 0;
-  bool any_pair = false;        // a per-pair form of the pairwise graph in this launch: the instantiation that has them
-  for (int g = 0; g < n_groups; ++g) any_pair = any_pair || (groups[g].A != nullptr && !groups[g].node_form);
-  if (twin)
-    hipLaunchKernelGGL((agg_x_kernel<1, __bf16, false>), dim3(table_xcd_grid(T)), dim3(256), part_bytes, stream, T);
-  else if (xm) {
-    const int hm = x_mode(groups, n_groups, [](const gn_agg_group_t& G) {
-      return (G.A != nullptr ? G.W2h : G.W12h) != nullptr;
-    });
-    if (hm < 0) return GN_ERR_SHAPE;
-    const dim3 grid(table_xcd_grid(T));
-    if (hm && any_pair)
-      hipLaunchKernelGGL((agg_x_kernel<2, float, true>), grid, dim3(256), part_bytes, stream, T);
-    else if (hm)
-      hipLaunchKernelGGL((agg_x_kernel<2, float, false>), grid, dim3(256), part_bytes, stream, T);
-    else if (any_pair)
-      hipLaunchKernelGGL((agg_x_kernel<3, float, true>), grid, dim3(256), part_bytes, stream, T);
+  if (!xm) {
+    p.kernel = GN_K_AGG_MLP;
+    plan_grid(p, n, order, false, sw);
+    return GN_OK;
+  }
+  p.kernel = GN_K_AGG_X;
+  p.precision = 1;
+  if (!twin) {
+    const auto has_h = [](const gn_agg_group_t& G) { return (G.A != nullptr ? G.W2h : G.W12h) != nullptr; };
+    int hc = 0;
+    for (int i = 0; i < n; ++i) hc += has_h(groups[order[i]]) ? 1 : 0;
+    if (hc != 0 && hc != n) return GN_ERR_SHAPE;
+    p.precision = hc ? 2 : 3;
+    p.variant = any_pair ? 1 : 0;
+  }
+  p.dyn_lds = (int)(need_part ? (stage_need > kAggPartBytes ? stage_need : (size_t)kAggPartBytes) : 0);
+  plan_grid(p, n, order, true, sw);
+  return GN_OK;
+}
+template <typename F>
+static int agg_dispatch(const gn_launch_plan_t& p, F&& f) {
+  switch (p.kernel == GN_K_AGG_X ? 2 * p.precision + p.variant : -p.kernel) {
+    case 2: return f(agg_x_kernel<1, __bf16, false>);
+    case 4: return f(agg_x_kernel<2, float, false>);
+    case 5: return f(agg_x_kernel<2, float, true>);
+    case 6: return f(agg_x_kernel<3, float, false>);
+    case 7: return f(agg_x_kernel<3, float, true>);
+    case -GN_K_AGG_RB2: return f(agg_rb2_kernel<__bf16>);
+    default: return f(agg_mlp_kernel);
+  }
+}
+static int agg_launch(const gn_launch_plan_t& p, const int* order, int n, const gn_agg_group_t* groups, hipStream_t stream) {
+  for (int g = 0; g < p.n_groups; ++g)
+    if (p.pre_grid[g] > 0) {
+      hipLaunchKernelGGL((agg_scene_kernel<__bf16>), dim3(p.pre_grid[g]), dim3(256), (size_t)p.pre_lds[g], stream, groups[g]);
+      GN_CHECK(gn_check_launch());
+    }
+  if (n == 0) return GN_OK;
+  GroupTable<AggGroup> T{};
+  T.n = n;
+  for (int i = 0; i < n; ++i) {
+    const int g = order[i];
+    T.g[i] = AggGroup{groups[g], p.wpr[g], p.stage[g], p.lines[g], p.spw[g]};
+  }
+  table_first_wg(T, p, order);
+  if (p.kernel != GN_K_AGG_MLP) table_xcd_grid(T, p.xcd != 0);
+  return agg_dispatch(p, [&](auto k) {
+    if constexpr (std::is_invocable_v<decltype(k), decltype(T), int>)
+      hipLaunchKernelGGL(k, dim3(p.grid[0]), dim3(256), (size_t)p.dyn_lds, stream, T, p.stage_bytes);
     else
-      hipLaunchKernelGGL((agg_x_kernel<3, float, false>), grid, dim3(256), part_bytes, stream, T);
-  } else
-    hipLaunchKernelGGL(agg_mlp_kernel, dim3(wg), dim3(256), 0, stream, T);
-  return gn_check_launch();
+      hipLaunchKernelGGL(k, dim3(p.grid[0]), dim3(256), (size_t)p.dyn_lds, stream, T);
+    return gn_check_launch();
+  });
+}
+static int agg_entry(const gn_agg_group_t* groups, int n_groups, bool twin, gn_stream_t stream, gn_launch_plan_t* plan) {
+  gn_launch_plan_t p;
+  int order[GN_MAX_GROUPS], n = 0;
+  GN_CHECK(agg_plan(groups, n_groups, twin, gn_read_switches(), plan != nullptr ? *plan : p, order, n));
+  return plan != nullptr ? GN_OK : agg_launch(p, order, n, groups, (hipStream_t)stream);
 }
 extern "C" int gn_agg_mlp_f32(const gn_agg_group_t* groups, int n_groups, gn_stream_t stream) {
-  return agg_launch(groups, n_groups, (hipStream_t)stream, false);
+  return agg_entry(groups, n_groups, false, stream, nullptr);
 }
 extern "C" int gn_agg_mlp_bf16(const gn_agg_group_t* groups, int n_groups, gn_stream_t stream) {
-  return agg_launch(groups, n_groups, (hipStream_t)stream, true);
+  return agg_entry(groups, n_groups, true, stream, nullptr);
+}
+extern "C" int gn_agg_mlp_plan_f32(const gn_agg_group_t* groups, int n_groups, gn_launch_plan_t* plan) {
+  GN_REQUIRE_PTR(plan);
+  return agg_entry(groups, n_groups, false, nullptr, plan);
+}
+extern "C" int gn_agg_mlp_plan_bf16(const gn_agg_group_t* groups, int n_groups, gn_launch_plan_t* plan) {
+  GN_REQUIRE_PTR(plan);
+  return agg_entry(groups, n_groups, true, nullptr, plan);
 }
 
 extern "C" int gn_node_linear_f32(const float* x, const float* W, const float* bias, float* y, int rows, int dout,
@@ -1395,53 +1542,9 @@ extern "C" int gn_node_linear_f32(const float* x, const float* W, const float* b
   return gn_check_launch();
 }
 
-template <int P, typename T>
-static int mlp2_x_launch(GroupTable<gn_mlp2_group_t>& T_, int n_groups, int rows, int din, int dh, int dout, int ldy,
-                         int N, float divisor, hipStream_t s) {
-  const int OT = (dout + 31) / 32;
-  // a small launch: 4 waves per row block (mlp2_xs_kernel; its fused scatter reads every hyperedge of the scene, so
-  // hyper groups need E <= 16).  GN_MLP2_XS = 0 / 1 forces the choice (parity tests run both)
-  const int blocks32 = (rows + 31) / 32;
-  bool xs = (long long)blocks32 * n_groups <= 1536;      // (restated in tests/launch_forms.py expected_forms)
-  if (const char* e = getenv("GN_MLP2_XS")) xs = atoi(e) != 0;
-  for (int g = 0; g < n_groups; ++g)
-    if (T_.g[g].x == nullptr && T_.g[g].H != nullptr && T_.g[g].E > 16) xs = false;
-  if (xs) {
-    for (int g = 0; g <= n_groups; ++g) T_.first_wg[g] = g * blocks32;
-    const dim3 grid(table_xcd_grid(T_)), block(256);
-#define GN_MLP2XS(IT, HT, OTv) \
-  hipLaunchKernelGGL((mlp2_xs_kernel<P, T, IT, HT, OTv>), grid, block, 0, s, T_, rows, dout, ldy, N, divisor)
-    if (din == 64 && dh == 128 && OT == 1) GN_MLP2XS(2, 4, 1);
-    else if (din == 64 && dh == 128) GN_MLP2XS(2, 4, 2);
-    else if (din == 128 && dh == 128 && OT == 1) GN_MLP2XS(4, 4, 1);
-    else if (din == 128 && dh == 128) GN_MLP2XS(4, 4, 2);
-    else if (din == 64 && dh == 256 && OT == 1) GN_MLP2XS(2, 8, 1);
-    else if (din == 64 && dh == 256) GN_MLP2XS(2, 8, 2);
-    else if (din == 128 && dh == 256 && OT == 1) GN_MLP2XS(4, 8, 1);
-    else if (din == 128 && dh == 256) GN_MLP2XS(4, 8, 2);
-    else return GN_ERR_SHAPE;
-#undef GN_MLP2XS
-    return gn_check_launch();
-  }
-  for (int g = 0; g <= n_groups; ++g) T_.first_wg[g] = g * row_grid(rows);
-  const dim3 grid(table_xcd_grid(T_)), block(256);
-#define GN_MLP2X(IT, HT, OTv) \
-  hipLaunchKernelGGL((mlp2_x_kernel<P, T, IT, HT, OTv>), grid, block, 0, s, T_, rows, dout, ldy, N, divisor)
-  if (din == 64 && dh == 128 && OT == 1) GN_MLP2X(2, 4, 1);
-  else if (din == 64 && dh == 128) GN_MLP2X(2, 4, 2);
-  else if (din == 128 && dh == 128 && OT == 1) GN_MLP2X(4, 4, 1);
-  else if (din == 128 && dh == 128) GN_MLP2X(4, 4, 2);
-  else if (din == 64 && dh == 256 && OT == 1) GN_MLP2X(2, 8, 1);
-  else if (din == 64 && dh == 256) GN_MLP2X(2, 8, 2);
-  else if (din == 128 && dh == 256 && OT == 1) GN_MLP2X(4, 8, 1);
-  else if (din == 128 && dh == 256) GN_MLP2X(4, 8, 2);
-  else return GN_ERR_SHAPE;
-#undef GN_MLP2X
-  return gn_check_launch();
-}
-
-static int mlp2_launch(const gn_mlp2_group_t* groups, int n_groups, int rows, int din, int dh, int dout, int ldy,
-                       int N, float divisor, hipStream_t s, bool twin) {
+// ---- closing MLP -------------------------------------------------------------------------------------------------
+static int mlp2_plan(const gn_mlp2_group_t* groups, int n_groups, int rows, int din, int dh, int dout, int ldy, int N,
+                     float divisor, bool twin, const GnSwitches& sw, gn_launch_plan_t& p) {
   GN_CHECK(check_groups(groups, n_groups));
   if (rows <= 0 || dout <= 0 || ldy < dout) return GN_ERR_SHAPE;
   int xm = x_mode(groups, n_groups, [](const gn_mlp2_group_t& G) { return G.Wx != nullptr; });
@@ -1452,8 +1555,9 @@ static int mlp2_launch(const gn_mlp2_group_t* groups, int n_groups, int rows, in
     for (int g = 0; g < n_groups; ++g)
       if (groups[g].W == nullptr) return GN_ERR_NULL;
   }
-  GroupTable<gn_mlp2_group_t> T{};
-  T.n = n_groups;
+  plan_begin(p, n_groups);
+  bool fused = false;   // (also set when activations are to be kept: only the whole-chain kernel writes them)
+  bool wide_hyper = false;
   for (int g = 0; g < n_groups; ++g) {
     const gn_mlp2_group_t& G = groups[g];
     if (G.x != nullptr) {
@@ -1471,48 +1575,104 @@ static int mlp2_launch(const gn_mlp2_group_t* groups, int n_groups, int rows, in
     GN_CHECK(need(G.bias, true));
     GN_CHECK(need(G.y, false));
     if (twin && (G.in_out != nullptr || G.hid_out != nullptr)) return GN_ERR_SHAPE;
-    T.g[g] = G;
+    fused = fused || G.x == nullptr || G.in_out != nullptr || G.hid_out != nullptr;
+    wide_hyper = wide_hyper || (G.x == nullptr && G.H != nullptr && G.E > 16);
+    p.pos[g] = g;
   }
-  if (twin) return mlp2_x_launch<1, __bf16>(T, n_groups, rows, din, dh, dout, ldy, N, divisor, s);
-  if (xm) {
-    const int hm = x_mode(groups, n_groups, [](const gn_mlp2_group_t& G) { return G.Wh != nullptr; });
-    if (hm < 0) return GN_ERR_SHAPE;
-    return hm ? mlp2_x_launch<2, float>(T, n_groups, rows, din, dh, dout, ldy, N, divisor, s)
-              : mlp2_x_launch<3, float>(T, n_groups, rows, din, dh, dout, ldy, N, divisor, s);
-  }
-  const dim3 block(256);
+  // the instantiation: 32-wide tiles of din (64 | 128) and dh (128 | 256); the bf16-core kernels also of dout (<= 64)
+  const bool widths_ok = (din == 64 || din == 128) && (dh == 128 || dh == 256);
+  p.tiles[0] = din / 32;
+  p.tiles[1] = dh / 32;
   const int blocks32 = (rows + 31) / 32;
-  bool fused = false;   // (also set when activations are to be kept: only the whole-chain kernel writes them)
-  for (int g = 0; g < n_groups; ++g)
-    fused = fused || groups[g].x == nullptr || groups[g].in_out != nullptr || groups[g].hid_out != nullptr;
+  if (xm) {
+    if (!twin) {
+      const int hm = x_mode(groups, n_groups, [](const gn_mlp2_group_t& G) { return G.Wh != nullptr; });
+      if (hm < 0) return GN_ERR_SHAPE;
+      p.precision = hm ? 2 : 3;
+    } else
+      p.precision = 1;
+    if (!widths_ok) return GN_ERR_SHAPE;
+    p.tiles[2] = dout <= 32 ? 1 : 2;
+    // a small launch: 4 waves per row block (mlp2_xs_kernel; its fused scatter reads every hyperedge of the scene, so
+    // hyper groups need E <= 16).  GN_MLP2_XS = 0 / 1 forces the choice (parity tests run both)
+    const bool xs = (sw.mlp2_xs >= 0 ? sw.mlp2_xs != 0 : (long long)blocks32 * n_groups <= 1536) && !wide_hyper;
+    p.kernel = xs ? GN_K_MLP2_XS : GN_K_MLP2_X;
+    for (int g = 0; g < n_groups; ++g) p.wgs[g] = xs ? blocks32 : row_grid(rows);
+    plan_grid(p, n_groups, nullptr, true, sw);
+    return GN_OK;
+  }
   const bool use_split = dh == 128 && dout <= 64 && (long long)blocks32 * n_groups <= 1024 && (din == 64 || din == 128) &&
                          !fused;   // the fused-scatter prologue would be repeated by all 4 waves of a row block
-  if (use_split) {
-    const dim3 grid(blocks32, n_groups);
-    if (din == 64)
-      hipLaunchKernelGGL((mlp2_split_kernel<2>), grid, block, 0, s, T, rows, dout, ldy, N, divisor);
-    else
-      hipLaunchKernelGGL((mlp2_split_kernel<4>), grid, block, 0, s, T, rows, dout, ldy, N, divisor);
-    return gn_check_launch();
+  if (!use_split && !widths_ok) return GN_ERR_SHAPE;
+  p.kernel = use_split ? GN_K_MLP2_SPLIT : GN_K_MLP2;
+  p.grid[0] = use_split ? blocks32 : row_grid(rows);
+  p.grid[1] = n_groups;
+  for (int g = 0; g < n_groups; ++g) p.wgs[g] = p.grid[0];
+  return GN_OK;
+}
+// the (IT, HT, OT) instantiations of the two bf16-core kernels
+template <int P, typename T, typename F>
+static int mlp2_x_dispatch(const gn_launch_plan_t& p, F&& f) {
+  const bool xs = p.kernel == GN_K_MLP2_XS;
+#define GN_MLP2_CASE(IT, HT, OT) \
+  case IT * 100 + HT * 10 + OT: return xs ? f(mlp2_xs_kernel<P, T, IT, HT, OT>) : f(mlp2_x_kernel<P, T, IT, HT, OT>)
+  switch (p.tiles[0] * 100 + p.tiles[1] * 10 + p.tiles[2]) {
+    GN_MLP2_CASE(2, 4, 1);
+    GN_MLP2_CASE(2, 4, 2);
+    GN_MLP2_CASE(4, 4, 1);
+    GN_MLP2_CASE(4, 4, 2);
+    GN_MLP2_CASE(2, 8, 1);
+    GN_MLP2_CASE(2, 8, 2);
+    GN_MLP2_CASE(4, 8, 1);
+    GN_MLP2_CASE(4, 8, 2);
   }
-  const dim3 grid(row_grid(rows), n_groups);
-  if (din == 64 && dh == 128)
-    hipLaunchKernelGGL((mlp2_kernel<2, 4>), grid, block, 0, s, T, rows, dout, ldy, N, divisor);
-  else if (din == 64 && dh == 256)
-    hipLaunchKernelGGL((mlp2_kernel<2, 8>), grid, block, 0, s, T, rows, dout, ldy, N, divisor);
-  else if (din == 128 && dh == 128)
-    hipLaunchKernelGGL((mlp2_kernel<4, 4>), grid, block, 0, s, T, rows, dout, ldy, N, divisor);
-  else if (din == 128 && dh == 256)
-    hipLaunchKernelGGL((mlp2_kernel<4, 8>), grid, block, 0, s, T, rows, dout, ldy, N, divisor);
-  else
-    return GN_ERR_SHAPE;
-  return gn_check_launch();
+#undef GN_MLP2_CASE
+  return GN_ERR_SHAPE;
+}
+template <typename F>
+static int mlp2_dispatch(const gn_launch_plan_t& p, F&& f) {
+  if (p.precision == 1) return mlp2_x_dispatch<1, __bf16>(p, f);
+  if (p.precision == 2) return mlp2_x_dispatch<2, float>(p, f);
+  if (p.precision == 3) return mlp2_x_dispatch<3, float>(p, f);
+  if (p.kernel == GN_K_MLP2_SPLIT) return p.tiles[0] == 2 ? f(mlp2_split_kernel<2>) : f(mlp2_split_kernel<4>);
+  if (p.tiles[0] == 2) return p.tiles[1] == 4 ? f(mlp2_kernel<2, 4>) : f(mlp2_kernel<2, 8>);
+  return p.tiles[1] == 4 ? f(mlp2_kernel<4, 4>) : f(mlp2_kernel<4, 8>);
+}
+static int mlp2_launch(const gn_launch_plan_t& p, const gn_mlp2_group_t* groups, int rows, int dout, int ldy, int N,
+                       float divisor, hipStream_t s) {
+  GroupTable<gn_mlp2_group_t> T{};
+  T.n = p.n_groups;
+  for (int g = 0; g < T.n; ++g) T.g[g] = groups[g];
+  if (p.precision != 0) {
+    table_first_wg(T, p, nullptr);
+    table_xcd_grid(T, p.xcd != 0);
+  }
+  return mlp2_dispatch(p, [&](auto k) {
+    hipLaunchKernelGGL(k, dim3(p.grid[0], p.grid[1]), dim3(256), 0, s, T, rows, dout, ldy, N, divisor);
+    return gn_check_launch();
+  });
+}
+static int mlp2_entry(const gn_mlp2_group_t* groups, int n_groups, int rows, int din, int dh, int dout, int ldy, int N,
+                      float divisor, bool twin, gn_stream_t stream, gn_launch_plan_t* plan) {
+  gn_launch_plan_t p;
+  GN_CHECK(mlp2_plan(groups, n_groups, rows, din, dh, dout, ldy, N, divisor, twin, gn_read_switches(), plan != nullptr ? *plan : p));
+  return plan != nullptr ? GN_OK : mlp2_launch(p, groups, rows, dout, ldy, N, divisor, (hipStream_t)stream);
 }
 extern "C" int gn_mlp2_f32(const gn_mlp2_group_t* groups, int n_groups, int rows, int din, int dh, int dout, int ldy,
                            int N, float divisor, gn_stream_t stream) {
-  return mlp2_launch(groups, n_groups, rows, din, dh, dout, ldy, N, divisor, (hipStream_t)stream, false);
+  return mlp2_entry(groups, n_groups, rows, din, dh, dout, ldy, N, divisor, false, stream, nullptr);
 }
 extern "C" int gn_mlp2_bf16(const gn_mlp2_group_t* groups, int n_groups, int rows, int din, int dh, int dout, int ldy,
                             int N, float divisor, gn_stream_t stream) {
-  return mlp2_launch(groups, n_groups, rows, din, dh, dout, ldy, N, divisor, (hipStream_t)stream, true);
+  return mlp2_entry(groups, n_groups, rows, din, dh, dout, ldy, N, divisor, true, stream, nullptr);
+}
+extern "C" int gn_mlp2_plan_f32(const gn_mlp2_group_t* groups, int n_groups, int rows, int din, int dh, int dout, int ldy,
+                                int N, float divisor, gn_launch_plan_t* plan) {
+  GN_REQUIRE_PTR(plan);
+  return mlp2_entry(groups, n_groups, rows, din, dh, dout, ldy, N, divisor, false, nullptr, plan);
+}
+extern "C" int gn_mlp2_plan_bf16(const gn_mlp2_group_t* groups, int n_groups, int rows, int din, int dh, int dout, int ldy,
+                                 int N, float divisor, gn_launch_plan_t* plan) {
+  GN_REQUIRE_PTR(plan);
+  return mlp2_entry(groups, n_groups, rows, din, dh, dout, ldy, N, divisor, true, nullptr, plan);
 }

@@ -589,32 +589,27 @@ def node_form_enabled() -> bool:
     return os.environ.get("GN_NODE_FORM", "1") != "0"
 
 
+def _closing_askable(items, pks2: Sequence[dict]) -> bool:
+    """What a descriptor of the aggregation launch cannot say about its closing stage: the A/B switches, the closing MLP
+    being 128 -> 128 -> dout with its bf16-core image, and every group naming its nodes (an `eo` tensor does not)."""
+    return (BF16X6 and closing_fusion_enabled()
+            and all((pk2["din"], pk2["dh"]) == (2 * FEAT, 128) and _ximg(pk2, "mlp2", torch.float32) != 0 for pk2 in pks2)
+            and all(isinstance(src, (PairSpec, GatherSpec)) for src, _, _, _ in items))
+
+
+def _plan_takes_closing(arr, n: int, dt: torch.dtype) -> bool:
+    plan = _lib.LaunchPlan()
+    return _fn("gn_agg_mlp_plan", dt)(arr, n, ctypes.byref(plan)) == _lib.GN_OK and bool(plan.closing)
+
+
 def closing_fusable(items: Sequence[Tuple[object, Tensor, dict, int]], pks2: Sequence[dict]) -> bool:
-    """Can gn_agg_mlp_f32 apply the closing MLPs itself (gn_agg_group_t.y)?  Mirrors the launcher's rules: fp32
-    results on the 16-bit matrix cores, N <= 16, every group the node form of the pairwise graph or a hyper module with
-    the fused gather whose edge rows run more than one wave per row block (< 768 row blocks), a 128 -> 128 -> dout <= 64 MLP.
-    (tests/launch_forms.py expected_forms restates these rules.)"""
-    if not (BF16X6 and closing_fusion_enabled()):
+    """Can gn_agg_mlp_f32 apply the closing MLPs itself (gn_agg_group_t.y)?  Asks the launcher's plan
+    (gn_agg_mlp_plan_*) with the descriptors of that launch, outputs as placeholders: every launch rule is the library's
+    (`_closing_askable`: what a descriptor cannot say).  `agg_mlp_closing` asks and launches with one descriptor array."""
+    if not _closing_askable(items, pks2):
         return False
-    if os.environ.get("GN_AGG_HSTAGE", "1") == "0" or os.environ.get("GN_AGG_LINES", "1") == "0":
-        return False      # (the fused stage reads its scenes' rows from the LDS stage)
-    for (src, ef, pk, K), pk2 in zip(items, pks2):
-        if (pk2["din"], pk2["dh"]) != (2 * FEAT, 128) or not (32 < pk2["dout"] <= 64) or _ximg(pk2, "mlp2", torch.float32) == 0:
-            return False
-        if isinstance(src, PairSpec):
-            if not src.node or src.A.dtype != torch.float32:
-                return False
-        elif isinstance(src, GatherSpec):
-            if src.H is None or src.ori.dtype != torch.float32:
-                return False
-            B, E, N = src.H.shape
-            if N > 16 or E > 16 or (B * E + 31) // 32 >= 768 or (B * E + 31) // 32 < 1:
-                return False
-            if (B * E + 31) // 32 < 128 and K < 4:      # (the launcher would run one wave per row block)
-                return False
-        else:
-            return False
-    return True
+    arr, _, _, _, dt = _agg_descriptors(items, [(pk2, None, None) for pk2 in pks2], allocate=False)
+    return _plan_takes_closing(arr, len(items), dt)
 
 
 def closing_fusion_enabled() -> bool:
@@ -622,12 +617,13 @@ def closing_fusion_enabled() -> bool:
     return os.environ.get("GN_FUSE_CLOSING", "1") != "0"
 
 
-def agg_mlp_grouped(items: Sequence[Tuple[object, Tensor, dict, int]],
-                    closing: Optional[Sequence[Tuple[dict, Optional[Tensor], Tensor]]] = None) -> List[Tensor]:
-    """items = [(eo (B,E,64) | GatherSpec | PairSpec, edge_feat (B,E,K) fp32, pk{"W","b1","b2","xi"[,"W2t"]}, K)]
-    -> [feat (B,E,64)] in the storage type of the inputs (bf16 twin: eo / GatherSpec only).
-    ``closing`` (see `closing_fusable`): per item (pk of the closing MLP, out or None, ori (B,N,64)) — the launch then also
-    applies y = MLP(cat(H^T feat, ori) / N) and returns [y (B,N,dout)] instead of the features."""
+_PLACEHOLDER = 16      # an aligned non-NULL "address" of a tensor not allocated yet: a plan query never dereferences it
+
+
+def _agg_descriptors(items, closing=None, allocate: bool = True):
+    """The gn_agg_group_t array of a typed-aggregation launch (arguments of `agg_mlp_grouped`) -> (array, outputs, (flops,
+    reference flops), device, storage type).  allocate=False (a plan query): outputs, and an `ori` of the closing stage
+    that is not known yet (None), are placeholders."""
     _groups(len(items))
     arr = (_lib.AggGroup * len(items))()
     outs = []
@@ -670,16 +666,17 @@ def agg_mlp_grouped(items: Sequence[Tuple[object, Tensor, dict, int]],
         node = isinstance(eo, (PairSpec, GatherSpec)) and eo.node
         if closing is not None:
             pk2, out2, ori2 = closing[g]
-            _req(ori2, "ori", (B, N, FEAT))
-            y, ldy = _mlp2_out((B, N), pk2["dout"], out2, ori2)
+            if ori2 is not None:
+                _req(ori2, "ori", (B, N, FEAT))
+            y, ldy = _mlp2_out((B, N), pk2["dout"], out2, ori2) if allocate else (None, pk2["dout"])
             # (ori: the pairwise group's node form does not read it — the fused stage reads it from there)
-            fields.update(ori=ori2.data_ptr(), m2x=_ximg(pk2, "mlp2", like.dtype), m2h=_himg(pk2, "mlp2", like.dtype),
-                          m2bias=pk2["bias"].data_ptr(), y=y.data_ptr(), ldy=ldy, dout=pk2["dout"], divisor=float(N))
+            fields.update(ori=fields.get("ori", _PLACEHOLDER) if ori2 is None else ori2.data_ptr(), m2x=_ximg(pk2, "mlp2", like.dtype), m2h=_himg(pk2, "mlp2", like.dtype),
+                          m2bias=pk2["bias"].data_ptr(), y=y.data_ptr() if allocate else _PLACEHOLDER, ldy=ldy, dout=pk2["dout"], divisor=float(N))
             outs.append(y)
             flops2 += B * N * 2 * (128 * 128 + 128 * (((pk2["dout"] + 31) // 32) * 32))
         else:
-            feat = torch.empty((B, N if node else E, FEAT), dtype=like.dtype, device=like.device)
-            fields.update(feat=feat.data_ptr())
+            feat = torch.empty((B, N if node else E, FEAT), dtype=like.dtype, device=like.device) if allocate else None
+            fields.update(feat=feat.data_ptr() if allocate else _PLACEHOLDER)
             outs.append(feat)
         arr[g] = _lib.AggGroup(edge_feat=edge_feat.data_ptr(), W=pk[wkey].data_ptr(), b1=pk["b1"].data_ptr(),
                                b2=pk["b2"].data_ptr(), rows=B * E, K=K, **fields)
@@ -694,12 +691,40 @@ def agg_mlp_grouped(items: Sequence[Tuple[object, Tensor, dict, int]],
         # the pairwise graph — through both layers of every type
         pairwise = isinstance(eo, PairSpec) or (isinstance(eo, GatherSpec) and eo.H is None)
         ref_flops += B * (N * N if pairwise else E) * K * (2 * 64 * 128 + 2 * 128 * 64 + 2 * 64)
-    flops = (flops + flops2, ref_flops + flops2)
+    return arr, outs, (flops + flops2, ref_flops + flops2), dev0, dt
+
+
+def agg_mlp_grouped(items: Sequence[Tuple[object, Tensor, dict, int]],
+                    closing: Optional[Sequence[Tuple[dict, Optional[Tensor], Tensor]]] = None) -> List[Tensor]:
+    """items = [(eo (B,E,64) | GatherSpec | PairSpec, edge_feat (B,E,K) fp32, pk{"W","b1","b2","xi"[,"W2t"]}, K)]
+    -> [feat (B,E,64)] in the storage type of the inputs (bf16 twin: eo / GatherSpec only).
+    ``closing`` (see `closing_fusable`): per item (pk of the closing MLP, out or None, ori (B,N,64)) — the launch then also
+    applies y = MLP(cat(H^T feat, ori) / N) and returns [y (B,N,dout)] instead of the features."""
+    arr, outs, flops, dev0, dt = _agg_descriptors(items, closing)
+    return _agg_launch(arr, outs, flops, dev0, dt)
+
+
+def agg_mlp_closing(items, closing: Sequence[Tuple[dict, Optional[Tensor], Tensor]]) -> Optional[List[Tensor]]:
+    """`agg_mlp_grouped(items, closing)` where the launcher's plan takes the closing stage (`closing_fusable`), else None
+    and nothing is launched.  One descriptor array serves the question and the launch: it is built with placeholder
+    outputs, and the outputs are allocated once the plan has accepted."""
+    if not _closing_askable(items, [pk2 for pk2, _, _ in closing]):
+        return None
+    arr, outs, flops, dev0, dt = _agg_descriptors(items, closing, allocate=False)
+    if not _plan_takes_closing(arr, len(items), dt):
+        return None
+    for g, (pk2, out2, ori2) in enumerate(closing):
+        outs[g], arr[g].ldy = _mlp2_out(tuple(ori2.shape[:2]), pk2["dout"], out2, ori2)
+        arr[g].y = outs[g].data_ptr()
+    return _agg_launch(arr, outs, flops, dev0, dt)
+
+
+def _agg_launch(arr, outs, flops, dev0, dt) -> List[Tensor]:
     # (the scene-form groups of the twins run in their own kernel ahead of the others' launch, on the same stream: forked
     # onto a side stream beside it they were measured at config 4 — single-stream 0.791 -> 0.784 ms, but 4-stream
     # throughput 1.445 -> 1.338 M scenes/s — and the fork was not kept)
     with torch.cuda.device(dev0), _Probed("agg_mlp_kernel", flops):
-        check(_fn("gn_agg_mlp", dt)(arr, len(items), stream_handle()), "gn_agg_mlp")
+        check(_fn("gn_agg_mlp", dt)(arr, len(arr), stream_handle()), "gn_agg_mlp")
     return outs
 
 

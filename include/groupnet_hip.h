@@ -233,7 +233,7 @@ int gn_node_mlp_affinity_bf16(const gn_node_group_t* groups, int n_groups, int r
 size_t gn_affinity_tail_lds_limit(void);
 /* Resources of a launch instead of the launch (ABI 35; a host can check the residency it budgets for, the test suite
  * does): what gn_node_mlp_affinity_f32 would pass as dynamic LDS for these arguments (the scene tile of the affinity
- * tail), and the workgroups per CU the HIP runtime grants the kernel with it (hipOccupancyMaxActiveBlocksPerMultiprocessor).
+ * tail: gn_node_mlp_plan_f32's dyn_lds), and the workgroups per CU the HIP runtime grants the kernel with it (hipOccupancyMaxActiveBlocksPerMultiprocessor).
  * Same argument checks as the launcher; nothing is launched. */
 int gn_node_mlp_affinity_launch_info_f32(const gn_node_group_t* groups, int n_groups, int rows, const gn_affinity_job_t* job,
                                          size_t* dyn_lds, int* wgs_per_cu);
@@ -488,6 +488,82 @@ int gn_mlp2_f32(const gn_mlp2_group_t* groups, int n_groups, int rows, int din, 
 /* twin: dout <= 64 */
 int gn_mlp2_bf16(const gn_mlp2_group_t* groups, int n_groups, int rows, int din, int dh, int dout, int ldy,
                  int N, float divisor, gn_stream_t stream);
+
+/* ---- launch plans (ABI 36) ---------------------------------------------------------------------
+ * What a forward launcher would launch for its arguments, without launching: every launcher below is "plan, then launch",
+ * and gn_*_plan_* return the plan alone.  A plan is decided on the host from the descriptors, the scalar arguments, the
+ * storage type and the per-call environment switches (GN_XCD, GN_POOL_STAGE, GN_AGG_LINES, GN_AGG_HSTAGE, GN_AGG_RB2,
+ * GN_EDGE_RB2, GN_RB2_MIN_PAIRS, GN_MLP2_XS, GN_N2E_ROWS; read once per call): no HIP call, no GPU needed, device addresses
+ * are only tested for NULL and alignment (a not yet allocated output may be any aligned non-NULL placeholder).  The
+ * return value is the launcher's for the same arguments; on an error the plan's content is unspecified.
+ * Per-group arrays are in the caller's group order. */
+#define GN_K_NONE 0                  /* no main launch (every group ran in a launch of its own, see pre_grid) */
+#define GN_K_NODE_STAGE 1
+#define GN_K_NODE_MLP_SPLIT 2
+#define GN_K_NODE_MLP 3
+#define GN_K_EDGE_X 4
+#define GN_K_EDGE_RB2 5
+#define GN_K_EDGE_MLP_GUMBEL 6
+#define GN_K_AGG_X 7
+#define GN_K_AGG_RB2 8
+#define GN_K_AGG_MLP 9
+#define GN_K_MLP2_XS 10
+#define GN_K_MLP2_X 11
+#define GN_K_MLP2_SPLIT 12
+#define GN_K_MLP2 13
+#define GN_K_NODE2EDGE 14
+#define GN_K_AGG_GATHER 15
+typedef struct {
+  int kernel;        /* GN_K_*: the kernel of the launch (gn_kernel_name), instantiated for ... */
+  int precision;     /* ... 0: the plain fp32 weight stream, 1: bf16 storage (the twins), 2: f16x3, 3: bf16x6 */
+  int variant;       /* ... agg_x_kernel: 1 = with the per-pair forms of the pairwise graph; node2edge_kernel: 1 = row form
+                        (0 = banded) */
+  int tiles[3];      /* ... closing MLP: 32-wide tiles (IT, HT, OT) of din, dh and dout (OT = 0: any dout) */
+  int grid[3];       /* workgroups of the launch (x with XCD order: 8 x the largest per-XCD share) */
+  int dyn_lds;       /* dynamic LDS bytes of the launch */
+  int stage_bytes;   /* LDS stage the kernel is told: edge kernels the pool stage (-1 = GN_POOL_STAGE off), agg_rb2_kernel the
+                        staged ori rows */
+  int xcd;           /* 1: workgroups dealt over the XCDs section by section */
+  int closing;       /* typed aggregation: 1 = the launch carries the fused closing stage (gn_agg_group_t.y) */
+  int n_groups;
+  int wgs[GN_MAX_GROUPS];         /* workgroups of the group in the launch (0 for a group launched on its own) */
+  int wpr[GN_MAX_GROUPS];         /* typed aggregation: waves per 32-row block */
+  int spw[GN_MAX_GROUPS];         /* fused closing stage: scenes per workgroup (0: none) */
+  int stage[GN_MAX_GROUPS];       /* pair form: per-node pre-activations staged in LDS */
+  int lines[GN_MAX_GROUPS];       /* fused hyper gather: 0 per lane, 1 line layout, 2 from staged ori rows */
+  int node_form[GN_MAX_GROUPS];   /* node form (bf16 storage without A: the scene form, in a launch of its own) */
+  int unstaged[GN_MAX_GROUPS];    /* edge_x_kernel: hyper group pooled without a stage, one workgroup per 32-row block */
+  int pos[GN_MAX_GROUPS];         /* the group's position in the launch (typed aggregation: after the cost sort), -1 when
+                                     it is not part of it */
+  int pre_grid[GN_MAX_GROUPS];    /* > 0: the group runs in a launch of its own ahead of the main one, with this grid (bf16
+                                     scene form: agg_scene_kernel; pairwise gather: agg_gather_pairwise_kernel) ... */
+  int pre_lds[GN_MAX_GROUPS];     /* ... and this dynamic LDS */
+  int SGh, EBh;      /* node -> edge: scenes per workgroup and hyperedges per band of the hyper groups (row form: EBh = 0) */
+  int G, TE;         /* gather: scenes per workgroup and hyperedges per tile */
+} gn_launch_plan_t;
+/* "agg_x_kernel", ...: the kernel's name as a kernel trace shows it (without template arguments); NULL for an unknown id */
+const char* gn_kernel_name(int kernel);
+/* job may be NULL: gn_node_mlp_* without, gn_node_mlp_affinity_* with the affinity tail */
+int gn_node_mlp_plan_f32(const gn_node_group_t* groups, int n_groups, int rows, const gn_affinity_job_t* job,
+                         gn_launch_plan_t* plan);
+int gn_node_mlp_plan_bf16(const gn_node_group_t* groups, int n_groups, int rows, const gn_affinity_job_t* job,
+                          gn_launch_plan_t* plan);
+/* static_lds: the static LDS of the launch's kernel, which bounds the pool stage and which only the HIP runtime knows;
+ * negative = ask the runtime (what the launcher does; needs a GPU) */
+int gn_edge_mlp_gumbel_plan_f32(const gn_edge_group_t* groups, int n_groups, float tau, unsigned long long seed,
+                                const unsigned long long* offset_dev, long long static_lds, gn_launch_plan_t* plan);
+int gn_edge_mlp_gumbel_plan_bf16(const gn_edge_group_t* groups, int n_groups, float tau, unsigned long long seed,
+                                 const unsigned long long* offset_dev, long long static_lds, gn_launch_plan_t* plan);
+int gn_agg_mlp_plan_f32(const gn_agg_group_t* groups, int n_groups, gn_launch_plan_t* plan);
+int gn_agg_mlp_plan_bf16(const gn_agg_group_t* groups, int n_groups, gn_launch_plan_t* plan);
+int gn_mlp2_plan_f32(const gn_mlp2_group_t* groups, int n_groups, int rows, int din, int dh, int dout, int ldy, int N,
+                     float divisor, gn_launch_plan_t* plan);
+int gn_mlp2_plan_bf16(const gn_mlp2_group_t* groups, int n_groups, int rows, int din, int dh, int dout, int ldy, int N,
+                      float divisor, gn_launch_plan_t* plan);
+int gn_node2edge_plan_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan);
+int gn_node2edge_plan_bf16(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan);
+int gn_agg_gather_plan_f32(const gn_gather_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan);
+int gn_agg_gather_plan_bf16(const gn_gather_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan);
 
 /* ---- backward (training) building blocks — SURVEY.md §8f rank 2 -------------------------------
  * train_hyper_nba.py:116 back-propagates through the two modules.  The backward of the path is

@@ -36,7 +36,7 @@ def cdiv(a: int, b: int) -> int:
 def xcd_grid(counts: Sequence[int]) -> int:
     """Workgroups of a launch whose groups are dealt over the 8 XCDs in sections (gn_common.hpp gn_xcd_grid)."""
     total = sum(counts)
-    if len(counts) > 16 or total < 64:      # (GN_MAX_SECTIONS = 16)
+    if len(counts) > 32 or total < 64:      # (GN_MAX_SECTIONS = 32)
         return total
     worst = 0
     for x in range(8):
@@ -61,9 +61,9 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
     "mlp2", "n2e", "gather_spw"}; "scene_grid" / "mlp2" / "n2e" / "gather_spw" are None where that launch does not run.
     with_pair=False: the hyper modules alone (one MS_HGNN_hyper through the module API).
 
-    These rules restate the launchers' C code; the comment above each rule in the launchers points back here, and a
-    kernel trace of tests/test_launch_forms_gpu.py's forward cases shows the aggregation grid `agg_grid` (and the scene
-    form's `scene_grid`) for every case."""
+    These rules restate the launchers' plan functions independently of them: tests/test_launch_plan_cpu.py holds the two
+    against each other through the library's plan queries (no GPU), and a kernel trace of tests/test_launch_forms_gpu.py's
+    forward cases shows the aggregation grid `agg_grid` (and the scene form's `scene_grid`) for every case."""
     twin = dtype == "bf16"
     xm = twin or precision != "fp32"            # bf16-core images (ops.BF16X6) or the twins
     mods = ([("pair", None)] if with_pair else []) + [(f"hyper{s}", s) for s in scales]
@@ -137,6 +137,87 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
         gather_spw = G
     return dict(groups=groups, fused_closing=fused, agg_kernel=agg_kernel, agg_wgs=sum(wgs), agg_grid=grid,
                 scene_grid=scene_grid, mlp2=mlp2, n2e=n2e, gather_spw=gather_spw)
+
+
+PLACEHOLDER = 4096      # a 16-aligned non-NULL "device address": a plan query tests addresses, it never dereferences them
+
+
+def launch_descriptors(B: int, N: int, scales: Sequence[int], precision: str = "f16x3", dtype: str = "fp32",
+                       training: bool = False, block: bool = True, with_pair: bool = True) -> Dict:
+    """The C-ABI descriptor arrays `run_message_passing` passes for the last round of such a forward (arguments as
+    `expected_forms`), with its node-form, PoolSpec and closing decisions as `expected_forms` states them and PLACEHOLDER
+    for every device address.  -> {"twin", "edge": arr, "agg": arr (closing MLP in a launch of its own), "agg_closing": arr
+    (the closing stage in the aggregation launch), "mlp2": (arr, rows, din, dh, dout, ldy, N, divisor), "n2e": arr or None,
+    "gather": arr or None}; the group order is that of expected_forms' "groups"."""
+    from groupnet_amd import _lib as L
+    P = PLACEHOLDER
+    twin = dtype == "bf16"
+    xm = twin or precision != "fp32"
+    X = P if xm else 0                              # bf16-core images
+    Hh = P if (precision == "f16x3" and not twin) else 0      # fp16 two-part images
+    forms = expected_forms(B, N, scales, precision, dtype, training, block, with_pair)
+    groups = forms["groups"]
+    n = len(groups)
+    small = N <= FUSED_MAX_N
+    pool = not training and xm                      # run_message_passing.node2edge `fuse`, before the N limit of hyper groups
+    edge, agg, aggc, mlp2, n2e, gather = [], [], [], [], [], []
+    for g in groups:
+        pair, E, K, rows = g["name"] == "pair", g["E"], g["K"], g["rows"]
+        common = dict(bias=P, edge_feat=P, rows=rows, K=K, Wx=X, Wh=Hh, W=P, sym_N=N if pair else 0, dist=P)
+        if pool and (pair or small):
+            edge.append(L.EdgeGroup(xp=P, pq=P, w2=P, b2=P, pool_N=N, pool_H=0 if pair else P, pool_E=0 if pair else E,
+                                    **common))
+        else:
+            edge.append(L.EdgeGroup(edges=P, **common))
+            n2e.append(L.N2EGroup(xp=P, pq=P, H=0 if pair else P, w2=P, edges=P, b2=P, E=E, sym=int(pair)))
+        base = dict(edge_feat=P, W=P, b1=P, b2=P, rows=rows, K=K)
+        if pair and not twin:
+            a = dict(E=E, N=N, sym=1, A=P, W2x=X, W2h=Hh, node_form=int(g["node_form"]))
+        elif pair or small:
+            a = dict(ori=P, H=0 if pair else P, E=E, N=N, sym=int(pair), W12x=X, W12h=Hh, node_form=int(g["node_form"]))
+        else:
+            a = dict(eo=P, W12x=X, W12h=Hh)
+            gather.append(L.GatherGroup(ori=P, H=P, eo=P, E=E, sym=0))
+        agg.append(L.AggGroup(feat=P, **base, **a))
+        aggc.append(L.AggGroup(**base, **{**a, "ori": P}, m2x=X, m2h=Hh, m2bias=P, y=P, ldy=64 * (1 + n) if block else 64,
+                               dout=64, divisor=float(N)))
+        keep = dict(in_out=P, hid_out=P) if training else {}
+        m = dict(W=P, bias=P, y=P, Wx=X, Wh=Hh, **keep)
+        if g["node_form"]:
+            mlp2.append(L.Mlp2Group(feat=P, ori=P, **m))                                   # NodeAggSpec
+        elif small:
+            mlp2.append(L.Mlp2Group(feat=P, H=0 if pair else P, ori=P, E=E, sym=int(pair), **m))   # ScatterSpec
+        else:
+            mlp2.append(L.Mlp2Group(x=P, **m))                                             # stand-alone scatter's output
+    arr = lambda cls, xs: (cls * len(xs))(*xs) if xs else None
+    return dict(twin=twin, edge=arr(L.EdgeGroup, edge), agg=arr(L.AggGroup, agg), agg_closing=arr(L.AggGroup, aggc),
+                mlp2=(arr(L.Mlp2Group, mlp2), B * N, 128, 128, 64, 64 * (1 + n) if block else 64, N, float(N)),
+                n2e=arr(L.N2EGroup, n2e), gather=arr(L.GatherGroup, gather))
+
+
+def assert_plans_match(forms: Dict, agg, mlp2, n2e, gather, where) -> None:
+    """The launchers' plans of one forward (groupnet_amd._lib.LaunchPlan of gn_agg_mlp_plan_*, and of gn_mlp2_plan_* /
+    gn_node2edge_plan_* / gn_agg_gather_plan_* or None where that launch does not run) say what `forms` says."""
+    from groupnet_amd import _lib as L
+    name = lambda plan: L.load().gn_kernel_name(plan.kernel).decode()
+    groups = forms["groups"]
+    n = len(groups)
+    assert agg.n_groups == n and agg.closing == int(forms["fused_closing"]), where
+    for i, g in enumerate(groups):
+        assert (agg.wpr[i], agg.spw[i], bool(agg.node_form[i])) == (g["wpr"], g["spw"], g["node_form"]), (where, g)
+    scene = [agg.pre_grid[i] for i in range(n) if agg.pre_grid[i]]
+    assert scene == ([] if forms["scene_grid"] is None else [forms["scene_grid"]]), where
+    assert (name(agg), sum(agg.wgs[i] for i in range(n)), agg.grid[0]) == (
+        forms["agg_kernel"], forms["agg_wgs"], forms["agg_grid"]), where
+    assert sorted(agg.pos[i] for i in range(n) if not agg.pre_grid[i]) == list(range(n - len(scene))), where
+    assert (mlp2 is None) == (forms["mlp2"] is None) and (n2e is None) == (forms["n2e"] is None), where
+    assert (gather is None) == (forms["gather_spw"] is None), where
+    if mlp2 is not None:
+        assert name(mlp2) == forms["mlp2"], (where, name(mlp2))
+    if n2e is not None:
+        assert ("rows" if n2e.variant else "banded") == forms["n2e"] and (n2e.EBh == 0) == bool(n2e.variant), where
+    if gather is not None:
+        assert gather.G == forms["gather_spw"], (where, gather.G)
 
 
 def describe(forms: Dict) -> str:

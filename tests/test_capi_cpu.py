@@ -25,8 +25,10 @@ def declared_structs():
     src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     out = {}
     for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S):
-        # "const float* const* H_list;", "int ld, rows, cols, place_r;": the last word of every declarator
-        out[name] = [re.findall(r"\w+", d)[-1] for decl in body.split(";") if decl.strip() for d in decl.split(",")]
+        # "const float* const* H_list;", "int ld, rows, cols, place_r;", "int wgs[GN_MAX_GROUPS];": the last word of every
+        # declarator, before its array bound (the layout check below compares the array's size)
+        out[name] = [re.findall(r"\w+", re.sub(r"\[.*?\]", "", d))[-1]
+                     for decl in body.split(";") if decl.strip() for d in decl.split(",")]
     return out
 
 

@@ -18,8 +18,8 @@ Gates, the same at every size:
 import pytest
 import torch
 
-from launch_forms import (BACKWARD_CASES, FORWARD_CASES, block64, case_forms, clean_scenes, describe, hyper64,
-                          hyper_incidence, sample_scenes, state64)
+from launch_forms import (BACKWARD_CASES, FORWARD_CASES, assert_plans_match, block64, case_forms, clean_scenes, describe,
+                          hyper64, hyper_incidence, sample_scenes, state64)
 from test_backward_gpu import TOL_ANY, TOL_CLEAN
 from test_bf16_gpu import TOL_ORACLE, block_and_states, safe_rows
 
@@ -60,9 +60,34 @@ def _check_H(Hg, h, scenes, s, twin):
     return int((~ok).sum()), ok.numel()
 
 
+PLANNED = ("gn_agg_mlp", "gn_mlp2", "gn_node2edge", "gn_agg_gather")
+
+
+def _spy_plans(monkeypatch, log):
+    """Ask the library, at every launch of the PLANNED stages, for the plan of that launch with the very arguments the
+    product passes (without the stream): log gets (stem, rc, plan)."""
+    import ctypes
+    from groupnet_amd import _lib, ops
+    real = ops._fn
+
+    def fn(stem, dt):
+        f = real(stem, dt)
+        if stem not in PLANNED:
+            return f
+
+        def call(*a):
+            plan = _lib.LaunchPlan()
+            log.append((stem, real(stem + "_plan", dt)(*a[:-1], ctypes.byref(plan)), plan))
+            return f(*a)
+        return call
+    monkeypatch.setattr(ops, "_fn", fn)
+
+
 @pytest.mark.parametrize("case", FORWARD_CASES, ids=[c["id"] for c in FORWARD_CASES])
 def test_forward_forms_match_the_float64_oracle(case, monkeypatch):
     from groupnet_amd import multiscale
+    plans = []
+    _spy_plans(monkeypatch, plans)
     B, N, scales, twin = case["B"], case["N"], case["scales"], case["dtype"] == "bf16"
     forms = case_forms(case)
     scenes = sample_scenes(B, N, forms, n=_n_sample(N), seed=B + N)
@@ -118,6 +143,12 @@ def test_forward_forms_match_the_float64_oracle(case, monkeypatch):
             fcols = [(64 * (1 + i), 64 * (2 + i)) for i in range(1 + len(scales))]
     finally:
         _precision(old)
+    # the forward reached the forms the case names: one launch per planned stage (nmp = 1), each as `forms` says, the
+    # aggregation launch carrying the closing stage exactly when `fused_closing`
+    assert all(rc == 0 for _, rc, _ in plans), [(stem, rc) for stem, rc, _ in plans]
+    by_stem = {stem: [p for s_, _, p in plans if s_ == stem] for stem in PLANNED}
+    assert len(by_stem["gn_agg_mlp"]) == 1 and all(len(v) <= 1 for v in by_stem.values()), {k: len(v) for k, v in by_stem.items()}
+    assert_plans_match(forms, *[(by_stem[stem] or [None])[0] for stem in PLANNED], case["id"])
     errs = [float((out_g[..., a:b] - out_r[..., a:b]).abs().max()) / float(out_r[..., a:b].abs().max()) for a, b in fcols]
     ferrs = [float((fg - fr).abs().max()) for fg, fr in zip(facs_g, facs_r)]
     print(f"\n{case['id']}: {describe(forms)}\n   {len(scenes)} scenes: features rel err per module "

@@ -13,4 +13,4 @@ for Bb, Nn, sc in ((4096, 11, 5), (512, 11, 5), (1024, 50, 8), (64, 50, 8), (102
     tg = bench.time_kernel_ms(lambda: ops.agg_gather(ori, H))
     ts = bench.time_kernel_ms(lambda: ops.agg_scatter(feat, H, ori))
     by = bench.agg_hbm_bytes(Bb, Nn, Nn)
-    print(f"GN_GS_ROWS={os.environ.get('GN_GS_ROWS')} B={Bb} N={Nn}: gather {tg*1e3:.2f} us scatter {ts*1e3:.2f} us -> {by/((tg+ts)*1e-3)/1e9:.0f} GB/s")
+    print(f"B={Bb} N={Nn}: gather {tg*1e3:.2f} us scatter {ts*1e3:.2f} us -> {by/((tg+ts)*1e-3)/1e9:.0f} GB/s")
