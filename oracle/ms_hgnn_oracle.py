@@ -304,14 +304,14 @@ def ms_hgnn_hyper_forward(state: State, h: Tensor, corr: Tensor, scale: int, U_l
 
 def ms_hgnn_multiscale_forward(state_pair: State, states_hyper: Sequence[State], scales: Sequence[int],
                                h: Tensor, U_pair: List[Tensor], U_hyper: Sequence[List[Tensor]],
-                               decomposed: bool = False):
+                               decomposed: bool = False, nmp_layers: int = 1):
     """What ``PastEncoder.forward`` does around the path (model/GroupNet_nba.py:284-311):
     affinity, the pairwise module, one hyper module per scale, and the two concats."""
     corr = affinity(h)
-    inter, _ = ms_hgnn_pairwise_forward(state_pair, h, U_pair, decomposed=decomposed)
+    inter, _ = ms_hgnn_pairwise_forward(state_pair, h, U_pair, nmp_layers, decomposed=decomposed)
     feats, Hs = [h, inter], []
     for st, s, U in zip(states_hyper, scales, U_hyper):
-        nf, _, H = ms_hgnn_hyper_forward(st, h, corr, s, U, decomposed=decomposed)
+        nf, _, H = ms_hgnn_hyper_forward(st, h, corr, s, U, nmp_layers, decomposed=decomposed)
         feats.append(nf)
         Hs.append(H)
     return torch.cat(feats, dim=-1), (torch.cat(Hs, dim=1) if Hs else None), corr
