@@ -41,6 +41,15 @@ _GUMBEL_TAU = 0.5      # model/MS_HGNN_batch.py:45
 # 54 -> 303 us against 71 + 56 us of scatter launches).
 _FUSED_GATHER_MAX_N = 16      # eo = H @ ori inside the typed MLP kernel
 _FUSED_SCATTER_MAX_N = 16     # cat(H^T feat, ori)/N inside the closing MLP
+
+
+def masks_apply(N: int) -> bool:
+    """Whether a forward over N agents has launches that read the bit-mask form of an incidence: the form is switched on
+    (`ops.set_incidence_form` / GN_INC_MASKS=1) and N lies where the stand-alone gather / scatter run and a 64-bit word
+    holds a row (16 < N <= 64).  Elsewhere nobody asks for masks and no launch changes."""
+    return (ops.incidence_form() == "mask" and min(_FUSED_GATHER_MAX_N, _FUSED_SCATTER_MAX_N) < N <= ops.MASK_MAX_N)
+
+
 # node->edge pooling inside the edge kernel (inference); the parity tests clear it to compare against the node2edge launch
 _FUSE_POOL = True
 
@@ -289,9 +298,9 @@ class _MessagePassing(nn.Module):
     def _edge2node(self, edge_feat: Tensor, ori: Tensor, H: Optional[Tensor], idx: int) -> Tensor:
         return self.edge_aggregation_list[idx]._aggregate(edge_feat, H, ori)
 
-    def _run(self, h: Tensor, H: Optional[Tensor], E: int, noise_u, out: Optional[Tensor] = None
+    def _run(self, h: Tensor, H: Optional[Tensor], E: int, noise_u, out: Optional[Tensor] = None, masks=None
              ) -> Tuple[Tensor, Tensor]:
-        return run_message_passing([self], [h], [H], [noise_u], [out])[0]
+        return run_message_passing([self], [h], [H], [noise_u], [out], masks=None if masks is None else [masks])[0]
 
     def _forward_autograd(self, h: Tensor, H: Optional[Tensor], noise_u, out: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
         """Training path: fused forward + HIP backward through torch.autograd."""
@@ -318,7 +327,7 @@ class _Closed(list):
 
 def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor], Hs: Sequence[Optional[Tensor]],
                         noises: Sequence, outs: Sequence[Optional[Tensor]], traces=None, join=None, affinity=None,
-                        fuse_closing: bool = False) -> List[Tuple[Tensor, Tensor]]:
+                        fuse_closing: bool = False, masks: Optional[Sequence] = None) -> List[Tuple[Tensor, Tensor]]:
     """The message-passing rounds of SEVERAL modules over the same scenes, stage by stage, each stage
     ONE grouped launch (model/MS_HGNN_batch.py:174-195 and :425-441 for every module at once).
 
@@ -335,10 +344,15 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     `fuse_closing`: let the typed-aggregation launch apply the closing MLP of every stage itself where its launch shape
     allows (`ops.agg_mlp_closing`: the launcher's plan decides): one launch fewer per stage, bit-identical rows.  At B = 512, N = 11 the chain costs
     inside that launch what the closing launch cost on its own (single-stream forward 0.104 -> 0.103 ms, 4-stream
-    throughput -2 %): the block asks for it in its latency form only."""
+    throughput -2 %): the block asks for it in its latency form only.
+    `masks`: one `ops.IncidenceMasks` (or None) per module, the bit-mask form of Hs[i].  With the mask form switched on
+    (`masks_apply(N)`), in inference, and a mask for EVERY hyper module, the stand-alone gather and scatter launches read
+    the masks instead of Hs (bit-identical results); otherwise they are ignored."""
     n = len(mods)
     if not (n == len(hs) == len(Hs) == len(noises) == len(outs)) or n == 0:
         raise ValueError("run_message_passing: one h, H, noise and out per module")
+    if masks is not None and len(masks) != n:
+        raise ValueError("run_message_passing: one masks entry (or None) per module")
     nmp = mods[0].nmp_layers
     if any(m.nmp_layers != nmp or m.bottleneck_dim != mods[0].bottleneck_dim for m in mods):
         raise ValueError("grouped modules must share nmp_layers and bottleneck_dim")
@@ -348,6 +362,9 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     # MLP output and are summed into the same two nodes.  Its per-edge MLPs therefore run once per
     # unordered pair (N(N+1)/2 rows instead of N*N); only the Gumbel softmax runs per ordered edge.
     syms = [H is None for H in Hs]
+    use_masks = (masks is not None and traces is None and masks_apply(N)
+                 and all(sy or m is not None for sy, m in zip(syms, masks)))
+    mks = [m if (use_masks and not sy) else None for sy, m in zip(syms, masks)] if masks is not None else [None] * n
     given = [_noise_iter(u) for u in noises]
 
     def next_u(i: int):
@@ -413,7 +430,7 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
         items = []
         # larger graphs: eo = H @ ori of every hyper module from ONE stand-alone gather launch
         standalone = [i for i in range(n) if not syms[i] and N > _FUSED_GATHER_MAX_N]
-        eos = dict(zip(standalone, ops.agg_gather_grouped([(oris[i], Hs[i]) for i in standalone]))) if standalone else {}
+        eos = dict(zip(standalone, ops.agg_gather_grouped([(oris[i], Hs[i], False, mks[i]) for i in standalone]))) if standalone else {}
         for i in range(n):
             pk, K = aggs[i]._packed(), aggs[i].edge_types
             if syms[i] and not twin and pair_A[i] is not None:
@@ -447,7 +464,7 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
                     for f, H, o, sy, it in zip(feats, Hs, oris, syms, items)]
         # larger graphs: one stand-alone scatter launch for the modules whose aggregation wrote per-edge features
         rest = [i for i in range(n) if not node_item(items[i])]
-        scat = dict(zip(rest, ops.agg_scatter_grouped([(feats[i], Hs[i], oris[i], syms[i]) for i in rest]))) if rest else {}
+        scat = dict(zip(rest, ops.agg_scatter_grouped([(feats[i], Hs[i], oris[i], syms[i], mks[i]) for i in rest]))) if rest else {}
         return [scat[i] if i in scat else ops.NodeAggSpec(feats[i], oris[i]) for i in range(n)]
 
     res = edge_mlp([m.nmp_mlp_start for m in mods], node2edge(hs, 0), True)
@@ -582,9 +599,12 @@ class MS_HGNN_hyper(_MessagePassing):
     def edge2node(self, x, ori, H, idx):
         return self._edge2node(x, ori, H, idx)
 
-    def forward(self, h_states, corr, noise_u=None, H=None, out=None):
+    def forward(self, h_states, corr, noise_u=None, H=None, out=None, masks=None):
         """``H`` (optional) lets a caller that already built the incidence for every scale in one
-        fused launch (``ops.affinity_topk``) hand it in; by default it is built here from ``corr``."""
+        fused launch (``ops.affinity_topk``) hand it in; by default it is built here from ``corr``.
+        ``masks`` (optional, inference): the `ops.IncidenceMasks` of a caller-supplied ``H``, used when the mask form is
+        switched on (`masks_apply`); an ``H`` handed in without them stays dense (it may carry other weights than 0/1),
+        an ``H`` built here gets its masks from the builder."""
         ops._req(h_states, "h_states", (None, None, self.h_dim), ops._ACT_DTYPES)
         if h_states.shape[0] and _needs_grad(self, h_states):
             # H is a constant of the backward (top-k selection has no gradient; corr is only used to build it)
@@ -601,7 +621,8 @@ class MS_HGNN_hyper(_MessagePassing):
             return nf, h_states.new_empty((B, E, self.edge_types)), h_states.new_empty((B, E, N))
         if H is None:
             H = self._build_H(h_states, corr)
+            masks = ops.incidence_masks(H, assume_binary=True) if masks_apply(h_states.shape[1]) else None
         else:
             ops._req(H, "H", (h_states.shape[0], None, h_states.shape[1]))
-        node_feat, factor = self._run(h_states, H, H.shape[1], noise_u, out)
+        node_feat, factor = self._run(h_states, H, H.shape[1], noise_u, out, masks)
         return node_feat, factor, (H if H.dtype == h_states.dtype else H.to(h_states.dtype))    # type_as(feat), :376,384

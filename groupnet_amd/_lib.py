@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must be imported before the .so is loaded)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GROUPNET_HIP_LIB") or os.path.join(_HERE, "libgroupnet_hip.so")  # env: tuning builds
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 GN_OK = 0
 GN_ERR_K_RANGE = -3
@@ -58,7 +58,7 @@ class EdgeGroup(ctypes.Structure):
 class GatherGroup(ctypes.Structure):
     __slots__ = ()
     c_name = "gn_gather_group_t"
-    _fields_ = [("ori", _P), ("H", _P), ("eo", _P), ("E", _I), ("sym", _I)]
+    _fields_ = [("ori", _P), ("H", _P), ("eo", _P), ("E", _I), ("sym", _I), ("rowmask", _P)]
 
 
 class AggGroup(ctypes.Structure):
@@ -73,7 +73,7 @@ class AggGroup(ctypes.Structure):
 class ScatterGroup(ctypes.Structure):
     __slots__ = ()
     c_name = "gn_scatter_group_t"
-    _fields_ = [("feat", _P), ("H", _P), ("ori", _P), ("out", _P), ("E", _I), ("sym", _I)]
+    _fields_ = [("feat", _P), ("H", _P), ("ori", _P), ("out", _P), ("E", _I), ("sym", _I), ("colmask", _P)]
 
 
 class Mlp2Group(ctypes.Structure):
@@ -144,6 +144,7 @@ class LaunchPlan(ctypes.Structure):
 
 
 GEMM_TRANS_A, GEMM_TRANS_B, GEMM_RELU, GEMM_ACCUM, GEMM_TRANS_C = 1, 2, 4, 8, 16
+K_AGG_GATHER, K_AGG_GATHER_MASK = 15, 16      # GN_K_*: the two forms of the stand-alone gather
 MAX_GROUPS = 10
 
 # name -> (restype, argtypes); mirrors include/groupnet_hip.h one to one
@@ -154,9 +155,10 @@ SIGNATURES = {
     "gn_topk_incidence_f32": (_I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_I), _I, _I, _I, _P]),
     "gn_listall_incidence_f32": (_I, [_P, _P, _I, _I, _I, _P]),
     "gn_affinity_topk_f32": (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I), _I, _I, _I, _I,
-                                  ctypes.POINTER(BlockExtras), _P]),
+                                  ctypes.POINTER(BlockExtras), ctypes.POINTER(_P), ctypes.POINTER(_P), _P]),
     "gn_affinity_topk_bf16": (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I), _I, _I, _I, _I,
-                                   ctypes.POINTER(BlockExtras), _P]),
+                                   ctypes.POINTER(BlockExtras), ctypes.POINTER(_P), ctypes.POINTER(_P), _P]),
+    "gn_incidence_masks_f32": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     "gn_packed_elems": (_SZ, [_I, _I]),
     "gn_pack_linear_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "gn_split_bf16_f32": (_I, [_P, _P, _I, _I, _P]),

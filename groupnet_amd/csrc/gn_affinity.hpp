@@ -17,6 +17,13 @@ struct ScaleList {
   int cat_off[GN_MAX_SCALES];
   int cat_rows;
 };
+// Optional bit-mask form of every H_s (stand-alone launch only: the node stage's tail passes none, so its code is that
+// of a launch without masks).  row[s] (B, E_s), col[s] (B, N): bit n of row word (b,e) and bit e of column word (b,n)
+// are set iff H_s[b,e,n] != 0.  N <= 64.
+struct MaskList {
+  unsigned long long* row[GN_MAX_SCALES];
+  unsigned long long* col[GN_MAX_SCALES];
+};
 
 
 // Ranking key of affinity v in column j of its row: key_j > key_c  <=>  beats(v_j, j, v_c, c).  High word: the float's
@@ -52,9 +59,13 @@ __device__ __forceinline__ void emit_ranked(int rank, int N, int b, int i, int c
 // 16-byte row reads of different rows on different banks); corr is formed once per UNORDERED pair (the dot product
 // is symmetric term by term, so corr[j][i] is the same bits), optionally written out, and kept in LDS as ranking keys,
 // which are then ranked in place.  Needs N*(D+4)*4 + N*N*8 bytes of LDS.
-template <typename T>
+// MASKS (with `ml`): the ranking loop also ORs every member into 2 n_scales N 64-bit words behind the raw inputs (row words
+// of scale s at (2s)N, column words at (2s+1)N; zeroed before the first barrier), which one more barrier later go out
+// coalesced — read off the same ranks as H_s, order-independent, hence deterministic.
+template <typename T, bool MASKS = false>
 __device__ __forceinline__ void affinity_topk_body(const T* __restrict__ f, float* __restrict__ corr, const ScaleList& sl,
-                                                   int N, int D, const gn_block_extras_t& ex, int b, float* lds) {
+                                                   int N, int D, const gn_block_extras_t& ex, int b, float* lds,
+                                                   const MaskList* ml = nullptr) {
   constexpr int kBlock = 256;
   const int ldq = D + 4;
   float* q = lds;             // N x ldq
@@ -63,6 +74,12 @@ __device__ __forceinline__ void affinity_topk_body(const T* __restrict__ f, floa
   const int d4 = D >> 2;
   if (ex.counter != nullptr && b == 0 && threadIdx.x == 0) *ex.counter += ex.counter_add;
   float* xs = reinterpret_cast<float*>(keys + N * N);  // N x x_dim raw inputs (embedding form only)
+  unsigned long long* mw = nullptr;                    // 2 x n_scales x N mask words
+  if constexpr (MASKS) {
+    const int nx = ex.x_raw != nullptr ? N * ex.x_dim : 0;
+    mw = reinterpret_cast<unsigned long long*>(xs + nx + (nx & 1));
+    for (int idx = threadIdx.x; idx < 2 * sl.n * N; idx += kBlock) mw[idx] = 0ull;
+  }
   if (ex.x_raw != nullptr) {
     const float* xb = ex.x_raw + (size_t)b * N * ex.x_dim;
     for (int idx = threadIdx.x; idx < N * ex.x_dim; idx += kBlock) xs[idx] = xb[idx];
@@ -130,6 +147,27 @@ __device__ __forceinline__ void affinity_topk_body(const T* __restrict__ f, floa
     int rank = 0;
     for (int j = 0; j < N; ++j) rank += row[j] > kc ? 1 : 0;
     emit_ranked<T>(rank, N, b, i, c, sl);
+    if constexpr (MASKS) {
+      for (int s = 0; s < sl.n; ++s) {
+        if (sl.k[s] != N && rank < sl.k[s]) {
+          atomicOr(mw + (2 * s) * N + i, 1ull << c);
+          atomicOr(mw + (2 * s + 1) * N + c, 1ull << i);
+        }
+      }
+    }
+  }
+  if constexpr (MASKS) {
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < 2 * sl.n * N; idx += kBlock) {
+      const int s = idx / (2 * N), r = idx - s * 2 * N;
+      const bool all = sl.k[s] == N;          // the single all-ones hyperedge: row word 0 = the N low bits, columns = bit 0
+      if (r < N) {
+        if (!all) ml->row[s][(size_t)b * N + r] = mw[idx];
+        else if (r == 0) ml->row[s][b] = N == 64 ? ~0ull : (1ull << N) - 1ull;
+      } else {
+        ml->col[s][(size_t)b * N + (r - N)] = all ? 1ull : mw[idx];
+      }
+    }
   }
 }
 
@@ -156,5 +194,7 @@ inline int fill_scales(ScaleList& sl, float* const* H_list, const int* k_list, i
 inline size_t affinity_fused_lds(int N, int D, int x_dim) {
   return (size_t)N * (D + 4) * sizeof(float) + 8 + (size_t)N * N * 8 + (size_t)N * x_dim * sizeof(float);
 }
+// ... and of the mask words of a launch that also emits the bit-mask form
+inline size_t affinity_mask_lds(int N, int n_scales) { return 8 + (size_t)2 * n_scales * N * 8; }
 
 }  // namespace

@@ -54,6 +54,54 @@ __global__ __launch_bounds__(kBlock) void affinity_topk_kernel(const T* __restri
   affinity_topk_body<T>(f, corr, sl, N, D, ex, (int)blockIdx.x, lds);
 }
 
+// the same launch when the caller also wants the bit-mask form of every H_s (a kernel of its own: the launch without
+// masks keeps its code and its name)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void affinity_topk_masks_kernel(const T* __restrict__ f, float* __restrict__ corr,
+                                                                     ScaleList sl, int N, int D, gn_block_extras_t ex,
+                                                                     MaskList ml) {
+  extern __shared__ __align__(16) float lds[];
+  affinity_topk_body<T, true>(f, corr, sl, N, D, ex, (int)blockIdx.x, lds, &ml);
+}
+
+// Bit-mask form of a dense incidence H (B,E,N), E, N <= 64: rowmask (B,E), colmask (B,N).  A workgroup owns kMaskScenes
+// consecutive scenes, whose H tiles are contiguous: coalesced reads, one LDS OR per non-zero entry (top-k rows are sparse),
+// coalesced word writes.  Any entry that is neither 0 nor 1 (a NaN included) raises *nonbinary; its bit is set.
+constexpr int kMaskScenes = 4;
+__global__ __launch_bounds__(kBlock) void incidence_masks_kernel(const float* __restrict__ H, int B, int E, int N,
+                                                                 unsigned long long* __restrict__ rowmask,
+                                                                 unsigned long long* __restrict__ colmask,
+                                                                 int* __restrict__ nonbinary) {
+  __shared__ unsigned long long w[kMaskScenes * 128];   // per scene: E row words, then N column words
+  const int b0 = blockIdx.x * kMaskScenes;
+  const int g = min(kMaskScenes, B - b0);
+  const int per = E + N, EN = E * N;
+  for (int idx = threadIdx.x; idx < g * per; idx += kBlock) w[idx] = 0ull;
+  __syncthreads();
+  const float* src = H + (size_t)b0 * EN;
+  bool bad = false;
+  for (int idx = threadIdx.x; idx < g * EN; idx += kBlock) {
+    const float v = src[idx];
+    if (v != 0.f) {
+      const int s = idx / EN, r = idx - s * EN;
+      const int e = r / N, n = r - e * N;
+      atomicOr(w + s * per + e, 1ull << n);
+      atomicOr(w + s * per + E + n, 1ull << e);
+      bad |= v != 1.f;
+    }
+  }
+  if (bad && nonbinary != nullptr) *nonbinary = 1;
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < g * E; idx += kBlock) {
+    const int s = idx / E, e = idx - s * E;
+    rowmask[(size_t)b0 * E + idx] = w[s * per + e];
+  }
+  for (int idx = threadIdx.x; idx < g * N; idx += kBlock) {
+    const int s = idx / N, n = idx - s * N;
+    colmask[(size_t)b0 * N + idx] = w[s * per + E + n];
+  }
+}
+
 // Large-N affinity: one workgroup per (scene, 16-row band); the band and one 64-column
 // panel of q at a time live in LDS.
 __global__ __launch_bounds__(kBlock) void affinity_banded_kernel(const float* __restrict__ f,
@@ -673,6 +721,43 @@ __global__ __launch_bounds__(kBlock) void agg_gather_kernel(GatherTable T, int B
   }
 }
 
+// Mask form (gn_gather_group_t.rowmask, N <= 64): the g E row words of the scenes replace the g E N floats of H; a thread
+// walks the set bits of its hyperedge's word in ascending order, the same fmaf per member as the dense kernel (whose
+// non-members add fmaf(0, v, acc) == acc for finite v): bit-identical rows.
+template <typename TS>
+__global__ __launch_bounds__(kBlock) void agg_gather_mask_kernel(GatherTable T, int B, int N, int G) {
+  extern __shared__ __align__(16) float lds[];
+  const gn_gather_group_t Gr = T.g[blockIdx.z];
+  const int E = Gr.E;
+  const int b0 = blockIdx.x * G;
+  const int g = min(G, B - b0);
+  float* s_ori = lds;                                                                                   // g x N x 64
+  unsigned long long* s_m = reinterpret_cast<unsigned long long*>(lds + (size_t)G * N * GN_FEAT);     // g x E words
+  {
+    const TS* src = reinterpret_cast<const TS*>(Gr.ori) + (size_t)b0 * N * GN_FEAT;
+    f32x4* dst = reinterpret_cast<f32x4*>(s_ori);
+    for (int idx = threadIdx.x; idx < g * N * (GN_FEAT / 4); idx += kBlock) dst[idx] = ld4(src + 4 * idx);
+    const unsigned long long* ms = Gr.rowmask + (size_t)b0 * E;
+    for (int idx = threadIdx.x; idx < g * E; idx += kBlock) s_m[idx] = ms[idx];
+  }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < g * E * (GN_FEAT / 4); idx += kBlock) {
+    const int d = idx & 15, se = idx >> 4;
+    const int s = se / E;
+    const f32x4* o4 = reinterpret_cast<const f32x4*>(s_ori + (size_t)s * N * GN_FEAT) + d;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (unsigned long long m = s_m[se]; m != 0ull; m &= m - 1ull) {
+      const int n = __ffsll(m) - 1;
+      const f32x4 v = o4[n * (GN_FEAT / 4)];
+      acc[0] = fmaf(1.f, v[0], acc[0]);
+      acc[1] = fmaf(1.f, v[1], acc[1]);
+      acc[2] = fmaf(1.f, v[2], acc[2]);
+      acc[3] = fmaf(1.f, v[3], acc[3]);
+    }
+    st4(reinterpret_cast<TS*>(Gr.eo) + ((size_t)b0 * E + se) * GN_FEAT + 4 * d, acc);
+  }
+}
+
 // Pairwise graph: eo[(i,j)] = ori_i + ori_j (2 ori_i on the diagonal), H never materialised.
 template <bool SYM, typename TS>
 __global__ __launch_bounds__(kBlock) void agg_gather_pairwise_kernel(const TS* __restrict__ ori,
@@ -741,6 +826,50 @@ __global__ __launch_bounds__(kBlock) void agg_scatter_kernel(ScatterTable T, int
     st4(reinterpret_cast<TS*>(Gr.out) + ((size_t)(b0 + s) * N + n) * 2 * GN_FEAT + 4 * d, r);
   }
   // ... then the ori half of the concat
+  for (int idx = threadIdx.x; idx < g * N * 16; idx += kBlock) {
+    const int d = idx & 15, sn = idx >> 4;
+    const f32x4 acc = ld4(reinterpret_cast<const TS*>(Gr.ori) + ((size_t)b0 * N + sn) * GN_FEAT + 4 * d);
+    const f32x4 r = {acc[0] / fN, acc[1] / fN, acc[2] / fN, acc[3] / fN};
+    st4(reinterpret_cast<TS*>(Gr.out) + ((size_t)b0 * N + sn) * 2 * GN_FEAT + GN_FEAT + 4 * d, r);
+  }
+}
+
+// Mask form (gn_scatter_group_t.colmask, E, N <= 64): the g N column words replace the g E N floats of H; a thread walks
+// the hyperedges of its node in ascending order, as the dense kernel does (which skips zeros too): bit-identical rows.
+template <typename TS>
+__global__ __launch_bounds__(kBlock) void agg_scatter_mask_kernel(ScatterTable T, int B, int N, int G, int Emax,
+                                                                  float fN) {
+  extern __shared__ __align__(16) float lds[];
+  const gn_scatter_group_t Gr = T.g[blockIdx.y];
+  const int E = Gr.E;
+  const int b0 = blockIdx.x * G;
+  const int g = min(G, B - b0);
+  float* s_feat = lds;                                                                                    // g x E x 64
+  unsigned long long* s_m = reinterpret_cast<unsigned long long*>(lds + (size_t)G * Emax * GN_FEAT);    // g x N words
+  {
+    const TS* src = reinterpret_cast<const TS*>(Gr.feat) + (size_t)b0 * E * GN_FEAT;
+    f32x4* dst = reinterpret_cast<f32x4*>(s_feat);
+    for (int idx = threadIdx.x; idx < g * E * (GN_FEAT / 4); idx += kBlock) dst[idx] = ld4(src + 4 * idx);
+    const unsigned long long* ms = Gr.colmask + (size_t)b0 * N;
+    for (int idx = threadIdx.x; idx < g * N; idx += kBlock) s_m[idx] = ms[idx];
+  }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < g * N * 16; idx += kBlock) {
+    const int d = idx & 15, sn = idx >> 4;
+    const int s = sn / N;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const f32x4* f4 = reinterpret_cast<const f32x4*>(s_feat + (size_t)s * E * GN_FEAT) + d;
+    for (unsigned long long m = s_m[sn]; m != 0ull; m &= m - 1ull) {
+      const int e = __ffsll(m) - 1;
+      const f32x4 v = f4[e * 16];
+      acc[0] = fmaf(1.f, v[0], acc[0]);
+      acc[1] = fmaf(1.f, v[1], acc[1]);
+      acc[2] = fmaf(1.f, v[2], acc[2]);
+      acc[3] = fmaf(1.f, v[3], acc[3]);
+    }
+    const f32x4 r = {acc[0] / fN, acc[1] / fN, acc[2] / fN, acc[3] / fN};
+    st4(reinterpret_cast<TS*>(Gr.out) + ((size_t)b0 * N + sn) * 2 * GN_FEAT + 4 * d, r);
+  }
   for (int idx = threadIdx.x; idx < g * N * 16; idx += kBlock) {
     const int d = idx & 15, sn = idx >> 4;
     const f32x4 acc = ld4(reinterpret_cast<const TS*>(Gr.ori) + ((size_t)b0 * N + sn) * GN_FEAT + 4 * d);
@@ -1049,7 +1178,7 @@ inline int capped_grid(long long work_items, int per_block, int cap = 256 * 16) 
 
 }  // namespace
 
-extern "C" int gn_abi_version(void) { return 36; }
+extern "C" int gn_abi_version(void) { return 37; }
 
 extern "C" const char* gn_kernel_name(int kernel) {
   static const char* const names[] = {"",
@@ -1067,8 +1196,9 @@ extern "C" const char* gn_kernel_name(int kernel) {
                                       "mlp2_split_kernel",
                                       "mlp2_kernel",
                                       "node2edge_kernel",
-                                      "agg_gather_kernel"};
-  return kernel >= 0 && kernel <= GN_K_AGG_GATHER ? names[kernel] : nullptr;
+                                      "agg_gather_kernel",
+                                      "agg_gather_mask_kernel"};
+  return kernel >= 0 && kernel <= GN_K_AGG_GATHER_MASK ? names[kernel] : nullptr;
 }
 
 extern "C" const char* gn_strerror(int code) {
@@ -1151,7 +1281,8 @@ extern "C" int gn_listall_incidence_f32(const float* corr, float* H, int B, int 
 
 template <typename TS>
 static int affinity_topk_launch(const TS* f, float* corr, float* const* H_list, const int* k_list, int n_scales, int B,
-                                int N, int D, const gn_block_extras_t* extras, hipStream_t stream) {
+                                int N, int D, const gn_block_extras_t* extras, unsigned long long* const* rowmask_list,
+                                unsigned long long* const* colmask_list, hipStream_t stream) {
   const bool embed = extras != nullptr && extras->x_raw != nullptr;
   if (embed && sizeof(TS) != sizeof(float)) return GN_ERR_SHAPE;   // the embedding front-end is fp32 only
   if (!embed) {
@@ -1168,6 +1299,19 @@ static int affinity_topk_launch(const TS* f, float* corr, float* const* H_list, 
     if (!gn_aligned16(extras->c) || !gn_aligned16(extras->f_contig)) return GN_ERR_ALIGN;
     fused += (size_t)N * extras->x_dim * sizeof(float);
   }
+  const bool masks = rowmask_list != nullptr || colmask_list != nullptr;
+  MaskList ml{};
+  if (masks) {
+    if (rowmask_list == nullptr || colmask_list == nullptr) return GN_ERR_NULL;   // both forms or none
+    if (N > 64) return GN_ERR_SHAPE;
+    for (int s = 0; s < n_scales; ++s) {
+      if (rowmask_list[s] == nullptr || colmask_list[s] == nullptr) return GN_ERR_NULL;
+      if (!gn_aligned16(rowmask_list[s]) || !gn_aligned16(colmask_list[s])) return GN_ERR_ALIGN;
+      ml.row[s] = rowmask_list[s];
+      ml.col[s] = colmask_list[s];
+    }
+    fused += affinity_mask_lds(N, n_scales);
+  }
   if (fused > kLdsBudget) return GN_ERR_LDS;
   gn_block_extras_t ex{};
   if (extras != nullptr) {
@@ -1175,18 +1319,44 @@ static int affinity_topk_launch(const TS* f, float* corr, float* const* H_list, 
     if (ex.f_out != nullptr && (!gn_aligned16(ex.f_out) || ex.f_out_ld < D || (ex.f_out_ld & 3))) return GN_ERR_ALIGN;
     sl.H_cat = ex.H_cat;
   }
-  gn_allow_big_lds(affinity_topk_kernel<TS>);
-  hipLaunchKernelGGL(affinity_topk_kernel<TS>, dim3(B), dim3(kBlock), fused, stream, f, corr, sl, N, D, ex);
+  if (masks) {
+    gn_allow_big_lds(affinity_topk_masks_kernel<TS>);
+    hipLaunchKernelGGL(affinity_topk_masks_kernel<TS>, dim3(B), dim3(kBlock), fused, stream, f, corr, sl, N, D, ex, ml);
+  } else {
+    gn_allow_big_lds(affinity_topk_kernel<TS>);
+    hipLaunchKernelGGL(affinity_topk_kernel<TS>, dim3(B), dim3(kBlock), fused, stream, f, corr, sl, N, D, ex);
+  }
   return gn_check_launch();
 }
 extern "C" int gn_affinity_topk_f32(const float* f, float* corr, float* const* H_list, const int* k_list, int n_scales,
-                                    int B, int N, int D, const gn_block_extras_t* extras, gn_stream_t stream) {
-  return affinity_topk_launch<float>(f, corr, H_list, k_list, n_scales, B, N, D, extras, (hipStream_t)stream);
+                                    int B, int N, int D, const gn_block_extras_t* extras,
+                                    unsigned long long* const* rowmask_list, unsigned long long* const* colmask_list,
+                                    gn_stream_t stream) {
+  return affinity_topk_launch<float>(f, corr, H_list, k_list, n_scales, B, N, D, extras, rowmask_list, colmask_list,
+                                     (hipStream_t)stream);
 }
 extern "C" int gn_affinity_topk_bf16(const void* f, float* corr, float* const* H_list, const int* k_list, int n_scales,
-                                     int B, int N, int D, const gn_block_extras_t* extras, gn_stream_t stream) {
+                                     int B, int N, int D, const gn_block_extras_t* extras,
+                                     unsigned long long* const* rowmask_list, unsigned long long* const* colmask_list,
+                                     gn_stream_t stream) {
   return affinity_topk_launch<__bf16>(reinterpret_cast<const __bf16*>(f), corr, H_list, k_list, n_scales, B, N, D,
-                                      extras, (hipStream_t)stream);
+                                      extras, rowmask_list, colmask_list, (hipStream_t)stream);
+}
+
+extern "C" int gn_incidence_masks_f32(const float* H, int B, int E, int N, unsigned long long* rowmask,
+                                      unsigned long long* colmask, int* nonbinary, gn_stream_t stream) {
+  GN_REQUIRE_PTR(H);
+  GN_REQUIRE_PTR(rowmask);
+  GN_REQUIRE_PTR(colmask);
+  GN_REQUIRE_ALIGNED(H);
+  GN_REQUIRE_ALIGNED(rowmask);
+  GN_REQUIRE_ALIGNED(colmask);
+  if (B <= 0 || E <= 0 || N <= 0 || E > 64 || N > 64) return GN_ERR_SHAPE;
+  if (nonbinary != nullptr && hipMemsetAsync(nonbinary, 0, sizeof(int), (hipStream_t)stream) != hipSuccess)
+    return GN_ERR_LAUNCH;
+  hipLaunchKernelGGL(incidence_masks_kernel, dim3((B + kMaskScenes - 1) / kMaskScenes), dim3(kBlock), 0,
+                     (hipStream_t)stream, H, B, E, N, rowmask, colmask, nonbinary);
+  return gn_check_launch();
 }
 
 // ---- node -> edge and gather: plan, then launch (see the launch-plan comment in gn_mlp_mfma.hip) ------------------
@@ -1362,13 +1532,19 @@ static int gather_plan(const gn_gather_group_t* groups, int n_groups, int B, int
   p.n_groups = n_groups;
   p.precision = twin ? 1 : 0;
   p.grid[1] = p.grid[2] = 1;
-  int nh = 0, Emax = 0;
+  int nh = 0, nm = 0, Emax = 0;
   for (int g = 0; g < n_groups; ++g) {
     const gn_gather_group_t& G = groups[g];
     if (!G.ori || !G.eo) return GN_ERR_NULL;
     if (!gn_aligned16(G.ori) || !gn_aligned16(G.eo)) return GN_ERR_ALIGN;
     if (G.E <= 0) return GN_ERR_SHAPE;
-    if (G.H == nullptr) {
+    if (G.rowmask != nullptr) {      // mask form: H is not read
+      if (reinterpret_cast<uintptr_t>(G.rowmask) & 7u) return GN_ERR_ALIGN;
+      if (G.sym || N > 64) return GN_ERR_SHAPE;
+      p.pos[g] = nh++;
+      ++nm;
+      Emax = G.E > Emax ? G.E : Emax;
+    } else if (G.H == nullptr) {
       if ((long long)G.E != (G.sym ? (long long)gn_pair_count(N) : (long long)N * N)) return GN_ERR_SHAPE;
       p.pos[g] = -1;      // agg_gather_pairwise_kernel, a launch of its own
       p.pre_grid[g] = capped_grid((long long)B * G.E * 16, kBlock * 4);
@@ -1379,7 +1555,26 @@ static int gather_plan(const gn_gather_group_t* groups, int n_groups, int B, int
     }
   }
   if (nh == 0) return GN_OK;
+  if (nm != 0 && nm != nh) return GN_ERR_SHAPE;     // one form for every hyper group of a launch
   const size_t ori_b = (size_t)N * GN_FEAT * sizeof(float);
+  if (nm != 0) {
+    // the tile of a scene is its ori rows and Emax words: the same packing rule as the dense form below (24 KiB tile target,
+    // >= kGsMinWgs workgroups), which without the H tile admits more scenes per workgroup
+    const size_t per_scene = ori_b + (size_t)Emax * sizeof(unsigned long long);
+    int G = 1;
+    while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= kGsMinWgs)
+      G *= 2;
+    p.kernel = GN_K_AGG_GATHER_MASK;
+    p.G = G;
+    p.TE = Emax;
+    p.dyn_lds = (int)((size_t)G * per_scene);
+    p.grid[0] = (B + G - 1) / G;
+    p.grid[1] = 1;
+    p.grid[2] = nh;
+    for (int g = 0; g < n_groups; ++g)
+      if (groups[g].rowmask != nullptr) p.wgs[g] = p.grid[0], p.spw[g] = G;
+    return GN_OK;
+  }
   if (ori_b + (size_t)N * sizeof(float) > kLdsBudget) return GN_ERR_LDS;
   int G = 1, TE = Emax;
   const size_t per_scene = ori_b + (size_t)Emax * N * sizeof(float);
@@ -1407,7 +1602,7 @@ static int gather_launch(const gn_launch_plan_t& p, const gn_gather_group_t* gro
   GatherTable T{};
   for (int g = 0; g < p.n_groups; ++g) {
     const gn_gather_group_t& G = groups[g];
-    if (G.H != nullptr) {
+    if (G.H != nullptr || G.rowmask != nullptr) {
       T.g[p.pos[g]] = G;
       continue;
     }
@@ -1424,6 +1619,9 @@ static int gather_launch(const gn_launch_plan_t& p, const gn_gather_group_t* gro
     gn_allow_big_lds(agg_gather_kernel<TS>);
     hipLaunchKernelGGL(agg_gather_kernel<TS>, dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(kBlock), (size_t)p.dyn_lds, s, T,
                        B, N, p.G, p.TE);
+  } else if (p.kernel == GN_K_AGG_GATHER_MASK) {
+    hipLaunchKernelGGL(agg_gather_mask_kernel<TS>, dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(kBlock), (size_t)p.dyn_lds,
+                       s, T, B, N, p.G);
   }
   return gn_check_launch();
 }
@@ -1455,22 +1653,33 @@ static int scatter_launch(const gn_scatter_group_t* groups, int n_groups, int B,
   if (B <= 0 || N <= 0 || !(divisor != 0.f)) return GN_ERR_SHAPE;
   const long long total4 = (long long)B * N * 32;
   ScatterTable T{};
-  int nh = 0, Emax = 0;
+  int nh = 0, Emax = 0, n_mask = 0, n_dense = 0;
   for (int g = 0; g < n_groups; ++g) {
     const gn_scatter_group_t& G = groups[g];
     if (!G.feat || !G.ori || !G.out) return GN_ERR_NULL;
     if (!gn_aligned16(G.feat) || !gn_aligned16(G.ori) || !gn_aligned16(G.out)) return GN_ERR_ALIGN;
     if (G.E <= 0) return GN_ERR_SHAPE;
+    if (G.colmask != nullptr) {      // mask form: H is not read
+      if (reinterpret_cast<uintptr_t>(G.colmask) & 7u) return GN_ERR_ALIGN;
+      if (G.sym || N > 64 || G.E > 64) return GN_ERR_SHAPE;
+      ++n_mask;
+      continue;
+    }
+    n_dense += G.H != nullptr;
     if (G.H == nullptr && (long long)G.E != (G.sym ? (long long)gn_pair_count(N) : (long long)N * N))
       return GN_ERR_SHAPE;
     if (G.H != nullptr && G.sym) return GN_ERR_SHAPE;
   }
+  if (n_mask != 0 && n_dense != 0) return GN_ERR_SHAPE;     // one form for every hyper group of a launch
   for (int g = 0; g < n_groups; ++g) {
     const gn_scatter_group_t& G = groups[g];
     const TS* feat = reinterpret_cast<const TS*>(G.feat);
     const TS* ori = reinterpret_cast<const TS*>(G.ori);
     TS* out = reinterpret_cast<TS*>(G.out);
-    if (G.H == nullptr && G.sym && N * 16 <= kBlock * kPairItems && B >= 256 && sw.scatter_pairs) {
+    if (G.colmask != nullptr) {
+      T.g[nh++] = G;
+      Emax = G.E > Emax ? G.E : Emax;
+    } else if (G.H == nullptr && G.sym && N * 16 <= kBlock * kPairItems && B >= 256 && sw.scatter_pairs) {
       // one workgroup per scene, every pair row read once (enough scenes to fill the chip; GN_SCATTER_PAIRS = 0 keeps
       // the direct kernel: parity tests run both)
       hipLaunchKernelGGL((agg_scatter_pairs_kernel<TS>), dim3(B), dim3(kBlock), 0, s, feat, ori, out, N, divisor);
@@ -1488,7 +1697,15 @@ static int scatter_launch(const gn_scatter_group_t* groups, int n_groups, int B,
       Emax = G.E > Emax ? G.E : Emax;
     }
   }
-  if (nh > 0) {
+  if (nh > 0 && n_mask != 0) {
+    // agg_scatter_mask_kernel: the scene's tile is its feat rows and N words; packing rule as below
+    const size_t per_scene = (size_t)Emax * GN_FEAT * sizeof(float) + (size_t)N * sizeof(unsigned long long);
+    int G = 1;
+    while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= kGsMinWgs)
+      G *= 2;
+    hipLaunchKernelGGL(agg_scatter_mask_kernel<TS>, dim3((B + G - 1) / G, nh), dim3(kBlock), (size_t)G * per_scene, s, T, B,
+                       N, G, Emax, divisor);
+  } else if (nh > 0) {
     const size_t per_scene = (size_t)Emax * (GN_FEAT + N) * sizeof(float);
     int G = 1;
     while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= kGsMinWgs)

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .MS_HGNN_batch import MS_HGNN_hyper, MS_HGNN_oridinary, _needs_grad, _plist, run_message_passing
+from .MS_HGNN_batch import MS_HGNN_hyper, MS_HGNN_oridinary, _needs_grad, _plist, masks_apply, run_message_passing
 
 Tensor = torch.Tensor
 
@@ -143,6 +143,8 @@ class MultiScaleHGNN(nn.Module):
         final = torch.empty((B, N, self.out_features), dtype=f.dtype, device=f.device)
         cols = [final[..., D * (1 + i):D * (2 + i)] for i in range(1 + S)]   # written in place by the last MLP
         join = None
+        want_masks = masks_apply(N)       # mask form on and 16 < N <= 64: the fused launch also emits the member words
+        masks = None
         if S and ops.fused_affinity_fits(N, D):
             # one launch: affinity, incidence of every scale, f -> final[..., :D], cat(H_s), Philox bump.
             # The node stage of the first round needs only f: inside a graph capture the two launches are forked
@@ -155,7 +157,7 @@ class MultiScaleHGNN(nn.Module):
             if fork:
                 side.wait_stream(main)
             tail = None
-            if self.grouped and not fork and self.affinity_tail:
+            if self.grouped and not fork and self.affinity_tail and not want_masks:
                 # the launch is DEFERRED: it rides as the tail workgroups of the first node-stage launch (which needs only
                 # f), or is issued right before it when that launch cannot take it — one launch and one boundary fewer
                 tail = ops.AffinityTail(f, self.hyper_scales, want_corr=False, f_out=final[..., :D], want_H_cat=True,
@@ -163,9 +165,11 @@ class MultiScaleHGNN(nn.Module):
                 Hs, new_H = tail.Hs, tail.H_cat
             else:
                 with (torch.cuda.stream(side) if fork else contextlib.nullcontext()):
-                    _, Hs, new_H = ops.affinity_topk(f, self.hyper_scales, want_corr=False, f_out=final[..., :D],
-                                                     want_H_cat=True, counter=advance[0] if advance else None,
-                                                     counter_add=advance[1] if advance else 0)
+                    res = ops.affinity_topk(f, self.hyper_scales, want_corr=False, f_out=final[..., :D],
+                                            want_H_cat=True, counter=advance[0] if advance else None,
+                                            counter_add=advance[1] if advance else 0, want_masks=want_masks)
+                    Hs, new_H = res[1], res[2]
+                    masks = [None, *res[3]] if want_masks else None
             if fork:
                 join = lambda: main.wait_stream(side)
         elif S:
@@ -187,8 +191,8 @@ class MultiScaleHGNN(nn.Module):
             # (latency form — `affinity_tail` — also folds the closing MLPs into the aggregation launch: 4 launches)
             run_message_passing(mods, [f] * (1 + S), [None, *Hs], list(noise_u), cols, join=join,
                                 affinity=tail if (S and ops.fused_affinity_fits(N, D)) else None,
-                                fuse_closing=self.affinity_tail)
+                                fuse_closing=self.affinity_tail, masks=masks)
         else:
-            for m, H, u, c in zip(mods, [None, *Hs], noise_u, cols):
-                run_message_passing([m], [f], [H], [u], [c])
+            for m, H, u, c, mk in zip(mods, [None, *Hs], noise_u, cols, masks or [None] * (1 + S)):
+                run_message_passing([m], [f], [H], [u], [c], masks=[mk])
         return final, new_H

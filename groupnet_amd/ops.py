@@ -69,6 +69,32 @@ F16X3 = _PRECISION not in ("bf16x6", "fp32")      # ... from fp16 parts
 _AFFINITY_TAIL = os.environ.get("GN_AFFINITY_TAIL", "1") != "0"
 
 
+# Form in which the stand-alone gather / scatter launches of the engine read a hyperedge incidence: "dense" (default) — the
+# fp32 H (B,E,N) — or "mask" — 64-bit member words (`IncidenceMasks`), inference, 16 < N <= 64.  None: not set by
+# `set_incidence_form`, the environment decides per call (GN_INC_MASKS=1: mask).
+_INCIDENCE_FORM: Optional[str] = None
+MASK_MAX_N = 64        # one 64-bit word per hyperedge / node
+
+
+def incidence_form() -> str:
+    """'dense' or 'mask': what `set_incidence_form` chose, else GN_INC_MASKS=1 selects 'mask' (A/B switch, read per
+    call).  Results are bit-identical either way."""
+    if _INCIDENCE_FORM is not None:
+        return _INCIDENCE_FORM
+    return "mask" if os.environ.get("GN_INC_MASKS", "0") == "1" else "dense"
+
+
+def set_incidence_form(form: Optional[str]) -> None:
+    """'dense' | 'mask' for launches issued from now on (captured graphs keep the form they were captured with); None
+    hands the choice back to the environment."""
+    global _INCIDENCE_FORM
+    if form is not None:
+        form = form.lower()
+        if form not in ("dense", "mask"):
+            raise ValueError("incidence form: 'dense' or 'mask'")
+    _INCIDENCE_FORM = form
+
+
 def precision() -> str:
     """Matrix path of the fp32 entry points: 'f16x3' (default), 'bf16x6' or 'fp32' (the fp32 matrix cores)."""
     return "f16x3" if (BF16X6 and F16X3) else ("bf16x6" if BF16X6 else "fp32")
@@ -198,6 +224,48 @@ def listall_incidence(corr: Tensor, scale: int) -> Tensor:
     return H
 
 
+class IncidenceMasks:
+    """Bit-mask form of a 0/1 incidence H (B,E,N), N <= 64 (hence E <= 64), as int64 tensors: bit n of ``row[b,e]`` and bit
+    e of ``col[b,n]`` are set iff H[b,e,n] != 0 (include/groupnet_hip.h).  Made by `incidence_masks`,
+    `affinity_topk(want_masks=True)` or `AffinityTail(want_masks=True)`; consumed by `agg_gather*` (row) and
+    `agg_scatter*` (col)."""
+    __slots__ = ("row", "col")
+
+    def __init__(self, row: Tensor, col: Tensor):
+        _req(row, "row", (None, None), torch.int64)
+        _req(col, "col", (row.shape[0], None), torch.int64)
+        _same_device(row, col)
+        if row.shape[1] > MASK_MAX_N or col.shape[1] > MASK_MAX_N:
+            raise ValueError(f"IncidenceMasks: at most {MASK_MAX_N} hyperedges and nodes")
+        self.row, self.col = row, col
+
+
+def _alloc_masks(B: int, E: int, N: int, device) -> IncidenceMasks:
+    if N > MASK_MAX_N or E > MASK_MAX_N:
+        raise ValueError(f"the bit-mask form of an incidence needs N <= {MASK_MAX_N} and E <= {MASK_MAX_N}")
+    return IncidenceMasks(torch.empty((B, E), dtype=torch.int64, device=device),
+                          torch.empty((B, N), dtype=torch.int64, device=device))
+
+
+def incidence_masks(H: Tensor, assume_binary: bool = False) -> IncidenceMasks:
+    """The bit-mask form of a dense fp32 H (B,E,N), E, N <= 64 (gn_incidence_masks_f32).  Without ``assume_binary`` the
+    launch also checks that H holds only 0 and 1 and the flag is read back — ONE HOST SYNCHRONISATION, not capturable in
+    a graph — raising ValueError otherwise (such an H keeps the dense form).  Pass ``assume_binary=True`` for an H the
+    library built itself."""
+    _req(H, "H", (None, None, None))
+    B, E, N = H.shape
+    m = _alloc_masks(B, E, N, H.device)
+    if B == 0:
+        return m
+    flag = None if assume_binary else torch.empty((1,), dtype=torch.int32, device=H.device)
+    with torch.cuda.device(H.device):
+        check(load().gn_incidence_masks_f32(addr(H), B, E, N, addr(m.row), addr(m.col), addr(flag), stream_handle()),
+              "gn_incidence_masks_f32")
+    if flag is not None and int(flag.item()) != 0:
+        raise ValueError("incidence_masks: H holds entries other than 0 and 1; it has no bit-mask form")
+    return m
+
+
 def fused_affinity_fits(N: int, D: int, x_dim: int = 0) -> bool:
     """Whether one scene's tile of the fused affinity+top-k launch fits its 128 KiB LDS budget."""
     return N * (D + 4 + x_dim) * 4 + 8 + N * N * 8 <= 128 * 1024      # rows + 64-bit ranking keys (+ raw inputs)
@@ -205,8 +273,9 @@ def fused_affinity_fits(N: int, D: int, x_dim: int = 0) -> bool:
 
 def affinity_topk(f: Optional[Tensor], scales: Sequence[int], want_corr: bool = True, f_out: Optional[Tensor] = None,
                   want_H_cat: bool = False, counter: Optional[Tensor] = None, counter_add: int = 0,
-                  embed: Optional[Tuple[Tensor, Tensor, Tensor]] = None):
-    """Fused A0+A1: f -> (corr, [H_s], H_cat) in one launch.
+                  embed: Optional[Tuple[Tensor, Tensor, Tensor]] = None, want_masks: bool = False):
+    """Fused A0+A1: f -> (corr, [H_s], H_cat) in one launch.  ``want_masks`` (N <= 64): the launch also writes the
+    bit-mask form of every H_s; the LAST return value then is the list of `IncidenceMasks`, one per scale.
 
     Extras for the multiscale block (no copy kernels after this launch): ``f_out`` — a last-dim slice
     (B, N, D) of a wider contiguous tensor that also receives f; ``want_H_cat`` — also build
@@ -224,26 +293,35 @@ def affinity_topk(f: Optional[Tensor], scales: Sequence[int], want_corr: bool = 
         _same_device(x_raw, M, c)
         f = torch.empty((B, N, D), dtype=x_raw.dtype, device=x_raw.device)   # the launch writes it (f_contig)
         front = dict(x_raw=x_raw.data_ptr(), x_dim=xd, M=M.data_ptr(), c=c.data_ptr(), f_contig=f.data_ptr())
-    job = AffinityTail(f, scales, want_corr, f_out, want_H_cat, counter, counter_add, _front_end=front)
+    job = AffinityTail(f, scales, want_corr, f_out, want_H_cat, counter, counter_add, _front_end=front,
+                       want_masks=want_masks)
     job.launch()
-    return (job.corr, job.Hs, job.H_cat) + ((f,) if embed is not None else ())
+    return (job.corr, job.Hs, job.H_cat) + ((f,) if embed is not None else ()) + ((job.masks,) if want_masks else ())
 
 
 class AffinityTail:
     """The fused affinity + top-k launch of a forward, DEFERRED: outputs are allocated now, the work is issued as the tail
     workgroups of the first node-stage launch (`node_stage_grouped(..., affinity=job)` -> gn_node_mlp_affinity_*), or —
     when nothing picks it up — by `launch()` as the stand-alone launch.  Same arguments as `affinity_topk` (without the
-    embedding front-end, whose extras fields only `affinity_topk` passes in ``_front_end``)."""
+    embedding front-end, whose extras fields only `affinity_topk` passes in ``_front_end``).
+    ``want_masks``: also emit the bit-mask form of every H_s (``masks``: one `IncidenceMasks` per scale).  Only the
+    stand-alone launch emits masks, so the job then declines the tail (`fits_tail()` is False)."""
 
     def __init__(self, f: Tensor, scales: Sequence[int], want_corr: bool = False, f_out: Optional[Tensor] = None,
                  want_H_cat: bool = False, counter: Optional[Tensor] = None, counter_add: int = 0,
-                 _front_end: Optional[dict] = None):
+                 _front_end: Optional[dict] = None, want_masks: bool = False):
         _req(f, "f", (None, None, None), _ACT_DTYPES)
         self.f, self.scales = f, [int(s) for s in scales]
         B, N, D = f.shape
         self.corr = torch.empty((B, N, N), dtype=torch.float32, device=f.device) if want_corr else None
         self.Hs = _alloc_incidence(B, N, self.scales, f.device)
         self._Hl, self._kl, n = _scale_args(self.Hs, self.scales)
+        self.masks: Optional[List[IncidenceMasks]] = None
+        self._rl = self._cl = None
+        if want_masks:
+            self.masks = [_alloc_masks(B, h.shape[1], N, f.device) for h in self.Hs]
+            self._rl = (_P * n)(*[m.row.data_ptr() for m in self.masks])
+            self._cl = (_P * n)(*[m.col.data_ptr() for m in self.masks])
         ex = dict(_front_end or {})
         self.H_cat = None
         if f_out is not None:
@@ -266,7 +344,7 @@ class AffinityTail:
 
     def fits_tail(self) -> bool:
         B, N, D = self.f.shape
-        return N * (D + 4) * 4 + 8 + N * N * 8 <= load().gn_affinity_tail_lds_limit()
+        return self.masks is None and N * (D + 4) * 4 + 8 + N * N * 8 <= load().gn_affinity_tail_lds_limit()
 
     def launch(self) -> None:
         """The stand-alone launch (nothing took the job along)."""
@@ -275,7 +353,8 @@ class AffinityTail:
         B, N, D = self.f.shape
         with torch.cuda.device(self.f.device):
             check(_fn("gn_affinity_topk", self.f.dtype)(addr(self.f), addr(self.corr), self._Hl, self._kl, len(self.Hs), B, N, D,
-                                                        ctypes.byref(self._ex), stream_handle()), "gn_affinity_topk")
+                                                        ctypes.byref(self._ex), self._rl, self._cl, stream_handle()),
+                  "gn_affinity_topk")
         self.done = True
 
 
@@ -517,7 +596,17 @@ def edge_mlp_gumbel(edges: Tensor, U, pk: dict, K: int, tau: float = 0.5) -> Tup
 
 
 # ---- A5 ------------------------------------------------------------------------------------------
-def _edge_count(H: Optional[Tensor], B: int, N: int, sym: bool = False) -> int:
+def _edge_count(H: Optional[Tensor], B: int, N: int, sym: bool = False, masks: Optional[IncidenceMasks] = None) -> int:
+    if masks is not None:
+        if sym:
+            raise ValueError("sym applies to the pairwise graph (H=None) only")
+        if not isinstance(masks, IncidenceMasks):
+            raise ValueError("masks: expected an ops.IncidenceMasks")
+        _req(masks.row, "masks.row", (B, None), torch.int64)
+        _req(masks.col, "masks.col", (B, N), torch.int64)
+        if H is not None:
+            _req(H, "H", (B, masks.row.shape[1], N))
+        return masks.row.shape[1]
     if H is None:
         return pair_count(N) if sym else N * N
     if sym:
@@ -527,7 +616,9 @@ def _edge_count(H: Optional[Tensor], B: int, N: int, sym: bool = False) -> int:
 
 
 def agg_gather_grouped(items: Sequence[tuple]) -> List[Tensor]:
-    """items = [(ori (B,N,64), H (B,E,N) or None[, sym])] -> [eo (B,E,64)]."""
+    """items = [(ori (B,N,64), H (B,E,N) or None[, sym[, masks]])] -> [eo (B,E,64)].  ``masks`` (an `IncidenceMasks`,
+    N <= 64): the group is gathered from its row words instead of H (which may then be None); every hyper group of a call
+    in the same form."""
     _groups(len(items))
     o0 = _req(items[0][0], "ori", (None, None, FEAT), _ACT_DTYPES)
     dt = o0.dtype
@@ -537,19 +628,21 @@ def agg_gather_grouped(items: Sequence[tuple]) -> List[Tensor]:
     for g, item in enumerate(items):
         ori, H = item[:2]
         sym = bool(item[2]) if len(item) > 2 else False
+        masks = item[3] if len(item) > 3 else None
         _req(ori, "ori", (B, N, FEAT), dt)
-        E = _edge_count(H, B, N, sym)
-        _same_device(o0, ori, H)
+        E = _edge_count(H, B, N, sym, masks)
+        _same_device(o0, ori, H, None if masks is None else masks.row)
         eo = torch.empty((B, E, FEAT), dtype=ori.dtype, device=ori.device)
-        arr[g] = _lib.GatherGroup(ori=ori.data_ptr(), H=addr(H), eo=eo.data_ptr(), E=E, sym=int(sym))
+        arr[g] = _lib.GatherGroup(ori=ori.data_ptr(), H=addr(H), eo=eo.data_ptr(), E=E, sym=int(sym),
+                                  rowmask=0 if masks is None else masks.row.data_ptr())
         outs.append(eo)
     with torch.cuda.device(o0.device):
         check(_fn("gn_agg_gather", dt)(arr, len(items), B, N, stream_handle()), "gn_agg_gather")
     return outs
 
 
-def agg_gather(ori: Tensor, H: Optional[Tensor], sym: bool = False) -> Tensor:
-    return agg_gather_grouped([(ori, H, sym)])[0]
+def agg_gather(ori: Tensor, H: Optional[Tensor], sym: bool = False, masks: Optional[IncidenceMasks] = None) -> Tensor:
+    return agg_gather_grouped([(ori, H, sym, masks)])[0]
 
 
 class GatherSpec:
@@ -746,8 +839,9 @@ def node_linear(x: Tensor, W: Tensor, bias: Tensor, dout: int) -> Tensor:
 
 
 def agg_scatter_grouped(items: Sequence[tuple], divisor: Optional[float] = None) -> List[Tensor]:
-    """items = [(feat (B,E,64), H or None, ori (B,N,64)[, sym])] -> [cat(H^T feat, ori) / divisor
-    (B,N,128)]; divisor defaults to N (edge2node, model/MS_HGNN_batch.py:120,355)."""
+    """items = [(feat (B,E,64), H or None, ori (B,N,64)[, sym[, masks]])] -> [cat(H^T feat, ori) / divisor
+    (B,N,128)]; divisor defaults to N (edge2node, model/MS_HGNN_batch.py:120,355).  ``masks``: as `agg_gather_grouped`
+    (the column words are read)."""
     _groups(len(items))
     o0 = _req(items[0][2], "ori", (None, None, FEAT), _ACT_DTYPES)
     dt = o0.dtype
@@ -757,13 +851,14 @@ def agg_scatter_grouped(items: Sequence[tuple], divisor: Optional[float] = None)
     for g, item in enumerate(items):
         feat, H, ori = item[:3]
         sym = bool(item[3]) if len(item) > 3 else False
+        masks = item[4] if len(item) > 4 else None
         _req(ori, "ori", (B, N, FEAT), dt)
-        E = _edge_count(H, B, N, sym)
+        E = _edge_count(H, B, N, sym, masks)
         _req(feat, "feat", (B, E, FEAT), dt)
-        _same_device(o0, feat, ori, H)
+        _same_device(o0, feat, ori, H, None if masks is None else masks.col)
         out = torch.empty((B, N, 2 * FEAT), dtype=ori.dtype, device=ori.device)
         arr[g] = _lib.ScatterGroup(feat=feat.data_ptr(), H=addr(H), ori=ori.data_ptr(), out=out.data_ptr(), E=E,
-                                   sym=int(sym))
+                                   sym=int(sym), colmask=0 if masks is None else masks.col.data_ptr())
         outs.append(out)
     with torch.cuda.device(o0.device):
         check(_fn("gn_agg_scatter", dt)(arr, len(items), B, N, float(N if divisor is None else divisor),
@@ -772,8 +867,8 @@ def agg_scatter_grouped(items: Sequence[tuple], divisor: Optional[float] = None)
 
 
 def agg_scatter(feat: Tensor, H: Optional[Tensor], ori: Tensor, divisor: Optional[float] = None,
-                sym: bool = False) -> Tensor:
-    return agg_scatter_grouped([(feat, H, ori, sym)], divisor)[0]
+                sym: bool = False, masks: Optional[IncidenceMasks] = None) -> Tensor:
+    return agg_scatter_grouped([(feat, H, ori, sym, masks)], divisor)[0]
 
 
 # ---- A6 ------------------------------------------------------------------------------------------

@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from . import ops
 from .MS_HGNN_batch import (MS_HGNN_hyper, MS_HGNN_oridinary, _NoiseState, _draw_uniform, _needs_grad, _param_key,
-                            run_message_passing)
+                            masks_apply, run_message_passing)
 
 Tensor = torch.Tensor
 
@@ -171,17 +171,19 @@ class _TrajectoryEncoder(nn.Module):
         final = torch.empty((B, N, D * (2 + S)), dtype=inputs.dtype, device=inputs.device)
         cols = [final[..., D * (1 + i):D * (2 + i)] for i in range(1 + S)]
         adv = self.__dict__.get("_advance")      # (device counter, draws per call): set by graphs.GraphedPastEncoder
-        _, Hs, new_H, f = ops.affinity_topk(None, scales or [N], want_corr=False, f_out=final[..., :D],
-                                            want_H_cat=S > 1, embed=(x_raw, M, c),
-                                            counter=adv[0] if adv else None,
-                                            counter_add=adv[1] if adv else 0)        # >= 1 scale per launch; N = the
-        if S == 0:                                                                     # cheap all-ones edge
+        want_masks = S > 0 and masks_apply(N)     # mask form on and 16 < N <= 64: the launch also emits the member words
+        res = ops.affinity_topk(None, scales or [N], want_corr=False, f_out=final[..., :D],
+                                want_H_cat=S > 1, embed=(x_raw, M, c),
+                                counter=adv[0] if adv else None,
+                                counter_add=adv[1] if adv else 0, want_masks=want_masks)     # >= 1 scale per launch; N =
+        (_, Hs, new_H, f), masks = res[:4], ([None, *res[4]] if want_masks else None)       # the cheap all-ones edge
+        if S == 0:
             Hs, new_H = [], None
         elif S == 1:
             new_H = None      # the reference only builds new_H from two scales on (:296); its S==1 path raises
         mods = [self.interaction, *hypers]
         noise = [[_draw_uniform((B, N * N, 6), f.device)]] + [[_draw_uniform((B, H.shape[1], 10), f.device)] for H in Hs]
-        run_message_passing(mods, [f] * (1 + S), [None, *Hs], noise, cols)
+        run_message_passing(mods, [f] * (1 + S), [None, *Hs], noise, cols, masks=masks)
         return final, new_H
 
 

@@ -49,6 +49,13 @@
  *     takes that aggregate with E = 0.
  *   - Closing stage in the aggregation launch (gn_agg_group_t.y ...; ABI 34): the same launch also applies the closing
  *     MLP to cat(H^T feat, ori) / divisor — one launch per message-passing stage fewer, rows bit-identical.
+ *   - Bit-mask form of a hyperedge incidence (ABI 37): for N <= 64 (hence E <= 64: E is N or 1) and an H (B,E,N) that holds
+ *     only 0 and 1 — every incidence the library builds: top-k, listall, the all-ones edge of scale == N —
+ *         rowmask (B,E) 64-bit words: bit n of word (b,e) is set iff H[b,e,n] != 0   (the members of hyperedge e),
+ *         colmask (B,N) 64-bit words: bit e of word (b,n) is set iff H[b,e,n] != 0   (the hyperedges of node n).
+ *     gn_affinity_topk_* emit it next to H_s, gn_incidence_masks_f32 builds it from any dense H, and the stand-alone gather
+ *     and scatter (gn_gather_group_t.rowmask, gn_scatter_group_t.colmask) walk its set bits instead of all N (E) columns
+ *     of a dense row.  An H with other weights keeps the dense form.
  */
 #ifndef GROUPNET_HIP_H
 #define GROUPNET_HIP_H
@@ -122,7 +129,12 @@ int gn_listall_incidence_f32(const float* corr, float* H, int B, int N, int scal
  *             with x_raw (B,N,x_dim), M (D,x_dim), c (N,D) — the embedding front-end of
  *             PastEncoder.forward (model/GroupNet_nba.py:269-280), which in eval mode is one affine map
  *             per agent slot; the `f` argument is then ignored and f is ALSO written contiguously to
- *             f_contig (B,N,D), the h_states input of the modules. */
+ *             f_contig (B,N,D), the h_states input of the modules.
+ * `rowmask_list` / `colmask_list` (ABI 37; both NULL: not written, else both given): HOST arrays of n_scales device
+ * pointers; scale s also receives the bit-mask form of H_s (header comment; the incidence model/MS_HGNN_batch.py:263,267
+ * consume) — rowmask_list[s] (B,E_s) and colmask_list[s] (B,N) 64-bit words, 16-byte aligned, read off the same ranks as
+ * H_s (the same tie and NaN rules).  k_s == N: rowmask[b,0] = the N low bits, colmask[b,n] = 1.  N <= 64, else
+ * GN_ERR_SHAPE.  The tail form of the launch (gn_node_mlp_affinity_*) does not emit masks. */
 typedef struct {
   float* f_out;
   int f_out_ld;
@@ -137,13 +149,22 @@ typedef struct {
 } gn_block_extras_t;
 int gn_affinity_topk_f32(const float* f, float* corr, float* const* H_list, const int* k_list,
                          int n_scales, int B, int N, int D, const gn_block_extras_t* extras,
+                         unsigned long long* const* rowmask_list, unsigned long long* const* colmask_list,
                          gn_stream_t stream);
 /* twin: f, extras->f_out and extras->H_cat are bf16 (H values 0/1 are exact in bf16); the normalisation, the
  * affinity and the ranking run in fp32 on the bf16 inputs, corr (may be NULL) and every H_s stay fp32; the
  * embedding front-end (extras->x_raw) is not part of the twin. */
 int gn_affinity_topk_bf16(const void* f, float* corr, float* const* H_list, const int* k_list,
                           int n_scales, int B, int N, int D, const gn_block_extras_t* extras,
+                          unsigned long long* const* rowmask_list, unsigned long long* const* colmask_list,
                           gn_stream_t stream);
+
+/* Bit-mask form (header comment) of a dense incidence H (B,E,N) — a caller-supplied H, gn_listall_incidence_f32's, the
+ * banded top-k's of large N, or one that came out of the node stage's tail: rowmask (B,E), colmask (B,N), the incidence
+ * as model/MS_HGNN_batch.py:263,267 consume it.  `nonbinary` (device, may be NULL) receives 1 if any entry is neither 0
+ * nor 1 (such an H cannot take this form: keep the dense path), else 0.  E <= 64 and N <= 64, else GN_ERR_SHAPE. */
+int gn_incidence_masks_f32(const float* H, int B, int E, int N, unsigned long long* rowmask,
+                           unsigned long long* colmask, int* nonbinary, gn_stream_t stream);
 
 /* ---- weight packing -------------------------------------------------------------------
  * Number of floats of the packed image of an (out x in) nn.Linear weight. */
@@ -338,6 +359,12 @@ typedef struct {
   float* eo;          /* [T] */
   int E;
   int sym;
+  const unsigned long long* rowmask;   /* optional (ABI 37): the bit-mask form of H, (B,E) words (model/MS_HGNN_batch.py:263:
+                                          eo[b,e] = the sum of ori[b,n] over the set bits n, ascending).  With it H is not
+                                          read (may be NULL), sym must be 0 and N <= 64 (else GN_ERR_SHAPE); all hyper
+                                          groups of a launch use one form (else GN_ERR_SHAPE).  Rows equal the dense
+                                          form's bit for bit on finite ori; the dense form lets a non-finite value of a
+                                          NON-member row leak (0 * inf), the mask form does not. */
 } gn_gather_group_t;
 int gn_agg_gather_f32(const gn_gather_group_t* groups, int n_groups, int B, int N, gn_stream_t stream);
 int gn_agg_gather_bf16(const gn_gather_group_t* groups, int n_groups, int B, int N, gn_stream_t stream);
@@ -446,6 +473,10 @@ typedef struct {
   float* out;          /* [T] */
   int E;
   int sym;
+  const unsigned long long* colmask;   /* optional (ABI 37): the bit-mask form of H, (B,N) words (model/MS_HGNN_batch.py:267:
+                                          node n adds feat[b,e] over the set bits e, ascending).  With it H is not read
+                                          (may be NULL), sym must be 0, N <= 64 and E <= 64 (else GN_ERR_SHAPE); all hyper
+                                          groups of a launch use one form.  Bit-identical to the dense form. */
 } gn_scatter_group_t;
 int gn_agg_scatter_f32(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
                        gn_stream_t stream);
@@ -513,6 +544,7 @@ int gn_mlp2_bf16(const gn_mlp2_group_t* groups, int n_groups, int rows, int din,
 #define GN_K_MLP2 13
 #define GN_K_NODE2EDGE 14
 #define GN_K_AGG_GATHER 15
+#define GN_K_AGG_GATHER_MASK 16      /* the gather of groups with rowmask (ABI 37) */
 typedef struct {
   int kernel;        /* GN_K_*: the kernel of the launch (gn_kernel_name), instantiated for ... */
   int precision;     /* ... 0: the plain fp32 weight stream, 1: bf16 storage (the twins), 2: f16x3, 3: bf16x6 */
@@ -539,7 +571,7 @@ typedef struct {
                                      scene form: agg_scene_kernel; pairwise gather: agg_gather_pairwise_kernel) ... */
   int pre_lds[GN_MAX_GROUPS];     /* ... and this dynamic LDS */
   int SGh, EBh;      /* node -> edge: scenes per workgroup and hyperedges per band of the hyper groups (row form: EBh = 0) */
-  int G, TE;         /* gather: scenes per workgroup and hyperedges per tile */
+  int G, TE;         /* gather: scenes per workgroup and hyperedges per tile (mask form: TE = the largest E, one tile) */
 } gn_launch_plan_t;
 /* "agg_x_kernel", ...: the kernel's name as a kernel trace shows it (without template arguments); NULL for an unknown id */
 const char* gn_kernel_name(int kernel);
