@@ -44,9 +44,10 @@ _FUSED_SCATTER_MAX_N = 16     # cat(H^T feat, ori)/N inside the closing MLP
 
 
 def masks_apply(N: int) -> bool:
-    """Whether a forward over N agents has launches that read the bit-mask form of an incidence: the form is switched on
-    (`ops.set_incidence_form` / GN_INC_MASKS=1) and N lies where the stand-alone gather / scatter run and a 64-bit word
-    holds a row (16 < N <= 64).  Elsewhere nobody asks for masks and no launch changes."""
+    """Whether a forward (inference or training) over N agents has launches that read the bit-mask form of an incidence:
+    the form is switched on (`ops.set_incidence_form` / GN_INC_MASKS=1) and N lies where the stand-alone gather /
+    scatter and the node->edge launch run and a 64-bit word holds a row (16 < N <= 64).  Elsewhere nobody asks for masks
+    and no launch changes."""
     return (ops.incidence_form() == "mask" and min(_FUSED_GATHER_MAX_N, _FUSED_SCATTER_MAX_N) < N <= ops.MASK_MAX_N)
 
 
@@ -302,8 +303,10 @@ class _MessagePassing(nn.Module):
              ) -> Tuple[Tensor, Tensor]:
         return run_message_passing([self], [h], [H], [noise_u], [out], masks=None if masks is None else [masks])[0]
 
-    def _forward_autograd(self, h: Tensor, H: Optional[Tensor], noise_u, out: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
-        """Training path: fused forward + HIP backward through torch.autograd."""
+    def _forward_autograd(self, h: Tensor, H: Optional[Tensor], noise_u, out: Optional[Tensor], masks=None
+                          ) -> Tuple[Tensor, Tensor]:
+        """Training path: fused forward + HIP backward through torch.autograd.  ``masks``: the
+        `ops.IncidenceMasks` of ``H`` (or None), read by the forward and the backward where `masks_apply` holds."""
         from .backward import MSHGNNFunction
         if out is not None:
             raise ValueError("out= is an inference-time extra; under autograd the module returns a new tensor")
@@ -313,12 +316,12 @@ class _MessagePassing(nn.Module):
             # then carry fp32 intermediates (within the twins' own tolerance of them), gradients are those of the fp32
             # function at the bf16-rounded inputs, and outputs / the input gradient come back in bf16 (the casts are
             # ordinary differentiable torch ops).
-            nf, fac = MSHGNNFunction.apply((self,), (None if H is None else H.float(),), (noise_u,), h.float(),
+            nf, fac = MSHGNNFunction.apply((self,), (None if H is None else H.float(),), (noise_u,), (masks,), h.float(),
                                            *_plist(self))
             return nf.to(torch.bfloat16), fac.to(torch.bfloat16)
         if h.dtype != torch.float32:
             raise NotImplementedError("activations must be fp32 or bf16")
-        return MSHGNNFunction.apply((self,), (H,), (noise_u,), h, *_plist(self))
+        return MSHGNNFunction.apply((self,), (H,), (noise_u,), (masks,), h, *_plist(self))
 
 
 class _Closed(list):
@@ -346,8 +349,10 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     inside that launch what the closing launch cost on its own (single-stream forward 0.104 -> 0.103 ms, 4-stream
     throughput -2 %): the block asks for it in its latency form only.
     `masks`: one `ops.IncidenceMasks` (or None) per module, the bit-mask form of Hs[i].  With the mask form switched on
-    (`masks_apply(N)`), in inference, and a mask for EVERY hyper module, the stand-alone gather and scatter launches read
-    the masks instead of Hs (bit-identical results); otherwise they are ignored."""
+    (`masks_apply(N)`) and a mask for EVERY hyper module, the stand-alone gather and scatter launches read the masks
+    instead of Hs, and so does the node->edge launch where it takes its row form (bit-identical results) — in inference
+    and in a training forward (`traces`; the backward reads the same masks off the traces); otherwise they are
+    ignored."""
     n = len(mods)
     if not (n == len(hs) == len(Hs) == len(noises) == len(outs)) or n == 0:
         raise ValueError("run_message_passing: one h, H, noise and out per module")
@@ -362,7 +367,7 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     # MLP output and are summed into the same two nodes.  Its per-edge MLPs therefore run once per
     # unordered pair (N(N+1)/2 rows instead of N*N); only the Gumbel softmax runs per ordered edge.
     syms = [H is None for H in Hs]
-    use_masks = (masks is not None and traces is None and masks_apply(N)
+    use_masks = (masks is not None and masks_apply(N)
                  and all(sy or m is not None for sy, m in zip(syms, masks)))
     mks = [m if (use_masks and not sy) else None for sy, m in zip(syms, masks)] if masks is not None else [None] * n
     given = [_noise_iter(u) for u in noises]
@@ -400,8 +405,8 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
         edges: List = [None] * n
         rest = [i for i in range(n) if not fuse[i]]
         if rest:
-            for i, e in zip(rest, ops.node2edge_grouped([(xpq[i][0], xpq[i][1], Hs[i], pks[i]["w2"], pks[i]["b2"], syms[i])
-                                                         for i in rest])):
+            for i, e in zip(rest, ops.node2edge_grouped([(xpq[i][0], xpq[i][1], Hs[i], pks[i]["w2"], pks[i]["b2"], syms[i],
+                                                          mks[i]) for i in rest])):
                 edges[i] = e
         for i in range(n):
             if fuse[i]:
@@ -602,7 +607,7 @@ class MS_HGNN_hyper(_MessagePassing):
     def forward(self, h_states, corr, noise_u=None, H=None, out=None, masks=None):
         """``H`` (optional) lets a caller that already built the incidence for every scale in one
         fused launch (``ops.affinity_topk``) hand it in; by default it is built here from ``corr``.
-        ``masks`` (optional, inference): the `ops.IncidenceMasks` of a caller-supplied ``H``, used when the mask form is
+        ``masks`` (optional): the `ops.IncidenceMasks` of a caller-supplied ``H``, used when the mask form is
         switched on (`masks_apply`); an ``H`` handed in without them stays dense (it may carry other weights than 0/1),
         an ``H`` built here gets its masks from the builder."""
         ops._req(h_states, "h_states", (None, None, self.h_dim), ops._ACT_DTYPES)
@@ -610,7 +615,8 @@ class MS_HGNN_hyper(_MessagePassing):
             # H is a constant of the backward (top-k selection has no gradient; corr is only used to build it)
             if H is None:
                 H = self._build_H(h_states.detach(), corr.detach())
-            node_feat, factor = self._forward_autograd(h_states, H, noise_u, out)
+                masks = ops.incidence_masks(H, assume_binary=True) if masks_apply(h_states.shape[1]) else None
+            node_feat, factor = self._forward_autograd(h_states, H, noise_u, out, masks)
             return node_feat, factor, H
         if h_states.shape[0] == 0:                  # empty batch: nothing to launch
             B, N = h_states.shape[0], h_states.shape[1]

@@ -173,6 +173,8 @@ SIGNATURES = {
                                                   ctypes.POINTER(_SZ), ctypes.POINTER(_I)]),
     "gn_node2edge_f32": (_I, [ctypes.POINTER(N2EGroup), _I, _I, _I, _P]),
     "gn_node2edge_bf16": (_I, [ctypes.POINTER(N2EGroup), _I, _I, _I, _P]),
+    "gn_node2edge_masks_f32": (_I, [ctypes.POINTER(N2EGroup), ctypes.POINTER(_P), _I, _I, _I, _P]),
+    "gn_node2edge_masks_bf16": (_I, [ctypes.POINTER(N2EGroup), ctypes.POINTER(_P), _I, _I, _I, _P]),
     "gn_edge_mlp_gumbel_f32": (_I, [ctypes.POINTER(EdgeGroup), _I, _F, _U64, _P, _P]),
     "gn_edge_mlp_gumbel_bf16": (_I, [ctypes.POINTER(EdgeGroup), _I, _F, _U64, _P, _P]),
     "gn_edge_mlp_gumbel_launch_info_f32": (_I, [ctypes.POINTER(EdgeGroup), _I, ctypes.POINTER(_SZ), ctypes.POINTER(_I)]),
@@ -198,6 +200,8 @@ SIGNATURES = {
     "gn_mlp2_plan_bf16": (_I, [ctypes.POINTER(Mlp2Group), _I, _I, _I, _I, _I, _I, _I, _F, ctypes.POINTER(LaunchPlan)]),
     "gn_node2edge_plan_f32": (_I, [ctypes.POINTER(N2EGroup), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
     "gn_node2edge_plan_bf16": (_I, [ctypes.POINTER(N2EGroup), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
+    "gn_node2edge_masks_plan_f32": (_I, [ctypes.POINTER(N2EGroup), ctypes.POINTER(_P), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
+    "gn_node2edge_masks_plan_bf16": (_I, [ctypes.POINTER(N2EGroup), ctypes.POINTER(_P), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
     "gn_agg_gather_plan_f32": (_I, [ctypes.POINTER(GatherGroup), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
     "gn_agg_gather_plan_bf16": (_I, [ctypes.POINTER(GatherGroup), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
     "gn_gemm_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _F, _F, _P]),

@@ -151,8 +151,9 @@ class _Pool:
 class ModuleTrace:
     """What one module's fused forward keeps for its backward."""
 
-    def __init__(self, mod, h: Tensor, H: Optional[Tensor]):
+    def __init__(self, mod, h: Tensor, H: Optional[Tensor], masks=None):
         self.mod, self.H = mod, H
+        self.masks = masks                   # `ops.IncidenceMasks` of H where the step runs in mask form, else None
         self.xs: List[Tensor] = [h]          # node features entering round j
         self.dists: List[Tensor] = []        # dist of round j (B,E,K)
         self.tails: List[dict] = []          # round j's closing MLP: {"x": cat(H^T feat, ori)/N, "hid": relu(layer 0)}
@@ -214,7 +215,7 @@ def round_backward(traces: Sequence[ModuleTrace], j: int, g_ys: Sequence[Optiona
         if npar is None:
             npar = t._npar[j] = sum(p.numel() for m in (mod.node2edge_start_mlp[j], mod.attention_mlp[j], st, agg,
                                                         nn.ModuleList([e0, e1])) for p in m.parameters())
-        S.append(dict(mod=mod, x=x, x2=x.reshape(B * N, D), H=Hx, sym=sym, B=B, N=N, E=E, K=K, R=B * E, s0=s0, s1=s1, a0=a0, a1=a1, i=st.init_MLP.layers, d=st.MLP_distribution.layers,
+        S.append(dict(mod=mod, x=x, x2=x.reshape(B * N, D), H=Hx, masks=t.masks, sym=sym, B=B, N=N, E=E, K=K, R=B * E, s0=s0, s1=s1, a0=a0, a1=a1, i=st.init_MLP.layers, d=st.MLP_distribution.layers,
                       f=st.MLP_factor.layers, agg=agg, tw=_bwd_weights(mod, j), e0=e0, e1=e1,
                       tail=t.tails[j], dist=t.dists[j].reshape(-1, K), g_y=None if g_y is None else g_y.reshape(B * N, -1).contiguous(),
                       g_d=None if g_d is None else g_d.reshape(-1, K).contiguous(),
@@ -277,7 +278,7 @@ def round_backward(traces: Sequence[ModuleTrace], j: int, g_ys: Sequence[Optiona
         live = [c for c in S if c["g_y"] is not None]
         if live:
             S_all, S = S, live
-            eos = ops.agg_gather_grouped([(c["x"], c["H"], c["sym"]) for c in S])
+            eos = ops.agg_gather_grouped([(c["x"], c["H"], c["sym"], c["masks"]) for c in S])
             for c, eo in zip(S, eos):
                 c["eo"], c["eo2"] = eo, eo.view(c["R"], D)
             stage(lambda c: c.update(Hc=gb.add(c["eo2"], c["tw"]["W1cat"], new(c["R"], c["K"] * _HID), tB=True,
@@ -294,7 +295,8 @@ def round_backward(traces: Sequence[ModuleTrace], j: int, g_ys: Sequence[Optiona
                 c["da"] = gb.add(c["dy1"], W(c["e0"])[:, :D], new(c["B"] * c["N"], D), alpha=inv)   # d(H^T feat)
                 c["dx"] = gb.add(c["dy1"], W(c["e0"])[:, D:], new(c["B"] * c["N"], D), alpha=inv)   # ori half of the cat
             stage(dagg_stage)
-            dfeats = ops.agg_gather_grouped([(c["da"].view(c["B"], c["N"], D), c["H"], c["sym"]) for c in S])   # adjoint of H^T feat
+            dfeats = ops.agg_gather_grouped([(c["da"].view(c["B"], c["N"], D), c["H"], c["sym"], c["masks"])
+                                             for c in S])                                      # adjoint of H^T feat
             for c, df in zip(S, dfeats):
                 c["dfeat"] = df.view(c["R"], D)
             stage(lambda c: c.update(T=gb.add(c["dfeat"], c["tw"]["W2cat"], new(c["R"], c["K"] * _HID))))
@@ -308,7 +310,8 @@ def round_backward(traces: Sequence[ModuleTrace], j: int, g_ys: Sequence[Optiona
             stage(lambda c: c.update(deo=gb.add(c["T"], c["tw"]["W1cat"], c["pool"].take(c["R"], D), accum=True,
                                                 rs=_pair_row_weights(c["B"], c["N"], dev) if c["sym"] else None)))
             # eo = H ori  ->  d ori += H^T d eo  (the scatter kernel with divisor 1; its ori half is unused)
-            scs = ops.agg_scatter_grouped([(c["deo"].view(c["B"], c["E"], D), c["H"], c["x"], c["sym"]) for c in S], 1.0)
+            scs = ops.agg_scatter_grouped([(c["deo"].view(c["B"], c["E"], D), c["H"], c["x"], c["sym"], c["masks"])
+                                           for c in S], 1.0)
             for c, sc in zip(S, scs):
                 axpby(c["dx"], sc.view(c["B"] * c["N"], 2 * D)[:, :D], 1.0, 1.0)
 
@@ -427,17 +430,26 @@ def modules_backward(traces: Sequence[ModuleTrace], g_nfs: Sequence[Optional[Ten
 class MSHGNNFunction(torch.autograd.Function):
     """Several modules on their inputs: forward = the grouped fused HIP path, backward = `modules_backward`.
 
-    apply(mods, Hs, noises, n_params_per_module, h_0..h_{n-1}, *params) -> (nf_0, fac_0, nf_1, fac_1, ...)."""
+    apply(mods, Hs, noises, masks, h_0..h_{n-1}, *params) -> (nf_0, fac_0, nf_1, fac_1, ...).  ``masks``: None, or
+    one `ops.IncidenceMasks` / None per module (None for the pairwise one) — kept on the traces; forward and backward
+    read them instead of Hs where `run_message_passing` decides for the mask form."""
 
     @staticmethod
-    def forward(ctx, mods, Hs, noises, *tensors):
+    def forward(ctx, mods, Hs, noises, masks, *tensors):
         from . import MS_HGNN_batch as M
         n = len(mods)
         hs, params = tensors[:n], tensors[n:]
-        traces = [ModuleTrace(m, h.detach(), H) for m, h, H in zip(mods, hs, Hs)]
+        if masks is not None and len(masks) != n:
+            raise ValueError("MSHGNNFunction: one masks entry (or None) per module")
+        # the same decision as run_message_passing's, so that forward and backward of a step run in one form
+        use = (masks is not None and M.masks_apply(hs[0].shape[1])
+               and all(H is None or mk is not None for H, mk in zip(Hs, masks)))
+        masks = [mk if (use and H is not None) else None for H, mk in zip(Hs, masks)] if use else None
+        traces = [ModuleTrace(m, h.detach(), H, None if masks is None else masks[i])
+                  for i, (m, h, H) in enumerate(zip(mods, hs, Hs))]
         with torch.no_grad(), M.training_call():     # a training step: packed-weight caches are not trusted
             res = M.run_message_passing(list(mods), [t.xs[0] for t in traces], list(Hs), list(noises), [None] * n,
-                                        traces=traces)
+                                        traces=traces, masks=masks)
         ctx.traces, ctx.params, ctx.n = traces, params, n
         # the backward reads the LIVE weights (and re-packs them): remember which versions the activations belong to
         ctx.param_key = M._param_key(params)
@@ -465,4 +477,4 @@ class MSHGNNFunction(torch.autograd.Function):
                                         [g_facs[i] for i in live])
             for i, dh in zip(live, d):
                 dhs[i] = dh
-        return (None, None, None) + tuple(dhs) + tuple(grads.get(p) for p in ctx.params)
+        return (None, None, None, None) + tuple(dhs) + tuple(grads.get(p) for p in ctx.params)

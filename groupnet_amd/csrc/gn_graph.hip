@@ -377,8 +377,12 @@ __device__ __forceinline__ void node2edge_hyper_body(const WaveTable<gn_n2e_grou
 // (first pass: running max and sum of the softmax over ALL N nodes; second pass: the weights), the pooled features —
 // no scratch, no barrier after the stage.  Same formulas as the banded form (softmax(att*H)*H incl. the non-members'
 // exp(0 - max)); the running max/sum rounds differently in the last bits.
+// WORDS: the bit-mask form of the incidence (gn_node2edge_masks_*).  The launcher puts each group's rowmask (B,E) into
+// the table's H slot; a pair loads the one word of its hyperedge (the same address in both lanes) instead of scanning
+// the dense row, and every member's weight is the constant 1: fmaf(1, v, Q), (t + b2) * 1 and p * 1 are exact, so on a
+// 0/1 H the rows are bit-identical to the dense instantiation's.
 constexpr int kRowPitch = GN_FEAT + 4;
-template <typename TS>
+template <typename TS, bool WORDS>
 __device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e_group_t>& T, int B, int N, int SG, int wg) {
   extern __shared__ __align__(16) float lds[];
   const int gi = gn_uniform(find_wave_group(T, wg));
@@ -409,13 +413,20 @@ __device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e
     const bool live = r < total;
     const int rr = live ? r : total - 1;
     const int s = rr / E;
-    const float* Hrow = G.H + ((size_t)b0 * E + rr) * N;
+    const float* Hrow = WORDS ? nullptr : G.H + ((size_t)b0 * E + rr) * N;
     const float* pqb = s_pq + (size_t)s * N * kRowPitch;
     const float* xpb = s_xp + (size_t)s * N * kRowPitch;
-    // members: lane h scans the nodes n = h, h+2, ...; the pair ORs its halves
+    auto hval = [&](int n) {                               // H[e,n] of a member
+      if constexpr (WORDS) return 1.f;
+      else return Hrow[n];
+    };
     unsigned long long mask = 0ull;
-    for (int n = h; n < N; n += 2) mask |= (unsigned long long)(Hrow[n] != 0.f) << n;
-    {
+    if constexpr (WORDS) {
+      // members: the hyperedge's word (bits >= N cannot address a staged row)
+      mask = reinterpret_cast<const unsigned long long*>(G.H)[(size_t)b0 * E + rr] & (~0ull >> (64 - N));
+    } else {
+      // members: lane h scans the nodes n = h, h+2, ...; the pair ORs its halves
+      for (int n = h; n < N; n += 2) mask |= (unsigned long long)(Hrow[n] != 0.f) << n;
       const unsigned lo = (unsigned)mask, hi = (unsigned)(mask >> 32);
       const unsigned olo = (unsigned)__shfl_xor((int)lo, 32, GN_WAVE), ohi = (unsigned)__shfl_xor((int)hi, 32, GN_WAVE);
       mask |= ((unsigned long long)ohi << 32) | olo;
@@ -450,7 +461,7 @@ __device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e
 #pragma unroll
         for (int k = 0; k < MK; ++k) {
           mem[k] = m != 0ull ? __builtin_ctzll(m) : 0;
-          hvv[k] = k < cnt ? Hrow[mem[k]] : 0.f;
+          hvv[k] = WORDS ? 1.f : k < cnt ? hval(mem[k]) : 0.f;
           m &= m - 1ull;                                   // (0 stays 0)
         }
       }
@@ -501,7 +512,7 @@ __device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e
       // any number of members: running max / sum of the softmax, logits evaluated a second time for the weights
       for (unsigned long long m = mask; m != 0ull; m &= m - 1ull) {
         const int n = __builtin_ctzll(m);
-        const float hv = Hrow[n];
+        const float hv = hval(n);
         const float* q = pqb + n * kRowPitch + 32 + 16 * h;
 #pragma unroll
         for (int c4 = 0; c4 < 4; ++c4) {
@@ -515,7 +526,7 @@ __device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e
       for (unsigned long long m = mask; __any(m != 0ull); m &= m - 1ull) {
         const bool on = m != 0ull;
         const int n = on ? __builtin_ctzll(m) : 0;
-        const float v = logit(n, Hrow[n]);
+        const float v = logit(n, hval(n));
         if (on) {
           const float nm = fmaxf(mx, v);
           sum = sum * expf(mx - nm) + expf(v - nm);
@@ -526,7 +537,7 @@ __device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e
       for (unsigned long long m = mask; __any(m != 0ull); m &= m - 1ull) {
         const bool on = m != 0ull;
         const int n = on ? __builtin_ctzll(m) : 0;
-        const float hv = Hrow[n];
+        const float hv = hval(n);
         const float lv = logit(n, hv);
         if (on) {
           const float w = expf(lv - mx) / sum * hv;
@@ -657,7 +668,8 @@ struct PairTable {
 };
 // ROWS: the hyper groups in the lane-pair-per-hyperedge form (a kernel of its own: that form keeps member lists and
 // logits in registers, which the banded form's occupancy must not pay for)
-template <typename TS, bool ROWS>
+// WORDS (with ROWS): the row form reading member words, see node2edge_hyper_rows_body
+template <typename TS, bool ROWS, bool WORDS = false>
 __global__ __launch_bounds__(kBlock) void node2edge_kernel(WaveTable<gn_n2e_group_t> T, PairTable pair, int B, int N,
                                                            int SGh, int EBh, XcdSections xs) {
   const int wg = gn_uniform(gn_xcd_logical(xs, blockIdx.x));     // sections: the pairwise groups, then the hyper groups
@@ -668,7 +680,7 @@ __global__ __launch_bounds__(kBlock) void node2edge_kernel(WaveTable<gn_n2e_grou
     while (g + 1 < pair.n && wg >= pair.first_wg[g + 1]) ++g;
     node2edge_pairwise_body<TS>(pair.g[g], B, N, pair.SG[g], pair.bands[g], wg - pair.first_wg[g]);
   } else if constexpr (ROWS) {
-    node2edge_hyper_rows_body<TS>(T, B, N, SGh, wg - n_pair_wgs);      // one lane pair per hyperedge (N <= 64)
+    node2edge_hyper_rows_body<TS, WORDS>(T, B, N, SGh, wg - n_pair_wgs);      // one lane pair per hyperedge (N <= 64)
   } else {
     node2edge_hyper_body<TS>(T, B, N, SGh, EBh, wg - n_pair_wgs);
   }
@@ -1371,8 +1383,11 @@ static void n2e_pair_shape(int B, int N, int E, int& SG, int& bands) {
   while (bands < 64 && edges_per_wg / (bands * 2) >= 2048 && (long long)((B + SG - 1) / SG) * bands < 2048)
     bands *= 2;
 }
-static int node2edge_plan(const gn_n2e_group_t* groups, int n_groups, int B, int N, bool twin, const GnSwitches& sw,
-                          gn_launch_plan_t& p) {
+// rowmasks: nullptr, or per group the (B,E) member words of a hyper group / NULL (gn_node2edge_masks_*).  Words on every
+// hyper group turn the row form into its word-reading instantiation (variant 2) and change nothing else of the plan;
+// the banded form ignores them.
+static int node2edge_plan(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks, int n_groups, int B,
+                          int N, bool twin, const GnSwitches& sw, gn_launch_plan_t& p) {
   int rc = check_groups(groups, n_groups);
   if (rc != GN_OK) return rc;
   if (B <= 0 || N <= 0) return GN_ERR_SHAPE;
@@ -1382,7 +1397,7 @@ static int node2edge_plan(const gn_n2e_group_t* groups, int n_groups, int B, int
   p.precision = twin ? 1 : 0;
   p.grid[1] = p.grid[2] = 1;
   const size_t per_scene = (size_t)N * (GN_FEAT + GN_FEAT + 1) * sizeof(float);
-  int nh = 0, maxE = 1, pair_wgs = 0;
+  int nh = 0, nwords = 0, maxE = 1, pair_wgs = 0;
   long long hyper_rows = 0;
   size_t lds = 0;
   for (int g = 0; g < n_groups; ++g) {
@@ -1390,6 +1405,12 @@ static int node2edge_plan(const gn_n2e_group_t* groups, int n_groups, int B, int
     if (!G.xp || !G.pq || !G.w2 || !G.b2 || !G.edges) return GN_ERR_NULL;
     if (G.E <= 0) return GN_ERR_SHAPE;
     if (!gn_aligned16(G.xp) || !gn_aligned16(G.pq) || !gn_aligned16(G.edges)) return GN_ERR_ALIGN;
+    const unsigned long long* words = rowmasks != nullptr ? rowmasks[g] : nullptr;
+    if (words != nullptr) {
+      if (G.H == nullptr || N > 64) return GN_ERR_SHAPE;     // the pairwise graph has no words; a word holds 64 members
+      if ((reinterpret_cast<uintptr_t>(words) & 7u) != 0) return GN_ERR_ALIGN;
+      ++nwords;
+    }
     if (G.H == nullptr) {
       if ((long long)G.E != (G.sym ? (long long)gn_pair_count(N) : (long long)N * N)) return GN_ERR_SHAPE;
       const size_t fixed = (3 * kBlock + 32) * sizeof(float);
@@ -1407,6 +1428,7 @@ static int node2edge_plan(const gn_n2e_group_t* groups, int n_groups, int B, int
     maxE = maxE > G.E ? maxE : G.E;
     hyper_rows += (long long)B * G.E;
   }
+  if (nwords != 0 && nwords != nh) return GN_ERR_SHAPE;      // one form per launch
   // hyper groups: scenes per workgroup so that the staged rows stay <= 32 KiB while the grid keeps >= ~1024 workgroups
   int SGh = 1, EBh = 1;
   if (nh > 0) {
@@ -1435,7 +1457,7 @@ static int node2edge_plan(const gn_n2e_group_t* groups, int n_groups, int B, int
       EBh = 0;
       scratch = 0;
       stage = (size_t)SGh * row_scene;
-      p.variant = 1;
+      p.variant = nwords != 0 ? 2 : 1;
     }
     if (stage + scratch > 158 * 1024) return GN_ERR_LDS;
     const size_t l = stage + scratch;
@@ -1462,7 +1484,8 @@ static int node2edge_plan(const gn_n2e_group_t* groups, int n_groups, int B, int
   return GN_OK;
 }
 template <typename TS>
-static int node2edge_launch(const gn_launch_plan_t& p, const gn_n2e_group_t* groups, int B, int N, hipStream_t s) {
+static int node2edge_launch(const gn_launch_plan_t& p, const gn_n2e_group_t* groups,
+                            const unsigned long long* const* rowmasks, int B, int N, hipStream_t s) {
   WaveTable<gn_n2e_group_t> T{};
   PairTable P{};
   XcdSections xs{};
@@ -1484,6 +1507,7 @@ static int node2edge_launch(const gn_launch_plan_t& p, const gn_n2e_group_t* gro
   for (int g = 0; g < p.n_groups; ++g) {
     if (groups[g].H == nullptr) continue;
     T.g[T.n] = groups[g];
+    if (p.variant == 2) T.g[T.n].H = reinterpret_cast<const float*>(rowmasks[g]);   // the kernel's H slot: the words
     T.first[T.n++] = waves;
     xs.first[xs.n++] = pair_wgs + (int)waves;
     waves += p.wgs[g];
@@ -1496,27 +1520,48 @@ static int node2edge_launch(const gn_launch_plan_t& p, const gn_n2e_group_t* gro
     hipLaunchKernelGGL(k, dim3((unsigned)p.grid[0]), dim3(kBlock), (size_t)p.dyn_lds, s, T, P, B, N, p.SGh, p.EBh, xs);
     return gn_check_launch();
   };
+  if (p.variant == 2) return launch(node2edge_kernel<TS, true, true>);
   return p.variant ? launch(node2edge_kernel<TS, true>) : launch(node2edge_kernel<TS, false>);
 }
 template <typename TS>
-static int node2edge_entry(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_stream_t stream,
-                           gn_launch_plan_t* plan) {
+static int node2edge_entry(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks, int n_groups, int B,
+                           int N, gn_stream_t stream, gn_launch_plan_t* plan) {
   gn_launch_plan_t p;
-  int rc = node2edge_plan(groups, n_groups, B, N, sizeof(TS) != sizeof(float), gn_read_switches(), plan != nullptr ? *plan : p);
+  int rc = node2edge_plan(groups, rowmasks, n_groups, B, N, sizeof(TS) != sizeof(float), gn_read_switches(),
+                          plan != nullptr ? *plan : p);
   if (rc != GN_OK || plan != nullptr) return rc;
-  return node2edge_launch<TS>(p, groups, B, N, (hipStream_t)stream);
+  return node2edge_launch<TS>(p, groups, rowmasks, B, N, (hipStream_t)stream);
 }
+// (the entry points without words are the all-NULL case of the ones with)
 extern "C" int gn_node2edge_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_stream_t stream) {
-  return node2edge_entry<float>(groups, n_groups, B, N, stream, nullptr);
+  return node2edge_entry<float>(groups, nullptr, n_groups, B, N, stream, nullptr);
 }
 extern "C" int gn_node2edge_bf16(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_stream_t stream) {
-  return node2edge_entry<__bf16>(groups, n_groups, B, N, stream, nullptr);
+  return node2edge_entry<__bf16>(groups, nullptr, n_groups, B, N, stream, nullptr);
 }
 extern "C" int gn_node2edge_plan_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan) {
-  return plan == nullptr ? GN_ERR_NULL : node2edge_entry<float>(groups, n_groups, B, N, nullptr, plan);
+  return plan == nullptr ? GN_ERR_NULL : node2edge_entry<float>(groups, nullptr, n_groups, B, N, nullptr, plan);
 }
 extern "C" int gn_node2edge_plan_bf16(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan) {
-  return plan == nullptr ? GN_ERR_NULL : node2edge_entry<__bf16>(groups, n_groups, B, N, nullptr, plan);
+  return plan == nullptr ? GN_ERR_NULL : node2edge_entry<__bf16>(groups, nullptr, n_groups, B, N, nullptr, plan);
+}
+extern "C" int gn_node2edge_masks_f32(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks, int n_groups,
+                                      int B, int N, gn_stream_t stream) {
+  return rowmasks == nullptr ? GN_ERR_NULL : node2edge_entry<float>(groups, rowmasks, n_groups, B, N, stream, nullptr);
+}
+extern "C" int gn_node2edge_masks_bf16(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks,
+                                       int n_groups, int B, int N, gn_stream_t stream) {
+  return rowmasks == nullptr ? GN_ERR_NULL : node2edge_entry<__bf16>(groups, rowmasks, n_groups, B, N, stream, nullptr);
+}
+extern "C" int gn_node2edge_masks_plan_f32(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks,
+                                           int n_groups, int B, int N, gn_launch_plan_t* plan) {
+  if (rowmasks == nullptr || plan == nullptr) return GN_ERR_NULL;
+  return node2edge_entry<float>(groups, rowmasks, n_groups, B, N, nullptr, plan);
+}
+extern "C" int gn_node2edge_masks_plan_bf16(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks,
+                                            int n_groups, int B, int N, gn_launch_plan_t* plan) {
+  if (rowmasks == nullptr || plan == nullptr) return GN_ERR_NULL;
+  return node2edge_entry<__bf16>(groups, rowmasks, n_groups, B, N, nullptr, plan);
 }
 
 // workgroups a gather / scatter launch keeps at least when it packs several scenes into one.  2048 = two rounds of the

@@ -29,12 +29,17 @@ Tensor = torch.Tensor
 def multiscale_autograd(pair: MS_HGNN_oridinary, hypers: Sequence[MS_HGNN_hyper], scales: Sequence[int], f: Tensor,
                         noise_u: Optional[Sequence] = None) -> Tuple[Tensor, Optional[Tensor]]:
     """cat(f, pairwise(f), hyper_s(f, corr)...) and cat(H_s) with autograd attached: incidences from one fused
-    launch (constants of the backward), then ONE `MSHGNNFunction` node over all modules."""
+    launch (constants of the backward), then ONE `MSHGNNFunction` node over all modules.  In mask form
+    (`masks_apply(N)`) that launch also emits the member words, which the forward and the backward then read."""
     from .backward import MSHGNNFunction
     S = len(hypers)
     fd = f.detach().contiguous()
+    masks = None
     if S and ops.fused_affinity_fits(fd.shape[1], fd.shape[2]):
-        _, Hs, new_H = ops.affinity_topk(fd, list(scales), want_corr=False, want_H_cat=True)
+        want_masks = masks_apply(fd.shape[1])
+        res = ops.affinity_topk(fd, list(scales), want_corr=False, want_H_cat=True, want_masks=want_masks)
+        Hs, new_H = res[1], res[2]
+        masks = (None, *res[3]) if want_masks else None
     elif S:
         Hs = ops.topk_incidence(ops.affinity(fd), list(scales))
         new_H = torch.cat(Hs, dim=1)
@@ -52,7 +57,7 @@ def multiscale_autograd(pair: MS_HGNN_oridinary, hypers: Sequence[MS_HGNN_hyper]
     if len(nz) != 1 + S:
         raise ValueError(f"noise_u: need {1 + S} entries (pairwise + one per scale)")
     params = [p for m in mods for p in _plist(m)]
-    res = MSHGNNFunction.apply(mods, (None, *Hs), nz, *([f] * (1 + S)), *params)
+    res = MSHGNNFunction.apply(mods, (None, *Hs), nz, masks, *([f] * (1 + S)), *params)
     return torch.cat([f, *res[0::2]], dim=-1), new_H
 
 

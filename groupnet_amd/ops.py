@@ -437,19 +437,22 @@ def pair_count(N: int) -> int:
 
 
 def node2edge_grouped(items: Sequence[tuple]) -> List[Tensor]:
-    """items = [(xp, pq, H or None, w2 (32,), b2 (1,)[, sym])] over the same (B, N); returns [edges (B,E,64)].
+    """items = [(xp, pq, H or None, w2 (32,), b2 (1,)[, sym[, masks]])] over the same (B, N); returns [edges (B,E,64)].
     w2 / b2 = weight row and bias of attention layer 1, device tensors (the parameters themselves).
     H=None selects the implicit pairwise graph: E = N*N ordered edges, or with sym=True the
-    N(N+1)/2 unordered pairs (edges (i,j) and (j,i) carry the same feature)."""
+    N(N+1)/2 unordered pairs (edges (i,j) and (j,i) carry the same feature).
+    ``masks`` (an `IncidenceMasks` of a 0/1 H, N <= 64; every hyper group of a call or none): where the launch takes its
+    row form it reads the row words instead of H (gn_node2edge_masks_*); H stays in the item, the rows are the same."""
     _groups(len(items))
     xp0 = _req(items[0][0], "xp", (None, None, FEAT), _ACT_DTYPES)
     dt = xp0.dtype
     B, N, _ = xp0.shape
     arr = (_lib.N2EGroup * len(items))()
-    outs = []
+    outs, words = [], []
     for g, item in enumerate(items):
         xp, pq, H, w2, b2 = item[:5]
         sym = bool(item[5]) if len(item) > 5 else False
+        masks = item[6] if len(item) > 6 else None
         _req(xp, "xp", (B, N, FEAT), dt)
         _req(pq, "pq", (B, N, FEAT), dt)
         if H is None:
@@ -459,20 +462,34 @@ def node2edge_grouped(items: Sequence[tuple]) -> List[Tensor]:
                 raise ValueError("sym applies to the pairwise graph (H=None) only")
             _req(H, "H", (B, None, N))
             E = H.shape[1]
+        if masks is not None:
+            if H is None:
+                raise ValueError("masks apply to a hyper group (an explicit H) only")
+            if not isinstance(masks, IncidenceMasks):
+                raise ValueError("masks: expected an ops.IncidenceMasks")
+            _req(masks.row, "masks.row", (B, E), torch.int64)
+            words.append(masks.row)
+        else:
+            words.append(None)
         _req(w2, "w2", (32,))
         _req(b2, "b2", (1,))
-        _same_device(xp0, xp, pq, H, w2, b2)
+        _same_device(xp0, xp, pq, H, w2, b2, words[-1])
         edges = torch.empty((B, E, FEAT), dtype=xp.dtype, device=xp.device)
         arr[g] = _lib.N2EGroup(xp=xp.data_ptr(), pq=pq.data_ptr(), H=addr(H), w2=w2.data_ptr(), edges=edges.data_ptr(),
                                b2=b2.data_ptr(), E=E, sym=int(sym))
         outs.append(edges)
     with torch.cuda.device(xp0.device):
-        check(_fn("gn_node2edge", dt)(arr, len(items), B, N, stream_handle()), "gn_node2edge")
+        if any(w is not None for w in words):
+            rows = (ctypes.c_void_p * len(items))(*[None if w is None else w.data_ptr() for w in words])
+            check(_fn("gn_node2edge_masks", dt)(arr, rows, len(items), B, N, stream_handle()), "gn_node2edge_masks")
+        else:
+            check(_fn("gn_node2edge", dt)(arr, len(items), B, N, stream_handle()), "gn_node2edge")
     return outs
 
 
-def node2edge(xp: Tensor, pq: Tensor, H: Optional[Tensor], w2: Tensor, b2: Tensor, sym: bool = False) -> Tensor:
-    return node2edge_grouped([(xp, pq, H, w2, b2, sym)])[0]
+def node2edge(xp: Tensor, pq: Tensor, H: Optional[Tensor], w2: Tensor, b2: Tensor, sym: bool = False,
+              masks: Optional["IncidenceMasks"] = None) -> Tensor:
+    return node2edge_grouped([(xp, pq, H, w2, b2, sym, masks)])[0]
 
 
 # ---- A4 ------------------------------------------------------------------------------------------

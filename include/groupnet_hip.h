@@ -56,6 +56,10 @@
  *     gn_affinity_topk_* emit it next to H_s, gn_incidence_masks_f32 builds it from any dense H, and the stand-alone gather
  *     and scatter (gn_gather_group_t.rowmask, gn_scatter_group_t.colmask) walk its set bits instead of all N (E) columns
  *     of a dense row.  An H with other weights keeps the dense form.
+ *     Also ABI 37, additive (new symbols only: no struct, no signature and no kernel id changed, so the version stays):
+ *     gn_node2edge_masks_* hand the row form of the node -> edge pooling the same rowmask words, one 8-byte load per
+ *     hyperedge instead of a scan of its dense row.  What still reads the dense H: the banded form of the node -> edge
+ *     pooling, gn_node2edge_bwd_*, the pooling inside the edge kernel (N <= 16), and everything at N > 64.
  */
 #ifndef GROUPNET_HIP_H
 #define GROUPNET_HIP_H
@@ -282,6 +286,18 @@ typedef struct {
 } gn_n2e_group_t;
 int gn_node2edge_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_stream_t stream);
 int gn_node2edge_bf16(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_stream_t stream);
+/* The same launch with the bit-mask form of the hyper groups' incidences (ABI 37, additive; header comment).  `rowmasks`
+ * is a HOST array of n_groups device pointers: rowmasks[g] = the (B,E_g) member words of group g, or NULL.  A hyper group
+ * still carries its non-NULL H (H == NULL keeps meaning "pairwise", and the banded form reads H); its H must hold only
+ * 0 and 1, then the rows are bit-identical to gn_node2edge_*'s.  Where the launch takes the row form (plan variant 1
+ * without words) it reads the words instead of H (variant 2); where it takes the banded form the words are ignored.
+ * Checked before anything is launched: rowmasks == NULL: GN_ERR_NULL; a word pointer on a pairwise group, any word
+ * pointer with N > 64, or words on some hyper groups only (one form per launch): GN_ERR_SHAPE; a word pointer that is not
+ * 8-byte aligned: GN_ERR_ALIGN.  All entries NULL: exactly gn_node2edge_* (which are this case of the same code). */
+int gn_node2edge_masks_f32(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks, int n_groups, int B,
+                           int N, gn_stream_t stream);
+int gn_node2edge_masks_bf16(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks, int n_groups, int B,
+                            int N, gn_stream_t stream);
 
 /* ---- A4: per-edge MLPs + Gumbel-softmax edge typing ----------------------------------------
  * Replaces MLP_dict_softmax.forward + gumbel_softmax, MS_HGNN_batch.py:41-53,446-520:
@@ -549,7 +565,7 @@ typedef struct {
   int kernel;        /* GN_K_*: the kernel of the launch (gn_kernel_name), instantiated for ... */
   int precision;     /* ... 0: the plain fp32 weight stream, 1: bf16 storage (the twins), 2: f16x3, 3: bf16x6 */
   int variant;       /* ... agg_x_kernel: 1 = with the per-pair forms of the pairwise graph; node2edge_kernel: 1 = row form
-                        (0 = banded) */
+                        (0 = banded), 2 = row form reading member words (gn_node2edge_masks_*; see SGh, EBh) */
   int tiles[3];      /* ... closing MLP: 32-wide tiles (IT, HT, OT) of din, dh and dout (OT = 0: any dout) */
   int grid[3];       /* workgroups of the launch (x with XCD order: 8 x the largest per-XCD share) */
   int dyn_lds;       /* dynamic LDS bytes of the launch */
@@ -570,7 +586,8 @@ typedef struct {
   int pre_grid[GN_MAX_GROUPS];    /* > 0: the group runs in a launch of its own ahead of the main one, with this grid (bf16
                                      scene form: agg_scene_kernel; pairwise gather: agg_gather_pairwise_kernel) ... */
   int pre_lds[GN_MAX_GROUPS];     /* ... and this dynamic LDS */
-  int SGh, EBh;      /* node -> edge: scenes per workgroup and hyperedges per band of the hyper groups (row form: EBh = 0) */
+  int SGh, EBh;      /* node -> edge: scenes per workgroup and hyperedges per band of the hyper groups (row form: EBh = 0; so is variant
+                        2, whose plan equals variant 1's in every other field) */
   int G, TE;         /* gather: scenes per workgroup and hyperedges per tile (mask form: TE = the largest E, one tile) */
 } gn_launch_plan_t;
 /* "agg_x_kernel", ...: the kernel's name as a kernel trace shows it (without template arguments); NULL for an unknown id */
@@ -594,6 +611,10 @@ int gn_mlp2_plan_bf16(const gn_mlp2_group_t* groups, int n_groups, int rows, int
                       float divisor, gn_launch_plan_t* plan);
 int gn_node2edge_plan_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan);
 int gn_node2edge_plan_bf16(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan);
+int gn_node2edge_masks_plan_f32(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks, int n_groups,
+                                int B, int N, gn_launch_plan_t* plan);
+int gn_node2edge_masks_plan_bf16(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks, int n_groups,
+                                 int B, int N, gn_launch_plan_t* plan);
 int gn_agg_gather_plan_f32(const gn_gather_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan);
 int gn_agg_gather_plan_bf16(const gn_gather_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan);
 
