@@ -299,14 +299,13 @@ class _MessagePassing(nn.Module):
     def _edge2node(self, edge_feat: Tensor, ori: Tensor, H: Optional[Tensor], idx: int) -> Tensor:
         return self.edge_aggregation_list[idx]._aggregate(edge_feat, H, ori)
 
-    def _run(self, h: Tensor, H: Optional[Tensor], E: int, noise_u, out: Optional[Tensor] = None, masks=None
-             ) -> Tuple[Tensor, Tensor]:
-        return run_message_passing([self], [h], [H], [noise_u], [out], masks=None if masks is None else [masks])[0]
+    def _run(self, h: Tensor, H, E: int, noise_u, out: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        return run_message_passing([self], [h], [H], [noise_u], [out])[0]
 
-    def _forward_autograd(self, h: Tensor, H: Optional[Tensor], noise_u, out: Optional[Tensor], masks=None
+    def _forward_autograd(self, h: Tensor, H: Optional["ops.Incidence"], noise_u, out: Optional[Tensor]
                           ) -> Tuple[Tensor, Tensor]:
-        """Training path: fused forward + HIP backward through torch.autograd.  ``masks``: the
-        `ops.IncidenceMasks` of ``H`` (or None), read by the forward and the backward where `masks_apply` holds."""
+        """Training path: fused forward + HIP backward through torch.autograd.  ``H``: None or the
+        module's `ops.Incidence`, whose masks the forward and the backward read where `masks_apply` holds."""
         from .backward import MSHGNNFunction
         if out is not None:
             raise ValueError("out= is an inference-time extra; under autograd the module returns a new tensor")
@@ -316,25 +315,26 @@ class _MessagePassing(nn.Module):
             # then carry fp32 intermediates (within the twins' own tolerance of them), gradients are those of the fp32
             # function at the bf16-rounded inputs, and outputs / the input gradient come back in bf16 (the casts are
             # ordinary differentiable torch ops).
-            nf, fac = MSHGNNFunction.apply((self,), (None if H is None else H.float(),), (noise_u,), (masks,), h.float(),
-                                           *_plist(self))
+            H = None if H is None else ops.Incidence(H.H.float(), H.masks)
+            nf, fac = MSHGNNFunction.apply((self,), (H,), (noise_u,), h.float(), *_plist(self))
             return nf.to(torch.bfloat16), fac.to(torch.bfloat16)
         if h.dtype != torch.float32:
             raise NotImplementedError("activations must be fp32 or bf16")
-        return MSHGNNFunction.apply((self,), (H,), (noise_u,), (masks,), h, *_plist(self))
+        return MSHGNNFunction.apply((self,), (H,), (noise_u,), h, *_plist(self))
 
 
 class _Closed(list):
     """Outputs of closing MLPs that the aggregation launch applied itself."""
 
 
-def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor], Hs: Sequence[Optional[Tensor]],
-                        noises: Sequence, outs: Sequence[Optional[Tensor]], traces=None, join=None, affinity=None,
-                        fuse_closing: bool = False, masks: Optional[Sequence] = None) -> List[Tuple[Tensor, Tensor]]:
+def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor], Hs: Sequence, noises: Sequence,
+                        outs: Sequence[Optional[Tensor]], traces=None, join=None, affinity=None,
+                        fuse_closing: bool = False) -> List[Tuple[Tensor, Tensor]]:
     """The message-passing rounds of SEVERAL modules over the same scenes, stage by stage, each stage
     ONE grouped launch (model/MS_HGNN_batch.py:174-195 and :425-441 for every module at once).
 
-    mods[i] runs on hs[i] (B,N,64) with incidence Hs[i] (None = the implicit pairwise graph);
+    mods[i] runs on hs[i] (B,N,64) with incidence Hs[i] (None = the implicit pairwise graph, a dense tensor, or an
+    `ops.Incidence`: the dense tensor with its bit-mask form);
     noises[i] is None (draw), a tensor / PhiloxNoise, or a list of nmp_layers of them; outs[i]
     optionally receives node_feat.  Returns [(node_feat, factors)] per module.  All modules must
     share nmp_layers and bottleneck_dim (they do in every caller of the reference).
@@ -348,28 +348,30 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     allows (`ops.agg_mlp_closing`: the launcher's plan decides): one launch fewer per stage, bit-identical rows.  At B = 512, N = 11 the chain costs
     inside that launch what the closing launch cost on its own (single-stream forward 0.104 -> 0.103 ms, 4-stream
     throughput -2 %): the block asks for it in its latency form only.
-    `masks`: one `ops.IncidenceMasks` (or None) per module, the bit-mask form of Hs[i].  With the mask form switched on
-    (`masks_apply(N)`) and a mask for EVERY hyper module, the stand-alone gather and scatter launches read the masks
-    instead of Hs, and so does the node->edge launch where it takes its row form (bit-identical results) — in inference
-    and in a training forward (`traces`; the backward reads the same masks off the traces); otherwise they are
+    The mask form: with it switched on (`masks_apply(N)`) and masks on EVERY hyper module's incidence, the stand-alone
+    gather and scatter launches read the masks instead of H, and so does the node->edge launch where it takes its row
+    form (bit-identical results) — in inference and in a training forward (`traces`, which receive the masks the step
+    runs on: the backward reads them there, so both directions of a step run in one form); otherwise masks are
     ignored."""
     n = len(mods)
     if not (n == len(hs) == len(Hs) == len(noises) == len(outs)) or n == 0:
         raise ValueError("run_message_passing: one h, H, noise and out per module")
-    if masks is not None and len(masks) != n:
-        raise ValueError("run_message_passing: one masks entry (or None) per module")
     nmp = mods[0].nmp_layers
     if any(m.nmp_layers != nmp or m.bottleneck_dim != mods[0].bottleneck_dim for m in mods):
         raise ValueError("grouped modules must share nmp_layers and bottleneck_dim")
     B, N = hs[0].shape[0], hs[0].shape[1]
-    Es = [N * N if H is None else H.shape[1] for H in Hs]   # ordered edges: the shape of noise and factors
+    incs = [H if H is None or isinstance(H, ops.Incidence) else ops.Incidence(H) for H in Hs]
+    use_masks = masks_apply(N) and all(g is None or g.masks is not None for g in incs)
+    # every module's graph as the ops item tuples take it: (dense H or None, sym, masks where the step reads them)
     # The pairwise graph is symmetric: edges (i,j) and (j,i) pool the same feature, meet the same typed
     # MLP output and are summed into the same two nodes.  Its per-edge MLPs therefore run once per
     # unordered pair (N(N+1)/2 rows instead of N*N); only the Gumbel softmax runs per ordered edge.
-    syms = [H is None for H in Hs]
-    use_masks = (masks is not None and masks_apply(N)
-                 and all(sy or m is not None for sy, m in zip(syms, masks)))
-    mks = [m if (use_masks and not sy) else None for sy, m in zip(syms, masks)] if masks is not None else [None] * n
+    graphs = [(None, True, None) if g is None else (g.H, False, g.masks if use_masks else None) for g in incs]
+    syms = [sy for _, sy, _ in graphs]
+    Es = [N * N if H is None else H.shape[1] for H, _, _ in graphs]   # ordered edges: the shape of noise and factors
+    if traces is not None:
+        for t, (_, _, mk) in zip(traces, graphs):
+            t.masks = mk
     given = [_noise_iter(u) for u in noises]
 
     def next_u(i: int):
@@ -405,12 +407,12 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
         edges: List = [None] * n
         rest = [i for i in range(n) if not fuse[i]]
         if rest:
-            for i, e in zip(rest, ops.node2edge_grouped([(xpq[i][0], xpq[i][1], Hs[i], pks[i]["w2"], pks[i]["b2"], syms[i],
-                                                          mks[i]) for i in rest])):
+            for i, e in zip(rest, ops.node2edge_grouped([(xpq[i][0], xpq[i][1], graphs[i][0], pks[i]["w2"], pks[i]["b2"],
+                                                          *graphs[i][1:]) for i in rest])):
                 edges[i] = e
         for i in range(n):
             if fuse[i]:
-                edges[i] = ops.PoolSpec(xpq[i][0], xpq[i][1], Hs[i], pks[i]["w2"], pks[i]["b2"], syms[i])
+                edges[i] = ops.PoolSpec(xpq[i][0], xpq[i][1], graphs[i][0], pks[i]["w2"], pks[i]["b2"], syms[i])
         if traces is not None:      # kept for the backward: nothing of this round is re-computed there
             for t, kd, (xp, pq), e in zip(traces, keep, xpq, edges):
                 t.n2e.append(dict(x1=kd["hid"], xp=xp, pq=pq, edges=e))
@@ -435,7 +437,7 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
         items = []
         # larger graphs: eo = H @ ori of every hyper module from ONE stand-alone gather launch
         standalone = [i for i in range(n) if not syms[i] and N > _FUSED_GATHER_MAX_N]
-        eos = dict(zip(standalone, ops.agg_gather_grouped([(oris[i], Hs[i], False, mks[i]) for i in standalone]))) if standalone else {}
+        eos = dict(zip(standalone, ops.agg_gather_grouped([(oris[i], *graphs[i]) for i in standalone]))) if standalone else {}
         for i in range(n):
             pk, K = aggs[i]._packed(), aggs[i].edge_types
             if syms[i] and not twin and pair_A[i] is not None:
@@ -449,7 +451,7 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
                 src = ops.GatherSpec(oris[i], None, True,
                                      node=twin and ops.node_form_enabled() and N <= ops.SCENE_FORM_MAX_N)
             elif N <= _FUSED_GATHER_MAX_N:
-                src = ops.GatherSpec(oris[i], Hs[i], False)   # eo = H @ ori formed inside the kernel
+                src = ops.GatherSpec(oris[i], graphs[i][0], False)   # eo = H @ ori formed inside the kernel
             else:
                 src = eos[i]
             items.append((src, edge_feats[i], pk, K))
@@ -466,10 +468,10 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
             # cat(H^T feat, ori) / N is formed inside the MLP kernel that consumes it (node form: H^T feat is what the
             # aggregation kernel wrote)
             return [ops.NodeAggSpec(f, o) if node_item(it) else ops.ScatterSpec(f, H, o, sy)
-                    for f, H, o, sy, it in zip(feats, Hs, oris, syms, items)]
+                    for f, (H, sy, _), o, it in zip(feats, graphs, oris, items)]
         # larger graphs: one stand-alone scatter launch for the modules whose aggregation wrote per-edge features
         rest = [i for i in range(n) if not node_item(items[i])]
-        scat = dict(zip(rest, ops.agg_scatter_grouped([(feats[i], Hs[i], oris[i], syms[i], mks[i]) for i in rest]))) if rest else {}
+        scat = dict(zip(rest, ops.agg_scatter_grouped([(feats[i], graphs[i][0], oris[i], *graphs[i][1:]) for i in rest]))) if rest else {}
         return [scat[i] if i in scat else ops.NodeAggSpec(feats[i], oris[i]) for i in range(n)]
 
     res = edge_mlp([m.nmp_mlp_start for m in mods], node2edge(hs, 0), True)
@@ -616,7 +618,7 @@ class MS_HGNN_hyper(_MessagePassing):
             if H is None:
                 H = self._build_H(h_states.detach(), corr.detach())
                 masks = ops.incidence_masks(H, assume_binary=True) if masks_apply(h_states.shape[1]) else None
-            node_feat, factor = self._forward_autograd(h_states, H, noise_u, out, masks)
+            node_feat, factor = self._forward_autograd(h_states, ops.Incidence(H, masks), noise_u, out)
             return node_feat, factor, H
         if h_states.shape[0] == 0:                  # empty batch: nothing to launch
             B, N = h_states.shape[0], h_states.shape[1]
@@ -630,5 +632,5 @@ class MS_HGNN_hyper(_MessagePassing):
             masks = ops.incidence_masks(H, assume_binary=True) if masks_apply(h_states.shape[1]) else None
         else:
             ops._req(H, "H", (h_states.shape[0], None, h_states.shape[1]))
-        node_feat, factor = self._run(h_states, H, H.shape[1], noise_u, out, masks)
+        node_feat, factor = self._run(h_states, ops.Incidence(H, masks), H.shape[1], noise_u, out)
         return node_feat, factor, (H if H.dtype == h_states.dtype else H.to(h_states.dtype))    # type_as(feat), :376,384

@@ -151,9 +151,10 @@ class _Pool:
 class ModuleTrace:
     """What one module's fused forward keeps for its backward."""
 
-    def __init__(self, mod, h: Tensor, H: Optional[Tensor], masks=None):
-        self.mod, self.H = mod, H
-        self.masks = masks                   # `ops.IncidenceMasks` of H where the step runs in mask form, else None
+    def __init__(self, mod, h: Tensor, H):
+        self.mod = mod
+        self.H = H.H if isinstance(H, ops.Incidence) else H      # dense (None: the pairwise graph)
+        self.masks = None                    # `ops.IncidenceMasks` of H where `run_message_passing` ran the step on them
         self.xs: List[Tensor] = [h]          # node features entering round j
         self.dists: List[Tensor] = []        # dist of round j (B,E,K)
         self.tails: List[dict] = []          # round j's closing MLP: {"x": cat(H^T feat, ori)/N, "hid": relu(layer 0)}
@@ -430,26 +431,19 @@ def modules_backward(traces: Sequence[ModuleTrace], g_nfs: Sequence[Optional[Ten
 class MSHGNNFunction(torch.autograd.Function):
     """Several modules on their inputs: forward = the grouped fused HIP path, backward = `modules_backward`.
 
-    apply(mods, Hs, noises, masks, h_0..h_{n-1}, *params) -> (nf_0, fac_0, nf_1, fac_1, ...).  ``masks``: None, or
-    one `ops.IncidenceMasks` / None per module (None for the pairwise one) — kept on the traces; forward and backward
-    read them instead of Hs where `run_message_passing` decides for the mask form."""
+    apply(mods, Hs, noises, h_0..h_{n-1}, *params) -> (nf_0, fac_0, nf_1, fac_1, ...).  ``Hs``: per module None (the
+    pairwise graph), a dense tensor or an `ops.Incidence`; where `run_message_passing` decides for the mask form it
+    leaves the masks on the traces, and the backward reads them there."""
 
     @staticmethod
-    def forward(ctx, mods, Hs, noises, masks, *tensors):
+    def forward(ctx, mods, Hs, noises, *tensors):
         from . import MS_HGNN_batch as M
         n = len(mods)
         hs, params = tensors[:n], tensors[n:]
-        if masks is not None and len(masks) != n:
-            raise ValueError("MSHGNNFunction: one masks entry (or None) per module")
-        # the same decision as run_message_passing's, so that forward and backward of a step run in one form
-        use = (masks is not None and M.masks_apply(hs[0].shape[1])
-               and all(H is None or mk is not None for H, mk in zip(Hs, masks)))
-        masks = [mk if (use and H is not None) else None for H, mk in zip(Hs, masks)] if use else None
-        traces = [ModuleTrace(m, h.detach(), H, None if masks is None else masks[i])
-                  for i, (m, h, H) in enumerate(zip(mods, hs, Hs))]
+        traces = [ModuleTrace(m, h.detach(), H) for m, h, H in zip(mods, hs, Hs)]
         with torch.no_grad(), M.training_call():     # a training step: packed-weight caches are not trusted
             res = M.run_message_passing(list(mods), [t.xs[0] for t in traces], list(Hs), list(noises), [None] * n,
-                                        traces=traces, masks=masks)
+                                        traces=traces)
         ctx.traces, ctx.params, ctx.n = traces, params, n
         # the backward reads the LIVE weights (and re-packs them): remember which versions the activations belong to
         ctx.param_key = M._param_key(params)
@@ -477,4 +471,4 @@ class MSHGNNFunction(torch.autograd.Function):
                                         [g_facs[i] for i in live])
             for i, dh in zip(live, d):
                 dhs[i] = dh
-        return (None, None, None, None) + tuple(dhs) + tuple(grads.get(p) for p in ctx.params)
+        return (None, None, None) + tuple(dhs) + tuple(grads.get(p) for p in ctx.params)

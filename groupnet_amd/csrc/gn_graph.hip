@@ -1568,6 +1568,14 @@ extern "C" int gn_node2edge_masks_plan_bf16(const gn_n2e_group_t* groups, const 
 // chip at B = 4096, N = 11: the second round's loads overlap the first one's stores (3.90 -> 4.12 TB/s for the pair;
 // 4096 and 8192 measured the same as 2048)
 constexpr int kGsMinWgs = 2048;
+// scenes per workgroup of a staged gather / scatter launch: doubled while the tile (per_scene bytes a scene) stays
+// <= 24 KiB and the grid of nh groups stays >= kGsMinWgs
+static int gs_scenes_per_wg(size_t per_scene, int B, int nh) {
+  int G = 1;
+  while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= kGsMinWgs)
+    G *= 2;
+  return G;
+}
 
 static int gather_plan(const gn_gather_group_t* groups, int n_groups, int B, int N, bool twin, gn_launch_plan_t& p) {
   int rc = check_groups(groups, n_groups);
@@ -1601,45 +1609,26 @@ static int gather_plan(const gn_gather_group_t* groups, int n_groups, int B, int
   }
   if (nh == 0) return GN_OK;
   if (nm != 0 && nm != nh) return GN_ERR_SHAPE;     // one form for every hyper group of a launch
+  // a scene's tile is its ori rows and, for every hyperedge of its band, one member word (mask form: H is not staged, so
+  // more scenes fit a workgroup) or N floats of H
   const size_t ori_b = (size_t)N * GN_FEAT * sizeof(float);
-  if (nm != 0) {
-    // the tile of a scene is its ori rows and Emax words: the same packing rule as the dense form below (24 KiB tile target,
-    // >= kGsMinWgs workgroups), which without the H tile admits more scenes per workgroup
-    const size_t per_scene = ori_b + (size_t)Emax * sizeof(unsigned long long);
-    int G = 1;
-    while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= kGsMinWgs)
-      G *= 2;
-    p.kernel = GN_K_AGG_GATHER_MASK;
-    p.G = G;
-    p.TE = Emax;
-    p.dyn_lds = (int)((size_t)G * per_scene);
-    p.grid[0] = (B + G - 1) / G;
-    p.grid[1] = 1;
-    p.grid[2] = nh;
-    for (int g = 0; g < n_groups; ++g)
-      if (groups[g].rowmask != nullptr) p.wgs[g] = p.grid[0], p.spw[g] = G;
-    return GN_OK;
+  const size_t edge_b = nm != 0 ? sizeof(unsigned long long) : (size_t)N * sizeof(float);
+  int TE = Emax;
+  if (nm == 0) {
+    if (ori_b + edge_b > kLdsBudget) return GN_ERR_LDS;
+    if (ori_b + (size_t)Emax * edge_b > kLdsBudget) TE = (int)((kLdsBudget - ori_b) / edge_b);     // edge bands, G = 1
   }
-  if (ori_b + (size_t)N * sizeof(float) > kLdsBudget) return GN_ERR_LDS;
-  int G = 1, TE = Emax;
-  const size_t per_scene = ori_b + (size_t)Emax * N * sizeof(float);
-  if (per_scene <= kLdsBudget) {
-    // several scenes per workgroup while the tile stays <= 24 KiB and the grid stays >= kGsMinWgs
-    while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= kGsMinWgs)
-      G *= 2;
-  } else {
-    TE = (int)((kLdsBudget - ori_b) / ((size_t)N * sizeof(float)));
-    if (TE < 1) return GN_ERR_LDS;
-  }
-  p.kernel = GN_K_AGG_GATHER;
+  const size_t per_scene = ori_b + (size_t)TE * edge_b;
+  const int G = gs_scenes_per_wg(per_scene, B, nh);
+  p.kernel = nm != 0 ? GN_K_AGG_GATHER_MASK : GN_K_AGG_GATHER;
   p.G = G;
   p.TE = TE;
-  p.dyn_lds = (int)((size_t)G * ori_b + (size_t)G * TE * N * sizeof(float));
+  p.dyn_lds = (int)((size_t)G * per_scene);
   p.grid[0] = (B + G - 1) / G;
   p.grid[1] = (Emax + TE - 1) / TE;
   p.grid[2] = nh;
   for (int g = 0; g < n_groups; ++g)
-    if (groups[g].H != nullptr) p.wgs[g] = p.grid[0] * p.grid[1], p.spw[g] = G;
+    if (p.pos[g] >= 0) p.wgs[g] = p.grid[0] * p.grid[1], p.spw[g] = G;
   return GN_OK;
 }
 template <typename TS>
@@ -1742,22 +1731,18 @@ static int scatter_launch(const gn_scatter_group_t* groups, int n_groups, int B,
       Emax = G.E > Emax ? G.E : Emax;
     }
   }
-  if (nh > 0 && n_mask != 0) {
-    // agg_scatter_mask_kernel: the scene's tile is its feat rows and N words; packing rule as below
-    const size_t per_scene = (size_t)Emax * GN_FEAT * sizeof(float) + (size_t)N * sizeof(unsigned long long);
-    int G = 1;
-    while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= kGsMinWgs)
-      G *= 2;
-    hipLaunchKernelGGL(agg_scatter_mask_kernel<TS>, dim3((B + G - 1) / G, nh), dim3(kBlock), (size_t)G * per_scene, s, T, B,
-                       N, G, Emax, divisor);
-  } else if (nh > 0) {
-    const size_t per_scene = (size_t)Emax * (GN_FEAT + N) * sizeof(float);
-    int G = 1;
-    while (G < 16 && (size_t)(2 * G) * per_scene <= 24 * 1024 && (long long)((B + 2 * G - 1) / (2 * G)) * nh >= kGsMinWgs)
-      G *= 2;
-    gn_allow_big_lds(agg_scatter_kernel<TS>);
-    hipLaunchKernelGGL(agg_scatter_kernel<TS>, dim3((B + G - 1) / G, nh), dim3(kBlock), (size_t)G * per_scene, s, T, B,
-                       N, G, Emax, divisor);
+  if (nh > 0) {
+    // the scene's tile is its feat rows and N column words (mask form) or Emax N floats of H
+    const size_t per_scene = (size_t)Emax * GN_FEAT * sizeof(float) +
+                             (n_mask != 0 ? (size_t)N * sizeof(unsigned long long) : (size_t)Emax * N * sizeof(float));
+    const int G = gs_scenes_per_wg(per_scene, B, nh);
+    const dim3 grid((B + G - 1) / G, nh);
+    if (n_mask != 0) {
+      hipLaunchKernelGGL(agg_scatter_mask_kernel<TS>, grid, dim3(kBlock), (size_t)G * per_scene, s, T, B, N, G, Emax, divisor);
+    } else {
+      gn_allow_big_lds(agg_scatter_kernel<TS>);
+      hipLaunchKernelGGL(agg_scatter_kernel<TS>, grid, dim3(kBlock), (size_t)G * per_scene, s, T, B, N, G, Emax, divisor);
+    }
   }
   return gn_check_launch();
 }

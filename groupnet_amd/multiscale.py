@@ -34,17 +34,15 @@ def multiscale_autograd(pair: MS_HGNN_oridinary, hypers: Sequence[MS_HGNN_hyper]
     from .backward import MSHGNNFunction
     S = len(hypers)
     fd = f.detach().contiguous()
-    masks = None
     if S and ops.fused_affinity_fits(fd.shape[1], fd.shape[2]):
-        want_masks = masks_apply(fd.shape[1])
-        res = ops.affinity_topk(fd, list(scales), want_corr=False, want_H_cat=True, want_masks=want_masks)
-        Hs, new_H = res[1], res[2]
-        masks = (None, *res[3]) if want_masks else None
+        job = ops.AffinityTail(fd, list(scales), want_H_cat=True, want_masks=masks_apply(fd.shape[1]))
+        job.launch()
+        Hs, graphs, new_H = job.Hs, job.incidences, job.H_cat
     elif S:
-        Hs = ops.topk_incidence(ops.affinity(fd), list(scales))
+        Hs = graphs = ops.topk_incidence(ops.affinity(fd), list(scales))
         new_H = torch.cat(Hs, dim=1)
     else:
-        Hs, new_H = [], None
+        Hs, graphs, new_H = [], [], None
     mods = (pair, *hypers)
     if noise_u is None:
         # draw as the no-grad path (and the reference) does: module-major — every round of the pairwise module,
@@ -57,7 +55,7 @@ def multiscale_autograd(pair: MS_HGNN_oridinary, hypers: Sequence[MS_HGNN_hyper]
     if len(nz) != 1 + S:
         raise ValueError(f"noise_u: need {1 + S} entries (pairwise + one per scale)")
     params = [p for m in mods for p in _plist(m)]
-    res = MSHGNNFunction.apply(mods, (None, *Hs), nz, masks, *([f] * (1 + S)), *params)
+    res = MSHGNNFunction.apply(mods, (None, *graphs), nz, *([f] * (1 + S)), *params)
     return torch.cat([f, *res[0::2]], dim=-1), new_H
 
 
@@ -149,7 +147,6 @@ class MultiScaleHGNN(nn.Module):
         cols = [final[..., D * (1 + i):D * (2 + i)] for i in range(1 + S)]   # written in place by the last MLP
         join = None
         want_masks = masks_apply(N)       # mask form on and 16 < N <= 64: the fused launch also emits the member words
-        masks = None
         if S and ops.fused_affinity_fits(N, D):
             # one launch: affinity, incidence of every scale, f -> final[..., :D], cat(H_s), Philox bump.
             # The node stage of the first round needs only f: inside a graph capture the two launches are forked
@@ -161,20 +158,18 @@ class MultiScaleHGNN(nn.Module):
             side = _fork_stream(f.device) if fork else None
             if fork:
                 side.wait_stream(main)
-            tail = None
-            if self.grouped and not fork and self.affinity_tail and not want_masks:
-                # the launch is DEFERRED: it rides as the tail workgroups of the first node-stage launch (which needs only
-                # f), or is issued right before it when that launch cannot take it — one launch and one boundary fewer
-                tail = ops.AffinityTail(f, self.hyper_scales, want_corr=False, f_out=final[..., :D], want_H_cat=True,
-                                        counter=advance[0] if advance else None, counter_add=advance[1] if advance else 0)
-                Hs, new_H = tail.Hs, tail.H_cat
-            else:
-                with (torch.cuda.stream(side) if fork else contextlib.nullcontext()):
-                    res = ops.affinity_topk(f, self.hyper_scales, want_corr=False, f_out=final[..., :D],
-                                            want_H_cat=True, counter=advance[0] if advance else None,
-                                            counter_add=advance[1] if advance else 0, want_masks=want_masks)
-                    Hs, new_H = res[1], res[2]
-                    masks = [None, *res[3]] if want_masks else None
+            # the launch is DEFERRED where it can be: it rides as the tail workgroups of the first node-stage launch (which
+            # needs only f), or is issued right before it when that launch cannot take it — one launch and one boundary
+            # fewer; forked, ungrouped or emitting masks it is a launch of its own, here
+            deferred = self.grouped and not fork and self.affinity_tail and not want_masks
+            with (torch.cuda.stream(side) if fork else contextlib.nullcontext()):
+                job = ops.AffinityTail(f, self.hyper_scales, f_out=final[..., :D], want_H_cat=True,
+                                       counter=advance[0] if advance else None,
+                                       counter_add=advance[1] if advance else 0, want_masks=want_masks)
+                if not deferred:
+                    job.launch()
+            tail = job if deferred else None
+            Hs, new_H = job.incidences, job.H_cat
             if fork:
                 join = lambda: main.wait_stream(side)
         elif S:
@@ -196,8 +191,8 @@ class MultiScaleHGNN(nn.Module):
             # (latency form — `affinity_tail` — also folds the closing MLPs into the aggregation launch: 4 launches)
             run_message_passing(mods, [f] * (1 + S), [None, *Hs], list(noise_u), cols, join=join,
                                 affinity=tail if (S and ops.fused_affinity_fits(N, D)) else None,
-                                fuse_closing=self.affinity_tail, masks=masks)
+                                fuse_closing=self.affinity_tail)
         else:
-            for m, H, u, c, mk in zip(mods, [None, *Hs], noise_u, cols, masks or [None] * (1 + S)):
-                run_message_passing([m], [f], [H], [u], [c], masks=[mk])
+            for m, H, u, c in zip(mods, [None, *Hs], noise_u, cols):
+                run_message_passing([m], [f], [H], [u], [c])
         return final, new_H

@@ -240,6 +240,25 @@ class IncidenceMasks:
         self.row, self.col = row, col
 
 
+class Incidence:
+    """The graph a hyper module passes messages on, in both forms: the dense ``H`` (B,E,N) and, optionally, the
+    `IncidenceMasks` of that same H.  An entry of `run_message_passing`'s ``Hs`` (a plain tensor there is an `Incidence`
+    without masks, None the implicit pairwise graph)."""
+    __slots__ = ("H", "masks")
+
+    def __init__(self, H: Tensor, masks: Optional[IncidenceMasks] = None):
+        if not isinstance(H, torch.Tensor) or H.dim() != 3:
+            raise ValueError("H: expected a (B,E,N) tensor")
+        if masks is not None:
+            if not isinstance(masks, IncidenceMasks):
+                raise ValueError("masks: expected an ops.IncidenceMasks")
+            B, E, N = H.shape
+            _req(masks.row, "masks.row", (B, E), torch.int64)
+            _req(masks.col, "masks.col", (B, N), torch.int64)
+            _same_device(H, masks.row)
+        self.H, self.masks = H, masks
+
+
 def _alloc_masks(B: int, E: int, N: int, device) -> IncidenceMasks:
     if N > MASK_MAX_N or E > MASK_MAX_N:
         raise ValueError(f"the bit-mask form of an incidence needs N <= {MASK_MAX_N} and E <= {MASK_MAX_N}")
@@ -282,34 +301,34 @@ def affinity_topk(f: Optional[Tensor], scales: Sequence[int], want_corr: bool = 
     cat(H_s, dim=1); ``counter``/``counter_add`` — advance the device Philox position.
     ``embed`` = (x_raw (B,N,xd), M (D,xd), c (N,D)): f itself is computed in the launch as M x + c[n]
     (pass f=None, fp32 only); a fourth return value then carries f (B,N,D)."""
-    front = None
-    if embed is not None:
-        x_raw, M, c = embed
-        _req(x_raw, "x_raw", (None, None, None))
-        B, N, xd = x_raw.shape
-        _req(M, "M", (None, xd))
-        D = M.shape[0]
-        _req(c, "c", (N, D))
-        _same_device(x_raw, M, c)
-        f = torch.empty((B, N, D), dtype=x_raw.dtype, device=x_raw.device)   # the launch writes it (f_contig)
-        front = dict(x_raw=x_raw.data_ptr(), x_dim=xd, M=M.data_ptr(), c=c.data_ptr(), f_contig=f.data_ptr())
-    job = AffinityTail(f, scales, want_corr, f_out, want_H_cat, counter, counter_add, _front_end=front,
-                       want_masks=want_masks)
+    job = AffinityTail(f, scales, want_corr, f_out, want_H_cat, counter, counter_add, embed, want_masks)
     job.launch()
-    return (job.corr, job.Hs, job.H_cat) + ((f,) if embed is not None else ()) + ((job.masks,) if want_masks else ())
+    return (job.corr, job.Hs, job.H_cat) + ((job.f,) if embed is not None else ()) + ((job.masks,) if want_masks else ())
 
 
 class AffinityTail:
     """The fused affinity + top-k launch of a forward, DEFERRED: outputs are allocated now, the work is issued as the tail
     workgroups of the first node-stage launch (`node_stage_grouped(..., affinity=job)` -> gn_node_mlp_affinity_*), or —
-    when nothing picks it up — by `launch()` as the stand-alone launch.  Same arguments as `affinity_topk` (without the
-    embedding front-end, whose extras fields only `affinity_topk` passes in ``_front_end``).
+    when nothing picks it up — by `launch()` as the stand-alone launch.  Same arguments as `affinity_topk`; the results
+    are the attributes ``f``, ``corr``, ``Hs``, ``H_cat``, ``masks`` and ``incidences`` (one `Incidence` per scale: H_s with
+    its masks, what `run_message_passing` takes after the pairwise module's None).
     ``want_masks``: also emit the bit-mask form of every H_s (``masks``: one `IncidenceMasks` per scale).  Only the
     stand-alone launch emits masks, so the job then declines the tail (`fits_tail()` is False)."""
 
-    def __init__(self, f: Tensor, scales: Sequence[int], want_corr: bool = False, f_out: Optional[Tensor] = None,
-                 want_H_cat: bool = False, counter: Optional[Tensor] = None, counter_add: int = 0,
-                 _front_end: Optional[dict] = None, want_masks: bool = False):
+    def __init__(self, f: Optional[Tensor], scales: Sequence[int], want_corr: bool = False,
+                 f_out: Optional[Tensor] = None, want_H_cat: bool = False, counter: Optional[Tensor] = None,
+                 counter_add: int = 0, embed: Optional[Tuple[Tensor, Tensor, Tensor]] = None, want_masks: bool = False):
+        ex = {}
+        if embed is not None:
+            x_raw, M, c = embed
+            _req(x_raw, "x_raw", (None, None, None))
+            B, N, xd = x_raw.shape
+            _req(M, "M", (None, xd))
+            D = M.shape[0]
+            _req(c, "c", (N, D))
+            _same_device(x_raw, M, c)
+            f = torch.empty((B, N, D), dtype=x_raw.dtype, device=x_raw.device)   # the launch writes it (f_contig)
+            ex.update(x_raw=x_raw.data_ptr(), x_dim=xd, M=M.data_ptr(), c=c.data_ptr(), f_contig=f.data_ptr())
         _req(f, "f", (None, None, None), _ACT_DTYPES)
         self.f, self.scales = f, [int(s) for s in scales]
         B, N, D = f.shape
@@ -322,7 +341,7 @@ class AffinityTail:
             self.masks = [_alloc_masks(B, h.shape[1], N, f.device) for h in self.Hs]
             self._rl = (_P * n)(*[m.row.data_ptr() for m in self.masks])
             self._cl = (_P * n)(*[m.col.data_ptr() for m in self.masks])
-        ex = dict(_front_end or {})
+        self.incidences = [Incidence(H, m) for H, m in zip(self.Hs, self.masks or [None] * n)]
         self.H_cat = None
         if f_out is not None:
             if not (f_out.is_cuda and f_out.dtype == f.dtype and tuple(f_out.shape) == (B, N, D)

@@ -172,19 +172,16 @@ class _TrajectoryEncoder(nn.Module):
         cols = [final[..., D * (1 + i):D * (2 + i)] for i in range(1 + S)]
         adv = self.__dict__.get("_advance")      # (device counter, draws per call): set by graphs.GraphedPastEncoder
         want_masks = S > 0 and masks_apply(N)     # mask form on and 16 < N <= 64: the launch also emits the member words
-        res = ops.affinity_topk(None, scales or [N], want_corr=False, f_out=final[..., :D],
-                                want_H_cat=S > 1, embed=(x_raw, M, c),
-                                counter=adv[0] if adv else None,
-                                counter_add=adv[1] if adv else 0, want_masks=want_masks)     # >= 1 scale per launch; N =
-        (_, Hs, new_H, f), masks = res[:4], ([None, *res[4]] if want_masks else None)       # the cheap all-ones edge
-        if S == 0:
-            Hs, new_H = [], None
-        elif S == 1:
-            new_H = None      # the reference only builds new_H from two scales on (:296); its S==1 path raises
+        # >= 1 scale per launch; N = the cheap all-ones edge.  new_H: the reference only builds it from two scales on
+        # (:296); its S==1 path raises
+        job = ops.AffinityTail(None, scales or [N], f_out=final[..., :D], want_H_cat=S > 1, embed=(x_raw, M, c),
+                               counter=adv[0] if adv else None, counter_add=adv[1] if adv else 0, want_masks=want_masks)
+        job.launch()
+        f, incs = job.f, (job.incidences if S else [])
         mods = [self.interaction, *hypers]
-        noise = [[_draw_uniform((B, N * N, 6), f.device)]] + [[_draw_uniform((B, H.shape[1], 10), f.device)] for H in Hs]
-        run_message_passing(mods, [f] * (1 + S), [None, *Hs], noise, cols, masks=masks)
-        return final, new_H
+        noise = [[_draw_uniform((B, N * N, 6), f.device)]] + [[_draw_uniform((B, g.H.shape[1], 10), f.device)] for g in incs]
+        run_message_passing(mods, [f] * (1 + S), [None, *incs], noise, cols)
+        return final, job.H_cat
 
 
 class PastEncoder(_TrajectoryEncoder):
