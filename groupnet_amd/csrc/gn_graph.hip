@@ -1254,7 +1254,8 @@ extern "C" int gn_topk_incidence_f32(const float* corr, float* const* H_list, co
   ScaleList sl;
   const int rc = fill_scales(sl, H_list, k_list, n_scales, N);
   if (rc != GN_OK) return rc;
-  if ((size_t)N * sizeof(float) > kLdsBudget) return GN_ERR_LDS;
+  // a band holds at least one row of corr in half the budget: N <= 16 384 (beyond, RB below would be 0)
+  if ((size_t)N * sizeof(float) > kLdsBudget / 2) return GN_ERR_LDS;
   int RB = (int)(kLdsBudget / 2 / ((size_t)N * sizeof(float)));
   RB = RB > N ? N : RB;
   // enough bands to give the chip >= ~1024 workgroups when B is small

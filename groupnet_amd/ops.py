@@ -285,9 +285,27 @@ def incidence_masks(H: Tensor, assume_binary: bool = False) -> IncidenceMasks:
     return m
 
 
-def fused_affinity_fits(N: int, D: int, x_dim: int = 0) -> bool:
+AFFINITY_LDS_BUDGET = 128 * 1024      # gn_graph.hip kLdsBudget: the stand-alone fused affinity + top-k launch
+
+
+def affinity_tile_bytes(N: int, D: int, x_dim: int = 0, mask_scales: int = 0) -> int:
+    """LDS bytes of one scene's workgroup of the fused affinity + top-k code (gn_affinity.hpp `affinity_fused_lds`, plus
+    `affinity_mask_lds` for a launch that emits the bit-mask form of ``mask_scales`` scales): the one expression every
+    Python-side question about the form of that launch goes through."""
+    tile = N * (D + 4 + x_dim) * 4 + 8 + N * N * 8      # rows + 64-bit ranking keys (+ raw inputs of the embedding)
+    if mask_scales:
+        tile += 8 + 2 * mask_scales * N * 8             # row and column words of every scale
+    return tile
+
+
+def fused_affinity_fits(N: int, D: int, x_dim: int = 0, mask_scales: int = 0) -> bool:
     """Whether one scene's tile of the fused affinity+top-k launch fits its 128 KiB LDS budget."""
-    return N * (D + 4 + x_dim) * 4 + 8 + N * N * 8 <= 128 * 1024      # rows + 64-bit ranking keys (+ raw inputs)
+    return affinity_tile_bytes(N, D, x_dim, mask_scales) <= AFFINITY_LDS_BUDGET
+
+
+def affinity_tail_fits(N: int, D: int, x_dim: int = 0) -> bool:
+    """Whether that tile fits the smaller budget of the node stage's tail workgroups (gn_node_mlp_affinity_*)."""
+    return affinity_tile_bytes(N, D, x_dim) <= load().gn_affinity_tail_lds_limit()
 
 
 def affinity_topk(f: Optional[Tensor], scales: Sequence[int], want_corr: bool = True, f_out: Optional[Tensor] = None,
@@ -363,7 +381,7 @@ class AffinityTail:
 
     def fits_tail(self) -> bool:
         B, N, D = self.f.shape
-        return self.masks is None and N * (D + 4) * 4 + 8 + N * N * 8 <= load().gn_affinity_tail_lds_limit()
+        return self.masks is None and affinity_tail_fits(N, D, int(self._ex.x_dim))
 
     def launch(self) -> None:
         """The stand-alone launch (nothing took the job along)."""

@@ -122,6 +122,12 @@ class _TrajectoryEncoder(nn.Module):
         cat[10, 2] = 1                                            # IndexError for N <= 10, as the reference
         return cat
 
+    def fused_front_end_fits(self, N: int, T: int) -> bool:
+        """Whether an eval-mode forward over N agents and T time steps is served by the fused launch (the embedding as
+        one affine map inside the affinity + top-k launch): its scene tile, the raw inputs included, within the launch's
+        LDS budget.  Beyond it the forward runs the embedding on the HIP GEMM and the banded affinity / top-k pair."""
+        return ops.fused_affinity_fits(N, self.model_dim, T * self.input_fc.in_features)
+
     def _check_inputs(self, inputs: Tensor, B: int, N: int) -> int:
         ops._req(inputs, "inputs", (B * N, None, self.input_fc.in_features))
         T = inputs.shape[1]
@@ -166,11 +172,25 @@ class _TrajectoryEncoder(nn.Module):
             f = self._embed_autograd(inputs, B, N, T)
             final, new_H = multiscale_autograd(self.interaction, hypers, scales, f)
             return final, (new_H if S > 1 else None)
-        M, c = self._compose(T, N)
-        x_raw = inputs.reshape(B, N, T * inputs.shape[2])
         final = torch.empty((B, N, D * (2 + S)), dtype=inputs.dtype, device=inputs.device)
         cols = [final[..., D * (1 + i):D * (2 + i)] for i in range(1 + S)]
         adv = self.__dict__.get("_advance")      # (device counter, draws per call): set by graphs.GraphedPastEncoder
+        if not self.fused_front_end_fits(N, T):
+            # a scene tile beyond the fused launch's LDS budget (N >= 108 at 20 raw inputs per agent): the embedding layer
+            # by layer on the HIP GEMM as the training path runs it (dropout is the identity here), then the banded
+            # affinity and top-k launches; same noise order as below
+            with torch.no_grad():
+                f = self._embed_autograd(inputs, B, N, T).contiguous()
+            final[..., :D].copy_(f)
+            if adv:
+                ops.counter_add(adv[0], adv[1])
+            Hs = ops.topk_incidence(ops.affinity(f), scales) if S else []
+            mods = [self.interaction, *hypers]
+            noise = [[_draw_uniform((B, N * N, 6), f.device)]] + [[_draw_uniform((B, H.shape[1], 10), f.device)] for H in Hs]
+            run_message_passing(mods, [f] * (1 + S), [None, *Hs], noise, cols)
+            return final, (torch.cat(Hs, dim=1) if S > 1 else None)
+        M, c = self._compose(T, N)
+        x_raw = inputs.reshape(B, N, T * inputs.shape[2])
         want_masks = S > 0 and masks_apply(N)     # mask form on and 16 < N <= 64: the launch also emits the member words
         # >= 1 scale per launch; N = the cheap all-ones edge.  new_H: the reference only builds it from two scales on
         # (:296); its S==1 path raises

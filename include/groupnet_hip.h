@@ -108,7 +108,8 @@ int gn_affinity_f32(const float* f, float* corr, int B, int N, int D, gn_stream_
  *              largest entries of corr[b,i,:]  (ties: lowest index wins; NaN ranks first);
  *   k_s > N  : GN_ERR_K_RANGE.
  * H_list / k_list are HOST arrays of n_scales entries (1 <= n_scales <= GN_MAX_SCALES);
- * one pass over corr serves every scale. */
+ * one pass over corr serves every scale.  A workgroup stages a band of whole rows of corr in 64 KiB of LDS, so a row
+ * must fit there: N <= 16 384, else GN_ERR_LDS (nothing is launched). */
 int gn_topk_incidence_f32(const float* corr, float* const* H_list, const int* k_list, int n_scales,
                           int B, int N, gn_stream_t stream);
 
@@ -121,7 +122,9 @@ int gn_topk_incidence_f32(const float* corr, float* const* H_list, const int* k_
 int gn_listall_incidence_f32(const float* corr, float* H, int B, int N, int scale, gn_stream_t stream);
 
 /* A0+A1 fused: f -> corr (may be NULL: not written) and every H_s, without re-reading corr
- * from HBM.  Same contracts as the two functions above; N*(N+D)*4 bytes must fit in LDS.
+ * from HBM.  Same contracts as the two functions above; the scene tile, N (D + 4 + x_dim) 4 + 8 + 8 N N bytes (plus
+ * 8 + 16 n_scales N with mask lists), must fit 128 KiB of LDS (D = 64: N <= 112; 107 with x_dim = 20), else GN_ERR_LDS:
+ * beyond, call gn_affinity_f32 (which switches to its banded kernel there) and gn_topk_incidence_f32.
  * `extras` (may be NULL) lets this first launch of a multiscale forward also produce what the
  * caller's concatenations need, so that no copy kernels follow (model/GroupNet_nba.py:296-311):
  *   f_out   : f is also written to f_out with row stride f_out_ld floats (the first D columns of

@@ -139,6 +139,81 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
                 scene_grid=scene_grid, mlp2=mlp2, n2e=n2e, gather_spw=gather_spw)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the graph stage: cosine affinity + top-k incidence
+# ---------------------------------------------------------------------------------------------------------------------
+AFF_TAIL_LDS = 24 * 1024         # gn_mlp_mfma.hip kAffTailLds: a scene tile the node stage's tail workgroups may take
+AFF_LDS_BUDGET = 128 * 1024      # gn_graph.hip kLdsBudget: ... and the stand-alone fused launch
+AFF_BAND_ROWS, AFF_PANEL_COLS = 16, 64      # affinity_banded_kernel: rows of a workgroup's band, columns of a staged panel
+TOPK_MIN_WGS = 1024              # gn_topk_incidence_f32 halves its band while the launch has fewer workgroups ...
+TOPK_MIN_RB = 8                  # ... and more than this many rows per band
+
+
+def affinity_tile(N: int, D: int = 64, x_dim: int = 0, mask_scales: int = 0) -> int:
+    """LDS bytes of one scene of the fused affinity + top-k code (gn_affinity.hpp affinity_fused_lds: rows at stride
+    D + 4, the pad to 8 bytes, 64-bit ranking keys, the raw inputs of the embedding form; affinity_mask_lds: the row and
+    column words of every scale of a launch that emits masks)."""
+    tile = N * (D + 4) * 4 + 8 + N * N * 8 + N * x_dim * 4
+    return tile + (8 + 2 * mask_scales * N * 8 if mask_scales else 0)
+
+
+def topk_bands(B: int, N: int):
+    """(RB, bands, N % RB) of gn_topk_incidence_f32: RB rows of corr per workgroup — as many as half the LDS budget
+    holds, at most N, halved (rounding up) while the launch has fewer than 1024 workgroups and RB > 8.  None where the
+    entry refuses N (not one row fits)."""
+    RB = (AFF_LDS_BUDGET // 2) // (4 * N)
+    if RB == 0:
+        return None
+    RB = min(RB, N)
+    while RB > TOPK_MIN_RB and B * cdiv(N, RB) < TOPK_MIN_WGS:
+        RB = (RB + 1) // 2
+    return RB, cdiv(N, RB), N % RB
+
+
+def graph_forms(B: int, N: int, D: int = 64, x_dim: int = 0, masks: bool = False, scales: Sequence[int] = ()) -> Dict:
+    """Which form builds the graph of B scenes of N agents with D features (x_dim raw inputs per agent in the embedding
+    form; masks: the launch also emits the bit-mask form of every scale of `scales`):
+      "tail"   — tail workgroups of the node-stage launch (no masks; tile within AFF_TAIL_LDS),
+      "fused"  — the stand-alone fused launch (tile, mask words included, within AFF_LDS_BUDGET),
+      "banded" — affinity_banded_kernel + topk_incidence_kernel.
+    -> {"form", "tile" (bytes, of the fused code), "aff_grid" ((cdiv(N,16), B)), "aff_last" ((rows of the last band,
+    columns of the last panel)), "topk" ((RB, bands, N % RB))}; the last three are None unless the form is "banded".
+    Restates the launchers' arithmetic; tests/test_graph_forms_cpu.py holds it against the library without a launch."""
+    tile = affinity_tile(N, D, x_dim, len(scales) if masks else 0)
+    if not masks and tile <= AFF_TAIL_LDS:
+        form = "tail"
+    elif tile <= AFF_LDS_BUDGET:
+        form = "fused"
+    else:
+        form = "banded"
+    out = dict(form=form, tile=tile, aff_grid=None, aff_last=None, topk=None)
+    if form == "banded":
+        out.update(aff_grid=(cdiv(N, AFF_BAND_ROWS), B),
+                   aff_last=((N - 1) % AFF_BAND_ROWS + 1, (N - 1) % AFF_PANEL_COLS + 1), topk=topk_bands(B, N))
+    return out
+
+
+def largest_fused_n(D: int = 64, x_dim: int = 0, mask_scales: int = 0, budget: int = AFF_LDS_BUDGET) -> int:
+    """The largest N whose tile is within `budget` (the tile grows with N)."""
+    N = 1
+    while affinity_tile(N + 1, D, x_dim, mask_scales) <= budget:
+        N += 1
+    return N
+
+
+# the cases of tests/test_graph_forms_gpu.py (tests/test_graph_forms_cpu.py checks what they reach)
+# gn_affinity_f32 alone, (B, N, D): the ragged banded shapes, the existing exact one, the largest fused tile, the first N
+# beyond the tail; other D at a small N and at the switch pair of D = 128
+AFFINITY_CASES = [(2, 113, 64), (2, 129, 64), (1, 200, 64), (3, 256, 64), (2, 112, 64), (2, 41, 64)]
+AFFINITY_D_CASES = [(2, 11, 4), (2, 11, 36), (2, 11, 128), (2, 99, 128), (2, 100, 128)]
+# gn_topk_incidence_f32 alone, (B, N): one band of all N rows (twice), the LDS cap with a short last band, a halved band
+# with a remainder, RB < 8, RB = 8 with a last band of one row
+TOPK_CASES = [(1024, 11), (1024, 113), (1024, 200), (300, 200), (3, 200), (2, 113)]
+# the fused launch through ops.affinity_topk, (B, N), and the block through the engine
+FUSED_CASES = [(3, 40), (3, 41), (3, 112)]
+ENGINE_CASES = [(3, 40), (3, 41), (1, 112), (1, 113)]
+
+
 PLACEHOLDER = 4096      # a 16-aligned non-NULL "device address": a plan query tests addresses, it never dereferences them
 
 

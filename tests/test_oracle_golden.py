@@ -149,6 +149,26 @@ def test_c_oracle_topk_ties_nan_range():
         assert np.array_equal(H, O.topk_incidence_ranked(torch.from_numpy(big), s).numpy())
 
 
+def test_c_oracle_topk_infinities_and_signed_zeros():
+    """Heavy ties with -0.0 beside +0.0 (the two compare equal: the lower index wins), a NaN, +inf and -inf in one row:
+    the arg-max oracle and the ranked rule — the contract — agree for every k, and the row's order is NaN, +inf, the
+    finite values, -inf."""
+    lib = _c_oracle()
+    rng = np.random.default_rng(3)
+    corr = rng.integers(0, 3, size=(2, 11, 11)).astype(np.float32)
+    corr[:, 0, :5] = [-0.0, 0.0, np.nan, np.inf, -np.inf]
+    corr[0, 1, 1] = np.nan
+    for s in (0, 1, 2, 5, 9, 10, 11):
+        rc, H = _c_topk(lib, corr, s)
+        assert rc == 0 and np.array_equal(H, O.topk_incidence_ranked(torch.from_numpy(corr), s).numpy()), s
+    row = np.array([[[-0.0, 0.0, np.nan, np.inf, -np.inf, 0.0]]], dtype=np.float32).repeat(6, axis=1)
+    order = [2, 3, 0, 1, 5, 4]
+    for k in range(1, 6):
+        want = [1.0 if c in order[:k] else 0.0 for c in range(6)]
+        assert _c_topk(lib, row, k)[1][0, 0].tolist() == want, k
+        assert O.topk_incidence_ranked(torch.from_numpy(row), k)[0, 0].tolist() == want, k
+
+
 @pytest.mark.parametrize("name", ["n11_b6", "n7_b3", "n13_b2"])
 def test_listall_oracle_matches_reference_goldens(name):
     """oracle.listall_incidence == the reference's init_adj_attention_listall (MS_HGNN_batch.py:390-414) on

@@ -1261,12 +1261,15 @@ def test_pair_scatter_read_once_is_bit_identical(N, dtype, monkeypatch):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("B,N,scales", [(37, 11, [2, 5, 11]), (512, 11, [2, 5, 11]), (3, 30, [4, 30])])
+@pytest.mark.parametrize("B,N,scales", [(37, 11, [2, 5, 11]), (512, 11, [2, 5, 11]), (3, 30, [4, 30]), (3, 40, [2, 8, 40]),
+                                        (3, 41, [2, 8, 41])])
 def test_affinity_tail_of_the_node_stage_is_bit_identical(B, N, scales, dtype):
     """The fused affinity + top-k launch riding as the tail workgroups of the first node-stage launch
     (gn_node_mlp_affinity_*, the block's default) against the two separate launches (`ops._AFFINITY_TAIL = False`):
     same code for a scene either way — features, incidence and the f copy identical, and the launch really is gone
-    (the block issues one launch fewer)."""
+    (the block issues one launch fewer).  N = 40 is the last scene tile the tail takes (23 688 of 24 576 B); at N = 41 the
+    first call must NOT ride: one stand-alone launch per call, the same bits."""
+    tail = N <= 40
     from groupnet_amd import ops
     from groupnet_amd.multiscale import MultiScaleHGNN
     torch.manual_seed(5)
@@ -1292,7 +1295,10 @@ def test_affinity_tail_of_the_node_stage_is_bit_identical(B, N, scales, dtype):
                 ops._AFFINITY_TAIL = True
     finally:
         ops.AffinityTail.launch = orig
-    assert rode and counts.get("alone", 0) == 1          # first call rode in the node stage, second was its own launch
+    if tail:
+        assert rode and counts.get("alone", 0) == 1      # first call rode in the node stage, second was its own launch
+    else:
+        assert not rode and counts.get("alone", 0) == 2  # beyond the tail's tile: its own launch both times
     assert torch.equal(a, b) and torch.equal(Ha, Hb)
     assert torch.equal(a[..., :64], f)
 
