@@ -14,10 +14,11 @@ import torch  # noqa: F401  (must be imported before the .so is loaded)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GROUPNET_HIP_LIB") or os.path.join(_HERE, "libgroupnet_hip.so")  # env: tuning builds
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 GN_OK = 0
 GN_ERR_K_RANGE = -3
+GN_ERR_LDS = -6
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -140,11 +141,15 @@ class LaunchPlan(ctypes.Structure):
     _fields_ = [("kernel", _I), ("precision", _I), ("variant", _I), ("tiles", _I * 3), ("grid", _I * 3), ("dyn_lds", _I),
                 ("stage_bytes", _I), ("xcd", _I), ("closing", _I), ("n_groups", _I), ("wgs", _G), ("wpr", _G), ("spw", _G),
                 ("stage", _G), ("lines", _G), ("node_form", _G), ("unstaged", _G), ("pos", _G), ("pre_grid", _G),
-                ("pre_lds", _G), ("SGh", _I), ("EBh", _I), ("G", _I), ("TE", _I)]
+                ("pre_lds", _G), ("SGh", _I), ("EBh", _I), ("G", _I), ("TE", _I), ("pre_kernel", _G)]
 
 
 GEMM_TRANS_A, GEMM_TRANS_B, GEMM_RELU, GEMM_ACCUM, GEMM_TRANS_C = 1, 2, 4, 8, 16
 K_AGG_GATHER, K_AGG_GATHER_MASK = 15, 16      # GN_K_*: the two forms of the stand-alone gather
+K_AGG_SCENE, K_AGG_GATHER_PAIRWISE = 17, 18   # ... the kernels of a group's own launch (LaunchPlan.pre_kernel)
+K_AFFINITY_TOPK, K_AFFINITY_TOPK_MASKS, K_AFFINITY_BANDED, K_TOPK_INCIDENCE = 19, 20, 21, 22      # ... the graph stage
+K_AGG_SCATTER, K_AGG_SCATTER_MASK, K_AGG_SCATTER_DIRECT, K_AGG_SCATTER_PAIRS = 23, 24, 25, 26     # ... the scatter
+K_LAST = K_AGG_SCATTER_PAIRS
 MAX_GROUPS = 10
 
 # name -> (restype, argtypes); mirrors include/groupnet_hip.h one to one
@@ -204,6 +209,16 @@ SIGNATURES = {
     "gn_node2edge_masks_plan_bf16": (_I, [ctypes.POINTER(N2EGroup), ctypes.POINTER(_P), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
     "gn_agg_gather_plan_f32": (_I, [ctypes.POINTER(GatherGroup), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
     "gn_agg_gather_plan_bf16": (_I, [ctypes.POINTER(GatherGroup), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
+    "gn_agg_scatter_plan_f32": (_I, [ctypes.POINTER(ScatterGroup), _I, _I, _I, _F, ctypes.POINTER(LaunchPlan)]),
+    "gn_agg_scatter_plan_bf16": (_I, [ctypes.POINTER(ScatterGroup), _I, _I, _I, _F, ctypes.POINTER(LaunchPlan)]),
+    "gn_affinity_plan_f32": (_I, [_P, _P, _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
+    "gn_topk_incidence_plan_f32": (_I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_I), _I, _I, _I, ctypes.POINTER(LaunchPlan)]),
+    "gn_affinity_topk_plan_f32": (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I), _I, _I, _I, _I,
+                                       ctypes.POINTER(BlockExtras), ctypes.POINTER(_P), ctypes.POINTER(_P),
+                                       ctypes.POINTER(LaunchPlan)]),
+    "gn_affinity_topk_plan_bf16": (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I), _I, _I, _I, _I,
+                                        ctypes.POINTER(BlockExtras), ctypes.POINTER(_P), ctypes.POINTER(_P),
+                                        ctypes.POINTER(LaunchPlan)]),
     "gn_gemm_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _F, _F, _P]),
     "gn_gemm_grouped_f32": (_I, [ctypes.POINTER(GemmDesc), _I, _P]),
     "gn_typed_bwd_f32": (_I, [_P, _P, _P, _I, _P, _P, _P, ctypes.c_longlong, _I, _I, _P]),

@@ -197,4 +197,44 @@ inline size_t affinity_fused_lds(int N, int D, int x_dim) {
 // ... and of the mask words of a launch that also emits the bit-mask form
 inline size_t affinity_mask_lds(int N, int n_scales) { return 8 + (size_t)2 * n_scales * N * 8; }
 
+// host: the fused affinity + top-k job of B scenes — THE statement of its argument checks, in the order every entry that
+// issues it answers them, and of the scene tile it needs (`tile`: affinity_fused_lds, plus affinity_mask_lds with mask
+// lists), held against `budget`: gn_graph.hip's stand-alone launch allows a workgroup's LDS budget, the node stage's tail
+// (gn_mlp_mfma.hip node_plan; no mask lists) its smaller one.  Fills the kernel's scale and mask tables.
+// `twin`: bf16 storage.  Pure host code: addresses are tested for NULL and alignment only.
+inline int affinity_job_plan(bool twin, const void* f, float* const* H_list, const int* k_list, int n_scales, int B, int N,
+                             int D, const gn_block_extras_t* extras, unsigned long long* const* rowmask_list,
+                             unsigned long long* const* colmask_list, size_t budget, ScaleList& sl, MaskList& ml,
+                             size_t& tile) {
+  const bool embed = extras != nullptr && extras->x_raw != nullptr;
+  if (embed && twin) return GN_ERR_SHAPE;   // the embedding front-end is fp32 only
+  if (!embed) GN_CHECK(need(f, true));
+  if (B <= 0 || N <= 0 || D <= 0 || (D & 3) || D > 1024) return GN_ERR_SHAPE;
+  GN_CHECK(fill_scales(sl, H_list, k_list, n_scales, N));
+  if (embed) {
+    if (extras->x_dim <= 0 || !extras->M || !extras->c || !extras->f_contig) return GN_ERR_NULL;
+    if (!gn_aligned16(extras->c) || !gn_aligned16(extras->f_contig)) return GN_ERR_ALIGN;
+  }
+  tile = affinity_fused_lds(N, D, embed ? extras->x_dim : 0);
+  ml = MaskList{};
+  if (rowmask_list != nullptr || colmask_list != nullptr) {
+    if (rowmask_list == nullptr || colmask_list == nullptr) return GN_ERR_NULL;   // both forms or none
+    if (N > 64) return GN_ERR_SHAPE;
+    for (int s = 0; s < n_scales; ++s) {
+      if (rowmask_list[s] == nullptr || colmask_list[s] == nullptr) return GN_ERR_NULL;
+      if (!gn_aligned16(rowmask_list[s]) || !gn_aligned16(colmask_list[s])) return GN_ERR_ALIGN;
+      ml.row[s] = rowmask_list[s];
+      ml.col[s] = colmask_list[s];
+    }
+    tile += affinity_mask_lds(N, n_scales);
+  }
+  if (tile > budget) return GN_ERR_LDS;
+  if (extras != nullptr) {
+    if (extras->f_out != nullptr && (!gn_aligned16(extras->f_out) || extras->f_out_ld < D || (extras->f_out_ld & 3)))
+      return GN_ERR_ALIGN;
+    sl.H_cat = extras->H_cat;
+  }
+  return GN_OK;
+}
+
 }  // namespace

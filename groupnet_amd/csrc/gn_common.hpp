@@ -139,6 +139,13 @@ static inline GnSwitches gn_read_switches() {
   return sw;
 }
 
+// an empty launch plan of n_groups groups (every plan function starts here)
+static inline void plan_begin(gn_launch_plan_t& p, int n_groups) {
+  p = gn_launch_plan_t{};
+  p.n_groups = n_groups;
+  p.grid[1] = p.grid[2] = 1;
+}
+
 // ---- XCD-aware workgroup order ---------------------------------------------------------------------------------
 // The hardware deals the workgroups of a launch round-robin over the 8 XCDs (block p runs on the XCD of p % 8), and
 // every XCD has its own 4 MiB L2.  Every stage of the forward is a set of SECTIONS (one per module, or per module and

@@ -1190,7 +1190,7 @@ inline int capped_grid(long long work_items, int per_block, int cap = 256 * 16) 
 
 }  // namespace
 
-extern "C" int gn_abi_version(void) { return 37; }
+extern "C" int gn_abi_version(void) { return 38; }
 
 extern "C" const char* gn_kernel_name(int kernel) {
   static const char* const names[] = {"",
@@ -1209,8 +1209,18 @@ extern "C" const char* gn_kernel_name(int kernel) {
                                       "mlp2_kernel",
                                       "node2edge_kernel",
                                       "agg_gather_kernel",
-                                      "agg_gather_mask_kernel"};
-  return kernel >= 0 && kernel <= GN_K_AGG_GATHER_MASK ? names[kernel] : nullptr;
+                                      "agg_gather_mask_kernel",
+                                      "agg_scene_kernel",
+                                      "agg_gather_pairwise_kernel",
+                                      "affinity_topk_kernel",
+                                      "affinity_topk_masks_kernel",
+                                      "affinity_banded_kernel",
+                                      "topk_incidence_kernel",
+                                      "agg_scatter_kernel",
+                                      "agg_scatter_mask_kernel",
+                                      "agg_scatter_direct_kernel",
+                                      "agg_scatter_pairs_kernel"};
+  return kernel >= 0 && kernel <= GN_K_AGG_SCATTER_PAIRS ? names[kernel] : nullptr;
 }
 
 extern "C" const char* gn_strerror(int code) {
@@ -1226,44 +1236,95 @@ extern "C" const char* gn_strerror(int code) {
   }
 }
 
-extern "C" int gn_affinity_f32(const float* f, float* corr, int B, int N, int D, gn_stream_t stream) {
+// ---- the graph stage: plan, then launch (see the launch-plan comment in gn_mlp_mfma.hip) ---------------------------
+// Plans without groups: kernel, grid, dyn_lds.  The fused tile and the fused job's checks are gn_affinity.hpp's.
+static int affinity_plan(const float* f, const float* corr, int B, int N, int D, gn_launch_plan_t& p) {
   GN_REQUIRE_PTR(f);
   GN_REQUIRE_PTR(corr);
   GN_REQUIRE_ALIGNED(f);
   if (B <= 0 || N <= 0 || D <= 0 || (D & 3) || D > 1024) return GN_ERR_SHAPE;
-  const size_t fused = (size_t)N * (D + 4) * sizeof(float) + 8 + (size_t)N * N * 8;
-  if (fused <= kLdsBudget) {
+  plan_begin(p, 0);
+  const size_t fused = affinity_fused_lds(N, D, 0);
+  if (fused <= kLdsBudget) {      // the fused kernel without scales: corr alone
+    p.kernel = GN_K_AFFINITY_TOPK;
+    p.grid[0] = B;
+    p.dyn_lds = (int)fused;
+  } else {
+    p.kernel = GN_K_AFFINITY_BANDED;
+    p.grid[0] = (N + 15) / 16;
+    p.grid[1] = B;
+    p.dyn_lds = (int)((size_t)(16 + 64) * (D + 4) * sizeof(float));
+  }
+  return GN_OK;
+}
+static int affinity_launch(const gn_launch_plan_t& p, const float* f, float* corr, int N, int D, hipStream_t s) {
+  const dim3 grid(p.grid[0], p.grid[1]);
+  if (p.kernel == GN_K_AFFINITY_TOPK) {
     ScaleList sl{};
     sl.n = 0;
     gn_allow_big_lds(affinity_topk_kernel<float>);
-    hipLaunchKernelGGL(affinity_topk_kernel<float>, dim3(B), dim3(kBlock), fused, (hipStream_t)stream, f, corr, sl, N,
-                       D, gn_block_extras_t{});
+    hipLaunchKernelGGL(affinity_topk_kernel<float>, grid, dim3(kBlock), (size_t)p.dyn_lds, s, f, corr, sl, N, D,
+                       gn_block_extras_t{});
   } else {
-    const size_t lds = (size_t)(16 + 64) * (D + 4) * sizeof(float);
     gn_allow_big_lds(affinity_banded_kernel);
-    hipLaunchKernelGGL(affinity_banded_kernel, dim3((N + 15) / 16, B), dim3(kBlock), lds, (hipStream_t)stream, f, corr,
-                       N, D);
+    hipLaunchKernelGGL(affinity_banded_kernel, grid, dim3(kBlock), (size_t)p.dyn_lds, s, f, corr, N, D);
   }
   return gn_check_launch();
 }
+static int affinity_entry(const float* f, float* corr, int B, int N, int D, gn_stream_t stream, gn_launch_plan_t* plan) {
+  gn_launch_plan_t p;
+  const int rc = affinity_plan(f, corr, B, N, D, plan != nullptr ? *plan : p);
+  if (rc != GN_OK || plan != nullptr) return rc;
+  return affinity_launch(p, f, corr, N, D, (hipStream_t)stream);
+}
+extern "C" int gn_affinity_f32(const float* f, float* corr, int B, int N, int D, gn_stream_t stream) {
+  return affinity_entry(f, corr, B, N, D, stream, nullptr);
+}
+extern "C" int gn_affinity_plan_f32(const float* f, float* corr, int B, int N, int D, gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : affinity_entry(f, corr, B, N, D, nullptr, plan);
+}
 
-extern "C" int gn_topk_incidence_f32(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B,
-                                     int N, gn_stream_t stream) {
+// TE: rows of corr per band; sl: the kernel's scale table
+static int topk_plan(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B, int N,
+                     gn_launch_plan_t& p, ScaleList& sl) {
   GN_REQUIRE_PTR(corr);
   if (B <= 0 || N <= 0 || n_scales < 1) return GN_ERR_SHAPE;
-  ScaleList sl;
-  const int rc = fill_scales(sl, H_list, k_list, n_scales, N);
-  if (rc != GN_OK) return rc;
+  GN_CHECK(fill_scales(sl, H_list, k_list, n_scales, N));
   // a band holds at least one row of corr in half the budget: N <= 16 384 (beyond, RB below would be 0)
   if ((size_t)N * sizeof(float) > kLdsBudget / 2) return GN_ERR_LDS;
   int RB = (int)(kLdsBudget / 2 / ((size_t)N * sizeof(float)));
   RB = RB > N ? N : RB;
   // enough bands to give the chip >= ~1024 workgroups when B is small
   while (RB > 8 && (long long)B * ((N + RB - 1) / RB) < 1024) RB = (RB + 1) / 2;
+  plan_begin(p, 0);
+  p.kernel = GN_K_TOPK_INCIDENCE;
+  p.TE = RB;
+  p.grid[0] = (N + RB - 1) / RB;
+  p.grid[1] = B;
+  p.dyn_lds = (int)((size_t)RB * N * sizeof(float));
+  return GN_OK;
+}
+static int topk_launch(const gn_launch_plan_t& p, const float* corr, const ScaleList& sl, int N, hipStream_t s) {
   gn_allow_big_lds(topk_incidence_kernel);
-  hipLaunchKernelGGL(topk_incidence_kernel, dim3((N + RB - 1) / RB, B), dim3(kBlock), (size_t)RB * N * sizeof(float),
-                     (hipStream_t)stream, corr, sl, N, RB);
+  hipLaunchKernelGGL(topk_incidence_kernel, dim3(p.grid[0], p.grid[1]), dim3(kBlock), (size_t)p.dyn_lds, s, corr, sl, N,
+                     p.TE);
   return gn_check_launch();
+}
+static int topk_entry(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B, int N,
+                      gn_stream_t stream, gn_launch_plan_t* plan) {
+  gn_launch_plan_t p;
+  ScaleList sl;
+  const int rc = topk_plan(corr, H_list, k_list, n_scales, B, N, plan != nullptr ? *plan : p, sl);
+  if (rc != GN_OK || plan != nullptr) return rc;
+  return topk_launch(p, corr, sl, N, (hipStream_t)stream);
+}
+extern "C" int gn_topk_incidence_f32(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B,
+                                     int N, gn_stream_t stream) {
+  return topk_entry(corr, H_list, k_list, n_scales, B, N, stream, nullptr);
+}
+extern "C" int gn_topk_incidence_plan_f32(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B,
+                                          int N, gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : topk_entry(corr, H_list, k_list, n_scales, B, N, nullptr, plan);
 }
 
 extern "C" int gn_listall_incidence_f32(const float* corr, float* H, int B, int N, int scale, gn_stream_t stream) {
@@ -1292,68 +1353,83 @@ extern "C" int gn_listall_incidence_f32(const float* corr, float* H, int B, int 
   return gn_check_launch();
 }
 
+// the job's arguments as gn_affinity_topk_* take them (gn_affinity_job_t plus the mask lists)
+struct AffinityTopkArgs {
+  const void* f;
+  float* corr;
+  float* const* H_list;
+  const int* k_list;
+  int n_scales, B, N, D;
+  const gn_block_extras_t* extras;
+  unsigned long long* const* rowmask_list;
+  unsigned long long* const* colmask_list;
+};
+// sl, ml: the kernel's scale and mask tables
+static int affinity_topk_plan(const AffinityTopkArgs& a, bool twin, gn_launch_plan_t& p, ScaleList& sl, MaskList& ml) {
+  size_t tile;
+  GN_CHECK(affinity_job_plan(twin, a.f, a.H_list, a.k_list, a.n_scales, a.B, a.N, a.D, a.extras, a.rowmask_list,
+                             a.colmask_list, kLdsBudget, sl, ml, tile));
+  plan_begin(p, 0);
+  p.kernel = a.rowmask_list != nullptr ? GN_K_AFFINITY_TOPK_MASKS : GN_K_AFFINITY_TOPK;
+  p.precision = twin ? 1 : 0;
+  p.grid[0] = a.B;
+  p.dyn_lds = (int)tile;
+  return GN_OK;
+}
 template <typename TS>
-static int affinity_topk_launch(const TS* f, float* corr, float* const* H_list, const int* k_list, int n_scales, int B,
-                                int N, int D, const gn_block_extras_t* extras, unsigned long long* const* rowmask_list,
-                                unsigned long long* const* colmask_list, hipStream_t stream) {
-  const bool embed = extras != nullptr && extras->x_raw != nullptr;
-  if (embed && sizeof(TS) != sizeof(float)) return GN_ERR_SHAPE;   // the embedding front-end is fp32 only
-  if (!embed) {
-    GN_REQUIRE_PTR(f);
-    GN_REQUIRE_ALIGNED(f);
-  }
-  if (B <= 0 || N <= 0 || D <= 0 || (D & 3) || D > 1024) return GN_ERR_SHAPE;
-  ScaleList sl;
-  const int rc = fill_scales(sl, H_list, k_list, n_scales, N);
-  if (rc != GN_OK) return rc;
-  size_t fused = (size_t)N * (D + 4) * sizeof(float) + 8 + (size_t)N * N * 8;
-  if (embed) {
-    if (extras->x_dim <= 0 || !extras->M || !extras->c || !extras->f_contig) return GN_ERR_NULL;
-    if (!gn_aligned16(extras->c) || !gn_aligned16(extras->f_contig)) return GN_ERR_ALIGN;
-    fused += (size_t)N * extras->x_dim * sizeof(float);
-  }
-  const bool masks = rowmask_list != nullptr || colmask_list != nullptr;
-  MaskList ml{};
-  if (masks) {
-    if (rowmask_list == nullptr || colmask_list == nullptr) return GN_ERR_NULL;   // both forms or none
-    if (N > 64) return GN_ERR_SHAPE;
-    for (int s = 0; s < n_scales; ++s) {
-      if (rowmask_list[s] == nullptr || colmask_list[s] == nullptr) return GN_ERR_NULL;
-      if (!gn_aligned16(rowmask_list[s]) || !gn_aligned16(colmask_list[s])) return GN_ERR_ALIGN;
-      ml.row[s] = rowmask_list[s];
-      ml.col[s] = colmask_list[s];
-    }
-    fused += affinity_mask_lds(N, n_scales);
-  }
-  if (fused > kLdsBudget) return GN_ERR_LDS;
-  gn_block_extras_t ex{};
-  if (extras != nullptr) {
-    ex = *extras;
-    if (ex.f_out != nullptr && (!gn_aligned16(ex.f_out) || ex.f_out_ld < D || (ex.f_out_ld & 3))) return GN_ERR_ALIGN;
-    sl.H_cat = ex.H_cat;
-  }
-  if (masks) {
+static int affinity_topk_launch(const gn_launch_plan_t& p, const AffinityTopkArgs& a, const ScaleList& sl,
+                                const MaskList& ml, hipStream_t s) {
+  const TS* f = reinterpret_cast<const TS*>(a.f);
+  const gn_block_extras_t ex = a.extras != nullptr ? *a.extras : gn_block_extras_t{};
+  if (p.kernel == GN_K_AFFINITY_TOPK_MASKS) {
     gn_allow_big_lds(affinity_topk_masks_kernel<TS>);
-    hipLaunchKernelGGL(affinity_topk_masks_kernel<TS>, dim3(B), dim3(kBlock), fused, stream, f, corr, sl, N, D, ex, ml);
+    hipLaunchKernelGGL(affinity_topk_masks_kernel<TS>, dim3(p.grid[0]), dim3(kBlock), (size_t)p.dyn_lds, s, f, a.corr, sl,
+                       a.N, a.D, ex, ml);
   } else {
     gn_allow_big_lds(affinity_topk_kernel<TS>);
-    hipLaunchKernelGGL(affinity_topk_kernel<TS>, dim3(B), dim3(kBlock), fused, stream, f, corr, sl, N, D, ex);
+    hipLaunchKernelGGL(affinity_topk_kernel<TS>, dim3(p.grid[0]), dim3(kBlock), (size_t)p.dyn_lds, s, f, a.corr, sl, a.N,
+                       a.D, ex);
   }
   return gn_check_launch();
+}
+template <typename TS>
+static int affinity_topk_entry(const AffinityTopkArgs& a, gn_stream_t stream, gn_launch_plan_t* plan) {
+  gn_launch_plan_t p;
+  ScaleList sl;
+  MaskList ml;
+  const int rc = affinity_topk_plan(a, sizeof(TS) != sizeof(float), plan != nullptr ? *plan : p, sl, ml);
+  if (rc != GN_OK || plan != nullptr) return rc;
+  return affinity_topk_launch<TS>(p, a, sl, ml, (hipStream_t)stream);
 }
 extern "C" int gn_affinity_topk_f32(const float* f, float* corr, float* const* H_list, const int* k_list, int n_scales,
                                     int B, int N, int D, const gn_block_extras_t* extras,
                                     unsigned long long* const* rowmask_list, unsigned long long* const* colmask_list,
                                     gn_stream_t stream) {
-  return affinity_topk_launch<float>(f, corr, H_list, k_list, n_scales, B, N, D, extras, rowmask_list, colmask_list,
-                                     (hipStream_t)stream);
+  return affinity_topk_entry<float>({f, corr, H_list, k_list, n_scales, B, N, D, extras, rowmask_list, colmask_list},
+                                    stream, nullptr);
 }
 extern "C" int gn_affinity_topk_bf16(const void* f, float* corr, float* const* H_list, const int* k_list, int n_scales,
                                      int B, int N, int D, const gn_block_extras_t* extras,
                                      unsigned long long* const* rowmask_list, unsigned long long* const* colmask_list,
                                      gn_stream_t stream) {
-  return affinity_topk_launch<__bf16>(reinterpret_cast<const __bf16*>(f), corr, H_list, k_list, n_scales, B, N, D,
-                                      extras, rowmask_list, colmask_list, (hipStream_t)stream);
+  return affinity_topk_entry<__bf16>({f, corr, H_list, k_list, n_scales, B, N, D, extras, rowmask_list, colmask_list},
+                                     stream, nullptr);
+}
+extern "C" int gn_affinity_topk_plan_f32(const float* f, float* corr, float* const* H_list, const int* k_list,
+                                         int n_scales, int B, int N, int D, const gn_block_extras_t* extras,
+                                         unsigned long long* const* rowmask_list,
+                                         unsigned long long* const* colmask_list, gn_launch_plan_t* plan) {
+  if (plan == nullptr) return GN_ERR_NULL;
+  return affinity_topk_entry<float>({f, corr, H_list, k_list, n_scales, B, N, D, extras, rowmask_list, colmask_list},
+                                    nullptr, plan);
+}
+extern "C" int gn_affinity_topk_plan_bf16(const void* f, float* corr, float* const* H_list, const int* k_list,
+                                          int n_scales, int B, int N, int D, const gn_block_extras_t* extras,
+                                          unsigned long long* const* rowmask_list,
+                                          unsigned long long* const* colmask_list, gn_launch_plan_t* plan) {
+  if (plan == nullptr) return GN_ERR_NULL;
+  return affinity_topk_entry<__bf16>({f, corr, H_list, k_list, n_scales, B, N, D, extras, rowmask_list, colmask_list},
+                                     nullptr, plan);
 }
 
 extern "C" int gn_incidence_masks_f32(const float* H, int B, int E, int N, unsigned long long* rowmask,
@@ -1372,7 +1448,7 @@ extern "C" int gn_incidence_masks_f32(const float* H, int B, int E, int N, unsig
   return gn_check_launch();
 }
 
-// ---- node -> edge and gather: plan, then launch (see the launch-plan comment in gn_mlp_mfma.hip) ------------------
+// ---- node -> edge, gather and scatter: plan, then launch (see the launch-plan comment in gn_mlp_mfma.hip) ----------
 // pairwise groups: scenes per workgroup so that the staged rows stay <= 32 KiB; edge bands when one
 // scene alone has many more edges than a workgroup should walk
 static void n2e_pair_shape(int B, int N, int E, int& SG, int& bands) {
@@ -1582,10 +1658,8 @@ static int gather_plan(const gn_gather_group_t* groups, int n_groups, int B, int
   int rc = check_groups(groups, n_groups);
   if (rc != GN_OK) return rc;
   if (B <= 0 || N <= 0) return GN_ERR_SHAPE;
-  p = gn_launch_plan_t{};
-  p.n_groups = n_groups;
+  plan_begin(p, n_groups);
   p.precision = twin ? 1 : 0;
-  p.grid[1] = p.grid[2] = 1;
   int nh = 0, nm = 0, Emax = 0;
   for (int g = 0; g < n_groups; ++g) {
     const gn_gather_group_t& G = groups[g];
@@ -1600,7 +1674,8 @@ static int gather_plan(const gn_gather_group_t* groups, int n_groups, int B, int
       Emax = G.E > Emax ? G.E : Emax;
     } else if (G.H == nullptr) {
       if ((long long)G.E != (G.sym ? (long long)gn_pair_count(N) : (long long)N * N)) return GN_ERR_SHAPE;
-      p.pos[g] = -1;      // agg_gather_pairwise_kernel, a launch of its own
+      p.pos[g] = -1;      // a launch of its own
+      p.pre_kernel[g] = GN_K_AGG_GATHER_PAIRWISE;
       p.pre_grid[g] = capped_grid((long long)B * G.E * 16, kBlock * 4);
     } else {
       if (G.sym) return GN_ERR_SHAPE;
@@ -1680,14 +1755,15 @@ extern "C" int gn_agg_gather_plan_bf16(const gn_gather_group_t* groups, int n_gr
   return plan == nullptr ? GN_ERR_NULL : gather_entry<__bf16>(groups, n_groups, B, N, nullptr, plan);
 }
 
-template <typename TS>
-static int scatter_launch(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor, hipStream_t s,
-                          const GnSwitches& sw) {
+// Groups that share the staged (or mask) launch get a position in it; every other group runs in a launch of its own
+// (pre_kernel / pre_grid), in group order ahead of it.
+static int scatter_plan(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor, bool twin,
+                        const GnSwitches& sw, gn_launch_plan_t& p) {
   int rc = check_groups(groups, n_groups);
   if (rc != GN_OK) return rc;
   if (B <= 0 || N <= 0 || !(divisor != 0.f)) return GN_ERR_SHAPE;
-  const long long total4 = (long long)B * N * 32;
-  ScatterTable T{};
+  plan_begin(p, n_groups);
+  p.precision = twin ? 1 : 0;
   int nh = 0, Emax = 0, n_mask = 0, n_dense = 0;
   for (int g = 0; g < n_groups; ++g) {
     const gn_scatter_group_t& G = groups[g];
@@ -1708,52 +1784,94 @@ static int scatter_launch(const gn_scatter_group_t* groups, int n_groups, int B,
   if (n_mask != 0 && n_dense != 0) return GN_ERR_SHAPE;     // one form for every hyper group of a launch
   for (int g = 0; g < n_groups; ++g) {
     const gn_scatter_group_t& G = groups[g];
+    // a hyper group is staged while its feat rows and H fit half the budget
+    if (G.colmask != nullptr || (G.H != nullptr && (size_t)G.E * (GN_FEAT + N) * sizeof(float) <= kLdsBudget / 2)) {
+      p.pos[g] = nh++;
+      Emax = G.E > Emax ? G.E : Emax;
+      continue;
+    }
+    p.pos[g] = -1;
+    // the unordered pairs: one workgroup per scene, every pair row read once (enough scenes to fill the chip;
+    // GN_SCATTER_PAIRS = 0 keeps the direct kernel: parity tests run both)
+    const bool pairs = G.H == nullptr && G.sym && N * 16 <= kBlock * kPairItems && B >= 256 && sw.scatter_pairs;
+    p.pre_kernel[g] = pairs ? GN_K_AGG_SCATTER_PAIRS : GN_K_AGG_SCATTER_DIRECT;
+    p.pre_grid[g] = pairs ? B : capped_grid((long long)B * N * 32, kBlock);
+  }
+  if (nh == 0) return GN_OK;
+  // the scene's tile is its feat rows and N column words (mask form) or Emax N floats of H
+  const size_t per_scene = (size_t)Emax * GN_FEAT * sizeof(float) +
+                           (n_mask != 0 ? (size_t)N * sizeof(unsigned long long) : (size_t)Emax * N * sizeof(float));
+  const int G = gs_scenes_per_wg(per_scene, B, nh);
+  p.kernel = n_mask != 0 ? GN_K_AGG_SCATTER_MASK : GN_K_AGG_SCATTER;
+  p.G = G;
+  p.TE = Emax;
+  p.dyn_lds = (int)((size_t)G * per_scene);
+  p.grid[0] = (B + G - 1) / G;
+  p.grid[1] = nh;
+  for (int g = 0; g < n_groups; ++g)
+    if (p.pos[g] >= 0) p.wgs[g] = p.grid[0], p.spw[g] = G;
+  return GN_OK;
+}
+template <typename TS>
+static int scatter_launch(const gn_launch_plan_t& p, const gn_scatter_group_t* groups, int B, int N, float divisor,
+                          hipStream_t s) {
+  const long long total4 = (long long)B * N * 32;
+  ScatterTable T{};
+  for (int g = 0; g < p.n_groups; ++g) {
+    const gn_scatter_group_t& G = groups[g];
+    if (p.pos[g] >= 0) {
+      T.g[p.pos[g]] = G;
+      continue;
+    }
     const TS* feat = reinterpret_cast<const TS*>(G.feat);
     const TS* ori = reinterpret_cast<const TS*>(G.ori);
     TS* out = reinterpret_cast<TS*>(G.out);
-    if (G.colmask != nullptr) {
-      T.g[nh++] = G;
-      Emax = G.E > Emax ? G.E : Emax;
-    } else if (G.H == nullptr && G.sym && N * 16 <= kBlock * kPairItems && B >= 256 && sw.scatter_pairs) {
-      // one workgroup per scene, every pair row read once (enough scenes to fill the chip; GN_SCATTER_PAIRS = 0 keeps
-      // the direct kernel: parity tests run both)
-      hipLaunchKernelGGL((agg_scatter_pairs_kernel<TS>), dim3(B), dim3(kBlock), 0, s, feat, ori, out, N, divisor);
-    } else if (G.H == nullptr && G.sym) {
-      hipLaunchKernelGGL((agg_scatter_direct_kernel<2, TS>), dim3(capped_grid(total4, kBlock)), dim3(kBlock), 0, s,
-                         feat, G.H, ori, out, N, G.E, total4, divisor);
-    } else if (G.H == nullptr) {
-      hipLaunchKernelGGL((agg_scatter_direct_kernel<1, TS>), dim3(capped_grid(total4, kBlock)), dim3(kBlock), 0, s,
-                         feat, G.H, ori, out, N, G.E, total4, divisor);
-    } else if ((size_t)G.E * (GN_FEAT + N) * sizeof(float) > kLdsBudget / 2) {
-      hipLaunchKernelGGL((agg_scatter_direct_kernel<0, TS>), dim3(capped_grid(total4, kBlock)), dim3(kBlock), 0, s,
-                         feat, G.H, ori, out, N, G.E, total4, divisor);
-    } else {
-      T.g[nh++] = G;
-      Emax = G.E > Emax ? G.E : Emax;
-    }
+    const dim3 grid(p.pre_grid[g]);
+    if (p.pre_kernel[g] == GN_K_AGG_SCATTER_PAIRS)
+      hipLaunchKernelGGL((agg_scatter_pairs_kernel<TS>), grid, dim3(kBlock), 0, s, feat, ori, out, N, divisor);
+    else if (G.H == nullptr && G.sym)      // the direct kernel's mode is the group's: unordered pairs, ordered pairs, H
+      hipLaunchKernelGGL((agg_scatter_direct_kernel<2, TS>), grid, dim3(kBlock), 0, s, feat, G.H, ori, out, N, G.E, total4,
+                         divisor);
+    else if (G.H == nullptr)
+      hipLaunchKernelGGL((agg_scatter_direct_kernel<1, TS>), grid, dim3(kBlock), 0, s, feat, G.H, ori, out, N, G.E, total4,
+                         divisor);
+    else
+      hipLaunchKernelGGL((agg_scatter_direct_kernel<0, TS>), grid, dim3(kBlock), 0, s, feat, G.H, ori, out, N, G.E, total4,
+                         divisor);
   }
-  if (nh > 0) {
-    // the scene's tile is its feat rows and N column words (mask form) or Emax N floats of H
-    const size_t per_scene = (size_t)Emax * GN_FEAT * sizeof(float) +
-                             (n_mask != 0 ? (size_t)N * sizeof(unsigned long long) : (size_t)Emax * N * sizeof(float));
-    const int G = gs_scenes_per_wg(per_scene, B, nh);
-    const dim3 grid((B + G - 1) / G, nh);
-    if (n_mask != 0) {
-      hipLaunchKernelGGL(agg_scatter_mask_kernel<TS>, grid, dim3(kBlock), (size_t)G * per_scene, s, T, B, N, G, Emax, divisor);
-    } else {
-      gn_allow_big_lds(agg_scatter_kernel<TS>);
-      hipLaunchKernelGGL(agg_scatter_kernel<TS>, grid, dim3(kBlock), (size_t)G * per_scene, s, T, B, N, G, Emax, divisor);
-    }
+  const dim3 grid(p.grid[0], p.grid[1]);
+  if (p.kernel == GN_K_AGG_SCATTER_MASK) {
+    hipLaunchKernelGGL(agg_scatter_mask_kernel<TS>, grid, dim3(kBlock), (size_t)p.dyn_lds, s, T, B, N, p.G, p.TE, divisor);
+  } else if (p.kernel == GN_K_AGG_SCATTER) {
+    gn_allow_big_lds(agg_scatter_kernel<TS>);
+    hipLaunchKernelGGL(agg_scatter_kernel<TS>, grid, dim3(kBlock), (size_t)p.dyn_lds, s, T, B, N, p.G, p.TE, divisor);
   }
   return gn_check_launch();
 }
+template <typename TS>
+static int scatter_entry(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor, gn_stream_t stream,
+                         gn_launch_plan_t* plan) {
+  gn_launch_plan_t p;
+  int rc = scatter_plan(groups, n_groups, B, N, divisor, sizeof(TS) != sizeof(float), gn_read_switches(),
+                        plan != nullptr ? *plan : p);
+  if (rc != GN_OK || plan != nullptr) return rc;
+  return scatter_launch<TS>(p, groups, B, N, divisor, (hipStream_t)stream);
+}
 extern "C" int gn_agg_scatter_f32(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
                                   gn_stream_t stream) {
-  return scatter_launch<float>(groups, n_groups, B, N, divisor, (hipStream_t)stream, gn_read_switches());
+  return scatter_entry<float>(groups, n_groups, B, N, divisor, stream, nullptr);
 }
 extern "C" int gn_agg_scatter_bf16(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
                                    gn_stream_t stream) {
-  return scatter_launch<__bf16>(groups, n_groups, B, N, divisor, (hipStream_t)stream, gn_read_switches());
+  return scatter_entry<__bf16>(groups, n_groups, B, N, divisor, stream, nullptr);
+}
+extern "C" int gn_agg_scatter_plan_f32(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
+                                       gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : scatter_entry<float>(groups, n_groups, B, N, divisor, nullptr, plan);
+}
+extern "C" int gn_agg_scatter_plan_bf16(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
+                                        gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : scatter_entry<__bf16>(groups, n_groups, B, N, divisor, nullptr, plan);
 }
 
 // Pitched copy (rows x width bytes, 16-byte pieces): the column block of the feature tensor that a rank ships into its

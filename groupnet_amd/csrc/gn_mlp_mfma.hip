@@ -885,11 +885,6 @@ static int x_mode(const G* groups, int n, F has) {
   return cnt == 0 ? 0 : (cnt == n ? 1 : -1);
 }
 
-static void plan_begin(gn_launch_plan_t& p, int n_groups) {
-  p = gn_launch_plan_t{};
-  p.n_groups = n_groups;
-  p.grid[1] = p.grid[2] = 1;
-}
 // the launch's grid from the groups' workgroups in launch order `order` (nullptr: the caller's), XCD-aware when `xcd`
 static void plan_grid(gn_launch_plan_t& p, int n, const int* order, bool xcd, const GnSwitches& sw) {
   XcdSections xs{};
@@ -985,23 +980,13 @@ static int node_plan(const gn_node_group_t* groups, int n_groups, int rows, cons
   p.kernel = GN_K_NODE_STAGE;
   for (int g = 0; g < n_groups; ++g) p.wgs[g] = Tb.wgs_per_group + Tb.a_first[g + 1] - Tb.a_first[g], p.pos[g] = g;
   if (job != nullptr) {
-    // the affinity + top-k of job->B scenes as the launch's tail workgroups (same checks as gn_affinity_topk_*)
-    const bool embed = job->extras != nullptr && job->extras->x_raw != nullptr;
-    if (embed && twin) return GN_ERR_SHAPE;
-    if (!embed) GN_CHECK(need(job->f, true));
-    if (job->B <= 0 || job->N <= 0 || job->D <= 0 || (job->D & 3) || job->D > 1024) return GN_ERR_SHAPE;
+    // the affinity + top-k of job->B scenes as the launch's tail workgroups: the job's own checks, its tile against the
+    // tail's budget, no mask lists
     ScaleList sl;
-    GN_CHECK(fill_scales(sl, job->H_list, job->k_list, job->n_scales, job->N));
-    if (embed) {
-      if (job->extras->x_dim <= 0 || !job->extras->M || !job->extras->c || !job->extras->f_contig) return GN_ERR_NULL;
-      if (!gn_aligned16(job->extras->c) || !gn_aligned16(job->extras->f_contig)) return GN_ERR_ALIGN;
-    }
-    const size_t aff_lds = affinity_fused_lds(job->N, job->D, embed ? job->extras->x_dim : 0);
-    if (aff_lds > kAffTailLds) return GN_ERR_LDS;
-    if (job->extras != nullptr) {
-      const gn_block_extras_t& ex = *job->extras;
-      if (ex.f_out != nullptr && (!gn_aligned16(ex.f_out) || ex.f_out_ld < job->D || (ex.f_out_ld & 3))) return GN_ERR_ALIGN;
-    }
+    MaskList ml;
+    size_t aff_lds;
+    GN_CHECK(affinity_job_plan(twin, job->f, job->H_list, job->k_list, job->n_scales, job->B, job->N, job->D, job->extras,
+                               nullptr, nullptr, kAffTailLds, sl, ml, aff_lds));
     p.dyn_lds = (int)aff_lds;
     p.grid[0] += job->B;
   }
@@ -1308,6 +1293,7 @@ static int agg_plan(const gn_agg_group_t* groups, int n_groups_in, bool twin, co
     GN_CHECK(need(G.feat, true));
     p.pos[g] = -1;
     p.node_form[g] = p.wpr[g] = 1;
+    p.pre_kernel[g] = GN_K_AGG_SCENE;
     p.pre_grid[g] = G.rows / G.E * ((G.N + 31) / 32);
     p.pre_lds[g] = (int)((size_t)node_scene_lds_floats(G.N) * sizeof(float));
   }

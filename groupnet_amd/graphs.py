@@ -98,7 +98,7 @@ class GraphedPastEncoder:
         if not enc.fused_front_end_fits(N, enc._length):
             raise ValueError(f"GraphedPastEncoder captures the fused front-end only: the scene tile of N = {N} agents with "
                              f"{enc._length * enc.input_fc.in_features} raw inputs each exceeds the fused affinity launch's "
-                             f"{ops.AFFINITY_LDS_BUDGET} B of LDS; call the encoder eagerly")
+                             "LDS; call the encoder eagerly")
         self.enc, self.B, self.N, self.seed = enc, B, N, int(seed)
         self.x_in = torch.zeros((B * N, enc._length, enc.input_fc.in_features), dtype=torch.float32, device=self.device)
         self.counter = torch.zeros(1, dtype=torch.int64, device=self.device)

@@ -34,8 +34,11 @@ def multiscale_autograd(pair: MS_HGNN_oridinary, hypers: Sequence[MS_HGNN_hyper]
     from .backward import MSHGNNFunction
     S = len(hypers)
     fd = f.detach().contiguous()
-    if S and ops.fused_affinity_fits(fd.shape[1], fd.shape[2]):
-        job = ops.AffinityTail(fd, list(scales), want_H_cat=True, want_masks=masks_apply(fd.shape[1]))
+    want_masks = masks_apply(fd.shape[1])
+    # (the mask words cannot change the answer today: masks need N <= 64, where the tile at D = 64 with eight scales of
+    # mask words is 58 384 B of the 128 KiB — the question is asked about the launch that is then built)
+    if S and ops.graph_form(fd.shape[1], fd.shape[2], 0, S if want_masks else 0) != "banded":
+        job = ops.AffinityTail(fd, list(scales), want_H_cat=True, want_masks=want_masks)
         job.launch()
         Hs, graphs, new_H = job.Hs, job.incidences, job.H_cat
     elif S:
@@ -147,7 +150,10 @@ class MultiScaleHGNN(nn.Module):
         cols = [final[..., D * (1 + i):D * (2 + i)] for i in range(1 + S)]   # written in place by the last MLP
         join = None
         want_masks = masks_apply(N)       # mask form on and 16 < N <= 64: the fused launch also emits the member words
-        if S and ops.fused_affinity_fits(N, D):
+        # asked about the launch built below, mask words included (which cannot change the answer today: at D = 64 and
+        # N <= 64 the tile with eight scales of mask words is 58 384 B of the 128 KiB)
+        fused = bool(S) and ops.graph_form(N, D, 0, S if want_masks else 0) != "banded"
+        if fused:
             # one launch: affinity, incidence of every scale, f -> final[..., :D], cat(H_s), Philox bump.
             # The node stage of the first round needs only f: inside a graph capture the two launches are forked
             # (the graph then runs them side by side; eager launches stay on one stream)
@@ -190,7 +196,7 @@ class MultiScaleHGNN(nn.Module):
             # to fill the chip, and nothing depends on how streams map to hardware queues
             # (latency form — `affinity_tail` — also folds the closing MLPs into the aggregation launch: 4 launches)
             run_message_passing(mods, [f] * (1 + S), [None, *Hs], list(noise_u), cols, join=join,
-                                affinity=tail if (S and ops.fused_affinity_fits(N, D)) else None,
+                                affinity=tail if fused else None,
                                 fuse_closing=self.affinity_tail)
         else:
             for m, H, u, c in zip(mods, [None, *Hs], noise_u, cols):

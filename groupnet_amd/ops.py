@@ -8,6 +8,7 @@ CPU oracle or falls back to torch math.
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 import os
 from typing import List, Optional, Sequence, Tuple
@@ -285,27 +286,31 @@ def incidence_masks(H: Tensor, assume_binary: bool = False) -> IncidenceMasks:
     return m
 
 
-AFFINITY_LDS_BUDGET = 128 * 1024      # gn_graph.hip kLdsBudget: the stand-alone fused affinity + top-k launch
-
-
-def affinity_tile_bytes(N: int, D: int, x_dim: int = 0, mask_scales: int = 0) -> int:
-    """LDS bytes of one scene's workgroup of the fused affinity + top-k code (gn_affinity.hpp `affinity_fused_lds`, plus
-    `affinity_mask_lds` for a launch that emits the bit-mask form of ``mask_scales`` scales): the one expression every
-    Python-side question about the form of that launch goes through."""
-    tile = N * (D + 4 + x_dim) * 4 + 8 + N * N * 8      # rows + 64-bit ranking keys (+ raw inputs of the embedding)
+@functools.lru_cache(maxsize=None)
+def graph_form(N: int, D: int, x_dim: int = 0, mask_scales: int = 0) -> str:
+    """Which launches build the graph of scenes of N agents with D features (``x_dim`` raw inputs per agent with the
+    embedding front-end; ``mask_scales`` > 0: the launch also emits the bit-mask form of that many scales):
+      "tail"   — the fused affinity + top-k job rides as tail workgroups of the first node-stage launch,
+      "fused"  — it is a launch of its own (gn_affinity_topk_*),
+      "banded" — its scene tile does not fit: gn_affinity_f32 (banded there) + gn_topk_incidence_f32.
+    The library alone answers, from two plan queries with placeholder addresses (nothing is launched, no GPU is asked):
+    the tile rule and both budgets are stated in C only.  Memoised: an eager forward asks once per shape."""
+    P = _PLACEHOLDER      # a plan query tests addresses, it never reads through them
+    n = max(1, mask_scales)
+    Hl, kl = (_P * n)(*[P] * n), (ctypes.c_int * n)(*[1] * n)
+    ex = _lib.BlockExtras(x_raw=P, x_dim=x_dim, M=P, c=P, f_contig=P) if x_dim else _lib.BlockExtras()
+    words = (_P * n)(*[P] * n) if mask_scales else None
+    plan = _lib.LaunchPlan()
+    rc = load().gn_affinity_topk_plan_f32(P, None, Hl, kl, n, 1, N, D, ctypes.byref(ex), words, words, ctypes.byref(plan))
+    if rc == _lib.GN_ERR_LDS:
+        return "banded"
+    check(rc, "gn_affinity_topk_plan")
     if mask_scales:
-        tile += 8 + 2 * mask_scales * N * 8             # row and column words of every scale
-    return tile
-
-
-def fused_affinity_fits(N: int, D: int, x_dim: int = 0, mask_scales: int = 0) -> bool:
-    """Whether one scene's tile of the fused affinity+top-k launch fits its 128 KiB LDS budget."""
-    return affinity_tile_bytes(N, D, x_dim, mask_scales) <= AFFINITY_LDS_BUDGET
-
-
-def affinity_tail_fits(N: int, D: int, x_dim: int = 0) -> bool:
-    """Whether that tile fits the smaller budget of the node stage's tail workgroups (gn_node_mlp_affinity_*)."""
-    return affinity_tile_bytes(N, D, x_dim) <= load().gn_affinity_tail_lds_limit()
+        return "fused"        # only the stand-alone launch emits masks
+    g = (_lib.NodeGroup * 1)(_lib.NodeGroup(x=P, Wx=P, bias=P, xp=P, pq=P))
+    job = _lib.AffinityJob(f=P, H_list=Hl, k_list=kl, n_scales=n, B=1, N=N, D=D, extras=ctypes.pointer(ex))
+    rc = load().gn_node_mlp_plan_f32(g, 1, N, ctypes.byref(job), ctypes.byref(plan))
+    return "tail" if rc == _lib.GN_OK else "fused"
 
 
 def affinity_topk(f: Optional[Tensor], scales: Sequence[int], want_corr: bool = True, f_out: Optional[Tensor] = None,
@@ -381,7 +386,7 @@ class AffinityTail:
 
     def fits_tail(self) -> bool:
         B, N, D = self.f.shape
-        return self.masks is None and affinity_tail_fits(N, D, int(self._ex.x_dim))
+        return self.masks is None and graph_form(N, D, int(self._ex.x_dim)) == "tail"
 
     def launch(self) -> None:
         """The stand-alone launch (nothing took the job along)."""

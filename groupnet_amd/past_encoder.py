@@ -126,7 +126,7 @@ class _TrajectoryEncoder(nn.Module):
         """Whether an eval-mode forward over N agents and T time steps is served by the fused launch (the embedding as
         one affine map inside the affinity + top-k launch): its scene tile, the raw inputs included, within the launch's
         LDS budget.  Beyond it the forward runs the embedding on the HIP GEMM and the banded affinity / top-k pair."""
-        return ops.fused_affinity_fits(N, self.model_dim, T * self.input_fc.in_features)
+        return ops.graph_form(N, self.model_dim, T * self.input_fc.in_features) != "banded"
 
     def _check_inputs(self, inputs: Tensor, B: int, N: int) -> int:
         ops._req(inputs, "inputs", (B * N, None, self.input_fc.in_features))

@@ -539,15 +539,20 @@ int gn_mlp2_f32(const gn_mlp2_group_t* groups, int n_groups, int rows, int din, 
 int gn_mlp2_bf16(const gn_mlp2_group_t* groups, int n_groups, int rows, int din, int dh, int dout, int ldy,
                  int N, float divisor, gn_stream_t stream);
 
-/* ---- launch plans (ABI 36) ---------------------------------------------------------------------
+/* ---- launch plans (ABI 36; the graph stage and the scatter: ABI 38) ------------------------------
  * What a forward launcher would launch for its arguments, without launching: every launcher below is "plan, then launch",
  * and gn_*_plan_* return the plan alone.  A plan is decided on the host from the descriptors, the scalar arguments, the
  * storage type and the per-call environment switches (GN_XCD, GN_POOL_STAGE, GN_AGG_LINES, GN_AGG_HSTAGE, GN_AGG_RB2,
- * GN_EDGE_RB2, GN_RB2_MIN_PAIRS, GN_MLP2_XS, GN_N2E_ROWS; read once per call): no HIP call, no GPU needed, device addresses
- * are only tested for NULL and alignment (a not yet allocated output may be any aligned non-NULL placeholder).  The
- * return value is the launcher's for the same arguments; on an error the plan's content is unspecified.
- * Per-group arrays are in the caller's group order. */
-#define GN_K_NONE 0                  /* no main launch (every group ran in a launch of its own, see pre_grid) */
+ * GN_EDGE_RB2, GN_RB2_MIN_PAIRS, GN_MLP2_XS, GN_N2E_ROWS, GN_SCATTER_PAIRS; read once per call): no HIP call, no GPU needed,
+ * device addresses are only tested for NULL and alignment (a not yet allocated output may be any aligned non-NULL
+ * placeholder).  The return value is the launcher's for the same arguments; on an error the plan's content is unspecified.
+ * Per-group arrays are in the caller's group order.
+ * The graph stage (ABI 38): gn_affinity_f32, gn_topk_incidence_f32 and gn_affinity_topk_* are planned the same way (plans
+ * without groups: kernel, grid, dyn_lds).  The fused job's argument checks and its scene tile are stated once, for
+ * gn_affinity_topk_*'s plan (against the 128 KiB budget of a workgroup) and the node stage's tail (against
+ * gn_affinity_tail_lds_limit(), no masks) alike: which of the three forms builds a graph — tail, fused launch, or the
+ * banded pair — is what gn_node_mlp_plan_* and gn_affinity_topk_plan_* answer (GN_OK or GN_ERR_LDS). */
+#define GN_K_NONE 0                  /* no main launch (every group ran in a launch of its own, see pre_kernel) */
 #define GN_K_NODE_STAGE 1
 #define GN_K_NODE_MLP_SPLIT 2
 #define GN_K_NODE_MLP 3
@@ -564,6 +569,18 @@ int gn_mlp2_bf16(const gn_mlp2_group_t* groups, int n_groups, int rows, int din,
 #define GN_K_NODE2EDGE 14
 #define GN_K_AGG_GATHER 15
 #define GN_K_AGG_GATHER_MASK 16      /* the gather of groups with rowmask (ABI 37) */
+/* ABI 38: the kernels of the launches of their own (pre_kernel) and of the graph stage and the scatter */
+#define GN_K_AGG_SCENE 17            /* typed aggregation, bf16 storage: the pairwise group's scene form */
+#define GN_K_AGG_GATHER_PAIRWISE 18  /* gather of a pairwise group */
+#define GN_K_AFFINITY_TOPK 19        /* fused affinity + top-k, one workgroup per scene (gn_affinity_f32: without scales) */
+#define GN_K_AFFINITY_TOPK_MASKS 20  /* ... that also emits the bit-mask form */
+#define GN_K_AFFINITY_BANDED 21      /* gn_affinity_f32 beyond the fused tile: 16-row bands against 64-column panels */
+#define GN_K_TOPK_INCIDENCE 22
+#define GN_K_AGG_SCATTER 23          /* staged scatter of the hyper groups: G scenes per workgroup */
+#define GN_K_AGG_SCATTER_MASK 24     /* ... of groups with colmask */
+#define GN_K_AGG_SCATTER_DIRECT 25   /* scatter of one group from global memory (its mode is the group's: H, ordered pairs
+                                        or, sym, unordered pairs) */
+#define GN_K_AGG_SCATTER_PAIRS 26    /* scatter of the unordered pairs, one workgroup per scene */
 typedef struct {
   int kernel;        /* GN_K_*: the kernel of the launch (gn_kernel_name), instantiated for ... */
   int precision;     /* ... 0: the plain fp32 weight stream, 1: bf16 storage (the twins), 2: f16x3, 3: bf16x6 */
@@ -586,12 +603,14 @@ typedef struct {
   int unstaged[GN_MAX_GROUPS];    /* edge_x_kernel: hyper group pooled without a stage, one workgroup per 32-row block */
   int pos[GN_MAX_GROUPS];         /* the group's position in the launch (typed aggregation: after the cost sort), -1 when
                                      it is not part of it */
-  int pre_grid[GN_MAX_GROUPS];    /* > 0: the group runs in a launch of its own ahead of the main one, with this grid (bf16
-                                     scene form: agg_scene_kernel; pairwise gather: agg_gather_pairwise_kernel) ... */
-  int pre_lds[GN_MAX_GROUPS];     /* ... and this dynamic LDS */
+  int pre_grid[GN_MAX_GROUPS];    /* > 0: the group runs in a launch of its own ahead of the main one, with this grid ... */
+  int pre_lds[GN_MAX_GROUPS];     /* ... and this dynamic LDS ... */
   int SGh, EBh;      /* node -> edge: scenes per workgroup and hyperedges per band of the hyper groups (row form: EBh = 0; so is variant
                         2, whose plan equals variant 1's in every other field) */
-  int G, TE;         /* gather: scenes per workgroup and hyperedges per tile (mask form: TE = the largest E, one tile) */
+  int G, TE;         /* gather: scenes per workgroup and hyperedges per tile (mask form: TE = the largest E, one tile);
+                        scatter: scenes per workgroup and TE = the largest E of the staged groups (one tile);
+                        gn_topk_incidence_f32 reuses TE for the rows of corr per band (grid[0] bands of TE rows) */
+  int pre_kernel[GN_MAX_GROUPS];  /* ... of this kernel (GN_K_*; ABI 38, GN_K_NONE where pre_grid is 0) */
 } gn_launch_plan_t;
 /* "agg_x_kernel", ...: the kernel's name as a kernel trace shows it (without template arguments); NULL for an unknown id */
 const char* gn_kernel_name(int kernel);
@@ -620,6 +639,26 @@ int gn_node2edge_masks_plan_bf16(const gn_n2e_group_t* groups, const unsigned lo
                                  int B, int N, gn_launch_plan_t* plan);
 int gn_agg_gather_plan_f32(const gn_gather_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan);
 int gn_agg_gather_plan_bf16(const gn_gather_group_t* groups, int n_groups, int B, int N, gn_launch_plan_t* plan);
+/* The scatter (ABI 38).  A group in the staged (or mask) launch: pos / wgs / spw = G as in the gather's plan, kernel, grid =
+ * (ceil(B / G), staged groups), G, TE, dyn_lds.  A group launched on its own, in group order ahead of the staged launch:
+ * pos = -1, pre_kernel (the pairs kernel for sym groups with 16 N <= 1024 and B >= 256 unless GN_SCATTER_PAIRS = 0, else the
+ * direct kernel, which also takes a hyper group whose E (64 + N) floats exceed 64 KiB) and pre_grid. */
+int gn_agg_scatter_plan_f32(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
+                            gn_launch_plan_t* plan);
+int gn_agg_scatter_plan_bf16(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
+                             gn_launch_plan_t* plan);
+/* The graph stage (ABI 38): n_groups = 0.  gn_affinity_plan_f32: GN_K_AFFINITY_TOPK with grid (B) and the fused tile, or
+ * GN_K_AFFINITY_BANDED with grid (ceil(N / 16), B).  gn_topk_incidence_plan_f32: grid (bands, B), TE rows per band.
+ * gn_affinity_topk_plan_*: grid (B), dyn_lds = the scene tile; GN_ERR_LDS where the caller takes the banded pair. */
+int gn_affinity_plan_f32(const float* f, float* corr, int B, int N, int D, gn_launch_plan_t* plan);
+int gn_topk_incidence_plan_f32(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B, int N,
+                               gn_launch_plan_t* plan);
+int gn_affinity_topk_plan_f32(const float* f, float* corr, float* const* H_list, const int* k_list, int n_scales, int B,
+                              int N, int D, const gn_block_extras_t* extras, unsigned long long* const* rowmask_list,
+                              unsigned long long* const* colmask_list, gn_launch_plan_t* plan);
+int gn_affinity_topk_plan_bf16(const void* f, float* corr, float* const* H_list, const int* k_list, int n_scales, int B,
+                               int N, int D, const gn_block_extras_t* extras, unsigned long long* const* rowmask_list,
+                               unsigned long long* const* colmask_list, gn_launch_plan_t* plan);
 
 /* ---- backward (training) building blocks — SURVEY.md §8f rank 2 -------------------------------
  * train_hyper_nba.py:116 back-propagates through the two modules.  The backward of the path is

@@ -23,6 +23,9 @@ FUSED_MAX_N = 16                 # MS_HGNN_batch._FUSED_GATHER_MAX_N / _FUSED_SC
 RB2_MIN_PAIRS = 2048             # gn_mlp_mfma.hip rb2_min_pairs() without the test knob
 GS_MIN_WGS = 2048                # gn_graph.hip kGsMinWgs
 GS_LDS_BUDGET = 128 * 1024       # gn_graph.hip kLdsBudget
+GS_TILE_MAX = 24 * 1024          # gn_graph.hip gs_scenes_per_wg: the tile of a workgroup that packs several scenes
+SCATTER_PAIRS_MAX_N, SCATTER_PAIRS_MIN_B = 64, 256      # agg_scatter_pairs_kernel: 16 N <= 256 x 4 items, B fills the chip
+CAPPED_GRID = 256 * 16           # gn_graph.hip capped_grid: workgroups of a grid-stride launch
 
 
 def pair_count(N: int) -> int:
@@ -50,6 +53,66 @@ def agg_wpr(rows: int, K: int) -> int:
     return 1 if b32 >= 768 else (2 if b32 >= 128 and K >= 2 else (4 if K >= 4 else 1))
 
 
+def gs_scenes_per_wg(per_scene: int, B: int, nh: int) -> int:
+    """Scenes per workgroup of a staged gather / scatter launch of nh groups: doubled while the doubled tile stays within
+    GS_TILE_MAX and the grid keeps GS_MIN_WGS workgroups, 16 at most."""
+    G = 1
+    while G < 16 and 2 * G * per_scene <= GS_TILE_MAX and cdiv(B, 2 * G) * nh >= GS_MIN_WGS:
+        G *= 2
+    return G
+
+
+def scatter_forms(B: int, N: int, groups: Sequence[Dict], pairs_switch: bool = True) -> Optional[Dict]:
+    """The launches of one gn_agg_scatter_* call (gn_graph.hip scatter_plan, restated).  groups: [{"E", "sym" (the
+    unordered pairs of the pairwise graph), "H" (a hyper group with a dense incidence), "colmask" (... in mask form)}];
+    pairs_switch: GN_SCATTER_PAIRS is not 0.
+    -> {"own": {group: (kernel, grid)} — launched on their own, in group order: the pairs kernel (one workgroup per scene)
+    iff sym, 16 N <= 1024, B >= 256 and the switch; else the direct kernel, which also takes a hyper group whose feat rows
+    and H, E (64 + N) floats, exceed 64 KiB —, "pos": per group its position in the staged launch or -1, "kernel" (None
+    without staged groups), "grid", "G", "Emax", "dyn_lds"}; None for dense and mask hyper groups in one call (refused)."""
+    get = lambda g, k: bool(g.get(k))
+    n_mask = sum(get(g, "colmask") for g in groups)
+    if n_mask and any(get(g, "H") and not get(g, "colmask") for g in groups):
+        return None
+    own, pos, nh = {}, [], 0
+    for i, g in enumerate(groups):
+        if get(g, "colmask") or (get(g, "H") and g["E"] * (64 + N) * 4 <= GS_LDS_BUDGET // 2):
+            pos.append(nh)
+            nh += 1
+            continue
+        pos.append(-1)
+        if (not get(g, "H") and get(g, "sym") and N <= SCATTER_PAIRS_MAX_N and B >= SCATTER_PAIRS_MIN_B and pairs_switch):
+            own[i] = ("agg_scatter_pairs_kernel", B)
+        else:
+            own[i] = ("agg_scatter_direct_kernel", min(max(cdiv(B * N * 32, 256), 1), CAPPED_GRID))
+    out = dict(own=own, pos=pos, kernel=None, grid=None, G=0, Emax=0, dyn_lds=0)
+    if nh:
+        Emax = max(g["E"] for g, q in zip(groups, pos) if q >= 0)
+        per_scene = Emax * 256 + (N * 8 if n_mask else Emax * N * 4)
+        G = gs_scenes_per_wg(per_scene, B, nh)
+        out.update(kernel="agg_scatter_mask_kernel" if n_mask else "agg_scatter_kernel", grid=(cdiv(B, G), nh), G=G,
+                   Emax=Emax, dyn_lds=G * per_scene)
+    return out
+
+
+def assert_scatter_plan(sf: Dict, plan, where) -> None:
+    """A gn_agg_scatter_plan_* plan says what `sf` (scatter_forms) says."""
+    from groupnet_amd import _lib as L
+    name = lambda k: L.load().gn_kernel_name(k).decode()
+    n = len(sf["pos"])
+    assert plan.n_groups == n and list(plan.pos[:n]) == sf["pos"], (where, list(plan.pos[:n]))
+    for i in range(n):
+        if i in sf["own"]:
+            assert (name(plan.pre_kernel[i]), plan.pre_grid[i], plan.wgs[i], plan.spw[i]) == (*sf["own"][i], 0, 0), (where, i)
+        else:
+            assert (plan.pre_kernel[i], plan.pre_grid[i], plan.wgs[i], plan.spw[i]) == (0, 0, sf["grid"][0], sf["G"]), (where, i)
+    if sf["kernel"] is None:
+        assert plan.kernel == 0, where
+    else:
+        assert (name(plan.kernel), tuple(plan.grid), plan.G, plan.TE, plan.dyn_lds) == (
+            sf["kernel"], sf["grid"] + (1,), sf["G"], sf["Emax"], sf["dyn_lds"]), (where, sf)
+
+
 def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x3", dtype: str = "fp32",
                    training: bool = False, block: bool = True, with_pair: bool = True) -> Dict:
     """The forms the launchers pick for one forward of the multiscale block (`block=True`, latency form: closing fused
@@ -58,7 +121,8 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
 
     Returns {"groups": [per module: {"name", "E", "K", "rows", "node_form", "wpr", "spw"}], "fused_closing",
     "agg_kernel", "agg_wgs", "agg_grid" (of the launch of the groups that are not in the twins' scene form), "scene_grid",
-    "mlp2", "n2e", "gather_spw"}; "scene_grid" / "mlp2" / "n2e" / "gather_spw" are None where that launch does not run.
+    "mlp2", "n2e", "gather_spw", "scatter" (scatter_forms of the stand-alone scatter)}; "scene_grid" / "mlp2" / "n2e" /
+    "gather_spw" / "scatter" are None where that launch does not run.
     with_pair=False: the hyper modules alone (one MS_HGNN_hyper through the module API).
 
     These rules restate the launchers' plan functions independently of them: tests/test_launch_plan_cpu.py holds the two
@@ -130,12 +194,14 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
     if hyp and N > FUSED_MAX_N:
         Emax, nh = max(g["E"] for g in hyp), len(hyp)
         per_scene = N * 64 * 4 + Emax * N * 4
-        G = 1
-        if per_scene <= GS_LDS_BUDGET:
-            while G < 16 and 2 * G * per_scene <= 24 * 1024 and cdiv(B, 2 * G) * nh >= GS_MIN_WGS:
-                G *= 2
-        gather_spw = G
-    return dict(groups=groups, fused_closing=fused, agg_kernel=agg_kernel, agg_wgs=sum(wgs), agg_grid=grid,
+        gather_spw = gs_scenes_per_wg(per_scene, B, nh) if per_scene <= GS_LDS_BUDGET else 1
+    # stand-alone scatter for N > 16 (run_message_passing.edge2node): exactly the groups whose aggregation wrote per-edge
+    # features, i.e. that are not in node form
+    scatter = None
+    rest = [g for g in groups if not g["node_form"]]
+    if rest and N > FUSED_MAX_N:
+        scatter = scatter_forms(B, N, [dict(E=g["E"], sym=g["name"] == "pair", H=g["name"] != "pair") for g in rest])
+    return dict(scatter=scatter, groups=groups, fused_closing=fused, agg_kernel=agg_kernel, agg_wgs=sum(wgs), agg_grid=grid,
                 scene_grid=scene_grid, mlp2=mlp2, n2e=n2e, gather_spw=gather_spw)
 
 
@@ -214,6 +280,27 @@ FUSED_CASES = [(3, 40), (3, 41), (3, 112)]
 ENGINE_CASES = [(3, 40), (3, 41), (1, 112), (1, 113)]
 
 
+# gn_agg_scatter_* once per planned form (tests/test_graph_forms_gpu.py), at the smallest shapes that reach it:
+# (B, N, groups, storage types, what the plan must say: the kernel of the group's own launch, or the staged kernel and G).
+# groups: one letter per group — s: the unordered pairs, o: the ordered pairs, h: a hyper group (E = N, dense H), m: the
+# same in mask form.  B = 4095 (one group) and 3265 (ten groups) are the first B that pack 2 and 16 scenes per workgroup;
+# both leave ONE scene to the last workgroup.
+SCATTER_GPU_CASES = [
+    (256, 11, "s", ("fp32", "bf16"), ("agg_scatter_pairs_kernel", 0)), (256, 64, "s", ("fp32", "bf16"), ("agg_scatter_pairs_kernel", 0)),
+    (255, 11, "s", ("fp32",), ("agg_scatter_direct_kernel", 0)), (256, 65, "s", ("fp32",), ("agg_scatter_direct_kernel", 0)),
+    (3, 11, "o", ("fp32",), ("agg_scatter_direct_kernel", 0)), (2, 100, "h", ("fp32",), ("agg_scatter_direct_kernel", 0)),
+    (2, 99, "h", ("fp32",), ("agg_scatter_kernel", 1)), (4095, 3, "h", ("fp32",), ("agg_scatter_kernel", 2)),
+    (3265, 3, "h" * 10, ("fp32", "bf16"), ("agg_scatter_kernel", 16)),
+    (4095, 3, "m", ("fp32", "bf16"), ("agg_scatter_mask_kernel", 2)), (3265, 3, "m" * 10, ("fp32", "bf16"), ("agg_scatter_mask_kernel", 16)),
+]
+
+
+def scatter_case_groups(N: int, spec: str) -> List[Dict]:
+    """The `scatter_forms` groups of a SCATTER_GPU_CASES letter string."""
+    kinds = dict(s=dict(E=pair_count(N), sym=True), o=dict(E=N * N), h=dict(E=N, H=True), m=dict(E=N, colmask=True))
+    return [kinds[c] for c in spec]
+
+
 PLACEHOLDER = 4096      # a 16-aligned non-NULL "device address": a plan query tests addresses, it never dereferences them
 
 
@@ -223,7 +310,7 @@ def launch_descriptors(B: int, N: int, scales: Sequence[int], precision: str = "
     `expected_forms`), with its node-form, PoolSpec and closing decisions as `expected_forms` states them and PLACEHOLDER
     for every device address.  -> {"twin", "edge": arr, "agg": arr (closing MLP in a launch of its own), "agg_closing": arr
     (the closing stage in the aggregation launch), "mlp2": (arr, rows, din, dh, dout, ldy, N, divisor), "n2e": arr or None,
-    "gather": arr or None}; the group order is that of expected_forms' "groups"."""
+    "gather": arr or None, "scatter": arr or None}; the group order is that of expected_forms' "groups"."""
     from groupnet_amd import _lib as L
     P = PLACEHOLDER
     twin = dtype == "bf16"
@@ -235,7 +322,7 @@ def launch_descriptors(B: int, N: int, scales: Sequence[int], precision: str = "
     n = len(groups)
     small = N <= FUSED_MAX_N
     pool = not training and xm                      # run_message_passing.node2edge `fuse`, before the N limit of hyper groups
-    edge, agg, aggc, mlp2, n2e, gather = [], [], [], [], [], []
+    edge, agg, aggc, mlp2, n2e, gather, scatter = [], [], [], [], [], [], []
     for g in groups:
         pair, E, K, rows = g["name"] == "pair", g["E"], g["K"], g["rows"]
         common = dict(bias=P, edge_feat=P, rows=rows, K=K, Wx=X, Wh=Hh, W=P, sym_N=N if pair else 0, dist=P)
@@ -264,15 +351,17 @@ def launch_descriptors(B: int, N: int, scales: Sequence[int], precision: str = "
             mlp2.append(L.Mlp2Group(feat=P, H=0 if pair else P, ori=P, E=E, sym=int(pair), **m))   # ScatterSpec
         else:
             mlp2.append(L.Mlp2Group(x=P, **m))                                             # stand-alone scatter's output
+            scatter.append(L.ScatterGroup(feat=P, H=0 if pair else P, ori=P, out=P, E=E, sym=int(pair)))
     arr = lambda cls, xs: (cls * len(xs))(*xs) if xs else None
     return dict(twin=twin, edge=arr(L.EdgeGroup, edge), agg=arr(L.AggGroup, agg), agg_closing=arr(L.AggGroup, aggc),
                 mlp2=(arr(L.Mlp2Group, mlp2), B * N, 128, 128, 64, 64 * (1 + n) if block else 64, N, float(N)),
-                n2e=arr(L.N2EGroup, n2e), gather=arr(L.GatherGroup, gather))
+                n2e=arr(L.N2EGroup, n2e), gather=arr(L.GatherGroup, gather), scatter=arr(L.ScatterGroup, scatter))
 
 
-def assert_plans_match(forms: Dict, agg, mlp2, n2e, gather, where) -> None:
+def assert_plans_match(forms: Dict, agg, mlp2, n2e, gather, where, scatter=False) -> None:
     """The launchers' plans of one forward (groupnet_amd._lib.LaunchPlan of gn_agg_mlp_plan_*, and of gn_mlp2_plan_* /
-    gn_node2edge_plan_* / gn_agg_gather_plan_* or None where that launch does not run) say what `forms` says."""
+    gn_node2edge_plan_* / gn_agg_gather_plan_* / gn_agg_scatter_plan_* or None where that launch does not run; scatter=False:
+    the caller did not ask) say what `forms` says."""
     from groupnet_amd import _lib as L
     name = lambda plan: L.load().gn_kernel_name(plan.kernel).decode()
     groups = forms["groups"]
@@ -293,6 +382,10 @@ def assert_plans_match(forms: Dict, agg, mlp2, n2e, gather, where) -> None:
         assert ("rows" if n2e.variant else "banded") == forms["n2e"] and (n2e.EBh == 0) == bool(n2e.variant), where
     if gather is not None:
         assert gather.G == forms["gather_spw"], (where, gather.G)
+    if scatter is not False:
+        assert (scatter is None) == (forms["scatter"] is None), where
+        if scatter is not None:
+            assert_scatter_plan(forms["scatter"], scatter, where)
 
 
 def describe(forms: Dict) -> str:

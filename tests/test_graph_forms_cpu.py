@@ -1,11 +1,11 @@
 """The stage that builds the graph — cosine affinity, then the top-k incidence — at its form edges, without a GPU and
 without a launch: what the case table of tests/test_graph_forms_gpu.py reaches (tests/launch_forms.py `graph_forms`, the
-tests' own statement of the launchers' arithmetic), and that statement and the Python predicates of groupnet_amd.ops
-against the C library at every switch point.
+tests' own statement of the launchers' arithmetic), and that statement and `groupnet_amd.ops.graph_form` against the C
+library at every switch point.
 
-The library is asked without launching: `gn_affinity_topk_f32` and the node stage's plan check the LDS budget BEFORE the
-alignment of `extras->f_out`, so a call with aligned placeholder addresses and a misaligned `f_out` answers GN_ERR_ALIGN
-exactly when the tile passed the budget, and GN_ERR_LDS when it did not."""
+The library is asked through its plan queries (`gn_affinity_plan_f32`, `gn_topk_incidence_plan_f32`,
+`gn_affinity_topk_plan_f32`, `gn_node_mlp_plan_f32`) with aligned placeholder addresses: GN_OK and the planned kernel,
+grid and LDS where a launch would follow, the launcher's error code where it would not."""
 import ctypes
 import os
 import subprocess
@@ -16,7 +16,7 @@ import pytest
 from launch_forms import (AFF_LDS_BUDGET, AFF_TAIL_LDS, AFFINITY_CASES, AFFINITY_D_CASES, ENGINE_CASES, FUSED_CASES,
                           PLACEHOLDER, TOPK_CASES, affinity_tile, graph_forms, largest_fused_n, topk_bands)
 
-GN_ERR_ALIGN, GN_ERR_LDS = -4, -6
+GN_OK, GN_ERR_LDS = 0, -6
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -62,66 +62,141 @@ def test_case_table_reaches_every_form():
     assert [f["aff_grid"] for f in banded] == [(8, 2), (9, 2), (13, 1), (16, 3)]
 
 
-def _fused_rc(N, D, x_dim=0, mask_scales=0):
-    """Return code of gn_affinity_topk_f32 for placeholder addresses and a misaligned extras->f_out: nothing is launched."""
+def _name(plan):
+    return _lib()[1].gn_kernel_name(plan.kernel).decode()
+
+
+def _fused_args(N, D, x_dim=0, mask_scales=0):
+    """The arguments of gn_affinity_topk_f32 / its plan query up to `colmask_list`, placeholder addresses throughout."""
     L, lib = _lib()
     P = PLACEHOLDER
     n = max(1, mask_scales)
     Hl, kl = (ctypes.c_void_p * n)(*[P] * n), (ctypes.c_int * n)(*[1] * n)
-    ex = L.BlockExtras(f_out=P + 4, f_out_ld=D)
+    ex = L.BlockExtras(f_out=P, f_out_ld=D)
     if x_dim:
         ex.x_raw, ex.x_dim, ex.M, ex.c, ex.f_contig = P, x_dim, P, P, P
     words = (ctypes.c_void_p * n)(*[P] * n) if mask_scales else None
-    return lib.gn_affinity_topk_f32(P, None, Hl, kl, n, 1, N, D, ctypes.byref(ex), words, words, None)
+    return (P, None, Hl, kl, n, 1, N, D, ctypes.byref(ex), words, words), ex
+
+
+def _fused_rc(N, D, x_dim=0, mask_scales=0):
+    """(return code, plan) of gn_affinity_topk_plan_f32 for placeholder addresses."""
+    L, lib = _lib()
+    args, keep = _fused_args(N, D, x_dim, mask_scales)
+    plan = L.LaunchPlan()
+    return lib.gn_affinity_topk_plan_f32(*args, ctypes.byref(plan)), plan
 
 
 @pytest.mark.parametrize("D,x_dim,mask_scales", [(64, 0, 0), (64, 20, 0), (64, 40, 0), (4, 0, 0), (128, 0, 0), (1024, 0, 0),
                                                  (1024, 0, 8)])
 def test_fused_launch_budget_is_the_one_python_states(D, x_dim, mask_scales):
-    """The largest N whose tile fits answers GN_ERR_ALIGN (the budget was passed), N + 1 answers GN_ERR_LDS; `graph_forms`
-    and `ops.fused_affinity_fits` say the same.  (1024, 0, 8): with mask lists — the mask words of eight scales move the
-    switch point from 30 | 31 to 29 | 30, so the case reads the mask term and not only the tile."""
+    """The largest N whose tile fits answers GN_OK with that tile as the launch's LDS, N + 1 answers GN_ERR_LDS — from the
+    plan query and from the launcher entry itself, which launches nothing there; `graph_forms` and `ops.graph_form` say the
+    same.  (1024, 0, 8): with mask lists — the mask words of eight scales move the switch point from 30 | 31 to 29 | 30, so
+    the case reads the mask term and not only the tile."""
     from groupnet_amd import ops
+    _, lib = _lib()
     N = largest_fused_n(D, x_dim, mask_scales)
     if (D, x_dim) == (64, 0):
         assert N == 112
     if D == 1024:
         assert N == (29 if mask_scales else 30)
-    assert (_fused_rc(N, D, x_dim, mask_scales), _fused_rc(N + 1, D, x_dim, mask_scales)) == (GN_ERR_ALIGN, GN_ERR_LDS)
+    (rc, plan), (rc1, _) = _fused_rc(N, D, x_dim, mask_scales), _fused_rc(N + 1, D, x_dim, mask_scales)
+    assert (rc, rc1) == (GN_OK, GN_ERR_LDS)
+    assert plan.dyn_lds == affinity_tile(N, D, x_dim, mask_scales) and list(plan.grid) == [1, 1, 1]
+    assert _name(plan) == ("affinity_topk_masks_kernel" if mask_scales else "affinity_topk_kernel")
+    args, keep = _fused_args(N + 1, D, x_dim, mask_scales)
+    assert lib.gn_affinity_topk_f32(*args, None) == GN_ERR_LDS
     scales = [1] * mask_scales
     for n, fits in ((N, True), (N + 1, False)):
-        assert ops.fused_affinity_fits(n, D, x_dim, mask_scales) is fits
-        assert ops.affinity_tile_bytes(n, D, x_dim, mask_scales) == affinity_tile(n, D, x_dim, mask_scales)
+        assert (ops.graph_form(n, D, x_dim, mask_scales) != "banded") is fits
         assert (graph_forms(1, n, D, x_dim, bool(mask_scales), scales)["form"] != "banded") is fits
 
 
 def _tail_rc(N, x_dim=0, D=64, B=3):
-    """Return code of the node stage's launch query with an affinity job of placeholder addresses and a misaligned
-    extras->f_out (the plan refuses before the runtime is asked anything)."""
+    """(return code, plan) of the node stage's plan query with an affinity job of placeholder addresses."""
     L, lib = _lib()
     P = PLACEHOLDER
     g = (L.NodeGroup * 1)(L.NodeGroup(x=P, Wx=P, bias=P, xp=P, pq=P))
     Hl, kl = (ctypes.c_void_p * 1)(P), (ctypes.c_int * 1)(1)
-    ex = L.BlockExtras(f_out=P + 4, f_out_ld=D)
+    ex = L.BlockExtras(f_out=P, f_out_ld=D)
     if x_dim:
         ex.x_raw, ex.x_dim, ex.M, ex.c, ex.f_contig = P, x_dim, P, P, P
     job = L.AffinityJob(f=P, H_list=Hl, k_list=kl, n_scales=1, B=B, N=N, D=D, extras=ctypes.pointer(ex))
-    lds, occ = ctypes.c_size_t(0), ctypes.c_int(0)
-    return lib.gn_node_mlp_affinity_launch_info_f32(g, 1, B * N, ctypes.byref(job), ctypes.byref(lds), ctypes.byref(occ))
+    plan = L.LaunchPlan()
+    return lib.gn_node_mlp_plan_f32(g, 1, B * N, ctypes.byref(job), ctypes.byref(plan)), plan
 
 
 @pytest.mark.parametrize("x_dim,N", [(0, 40), (20, 37)])
 def test_tail_budget_is_the_one_python_states(x_dim, N):
-    """The node stage takes the job up to N (40; 37 with 20 raw inputs per agent) and refuses N + 1 with GN_ERR_LDS;
-    `ops.affinity_tail_fits` — what `AffinityTail.fits_tail` asks — and `graph_forms` say the same, raw inputs counted."""
+    """The node stage takes the job up to N (40; 37 with 20 raw inputs per agent) and refuses N + 1 with GN_ERR_LDS — the
+    plan query and the launcher entry alike; `ops.graph_form` — what `AffinityTail.fits_tail` asks — and `graph_forms` say
+    the same, raw inputs counted."""
     from groupnet_amd import ops
-    _, lib = _lib()
+    L, lib = _lib()
     assert lib.gn_affinity_tail_lds_limit() == AFF_TAIL_LDS
     assert N == largest_fused_n(64, x_dim, budget=AFF_TAIL_LDS)
-    assert (_tail_rc(N, x_dim), _tail_rc(N + 1, x_dim)) == (GN_ERR_ALIGN, GN_ERR_LDS)
+    (rc, plan), (rc1, _) = _tail_rc(N, x_dim), _tail_rc(N + 1, x_dim)
+    assert (rc, rc1) == (GN_OK, GN_ERR_LDS)
+    assert plan.dyn_lds == affinity_tile(N, 64, x_dim) and _name(plan) == "node_stage_kernel"
+    # the launcher entry at N + 1: refused before anything is launched
+    P = PLACEHOLDER
+    g = (L.NodeGroup * 1)(L.NodeGroup(x=P, Wx=P, bias=P, xp=P, pq=P))
+    Hl, kl = (ctypes.c_void_p * 1)(P), (ctypes.c_int * 1)(1)
+    ex = L.BlockExtras(x_raw=P, x_dim=x_dim, M=P, c=P, f_contig=P) if x_dim else L.BlockExtras()
+    job = L.AffinityJob(f=P, H_list=Hl, k_list=kl, n_scales=1, B=3, N=N + 1, D=64, extras=ctypes.pointer(ex))
+    assert lib.gn_node_mlp_affinity_f32(g, 1, 3 * (N + 1), ctypes.byref(job), None) == GN_ERR_LDS
     for n, fits in ((N, True), (N + 1, False)):
-        assert ops.affinity_tail_fits(n, 64, x_dim) is fits
+        assert (ops.graph_form(n, 64, x_dim) == "tail") is fits
         assert (graph_forms(3, n, 64, x_dim)["form"] == "tail") is fits
+
+
+def test_graph_form_is_the_tests_statement_everywhere():
+    """`ops.graph_form` against `graph_forms` over every N up to beyond the last switch point, with and without raw inputs
+    and mask words."""
+    from groupnet_amd import _lib as L, ops
+    with pytest.raises(L.GroupNetHipError):
+        ops.graph_form(65, 64, 0, 1)
+    for x_dim, ms in ((0, 0), (20, 0), (0, 3), (0, 8)):
+        for N in range(1, 65 if ms else 120):      # (mask words: N <= 64, else the query raises as the launch would)
+            assert ops.graph_form(N, 64, x_dim, ms) == graph_forms(1, N, 64, x_dim, bool(ms), [1] * ms)["form"], (N, x_dim, ms)
+
+
+def _topk_plan(B, N):
+    L, lib = _lib()
+    P = PLACEHOLDER
+    Hl, kl = (ctypes.c_void_p * 1)(P), (ctypes.c_int * 1)(2)
+    plan = L.LaunchPlan()
+    return lib.gn_topk_incidence_plan_f32(P, Hl, kl, 1, B, N, ctypes.byref(plan)), plan
+
+
+def test_topk_plan_is_the_band_arithmetic_python_states():
+    """`topk_bands` against gn_topk_incidence_plan_f32 for the GPU cases and the engine's banded cases: rows per band in
+    TE, grid (bands, B), a band of rows as the LDS; GN_ERR_LDS, before any division, where not one row fits."""
+    for B, N in TOPK_CASES + [(B, N) for B, N in ENGINE_CASES if graph_forms(B, N)["form"] == "banded"] + [(1, 16384)]:
+        rc, plan = _topk_plan(B, N)
+        RB, bands, rem = topk_bands(B, N)
+        assert rc == GN_OK and _name(plan) == "topk_incidence_kernel", (B, N)
+        assert (plan.TE, list(plan.grid), plan.dyn_lds) == (RB, [bands, B, 1], RB * N * 4), (B, N)
+    for N in (16385, 32768):
+        assert topk_bands(1, N) is None and _topk_plan(1, N)[0] == GN_ERR_LDS
+
+
+def test_affinity_plan_is_the_form_python_states():
+    """`graph_forms` against gn_affinity_plan_f32 for every stand-alone affinity case: the fused kernel on (B) workgroups
+    with the fused tile, or the banded kernel on `aff_grid` with 16 band rows and a 64-column panel at stride D + 4."""
+    L, lib = _lib()
+    P = PLACEHOLDER
+    for B, N, D in AFFINITY_CASES + AFFINITY_D_CASES:
+        plan = L.LaunchPlan()
+        assert lib.gn_affinity_plan_f32(P, P, B, N, D, ctypes.byref(plan)) == GN_OK
+        form = graph_forms(B, N, D)
+        if form["form"] == "banded":
+            assert _name(plan) == "affinity_banded_kernel" and tuple(plan.grid) == form["aff_grid"] + (1,), (B, N, D)
+            assert plan.dyn_lds == 80 * (D + 4) * 4
+        else:
+            assert _name(plan) == "affinity_topk_kernel" and list(plan.grid) == [B, 1, 1], (B, N, D)
+            assert plan.dyn_lds == affinity_tile(N, D) == form["tile"]
 
 
 _TOPK_CHILD = """

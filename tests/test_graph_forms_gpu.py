@@ -13,8 +13,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from incidence_mask_cases import np_masks
-from launch_forms import (AFFINITY_CASES, AFFINITY_D_CASES, FUSED_CASES, TOPK_CASES, _spread, graph_forms, topk_bands)
+from incidence_mask_cases import np_masks, random_incidence
+from launch_forms import (AFFINITY_CASES, AFFINITY_D_CASES, FUSED_CASES, SCATTER_GPU_CASES, TOPK_CASES, _spread,
+                          assert_scatter_plan, graph_forms, scatter_case_groups, scatter_forms, topk_bands)
 from oracle import ms_hgnn_oracle as O
 from oracle import past_encoder_oracle as PO
 from test_parity_gpu import TOL, TOL_CORR, maxerr
@@ -324,3 +325,113 @@ def test_past_encoder_eval_on_both_sides_of_the_fused_tile(N, seed):
     assert out.shape == want.shape
     close_to(out, want, f"PastEncoder N={N} vs oracle")
     assert torch.equal(new_H.cpu(), torch.cat(Hs, dim=1))
+
+
+# ---- the scatter, once per planned form -----------------------------------------------------------------------------
+def scatter_case_inputs(B, N, spec, dtype, seed=0):
+    """Per group of a SCATTER_GPU_CASES case, on the GPU: {"feat" (as the launch reads it, storage type `dtype`), "ori",
+    "H" (dense (B,E,N) fp32 or None), "col" (column words or None), "E", "sym", and for the reference "Hd" (the dense
+    incidence, (E,N) shared by all scenes for the pairwise graph) and "fd" (the features `Hd` multiplies)}.
+    Pairwise groups: ordered features (B, N*N, 64) against the oracle's `pairwise_incidence`; the unordered-pair features
+    are formed from them exactly as test_symmetric_pairwise_stages_equal_ordered_ones does — diagonal doubled,
+    off-diagonal summed.  bf16 storage: the ordered features are multiples of 1/8 within +-4, so that sum is exact in bf16
+    and the launch reads the very numbers the reference sums."""
+    g = torch.Generator(device=dev()).manual_seed(1000 * N + B + seed)
+    rnd = lambda *shape: torch.randn(*shape, generator=g, device=dev())
+    store = lambda t: t.to(dtype).contiguous()
+    out = []
+    for i, c in enumerate(spec):
+        ori = store(rnd(B, N, 64))
+        if c in "so":
+            fd = rnd(B, N * N, 64)
+            if dtype == torch.bfloat16:
+                fd = (fd * 8).round().clamp(-32, 32) / 8
+            Hd = O.pairwise_incidence(N, 1, torch.float64)[0].to(dev())
+            feat = fd
+            if c == "s":
+                pr = [(a, b) for a in range(N) for b in range(a, N)]
+                ij = torch.tensor([a * N + b for a, b in pr], device=dev())
+                ji = torch.tensor([b * N + a for a, b in pr], device=dev())
+                diag = torch.tensor([a == b for a, b in pr], device=dev())
+                feat = torch.where(diag[None, :, None], 2 * fd[:, ij], fd[:, ij] + fd[:, ji])
+            feat = store(feat)
+            out.append(dict(feat=feat, ori=ori, H=None, col=None, E=feat.shape[1], sym=c == "s", Hd=Hd, fd=store(fd)))
+        else:
+            H = random_incidence(B, N, N, seed=17 * i + N + B)
+            col = torch.from_numpy(np_masks(H.numpy())[1]).to(dev()) if c == "m" else None
+            feat = store(rnd(B, N, 64))
+            H = H.to(dev())
+            out.append(dict(feat=feat, ori=ori, H=None if c == "m" else H, col=col, E=N, sym=False, Hd=H.double(), fd=feat))
+    return out
+
+
+def scatter_reference(grp, N, dtype, chunk=32):
+    """float64 cat(H^T feat, ori) / N of one group and the a-priori bar per element.  fp32: the kernel rounds once per
+    term it adds into a node (E_n terms: the non-zero entries of the node's column of H) and once for the division, the
+    pair features once more where they were summed from the ordered ones: (E_n + 4) 2^-24 sum|H feat| / N covers them (the
+    ori half: one division, 4 2^-24 |ori| / N).  bf16 storage: fp32 accumulation of the stored values, then the output
+    rounding, 2^-8 |ref|."""
+    Hd, B = grp["Hd"], grp["ori"].shape[0]
+    refs, bars = [], []
+    for b0 in range(0, B, chunk):
+        sl = slice(b0, min(B, b0 + chunk))
+        Ht = (Hd if Hd.dim() == 2 else Hd[sl]).transpose(-1, -2)            # (N, E) or (b, N, E)
+        f, o = grp["fd"][sl].double(), grp["ori"][sl].double()
+        terms = (Ht != 0).sum(-1, keepdim=True).double()                     # E_n
+        terms = terms.expand(f.shape[0], N, 1) if terms.dim() == 2 else terms
+        refs.append(torch.cat([Ht @ f, o], dim=-1) / N)
+        bars.append(torch.cat([(terms + 4) * (Ht.abs() @ f.abs()), 4 * o.abs()], dim=-1) / N * 2.0 ** -24)
+    ref, bar = torch.cat(refs), torch.cat(bars)
+    return ref, bar + (2.0 ** -8 * ref.abs() if dtype == torch.bfloat16 else 0)
+
+
+def scatter_descriptors(grps, outs):
+    from groupnet_amd import _lib as L
+    return (L.ScatterGroup * len(grps))(*[
+        L.ScatterGroup(feat=g["feat"].data_ptr(), H=L.addr(g["H"]), ori=g["ori"].data_ptr(), out=o.data_ptr(), E=g["E"],
+                       sym=int(g["sym"]), colmask=L.addr(g["col"])) for g, o in zip(grps, outs)])
+
+
+SCATTER_IDS = [f"B{B}-N{N}-{spec[0]}x{len(spec)}-{dt}" for B, N, spec, dts, _ in SCATTER_GPU_CASES for dt in dts]
+
+
+@pytest.mark.parametrize("B,N,spec,dt,form", [(B, N, spec, dt, form) for B, N, spec, dts, form in SCATTER_GPU_CASES for dt in dts],
+                         ids=SCATTER_IDS)
+def test_scatter_entry_in_every_planned_form(B, N, spec, dt, form, monkeypatch):
+    """gn_agg_scatter_* once per form its plan can take — the pairs kernel at both ends of its N range, the direct kernel in
+    its three modes (unordered pairs below B = 256 and beyond N = 64, ordered pairs, a hyper group beyond the staged
+    tile), the staged kernel with 1, 2 and 16 scenes per workgroup (the last workgroup holding ONE scene) and the mask
+    kernel likewise — against float64 cat(H^T feat, ori) / N with the dense H, at the a-priori bar of `scatter_reference`.
+    The plan's form is asserted first.  Outputs are pre-filled with NaN and one scene longer than B."""
+    from groupnet_amd import _lib as L
+    monkeypatch.delenv("GN_SCATTER_PAIRS", raising=False)
+    lib = L.load()
+    dtype = torch.bfloat16 if dt == "bf16" else torch.float32
+    sfx = "bf16" if dt == "bf16" else "f32"
+    grps = scatter_case_inputs(B, N, spec, dtype)
+    outs = [torch.full((B + 1, N, 128), NAN, dtype=dtype, device=dev()) for _ in grps]
+    arr = scatter_descriptors(grps, outs)
+    plan = L.LaunchPlan()
+    assert getattr(lib, f"gn_agg_scatter_plan_{sfx}")(arr, len(grps), B, N, float(N), ctypes.byref(plan)) == 0
+    sf = scatter_forms(B, N, scatter_case_groups(N, spec))
+    assert_scatter_plan(sf, plan, (B, N, spec, dt))
+    kernel, G = form
+    if G:
+        assert (lib.gn_kernel_name(plan.kernel).decode(), plan.G) == (kernel, G) and (G == 1 or B % G == 1)
+    else:
+        assert plan.kernel == 0 and lib.gn_kernel_name(plan.pre_kernel[0]).decode() == kernel
+    with torch.cuda.device(dev()):
+        rc = getattr(lib, f"gn_agg_scatter_{sfx}")(arr, len(grps), B, N, float(N), L.stream_handle())
+    torch.cuda.synchronize()
+    assert rc == 0
+    worst = 0.0
+    for i, (grp, out) in enumerate(zip(grps, outs)):
+        assert bool(torch.isnan(out[B]).all()), f"group {i}: a write past the last scene"
+        got = out[:B].double()
+        assert not bool(torch.isnan(got).any()), f"group {i}: an element was not written"
+        ref, bar = scatter_reference(grp, N, dtype)
+        excess = ((got - ref).abs() - bar).max().item()
+        worst = max(worst, ((got - ref).abs() / bar.clamp_min(1e-300)).max().item())
+        assert excess <= 0, f"group {i}: |got - ref| exceeds the bar by {excess:.3e}"
+    print(f"\nscatter B={B} N={N} {spec[0]}x{len(spec)} {dt}: {kernel} G={G}, worst |err| / bar = {worst:.3f}")
+

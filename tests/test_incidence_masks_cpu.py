@@ -37,7 +37,7 @@ def _scatter(groups, B, N, divisor=1.0):
 def test_symbols_and_trailing_fields():
     L, lib = _lib()
     from groupnet_amd import ops
-    assert lib.gn_abi_version() == L.ABI_VERSION == 37
+    assert lib.gn_abi_version() == L.ABI_VERSION >= 37
     assert hasattr(lib, "gn_incidence_masks_f32") and "gn_incidence_masks_f32" in L.SIGNATURES
     # trailing: a descriptor filled by field name without the mask stays the dense / pairwise form
     assert L.GatherGroup._fields_[-1][0] == "rowmask" and L.ScatterGroup._fields_[-1][0] == "colmask"
@@ -45,7 +45,7 @@ def test_symbols_and_trailing_fields():
     assert len(L.SIGNATURES["gn_affinity_topk_f32"][1]) == len(L.SIGNATURES["gn_affinity_topk_bf16"][1]) == 12
     assert lib.gn_kernel_name(L.K_AGG_GATHER) == b"agg_gather_kernel"
     assert lib.gn_kernel_name(L.K_AGG_GATHER_MASK) == b"agg_gather_mask_kernel"
-    assert lib.gn_kernel_name(L.K_AGG_GATHER_MASK + 1) is None
+    assert lib.gn_kernel_name(L.K_LAST + 1) is None
     for name in ("IncidenceMasks", "incidence_masks", "set_incidence_form", "incidence_form"):
         assert hasattr(ops, name), name
 

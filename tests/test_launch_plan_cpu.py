@@ -6,8 +6,9 @@ import itertools
 
 import pytest
 
-from launch_forms import (BACKWARD_CASES, FORWARD_CASES, assert_plans_match, case_forms, expected_forms,
-                          launch_descriptors)
+from launch_forms import (BACKWARD_CASES, FORWARD_CASES, PLACEHOLDER, SCATTER_GPU_CASES, assert_plans_match,
+                          assert_scatter_plan, case_forms, expected_forms, launch_descriptors, pair_count, scatter_case_groups,
+                          scatter_forms)
 
 SWEEP_B = (1, 5, 64, 369, 370, 512, 2231, 2232, 4064, 4065, 4096, 24544, 24545)
 SWEEP_N = (3, 11, 16, 17, 50, 64, 65)
@@ -48,8 +49,9 @@ def check_plans(forms, d, block, where):
              # (training and the fp32 cores also pool the pairwise group in that launch: its form is the hyper groups')
              _ask("node2edge", twin, d["n2e"], B, N) if d["n2e"] is not None and any(x.H for x in d["n2e"]) else None,
              _ask("agg_gather", twin, d["gather"], B, N) if d["gather"] is not None else None]
-    assert all(p is None or p[0] == 0 for p in plans), (where, [p and p[0] for p in plans])
-    assert_plans_match(forms, *[p and p[1] for p in plans], where)
+    scatter = _ask("agg_scatter", twin, d["scatter"], B, N, ctypes.c_float(N)) if d["scatter"] is not None else None
+    assert all(p is None or p[0] == 0 for p in plans + [scatter]), (where, [p and p[0] for p in plans + [scatter]])
+    assert_plans_match(forms, *[p and p[1] for p in plans], where, scatter=scatter and scatter[1])
 
 
 def _kw(case):
@@ -84,7 +86,7 @@ def test_switches_move_the_plan(monkeypatch):
     """Every switch is read per call: set and unset between two queries of one process, it moves the plan as its comment
     in the launchers says."""
     for v in ("GN_AGG_RB2", "GN_EDGE_RB2", "GN_RB2_MIN_PAIRS", "GN_MLP2_XS", "GN_N2E_ROWS", "GN_AGG_LINES", "GN_AGG_HSTAGE",
-              "GN_XCD", "GN_POOL_STAGE"):
+              "GN_XCD", "GN_POOL_STAGE", "GN_SCATTER_PAIRS"):
         monkeypatch.delenv(v, raising=False)
 
     def name(stem, twin, *a):
@@ -152,6 +154,89 @@ def test_switches_move_the_plan(monkeypatch):
     assert plan.xcd == 0 and plan.grid[0] == wgs
     monkeypatch.delenv("GN_XCD")
     assert closing()[1].xcd == 1
+
+
+def _scatter_groups(N, spec):
+    """spec: a string of group kinds — s: the unordered pairs, o: the ordered pairs, h: a hyper group (E = N) with a dense
+    H, m: ... in mask form, 1: the one-hyperedge group (E = 1, dense), w: ... in mask form."""
+    kinds = dict(s=dict(E=pair_count(N), sym=True), o=dict(E=N * N), h=dict(E=N, H=True), m=dict(E=N, colmask=True),
+                 w=dict(E=1, colmask=True))
+    kinds["1"] = dict(E=1, H=True)
+    return [kinds[c] for c in spec]
+
+
+def _scatter_plan(B, N, groups, twin):
+    L, _ = _lib()
+    P = PLACEHOLDER
+    arr = (L.ScatterGroup * len(groups))(*[L.ScatterGroup(feat=P, ori=P, out=P, E=g["E"], sym=int(bool(g.get("sym"))),
+                                                         H=P if g.get("H") else 0, colmask=P if g.get("colmask") else 0)
+                                           for g in groups])
+    return _ask("agg_scatter", twin, arr, B, N, ctypes.c_float(N))
+
+
+# (B, N, groups): both sides of every rule of scatter_plan
+SCATTER_SWITCH_POINTS = (
+    # the pairs kernel: B >= 256 and 16 N <= 1024, beside a hyper group and alone; the ordered pairs never take it
+    [(B, N, spec) for B in (255, 256) for N in (64, 65) for spec in ("s", "sh", "o")]
+    # a hyper group is staged while E (64 + N) floats fit 64 KiB: N = E = 99 | 100
+    + [(2, N, spec) for N in (99, 100) for spec in ("h", "hs")]
+    # scenes per workgroup: 1 | 2 at 2048 workgroups of one and of two groups, 8 | 16 with ten groups; a tile beyond
+    # 12 KiB (N = E = 64) is never doubled
+    + [(B, 3, spec) for B in (4094, 4095) for spec in ("h", "m")] + [(B, 3, spec) for B in (2046, 2047) for spec in ("hh", "mm")]
+    + [(B, 3, spec) for B in (3264, 3265) for spec in ("h" * 10, "m" * 10, "mmmmwmmmmw")]
+    + [(4095, 64, "h"), (4095, 64, "m"), (4095, 64, "mw"), (70000, 17, "h1s"), (70000, 17, "mws")])
+
+
+@pytest.mark.parametrize("twin", [False, True], ids=["f32", "bf16"])
+@pytest.mark.parametrize("pairs_env", [None, "0", "1"], ids=["unset", "pairs0", "pairs1"])
+def test_scatter_plans_at_the_switch_points(twin, pairs_env, monkeypatch):
+    """gn_agg_scatter_plan_* against `scatter_forms` on both sides of every rule, GN_SCATTER_PAIRS unset, 0 and 1 (read
+    per call), both storage types; and the case table reaches every form and every G."""
+    if pairs_env is None:
+        monkeypatch.delenv("GN_SCATTER_PAIRS", raising=False)
+    else:
+        monkeypatch.setenv("GN_SCATTER_PAIRS", pairs_env)
+    seen = set()
+    for B, N, spec in SCATTER_SWITCH_POINTS:
+        groups = _scatter_groups(N, spec)
+        sf = scatter_forms(B, N, groups, pairs_switch=pairs_env != "0")
+        rc, plan = _scatter_plan(B, N, groups, twin)
+        assert rc == 0 and plan.precision == int(twin), (B, N, spec, rc)
+        assert_scatter_plan(sf, plan, (B, N, spec))
+        seen |= {(N, B, spec[i], k) for i, (k, _) in sf["own"].items()} | {(sf["kernel"], len(spec), B, sf["G"])}
+    pairs = pairs_env != "0"
+    for B, N in ((255, 64), (256, 64), (255, 65), (256, 65)):
+        assert (N, B, "s", "agg_scatter_pairs_kernel" if pairs and (B, N) == (256, 64) else "agg_scatter_direct_kernel") in seen
+        assert (N, B, "o", "agg_scatter_direct_kernel") in seen
+    assert (99, 2, "h", "agg_scatter_direct_kernel") not in seen and (100, 2, "h", "agg_scatter_direct_kernel") in seen
+    for kern in ("agg_scatter_kernel", "agg_scatter_mask_kernel"):
+        assert {(kern, 1, 4094, 1), (kern, 1, 4095, 2), (kern, 2, 2046, 1), (kern, 2, 2047, 2), (kern, 10, 3264, 8),
+                (kern, 10, 3265, 16)} <= seen
+    assert ("agg_scatter_kernel", 1, 4095, 1) in seen and ("agg_scatter_mask_kernel", 1, 4095, 1) in seen      # N = E = 64
+    # dense and mask hyper groups in one call: refused by both, nothing launched
+    for spec in ("hm", "mh", "sm1"):
+        groups = _scatter_groups(17, spec)
+        assert scatter_forms(5, 17, groups) is None and _scatter_plan(5, 17, groups, twin)[0] == -2, spec
+
+
+def test_scatter_gpu_cases_reach_the_forms_they_name(monkeypatch):
+    """Every case of the GPU test of the scatter's forms: the rules and the library's plan give the form the case names,
+    and the packed cases leave one scene to the last workgroup."""
+    monkeypatch.delenv("GN_SCATTER_PAIRS", raising=False)
+    for B, N, spec, dtypes, (kernel, G) in SCATTER_GPU_CASES:
+        groups = scatter_case_groups(N, spec)
+        sf = scatter_forms(B, N, groups)
+        if G:
+            assert (sf["kernel"], sf["G"], sf["own"]) == (kernel, G, {}) and (G == 1 or B % G == 1), (B, N, spec)
+        else:
+            assert sf["kernel"] is None and [k for k, _ in sf["own"].values()] == [kernel], (B, N, spec)
+        for dt in dtypes:
+            rc, plan = _scatter_plan(B, N, groups, dt == "bf16")
+            assert rc == 0
+            assert_scatter_plan(sf, plan, (B, N, spec, dt))
+    reached = {c[4] for c in SCATTER_GPU_CASES}
+    assert {k for k, _ in reached} == {"agg_scatter_pairs_kernel", "agg_scatter_direct_kernel", "agg_scatter_kernel",
+                                       "agg_scatter_mask_kernel"}
 
 
 def test_edge_plan_sizes_the_stage_from_the_static_lds(monkeypatch):
