@@ -2,6 +2,7 @@
 """bench.py — scenes/s of the GroupNet MS-HGNN forward on MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W                       (BASELINE config 2 / 3: N=11, fp32)
+    python bench.py --full ...                                          (the same, then every side measurement)
     python bench.py --config c4 ...                                     (BASELINE config 4: N=50, B=1024, bf16)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W          (N > 1, one rank per GPU)
@@ -14,8 +15,13 @@ concatenated (B, N, 64*(2+S)) tensor; with N > 1 ranks each rank owns its own sc
 `--streams` steps, on a side stream).  The step is a captured hipGraph; consecutive steps are issued round-robin
 on --streams (default 4) HIP streams, each with its own graph and output buffers, so the tail / small kernels /
 all-gather of one step overlap the next step's matrix work (every step is still a complete forward of its own
-batch).  A caller with a dependency between steps gets the single-stream figure, reported next to it
-(`value_single_stream`).
+batch).  A caller with a dependency between steps gets the single-stream figure, which a `--full` run reports
+next to it (`value_single_stream`).
+
+A plain run does only what the headline figure needs: set-up, the warm-up, the timed steps, `--dump-outputs`, the
+line.  Everything else the benchmark measures comes after the timed steps (and after the dump) of a `--full` run (only
+the single-stream figure's own graph is captured before them, as it always was), so the headline figure and the dumped
+arrays of the two kinds of run are the same; in a plain run those fields are null.
 
 The timed region is exactly K = --steps steps after W = --warmup untimed ones, between two fences; `ms_per_step` is
 its duration / K.  It is never repeated or lengthened: every step draws fresh device noise, so what the last step
@@ -23,13 +29,15 @@ computes depends on how many steps ran, and `--dump-outputs DIR` writes exactly 
 output: two builds compare output for output).  For a stable figure choose K so that the region is long: on MI355X
 the first ~16 ms after the warm-up run ~9 % slower (config 2: 200 steps read 0.082 ms, 20000 steps 0.075 ms).
 
-Rank 0 prints one JSON line.  Besides the contract fields it carries
+Rank 0 prints one JSON line.  Besides the contract fields a `--full` run carries (`full_legs` lists what ran)
+  value_single_stream  the same K steps of the latency form on ONE stream, back to back;
   roofline      the matrix-core kernel with the largest launch time: algorithmic FLOPs per launch / its average
                 duration, measured here with HIP events on the stream it is launched on, in an instrumented pass;
   agg_hbm       the hyperedge aggregation gather+scatter kernels against the HBM roofline at N=11/B=4096
                 (north_star target >= 30 %), measured the same way;
   cpu_baseline  the CPU oracle (a port of the reference's PyTorch path) timed on this box's host cores on a
-                bounded sample of the same workload — a baseline, not a target.
+                bounded sample of the same workload — a baseline, not a target;
+  parity_mode, per_module_us, train_step, configs.c4   the side legs (`--no-side-legs` and its kin drop them).
 """
 import argparse
 import json
@@ -448,6 +456,28 @@ def dump_outputs(out_dir, arrays, seed=0):
                 arrays={k: [n, *t.shape[1:]] for k, t in arrays.items()})
 
 
+def full_legs(args, world=1, twin=False):
+    """Names of the measurements a run makes BESIDES its timed steps, from its arguments alone.  A plain run makes
+    none; `--full` makes all that fit the run (one process or several, the configuration) less what the --no-*
+    switches drop.  `single` runs on every rank, the others on rank 0."""
+    if not args.full:
+        return frozenset()
+    distributed = world > 1 or args.force_dist
+    side = world == 1 and not args.no_side_legs
+    legs = {"roofline", "agg_hbm"}
+    if not distributed:
+        legs.add("single")
+    if side:
+        legs |= {"parity", "modules"}
+        if not args.no_train_leg and not twin:
+            legs.add("train")
+        if args.config == "c2" and not args.no_c4_leg:
+            legs.add("c4")
+    if world == 1 and not args.no_cpu_baseline:
+        legs.add("cpu")
+    return frozenset(legs)
+
+
 def self_launch(n_gpus, port, dry):
     """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nnodes=1
     --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>` as a CHILD process and return its exit
@@ -466,7 +496,7 @@ def self_launch(n_gpus, port, dry):
     return subprocess.call(argv, env=env)
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -474,15 +504,20 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2",
                     help="c2: BASELINE metric configuration (N=11, B=512 per GPU, fp32); c4: N=50, B=1024, bf16 twins")
     ap.add_argument("--batch-per-gpu", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps (and --dump-outputs) also measure everything else: the single-stream "
+                         "figure, the roofline pass, the HBM leg, parity mode, each module alone, the training step, "
+                         "config 4 and the CPU baseline.  Without it the run ends with the timed steps, and the --no-* "
+                         "switches of those legs have nothing to drop")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--streams", type=int, default=4,
                     help="consecutive steps are issued round-robin on this many HIP streams (each with its own "
                          "captured graph and output buffers), so the tail of one step overlaps the head of the next")
-    ap.add_argument("--no-train-leg", action="store_true", help="skip the training-step side measurement")
-    ap.add_argument("--no-c4-leg", action="store_true", help="skip the short BASELINE-config-4 side leg of the default run")
+    ap.add_argument("--no-train-leg", action="store_true", help="--full: skip the training-step side measurement")
+    ap.add_argument("--no-c4-leg", action="store_true", help="--full: skip the short BASELINE-config-4 side leg")
     ap.add_argument("--no-side-legs", action="store_true",
-                    help="profiling runs: only the timed regions, the roofline pass and the HBM leg (no parity-mode / "
+                    help="--full, profiling runs: only the timed regions, the roofline pass and the HBM leg (no parity-mode / "
                          "per-module / training / config-4 legs, whose launches of other sizes would mix into kernel statistics)")
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal: run the multi-GPU code path (process group, bucketed all-gather) with one rank")
@@ -494,6 +529,11 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one returned (rank 0: features, H) as DIR/<name>.npy "
                          "in float32; a fixed, seeded sample of the scenes when that exceeds 64 MB")
+    return ap
+
+
+def main():
+    ap = parser()
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
@@ -530,6 +570,7 @@ def main():
 
     Bl, N, SCALES = cfg["B"], cfg["N"], cfg["scales"]
     twin = cfg["dtype"] == "bf16"
+    legs = full_legs(args, world, twin)
     tdt = torch.bfloat16 if twin else torch.float32
     B_total = Bl * world
     torch.manual_seed(0)                      # same seeded default-init weights on every rank
@@ -563,7 +604,7 @@ def main():
             runs = [(lambda gr=gr: gr()) for gr in graphs]
             # the single-stream figure (a caller with a dependency between steps) uses the latency form
             lat_graph = None
-            if not distributed:
+            if "single" in legs:
                 lat_graph = graphs[0] if S == 1 else GraphedMultiScale(block, Bl, N, seed=99 + 1000 * rank, dtype=tdt,
                                                                        affinity_tail=True)
                 lat_graph.f_in.copy_(f)
@@ -613,35 +654,34 @@ def main():
                 else:
                     lat_graph()
         single = None
-        if not distributed:
+        if "single" in legs:
             for _ in range(min(args.warmup, 10)):
                 step1()
             single = statistics.median(timer.measure(args.steps, step1, n_regions))
 
         # ---- roofline leg: instrumented eager pass (rank 0) ---------------------------------------------
         roof = agg = mfma_kernels = train = parity = modules = c4 = None
-        if rank == 0:
+        if rank == 0 and args.full:
             roof, mfma_kernels = roofline_leg(block, f, args.config, twin, N, min(args.steps, 50))
             agg = agg_hbm_leg(dev)         # (its two kernels run in no forward at N = 11: they cannot mix into its statistics)
-            if world == 1 and not args.no_side_legs:
+            if "parity" in legs:
                 parity = parity_mode_leg(block, f, Bl, N)
                 modules = per_module_leg(block, f)
             G.set_noise_mode("host")
             # ---- one training step (fwd + loss + bwd + SGD) replayed from one hipGraph ------
             try:
-                train = (train_step_leg(N, Bl, SCALES, dev)
-                         if (world == 1 and not args.no_train_leg and not args.no_side_legs and not twin) else None)
+                train = train_step_leg(N, Bl, SCALES, dev) if "train" in legs else None
             except Exception as e:      # the headline forward numbers stand on their own
                 train = dict(error=f"{type(e).__name__}: {e}")
             # ---- BASELINE config 4 beside the metric's configuration (a short leg: driver-observed, not the headline) ----
-            if world == 1 and args.config == "c2" and not args.no_c4_leg and not args.no_side_legs:
+            if "c4" in legs:
                 try:
                     c4 = c4_leg(dev)
                 except Exception as e:
                     c4 = dict(error=f"{type(e).__name__}: {e}")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and "cpu" in legs:
         cpu = cpu_baseline(block_state, cfg)
 
     if rank == 0:
@@ -654,6 +694,7 @@ def main():
             "ms_per_step": round(ms_step, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": cfg["dtype"], "data": "synthetic",
+            "full": args.full, "full_legs": sorted(legs),
             "timed_regions": len(regions),
             "ms_per_step_min_max": [round(min(regions) / args.steps * 1e3, 4), round(max(regions) / args.steps * 1e3, 4)],
             "value_single_stream": None if single is None else round(Bl * args.steps / single, 1),

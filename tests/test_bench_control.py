@@ -134,3 +134,45 @@ def test_dump_outputs_float32_within_budget_same_sample(tmp_path, monkeypatch):
     assert all(np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)) for n in ("features.npy", "H.npy"))
     small = bench.dump_outputs(str(tmp_path / "c"), {"H": H[:4]})            # within budget: everything, as is
     assert small["scenes"] == 4 and np.array_equal(np.load(tmp_path / "c" / "H.npy"), H[:4].numpy())
+
+
+def _bench_args(*argv):
+    sys.path.insert(0, ROOT)
+    import bench
+    return bench, bench.parser().parse_args(list(argv))
+
+
+def test_plain_run_makes_no_side_measurement():
+    """Without --full a run ends with its timed steps: no leg, whatever else is asked, on one rank or several."""
+    for argv in (["--gpus", "1", "--steps", "5", "--warmup", "2"], ["--config", "c4"], ["--streams", "1"],
+                 ["--force-dist"], ["--dump-outputs", "d"], ["--no-graph"]):
+        bench, args = _bench_args(*argv)
+        assert args.full is False
+        for world in (1, 8):
+            assert bench.full_legs(args, world, twin=args.config == "c4") == frozenset()
+
+
+def test_full_run_makes_every_measurement_that_moved_behind_it():
+    """--full: what a run without arguments measured before the option existed, and the --no-* switches still drop
+    what they dropped."""
+    bench, args = _bench_args("--full")
+    assert bench.full_legs(args, 1, False) == {"single", "roofline", "agg_hbm", "parity", "modules", "train", "c4", "cpu"}
+    bench, args = _bench_args("--full", "--config", "c4")
+    assert bench.full_legs(args, 1, True) == {"single", "roofline", "agg_hbm", "parity", "modules", "cpu"}
+    bench, args = _bench_args("--full", "--no-cpu-baseline", "--no-side-legs", "--streams", "1")      # the profiling runs
+    assert bench.full_legs(args, 1, False) == {"single", "roofline", "agg_hbm"}
+    bench, args = _bench_args("--full", "--no-train-leg", "--no-c4-leg")
+    assert bench.full_legs(args, 1, False) == {"single", "roofline", "agg_hbm", "parity", "modules", "cpu"}
+    bench, args = _bench_args("--full", "--gpus", "8")
+    assert bench.full_legs(args, 8, False) == {"roofline", "agg_hbm"}
+    bench, args = _bench_args("--full", "--force-dist")
+    assert bench.full_legs(args, 1, False) == {"roofline", "agg_hbm", "parity", "modules", "train", "c4", "cpu"}
+
+
+def test_full_reaches_the_self_launched_ranks():
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--dry-launch"], capture_output=True, text=True,
+                       env=env, timeout=300)
+    assert r.returncode == 0, r.stderr
+    argv = json.loads(r.stdout.strip().splitlines()[-1])["launch"]
+    assert argv[argv.index(BENCH) + 1:] == ["--gpus", "2", "--full"]
