@@ -29,18 +29,12 @@ from typing import Iterator, List, Optional, Sequence, Tuple, Union
 import torch
 import torch.nn as nn
 
-from . import ops, weights
+from . import ops, route, weights
 from .weights import _param_key, _volatile, training_call  # noqa: F401  (cache policy, re-exported)
 
 Tensor = torch.Tensor
 _HDIM_EXTEND = 64      # model/MS_HGNN_batch.py:72,292
 _GUMBEL_TAU = 0.5      # model/MS_HGNN_batch.py:45
-# Beyond these N the stand-alone gather / scatter kernels (LDS-tiled, high occupancy) beat a per-lane scan of H rows /
-# a per-lane gather of N feature rows in the prologue of an MFMA kernel (latency-bound at 1-2 waves per SIMD; measured
-# again in round 2 at N = 50, B = 1024, bf16: typed MLP 390 -> 439 us against a 38-us gather launch, closing MLP
-# 54 -> 303 us against 71 + 56 us of scatter launches).
-_FUSED_GATHER_MAX_N = 16      # eo = H @ ori inside the typed MLP kernel
-_FUSED_SCATTER_MAX_N = 16     # cat(H^T feat, ori)/N inside the closing MLP
 
 
 def masks_apply(N: int) -> bool:
@@ -48,7 +42,7 @@ def masks_apply(N: int) -> bool:
     the form is switched on (`ops.set_incidence_form` / GN_INC_MASKS=1) and N lies where the stand-alone gather /
     scatter and the node->edge launch run and a 64-bit word holds a row (16 < N <= 64).  Elsewhere nobody asks for masks
     and no launch changes."""
-    return (ops.incidence_form() == "mask" and min(_FUSED_GATHER_MAX_N, _FUSED_SCATTER_MAX_N) < N <= ops.MASK_MAX_N)
+    return ops.incidence_form() == "mask" and route.masks_in_range(N)
 
 
 # node->edge pooling inside the edge kernel (inference); the parity tests clear it to compare against the node2edge launch
@@ -323,10 +317,6 @@ class _MessagePassing(nn.Module):
         return MSHGNNFunction.apply((self,), (H,), (noise_u,), h, *_plist(self))
 
 
-class _Closed(list):
-    """Outputs of closing MLPs that the aggregation launch applied itself."""
-
-
 def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor], Hs: Sequence, noises: Sequence,
                         outs: Sequence[Optional[Tensor]], traces=None, join=None, affinity=None,
                         fuse_closing: bool = False) -> List[Tuple[Tensor, Tensor]]:
@@ -338,6 +328,8 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     noises[i] is None (draw), a tensor / PhiloxNoise, or a list of nmp_layers of them; outs[i]
     optionally receives node_feat.  Returns [(node_feat, factors)] per module.  All modules must
     share nmp_layers and bottleneck_dim (they do in every caller of the reference).
+    Which launches the forward consists of and what each is asked to fuse is `route.message_passing_route`'s decision,
+    taken once per call from the sizes, the storage type and the per-call switches; the stages below follow it.
     `traces` (training): one `backward.ModuleTrace` per module, which receives the node features entering
     every round and the dist every round sampled — all the backward needs besides the inputs.
     `join`: called once after the first node stage has been launched and before anything reads Hs (a caller that
@@ -361,16 +353,22 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
         raise ValueError("grouped modules must share nmp_layers and bottleneck_dim")
     B, N = hs[0].shape[0], hs[0].shape[1]
     incs = [H if H is None or isinstance(H, ops.Incidence) else ops.Incidence(H) for H in Hs]
-    use_masks = masks_apply(N) and all(g is None or g.masks is not None for g in incs)
-    # every module's graph as the ops item tuples take it: (dense H or None, sym, masks where the step reads them)
-    # The pairwise graph is symmetric: edges (i,j) and (j,i) pool the same feature, meet the same typed
+    rt = route.message_passing_route(
+        N, tuple([(g is None, m.edge_types) for g, m in zip(incs, mods)]), twin=hs[0].dtype == torch.bfloat16,
+        training=traces is not None, matrix16=ops.BF16X6,
+        knobs=route.Knobs(_FUSE_POOL, ops.POOL_MAX_N, ops.node_form_enabled(),
+                          ops.incidence_form() == "mask" and all(g is None or g.masks is not None for g in incs)),
+        closing_asked=fuse_closing)
+    # every module's graph as the ops item tuples take it: the dense H (None: pairwise), sym, the masks where the step
+    # reads them.  The pairwise graph is symmetric: edges (i,j) and (j,i) pool the same feature, meet the same typed
     # MLP output and are summed into the same two nodes.  Its per-edge MLPs therefore run once per
     # unordered pair (N(N+1)/2 rows instead of N*N); only the Gumbel softmax runs per ordered edge.
-    graphs = [(None, True, None) if g is None else (g.H, False, g.masks if use_masks else None) for g in incs]
-    syms = [sy for _, sy, _ in graphs]
-    Es = [N * N if H is None else H.shape[1] for H, _, _ in graphs]   # ordered edges: the shape of noise and factors
+    dense = [None if g is None else g.H for g in incs]
+    syms = [g is None for g in incs]
+    masks = [g.masks if g is not None and rt.masks else None for g in incs]
+    Es = [N * N if H is None else H.shape[1] for H in dense]   # ordered edges: the shape of noise and factors
     if traces is not None:
-        for t, (_, _, mk) in zip(traces, graphs):
+        for t, mk in zip(traces, masks):
             t.masks = mk
     given = [_noise_iter(u) for u in noises]
 
@@ -382,41 +380,31 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
                 raise ValueError(f"noise_u: {nmp} uniform tensors of shape ({B},{Es[i]},{mods[i].edge_types}) needed")
         return _draw_uniform((B, Es[i], mods[i].edge_types), hs[i].device)
 
-    twin = hs[0].dtype == torch.bfloat16
-    if twin and traces is not None:
-        raise NotImplementedError("the bf16 twins are forward-only")
-    pair_A: List[Optional[Tensor]] = [None] * n     # per-node first layer of the typed MLP (pairwise groups)
-
-    def node2edge(xs: Sequence[Tensor], idx: int) -> List[Tensor]:
+    def node2edge(xs: Sequence[Tensor], idx: int) -> Tuple[List, List[Optional[Tensor]]]:
+        """-> per module the edge MLP's rows (an `edges` tensor or a PoolSpec) and the typed MLP's per-node first layer
+        A (None where the route does not form it)."""
         pks = [m._packed_n2e(idx) for m in mods]
         keep = [] if traces is not None else None
-        # the node rows entering this round also feed the typed aggregation MLP that closes it: for the pairwise
-        # graph its first layer is linear in the two nodes (eo = ori_i + ori_j) and runs once per NODE, in this
-        # same launch (fp32 path; the bf16 twin runs both layers per pair on the matrix cores instead)
-        specs = [((m.edge_aggregation_list[idx]._packed(), m.edge_aggregation_list[idx].edge_types)
-                  if (sy and not twin) else None) for m, sy in zip(mods, syms)]
+        # the node rows entering this round also feed the typed aggregation MLP that closes it: its first layer runs
+        # in this same launch where the route says so
+        aggs = [m.edge_aggregation_list[idx] for m in mods]
+        specs = [(a._packed(), a.edge_types) if r.first_layer else None for a, r in zip(aggs, rt.modules)]
         xpq, As = ops.node_stage_grouped([(x, pk) for x, pk in zip(xs, pks)], keep, specs,
                                          affinity if idx == 0 else None)
-        pair_A[:] = As
         if join is not None and idx == 0:
             join()       # the incidences were built on a forked stream beside the node stage (graph capture)
-        # Inference: the pooled edge rows feed only the edge MLP, so its kernel forms them itself (ops.PoolSpec) and
-        # `edges` never exists in HBM — always for the pairwise graph, for hyper modules up to ops.POOL_MAX_N nodes;
-        # larger hyper modules (and training, whose backward reads `edges`) keep the node2edge launch.
-        fuse = [_FUSE_POOL and traces is None and (twin or ops.BF16X6) and (sy or N <= ops.POOL_MAX_N) for sy in syms]
         edges: List = [None] * n
-        rest = [i for i in range(n) if not fuse[i]]
-        if rest:
-            for i, e in zip(rest, ops.node2edge_grouped([(xpq[i][0], xpq[i][1], graphs[i][0], pks[i]["w2"], pks[i]["b2"],
-                                                          *graphs[i][1:]) for i in rest])):
+        if rt.node2edge:
+            for i, e in zip(rt.node2edge, ops.node2edge_grouped([(xpq[i][0], xpq[i][1], dense[i], pks[i]["w2"], pks[i]["b2"],
+                                                                  syms[i], masks[i]) for i in rt.node2edge])):
                 edges[i] = e
-        for i in range(n):
-            if fuse[i]:
-                edges[i] = ops.PoolSpec(xpq[i][0], xpq[i][1], graphs[i][0], pks[i]["w2"], pks[i]["b2"], syms[i])
+        for i, r in enumerate(rt.modules):
+            if r.pool_in_edge_kernel:
+                edges[i] = ops.PoolSpec(xpq[i][0], xpq[i][1], dense[i], pks[i]["w2"], pks[i]["b2"], syms[i])
         if traces is not None:      # kept for the backward: nothing of this round is re-computed there
             for t, kd, (xp, pq), e in zip(traces, keep, xpq, edges):
                 t.n2e.append(dict(x1=kd["hid"], xp=xp, pq=pq, edges=e))
-        return edges
+        return edges, As
 
     def edge_mlp(stages, edges: Sequence[Tensor], want_dist: bool):
         # draws happen module by module, in the order given — the reference's RNG order per call site
@@ -429,52 +417,38 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
                 t.estage.append(kd)
         return res
 
-    def edge2node(edge_feats: Sequence[Tensor], oris: Sequence[Tensor], idx: int, closing=None) -> List[Tensor]:
-        """-> the inputs of the stage's closing MLPs (tensors / ScatterSpec / NodeAggSpec); with ``closing`` = [(packed
-        MLP, out or None)] per module and a launch shape that allows it, the closing MLPs' OUTPUTS (the aggregation launch
-        applies them itself) as a `_Closed` list."""
+    def edge2node(edge_feats: Sequence[Tensor], oris: Sequence[Tensor], As: Sequence[Optional[Tensor]], idx: int,
+                  closing: Sequence[Tuple[dict, Optional[Tensor]]]) -> Tuple[Optional[List[Tensor]], Optional[List]]:
+        """-> (None, the inputs of the stage's closing MLPs: tensors / ScatterSpec / NodeAggSpec), or (the closing MLPs'
+        OUTPUTS, None) where the route asks the aggregation launch to apply them itself — ``closing`` = (packed MLP, out
+        or None) per module — and its launch shape allows it."""
         aggs = [m.edge_aggregation_list[idx] for m in mods]
-        items = []
         # larger graphs: eo = H @ ori of every hyper module from ONE stand-alone gather launch
-        standalone = [i for i in range(n) if not syms[i] and N > _FUSED_GATHER_MAX_N]
-        eos = dict(zip(standalone, ops.agg_gather_grouped([(oris[i], *graphs[i]) for i in standalone]))) if standalone else {}
-        for i in range(n):
-            pk, K = aggs[i]._packed(), aggs[i].edge_types
-            if syms[i] and not twin and pair_A[i] is not None:
-                # pairwise: eo = ori_i + ori_j makes the typed MLP's first layer linear in the two nodes, so
-                # it ran once per node (N rows instead of N(N+1)/2 pairs) in this round's node stage; the
-                # pair form does the rest
-                src = ops.PairSpec(pair_A[i], node=(ops.node_form_enabled() and ops.BF16X6 and N <= ops.NODE_FORM_MAX_N
-                                                     and K <= ops.NODE_FORM_MAX_K and N <= _FUSED_SCATTER_MAX_N))
-            elif syms[i]:
-                # bf16 twin: both layers per NODE, one scene per workgroup (node form), or per unordered pair
-                src = ops.GatherSpec(oris[i], None, True,
-                                     node=twin and ops.node_form_enabled() and N <= ops.SCENE_FORM_MAX_N)
-            elif N <= _FUSED_GATHER_MAX_N:
-                src = ops.GatherSpec(oris[i], graphs[i][0], False)   # eo = H @ ori formed inside the kernel
-            else:
+        eos = dict(zip(rt.gather, ops.agg_gather_grouped([(oris[i], dense[i], syms[i], masks[i]) for i in rt.gather]))) if rt.gather else {}
+        items = []
+        for i, r in enumerate(rt.modules):
+            if r.first_layer:
+                src = ops.PairSpec(As[i], node=r.node_form)
+            elif r.source == route.EO:
                 src = eos[i]
-            items.append((src, edge_feats[i], pk, K))
-        if (fuse_closing and closing is not None and traces is None and not twin and N <= _FUSED_SCATTER_MAX_N
-                and len({(-1 if o is None else o.stride(-2)) for _, o in closing}) == 1):
+            else:       # eo formed inside the kernel: H @ ori, or the twins' ori_i + ori_j per node or per unordered pair
+                src = ops.GatherSpec(oris[i], dense[i], syms[i], node=r.node_form)
+            items.append((src, edge_feats[i], aggs[i]._packed(), aggs[i].edge_types))
+        if rt.ask_closing and len({(-1 if o is None else o.stride(-2)) for _, o in closing}) == 1:
             closed = ops.agg_mlp_closing(items, [(pk2, o, ori) for (pk2, o), ori in zip(closing, oris)])
             if closed is not None:
-                return _Closed(closed)
+                return closed, None
         feats = ops.agg_mlp_grouped(items)
-
-        def node_item(it) -> bool:
-            return isinstance(it[0], (ops.PairSpec, ops.GatherSpec)) and it[0].node
-        if N <= _FUSED_SCATTER_MAX_N:
-            # cat(H^T feat, ori) / N is formed inside the MLP kernel that consumes it (node form: H^T feat is what the
-            # aggregation kernel wrote)
-            return [ops.NodeAggSpec(f, o) if node_item(it) else ops.ScatterSpec(f, H, o, sy)
-                    for f, (H, sy, _), o, it in zip(feats, graphs, oris, items)]
         # larger graphs: one stand-alone scatter launch for the modules whose aggregation wrote per-edge features
-        rest = [i for i in range(n) if not node_item(items[i])]
-        scat = dict(zip(rest, ops.agg_scatter_grouped([(feats[i], graphs[i][0], oris[i], *graphs[i][1:]) for i in rest]))) if rest else {}
-        return [scat[i] if i in scat else ops.NodeAggSpec(feats[i], oris[i]) for i in range(n)]
+        scat = dict(zip(rt.scatter, ops.agg_scatter_grouped([(feats[i], dense[i], oris[i], syms[i], masks[i]) for i in rt.scatter]))) if rt.scatter else {}
+        # cat(H^T feat, ori) / N is formed inside the MLP kernel that consumes it (node form: H^T feat is what the
+        # aggregation kernel wrote), or is the scatter launch's output
+        return None, [ops.NodeAggSpec(feats[i], oris[i]) if r.closing_input == route.NODE_AGG else
+                      ops.ScatterSpec(feats[i], dense[i], oris[i], syms[i]) if r.closing_input == route.SCATTER_SPEC else
+                      scat[i] for i, r in enumerate(rt.modules)]
 
-    res = edge_mlp([m.nmp_mlp_start for m in mods], node2edge(hs, 0), True)
+    edges, As = node2edge(hs, 0)
+    res = edge_mlp([m.nmp_mlp_start for m in mods], edges, True)
     edge_feats, factors = [r[0] for r in res], [r[1] for r in res]
     if traces is not None:
         for t, r in zip(traces, res):
@@ -483,9 +457,10 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     for l in range(2 * (nmp - 1)):
         stages = [m.nmp_mlps[l] for m in mods]
         if l % 2 == 0:
-            agg = edge2node(edge_feats, node_feats, idx, [(m._packed_mlp2(st), None) for m, st in zip(mods, stages)])
+            closed, agg = edge2node(edge_feats, node_feats, As, idx,
+                                    [(m._packed_mlp2(st), None) for m, st in zip(mods, stages)])
             keep = [] if traces is not None else None
-            node_feats = (list(agg) if isinstance(agg, _Closed) else
+            node_feats = (closed if closed is not None else
                           ops.mlp2_grouped([(a, m._packed_mlp2(st), None) for a, m, st in zip(agg, mods, stages)], keep))
             idx += 1
             if traces is not None:
@@ -493,14 +468,16 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
                     t.xs.append(x)
                     t.tails.append(kd)
         else:
-            res = edge_mlp(stages, node2edge(node_feats, idx), traces is not None)
+            edges, As = node2edge(node_feats, idx)
+            res = edge_mlp(stages, edges, traces is not None)
             edge_feats = [r[0] for r in res]
             if traces is not None:
                 for t, r in zip(traces, res):
                     t.dists.append(r[1])
-    agg = edge2node(edge_feats, node_feats, idx, [(m._packed_mlp2(m.nmp_mlp_end), o) for m, o in zip(mods, outs)])
-    if isinstance(agg, _Closed):
-        return list(zip(list(agg), factors))
+    closed, agg = edge2node(edge_feats, node_feats, As, idx,
+                            [(m._packed_mlp2(m.nmp_mlp_end), o) for m, o in zip(mods, outs)])
+    if closed is not None:
+        return list(zip(closed, factors))
     ends = [(a, m._packed_mlp2(m.nmp_mlp_end), o) for a, m, o in zip(agg, mods, outs)]
     # the last MLP writes in place when `out` is given; grouped when every group has the same stride
     strides = {(-1 if o is None else o.stride(-2)) for o in outs}

@@ -17,6 +17,8 @@ import torch
 
 from . import _lib
 from ._lib import _P, addr, check, load, stream_handle
+# the kernel limits live beside the forward's route, which reads them without loading torch or the library
+from .route import MASK_MAX_N, NODE_FORM_MAX_K, NODE_FORM_MAX_N, POOL_KERNEL_MAX_N, SCENE_FORM_MAX_N  # noqa: F401
 
 Tensor = torch.Tensor
 FEAT = 64
@@ -74,7 +76,6 @@ _AFFINITY_TAIL = os.environ.get("GN_AFFINITY_TAIL", "1") != "0"
 # fp32 H (B,E,N) — or "mask" — 64-bit member words (`IncidenceMasks`), inference, 16 < N <= 64.  None: not set by
 # `set_incidence_form`, the environment decides per call (GN_INC_MASKS=1: mask).
 _INCIDENCE_FORM: Optional[str] = None
-MASK_MAX_N = 64        # one 64-bit word per hyperedge / node
 
 
 def incidence_form() -> str:
@@ -557,13 +558,12 @@ class PoolSpec:
         self.xp, self.pq, self.H, self.w2, self.b2, self.sym = xp, pq, H, w2, b2, bool(sym)
 
 
-# Hyper modules: largest N whose pooling the edge kernel may form itself (the kernel's bound is 16: a row's incidence
-# stays in registers), so that an inference forward at N <= 16 has no node2edge launch.  The edge kernel stages a
-# workgroup's scenes in LDS (pq, then x', through one buffer); groups that fit no stage (scale = N: one hyperedge per
-# scene) pool from global memory with one live row block per workgroup ("Edge-kernel prologue").
-POOL_KERNEL_MAX_N = 16
-# the hyper modules' limit run_message_passing applies: all the kernel covers (the parity tests lower it to 0 to compare
-# against the node2edge launch)
+# Hyper modules: POOL_KERNEL_MAX_N is the largest N whose pooling the edge kernel may form itself (the kernel's bound is
+# 16: a row's incidence stays in registers), so that an inference forward at N <= 16 has no node2edge launch.  The edge
+# kernel stages a workgroup's scenes in LDS (pq, then x', through one buffer); groups that fit no stage (scale = N: one
+# hyperedge per scene) pool from global memory with one live row block per workgroup ("Edge-kernel
+# prologue").  POOL_MAX_N is the hyper modules' limit the engine hands to its route per call: all the kernel covers (the
+# parity tests lower it to 0 to compare against the node2edge launch)
 POOL_MAX_N = POOL_KERNEL_MAX_N
 
 
@@ -716,9 +716,6 @@ class GatherSpec:
         self.ori, self.H, self.sym, self.node = ori, H, bool(sym), bool(node)
 
 
-SCENE_FORM_MAX_N = 64
-
-
 class PairSpec:
     """Pair form of the typed MLP for the pairwise graph: A (B,N,K*128) = node_linear(ori) holds the first
     layer per node; rows are the N(N+1)/2 unordered pairs.  Uses pk["W2t"] instead of pk["W"].
@@ -730,10 +727,6 @@ class PairSpec:
 
     def __init__(self, A: Tensor, node: bool = False):
         self.A, self.node = A, bool(node)
-
-
-NODE_FORM_MAX_N = 16
-NODE_FORM_MAX_K = 12
 
 
 def node_form_enabled() -> bool:

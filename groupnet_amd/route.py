@@ -1,0 +1,108 @@
+"""The route of a message-passing forward: which launches it consists of and what each is asked to fuse, decided in one
+pure function that `MS_HGNN_batch.run_message_passing` follows.
+
+A leaf module: no torch, no library, no environment.  The launchers' own decisions (work shapes, kernels, whether an
+aggregation launch takes the closing stage it was asked for) stay in their plan functions ("Launch plan").
+"""
+from __future__ import annotations
+
+import functools
+from dataclasses import dataclass
+from typing import NamedTuple, Tuple
+
+# Kernel limits (`ops` validates its items against them and re-exports them under these names)
+POOL_KERNEL_MAX_N = 16      # hyper pooling inside the edge kernel: a row's incidence stays in registers
+NODE_FORM_MAX_N = 16        # node form of the pair form (fp32 storage)
+NODE_FORM_MAX_K = 12
+SCENE_FORM_MAX_N = 64       # the twins' scene form
+MASK_MAX_N = 64             # one 64-bit word per hyperedge / node
+
+# The engine's own limits.  Beyond these N the stand-alone gather / scatter kernels (LDS-tiled, high occupancy) beat a
+# per-lane scan of H rows / a per-lane gather of N feature rows in the prologue of an MFMA kernel (latency-bound at 1-2
+# waves per SIMD; measured again in round 2 at N = 50, B = 1024, bf16: typed MLP 390 -> 439 us against a 38-us gather
+# launch, closing MLP 54 -> 303 us against 71 + 56 us of scatter launches).
+_FUSED_GATHER_MAX_N = 16      # eo = H @ ori inside the typed MLP kernel
+_FUSED_SCATTER_MAX_N = 16     # cat(H^T feat, ori)/N inside the closing MLP
+
+# The aggregation's source (`ModuleRoute.source`)
+PAIR = "pair"                   # ops.PairSpec: the pairwise graph's pair form on the per-node first layer A
+PAIR_NODE = "pair-node"         # ... in its node form
+SCENE = "scene"                 # ops.GatherSpec(node=True): the twins' scene form of the pairwise graph
+TWIN_PAIR = "twin-pair"         # ops.GatherSpec: the twins' per-pair gather of the pairwise graph
+FUSED_GATHER = "fused-gather"   # ops.GatherSpec: eo = H @ ori of a hyper module formed inside the kernel
+EO = "eo"                       # the eo tensor of the stand-alone gather launch
+# What feeds the closing MLP (`ModuleRoute.closing_input`)
+NODE_AGG = "node-agg"           # ops.NodeAggSpec: the aggregation wrote H^T feat per node
+SCATTER_SPEC = "scatter-spec"   # ops.ScatterSpec: cat(H^T feat, ori) / N formed inside the closing MLP's kernel
+SCATTER = "scatter"             # the output of the stand-alone scatter launch
+
+
+class Knobs(NamedTuple):
+    """Everything that can change per call."""
+    fuse_pool: bool         # node->edge pooling inside the edge kernel (MS_HGNN_batch._FUSE_POOL)
+    pool_max_n: int         # ... of a hyper module up to this N (ops.POOL_MAX_N)
+    node_form: bool         # ops.node_form_enabled()
+    masked: bool            # the mask form is on (ops.incidence_form()) and every hyper module came with its masks
+
+
+@dataclass(frozen=True)
+class ModuleRoute:
+    pool_in_edge_kernel: bool   # node->edge pooling: ops.PoolSpec in the edge kernel, else the node2edge launch
+    first_layer: bool           # the node stage forms the typed MLP's per-node first layer A for this module
+    source: str
+    node_form: bool             # ... is PAIR_NODE or SCENE: the aggregation writes H^T feat per node
+    closing_input: str
+
+
+@dataclass(frozen=True)
+class Route:
+    modules: Tuple[ModuleRoute, ...]
+    node2edge: Tuple[int, ...]      # the modules that share the node2edge launch (empty: no such launch) ...
+    gather: Tuple[int, ...]         # ... the stand-alone gather launch ...
+    scatter: Tuple[int, ...]        # ... and the stand-alone scatter launch
+    masks: bool                     # those three launches read the hyper modules' masks (and a training step keeps them)
+    ask_closing: bool               # ask the aggregation launch's plan to take the closing MLP (ops.agg_mlp_closing)
+
+
+def masks_in_range(N: int) -> bool:
+    """N lies where the stand-alone gather / scatter and the node->edge launch run and a 64-bit word holds a row."""
+    return min(_FUSED_GATHER_MAX_N, _FUSED_SCATTER_MAX_N) < N <= MASK_MAX_N
+
+
+@functools.lru_cache(maxsize=None)
+def message_passing_route(N: int, modules: Tuple[Tuple[bool, int], ...], *, twin: bool, training: bool, matrix16: bool,
+                          knobs: Knobs, closing_asked: bool) -> Route:
+    """The route of one forward over N agents.  modules: (pairwise, K edge types) per module in launch order; twin: bf16
+    storage; training: the forward keeps what a backward reads; matrix16: the 16-bit-core weight images are in use;
+    closing_asked: the caller would like the aggregation launch to apply the closing MLP."""
+    if twin and training:
+        raise NotImplementedError("the bf16 twins are forward-only")
+    mods = []
+    for pairwise, K in modules:
+        # Inference: the pooled edge rows feed only the edge MLP, so its kernel forms them itself and `edges` never
+        # exists in HBM — always for the pairwise graph, for hyper modules up to pool_max_n nodes; larger hyper modules
+        # (and training, whose backward reads `edges`) keep the node2edge launch.
+        pool = knobs.fuse_pool and not training and (twin or matrix16) and (pairwise or N <= knobs.pool_max_n)
+        # Pairwise, fp32 storage: eo = ori_i + ori_j makes the typed MLP's first layer linear in the two nodes, so it
+        # runs once per NODE, in the round's node stage, and the pair form does the rest.  The twins run both layers on
+        # the matrix cores: per node, one scene per workgroup (scene form), or per unordered pair.
+        first_layer = pairwise and not twin
+        if first_layer:
+            node = (knobs.node_form and matrix16 and N <= NODE_FORM_MAX_N and K <= NODE_FORM_MAX_K
+                    and N <= _FUSED_SCATTER_MAX_N)
+            source = PAIR_NODE if node else PAIR
+        elif pairwise:
+            node = knobs.node_form and N <= SCENE_FORM_MAX_N
+            source = SCENE if node else TWIN_PAIR
+        else:
+            node = False
+            source = FUSED_GATHER if N <= _FUSED_GATHER_MAX_N else EO
+        closing_input = NODE_AGG if node else (SCATTER_SPEC if N <= _FUSED_SCATTER_MAX_N else SCATTER)
+        mods.append(ModuleRoute(pool, first_layer, source, node, closing_input))
+    which = lambda pred: tuple(i for i, m in enumerate(mods) if pred(m))
+    return Route(modules=tuple(mods),
+                 node2edge=which(lambda m: not m.pool_in_edge_kernel),
+                 gather=which(lambda m: m.source == EO),
+                 scatter=which(lambda m: m.closing_input == SCATTER),
+                 masks=knobs.masked and masks_in_range(N),
+                 ask_closing=closing_asked and not training and not twin and N <= _FUSED_SCATTER_MAX_N)

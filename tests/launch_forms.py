@@ -17,9 +17,9 @@ import torch
 from oracle import ms_hgnn_oracle as O
 
 K_PAIR, K_HYPER = 6, 10          # edge types (MS_HGNN_batch.py: MS_HGNN_oridinary / MS_HGNN_hyper)
-NODE_FORM_MAX_N, NODE_FORM_MAX_K = 16, 12      # ops.NODE_FORM_MAX_N / NODE_FORM_MAX_K
-SCENE_FORM_MAX_N = 64                          # ops.SCENE_FORM_MAX_N
-FUSED_MAX_N = 16                 # MS_HGNN_batch._FUSED_GATHER_MAX_N / _FUSED_SCATTER_MAX_N / ops.POOL_MAX_N
+NODE_FORM_MAX_N, NODE_FORM_MAX_K = 16, 12      # route.NODE_FORM_MAX_N / NODE_FORM_MAX_K (ops re-exports the kernel limits)
+SCENE_FORM_MAX_N = 64                          # route.SCENE_FORM_MAX_N
+FUSED_MAX_N = 16                 # route._FUSED_GATHER_MAX_N / _FUSED_SCATTER_MAX_N / ops.POOL_MAX_N
 RB2_MIN_PAIRS = 2048             # gn_mlp_mfma.hip rb2_min_pairs() without the test knob
 GS_MIN_WGS = 2048                # gn_graph.hip kGsMinWgs
 GS_LDS_BUDGET = 128 * 1024       # gn_graph.hip kLdsBudget
@@ -135,15 +135,15 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
     for name, s in mods:
         if s is None:
             E, K = pair_count(N), K_PAIR
-            # run_message_passing.edge2node: PairSpec(node=BF16X6 and N <= NODE_FORM_MAX_N ...) on fp32 storage,
-            # GatherSpec(node=N <= SCENE_FORM_MAX_N) on the twins (ops.node_form_enabled() is on by default)
+            # route.message_passing_route: the pair form's node form (the 16-bit-core images, N <= NODE_FORM_MAX_N ...) on
+            # fp32 storage, the scene form (N <= SCENE_FORM_MAX_N) on the twins (ops.node_form_enabled() is on by default)
             node = (N <= SCENE_FORM_MAX_N) if twin else (xm and N <= NODE_FORM_MAX_N and K <= NODE_FORM_MAX_K)
         else:
             E, K, node = (1 if s == N else N), K_HYPER, False
         rows = B * E
         groups.append(dict(name=name, E=E, K=K, rows=rows, node_form=node, wpr=1 if node else agg_wpr(rows, K), spw=0))
     hyp = [g for g in groups if g["name"] != "pair"]
-    # ops.closing_fusable + run_message_passing.edge2node (and agg_launch's own checks): fp32 results on the 16-bit cores,
+    # ops.closing_fusable + the route's `ask_closing` (and agg_launch's own checks): fp32 results on the 16-bit cores,
     # N <= 16, the pairwise group in its node form, every hyper group with E <= 16 below 768 row blocks
     fused = (block and with_pair and not training and not twin and xm and N <= FUSED_MAX_N and groups[0]["node_form"]
              and all(g["E"] <= 16 and cdiv(g["rows"], 32) < 768 and not (cdiv(g["rows"], 32) < 128 and g["K"] < 4)
@@ -184,7 +184,7 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
             # the fp32 kernels: the 4-waves-per-block split kernel only without a fused scatter (N > 16)
             mlp2 = "mlp2_split_kernel" if (b32 * n <= 1024 and N > FUSED_MAX_N) else "mlp2_kernel"
     # node -> edge pooling of the hyper modules (gn_graph.hip node2edge_launch): launched for training, the fp32 cores and
-    # N > POOL_MAX_N (run_message_passing.node2edge `fuse`); row form when `maxE >= 24 || hyper_rows >= 49152`
+    # N > POOL_MAX_N (the route's `node2edge` launch); row form when `maxE >= 24 || hyper_rows >= 49152`
     n2e = None
     if hyp and (training or not xm or N > FUSED_MAX_N):
         hyper_rows = sum(g["rows"] for g in hyp)
@@ -195,7 +195,7 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
         Emax, nh = max(g["E"] for g in hyp), len(hyp)
         per_scene = N * 64 * 4 + Emax * N * 4
         gather_spw = gs_scenes_per_wg(per_scene, B, nh) if per_scene <= GS_LDS_BUDGET else 1
-    # stand-alone scatter for N > 16 (run_message_passing.edge2node): exactly the groups whose aggregation wrote per-edge
+    # stand-alone scatter for N > 16 (the route's `scatter` launch): exactly the groups whose aggregation wrote per-edge
     # features, i.e. that are not in node form
     scatter = None
     rest = [g for g in groups if not g["node_form"]]
@@ -306,9 +306,9 @@ PLACEHOLDER = 4096      # a 16-aligned non-NULL "device address": a plan query t
 
 def launch_descriptors(B: int, N: int, scales: Sequence[int], precision: str = "f16x3", dtype: str = "fp32",
                        training: bool = False, block: bool = True, with_pair: bool = True) -> Dict:
-    """The C-ABI descriptor arrays `run_message_passing` passes for the last round of such a forward (arguments as
-    `expected_forms`), with its node-form, PoolSpec and closing decisions as `expected_forms` states them and PLACEHOLDER
-    for every device address.  -> {"twin", "edge": arr, "agg": arr (closing MLP in a launch of its own), "agg_closing": arr
+    """The C-ABI descriptor arrays the engine passes for the last round of such a forward (arguments as `expected_forms`),
+    with the node-form, PoolSpec and closing decisions as `expected_forms` states them and PLACEHOLDER for every device
+    address (tests/test_route_cpu.py holds `route.message_passing_route`, which the engine follows, against them).  -> {"twin", "edge": arr, "agg": arr (closing MLP in a launch of its own), "agg_closing": arr
     (the closing stage in the aggregation launch), "mlp2": (arr, rows, din, dh, dout, ldy, N, divisor), "n2e": arr or None,
     "gather": arr or None, "scatter": arr or None}; the group order is that of expected_forms' "groups"."""
     from groupnet_amd import _lib as L
@@ -321,7 +321,7 @@ def launch_descriptors(B: int, N: int, scales: Sequence[int], precision: str = "
     groups = forms["groups"]
     n = len(groups)
     small = N <= FUSED_MAX_N
-    pool = not training and xm                      # run_message_passing.node2edge `fuse`, before the N limit of hyper groups
+    pool = not training and xm                      # pooling in the edge kernel (PoolSpec), before the N limit of hyper groups
     edge, agg, aggc, mlp2, n2e, gather, scatter = [], [], [], [], [], [], []
     for g in groups:
         pair, E, K, rows = g["name"] == "pair", g["E"], g["K"], g["rows"]
