@@ -207,6 +207,8 @@ class edge_aggregation(nn.Module):
         super().__init__()
         if input_dim != 64:
             raise NotImplementedError("HIP aggregation kernels are specialised to 64-wide features")
+        if not 1 <= edge_types <= 16:
+            raise NotImplementedError("edge_types must be in 1..16")      # GN_MAX_TYPES (include/groupnet_hip.h)
         self.edge_types = edge_types
         self.dict_dim = input_dim
         self.agg_mlp = nn.ModuleList(MLP(input_dim=input_dim, output_dim=input_dim, hidden_size=(128,))

@@ -102,8 +102,9 @@ class GraphedPastEncoder:
         self.enc, self.B, self.N, self.seed = enc, B, N, int(seed)
         self.x_in = torch.zeros((B * N, enc._length, enc.input_fc.in_features), dtype=torch.float32, device=self.device)
         self.counter = torch.zeros(1, dtype=torch.int64, device=self.device)
-        E = [1 if m.scale == N else N for m in (getattr(enc, n) for n in enc._hyper_names)]
-        self.draws_per_step = B * N * N * enc.interaction.edge_types + sum(B * e * 10 for e in E)
+        hypers = [getattr(enc, n) for n in enc._hyper_names]
+        self.draws_per_step = B * N * N * enc.interaction.edge_types + sum(
+            B * (1 if m.scale == N else N) * m.edge_types for m in hypers)
         self.graph = torch.cuda.CUDAGraph()
         prev = (_mods._NoiseState.mode, _mods._NoiseState.seed, _mods._NoiseState.offset, _mods._NoiseState.counter)
         try:

@@ -110,8 +110,8 @@ class MultiScaleHGNN(nn.Module):
     def noise_shapes(self, B: int, N: int) -> List[Tuple[int, int, int]]:
         """(B,E,K) of the uniforms each module draws per message-passing round, pairwise first."""
         out = [(B, N * N, self.interaction.edge_types)]
-        for s in self.hyper_scales:
-            out.append((B, 1 if s == N else N, 10))
+        for s, m in zip(self.hyper_scales, self.interaction_hyper):
+            out.append((B, 1 if s == N else N, m.edge_types))
         return out
 
     def forward(self, f: Tensor, noise_u: Optional[Sequence] = None, advance=None

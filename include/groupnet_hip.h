@@ -81,7 +81,13 @@ typedef void* gn_stream_t; /* hipStream_t */
 #define GN_ERR_LDS -6         /* the problem does not fit the 160 KiB LDS tile of the kernel */
 
 #define GN_FEAT 64            /* h_dim == hdim_extend == 64 (MS_HGNN_batch.py:72,292) */
-#define GN_MAX_TYPES 16       /* edge types K <= 16 (reference: 6 pairwise, 10 hyper) */
+#define GN_MAX_TYPES 16       /* edge types of the typed aggregation, 1 <= K <= 16 (reference: 6 pairwise, 10 hyper): its
+                               * per-node first layer and its weight images are laid out per type, up to 16 of them.
+                               * The edge head (gn_edge_mlp_gumbel_*) stops at K = 15: logits and factor share ONE 16-row
+                               * output tile, rows 0..K-1 the logits and row K the factor pre-activation, so K + 1 <= 16.
+                               * A module therefore has 1..15 types; K = 16 exists for the aggregation stage alone.
+                               * The node form of the pairwise aggregation (node_form with A) stops at K = 12: the type
+                               * weights of a row block, 32 x (16 K + 1) floats, share the LDS with its stage. */
 #define GN_MAX_SCALES 8
 
 /* Pitched device-to-device copy of `rows` rows of `width_bytes` (multiples of 16 bytes, 16-byte aligned): the column block of
@@ -313,7 +319,8 @@ int gn_node2edge_masks_bf16(const gn_n2e_group_t* groups, const unsigned long lo
  *   consumes them:  Wi0/Wi1: T0 T1 S0 T2 S1 T3 S2 S3 (S_t = Wi1 tiles (0,t),(1,t): 8 steps);
  *   Wd0/Wd1: T0 T1 S0 T2 S1 ... T7 S6 S7 (S_t = Wd1 tile (0,t): 4 steps); then 8 steps of padding;
  * bias = [128 | 64 | 256 | 32] in the same order (bd1: K logits biases, then the factor bias, zeros).
- * edges (rows,64), U (rows,K) uniforms in [0,1) -> edge_feat (rows,K), dist (rows,K).  K <= 15.
+ * edges (rows,64), U (rows,K) uniforms in [0,1) -> edge_feat (rows,K), dist (rows,K).  1 <= K <= 15 (row K of the
+ *   16-row tile of Wd1 is the factor head: see GN_MAX_TYPES); anything else is GN_ERR_SHAPE.
  * U == NULL: the uniforms are generated inside the kernel — element row*K + k is element
  * philox_offset (+ *offset_dev if not NULL) + row*K + k of the Philox stream `seed`, exactly what
  * gn_philox_uniform_f32 would have written into U.

@@ -273,14 +273,16 @@ def _message_passing(state: State, h: Tensor, H: Tensor, U_list: List[Tensor], n
     return node_feat, factors
 
 
-def noise_shapes(B: int, N: int, scale: Optional[int], nmp_layers: int = 1) -> List[Tuple[int, int, int]]:
+def noise_shapes(B: int, N: int, scale: Optional[int], nmp_layers: int = 1, edge_types: Optional[int] = None
+                 ) -> List[Tuple[int, int, int]]:
     """Shapes of the uniform draws one forward makes, in order: one (B,E,K) per
-    ``MLP_dict_softmax`` call.  ``scale=None`` means the pairwise module."""
+    ``MLP_dict_softmax`` call.  ``scale=None`` means the pairwise module; ``edge_types``: K of a
+    module built with another number of types than the reference's 6 / 10."""
     if scale is None:
         E, K = N * N, EDGE_TYPES_PAIRWISE
     else:
         E, K = (1 if scale == N else N), EDGE_TYPES_HYPER
-    return [(B, E, K)] * nmp_layers
+    return [(B, E, K if edge_types is None else int(edge_types))] * nmp_layers
 
 
 def ms_hgnn_pairwise_forward(state: State, h: Tensor, U_list: List[Tensor], nmp_layers: int = 1,

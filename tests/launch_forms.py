@@ -113,17 +113,30 @@ def assert_scatter_plan(sf: Dict, plan, where) -> None:
             sf["kernel"], sf["grid"] + (1,), sf["G"], sf["Emax"], sf["dyn_lds"]), (where, sf)
 
 
+def module_types(scales: Sequence[int], with_pair: bool = True, types: Optional[Sequence[int]] = None) -> List[int]:
+    """Edge types K per module in group order (the pairwise module first where present): `types` as given — one K per
+    module — or the reference's 6 / 10."""
+    n = int(with_pair) + len(scales)
+    if types is None:
+        return ([K_PAIR] if with_pair else []) + [K_HYPER] * len(scales)
+    assert len(types) == n, f"types: one K per module ({n}), got {tuple(types)}"
+    return [int(k) for k in types]
+
+
 def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x3", dtype: str = "fp32",
-                   training: bool = False, block: bool = True, with_pair: bool = True) -> Dict:
+                   training: bool = False, block: bool = True, with_pair: bool = True,
+                   types: Optional[Sequence[int]] = None) -> Dict:
     """The forms the launchers pick for one forward of the multiscale block (`block=True`, latency form: closing fused
     where allowed) or of the same modules launched one by one through the module API (`block=False`: no fused closing).
     precision: ops.precision() of the fp32 entry points ('f16x3' | 'bf16x6' | 'fp32'); dtype: 'fp32' | 'bf16' storage.
 
     Returns {"groups": [per module: {"name", "E", "K", "rows", "node_form", "wpr", "spw"}], "fused_closing",
-    "agg_kernel", "agg_wgs", "agg_grid" (of the launch of the groups that are not in the twins' scene form), "scene_grid",
+    "agg_kernel", "agg_wgs", "agg_grid" (of the launch of the groups that are not in the twins' scene form), "agg_pos"
+    (per module its position in that launch, -1 for the scene form), "scene_grid",
     "mlp2", "n2e", "gather_spw", "scatter" (scatter_forms of the stand-alone scatter)}; "scene_grid" / "mlp2" / "n2e" /
     "gather_spw" / "scatter" are None where that launch does not run.
     with_pair=False: the hyper modules alone (one MS_HGNN_hyper through the module API).
+    types: the edge types K of every module in group order, (K_pair, K_hyper, ...) (default: 6 and 10).
 
     These rules restate the launchers' plan functions independently of them: tests/test_launch_plan_cpu.py holds the two
     against each other through the library's plan queries (no GPU), and a kernel trace of tests/test_launch_forms_gpu.py's
@@ -132,22 +145,22 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
     xm = twin or precision != "fp32"            # bf16-core images (ops.BF16X6) or the twins
     mods = ([("pair", None)] if with_pair else []) + [(f"hyper{s}", s) for s in scales]
     groups = []
-    for name, s in mods:
+    for (name, s), Km in zip(mods, module_types(scales, with_pair, types)):
         if s is None:
-            E, K = pair_count(N), K_PAIR
+            E, K = pair_count(N), Km
             # route.message_passing_route: the pair form's node form (the 16-bit-core images, N <= NODE_FORM_MAX_N ...) on
             # fp32 storage, the scene form (N <= SCENE_FORM_MAX_N) on the twins (ops.node_form_enabled() is on by default)
             node = (N <= SCENE_FORM_MAX_N) if twin else (xm and N <= NODE_FORM_MAX_N and K <= NODE_FORM_MAX_K)
         else:
-            E, K, node = (1 if s == N else N), K_HYPER, False
+            E, K, node = (1 if s == N else N), Km, False
         rows = B * E
         groups.append(dict(name=name, E=E, K=K, rows=rows, node_form=node, wpr=1 if node else agg_wpr(rows, K), spw=0))
     hyp = [g for g in groups if g["name"] != "pair"]
     # ops.closing_fusable + the route's `ask_closing` (and agg_launch's own checks): fp32 results on the 16-bit cores,
-    # N <= 16, the pairwise group in its node form, every hyper group with E <= 16 below 768 row blocks
+    # N <= 16, the pairwise group in its node form, every hyper group with E <= 16 and more than one wave per row block
+    # (below 768 row blocks; K >= 4 below 128 row blocks, K >= 2 from there on)
     fused = (block and with_pair and not training and not twin and xm and N <= FUSED_MAX_N and groups[0]["node_form"]
-             and all(g["E"] <= 16 and cdiv(g["rows"], 32) < 768 and not (cdiv(g["rows"], 32) < 128 and g["K"] < 4)
-                     for g in hyp))
+             and all(g["E"] <= 16 and g["wpr"] > 1 for g in hyp))
     if fused:
         for g in hyp:       # agg_launch: `spw = (128 / wpr) / E`, capped at node_cap / N nodes
             g["spw"] = min((128 // g["wpr"]) // g["E"], (160 if g["E"] == 1 else 64) // N)
@@ -165,6 +178,11 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
             wgs.append(cdiv(B, g["spw"]))
         else:
             wgs.append(cdiv(cdiv(g["rows"], 32) * g["wpr"], 4))
+    # the groups' order inside that launch (agg_plan's `cost`): longest waves first — types x layers of a wave's share,
+    # the node form last —, equal costs in the caller's order
+    cost = lambda g: 1 if g["node_form"] else g["K"] * (1 if g["name"] == "pair" and not twin else 2) * 4 // g["wpr"]
+    by_cost = sorted(range(len(main)), key=lambda i: -cost(main[i]))
+    agg_pos = [-1] * (len(groups) - len(main)) + [by_cost.index(i) for i in range(len(main))]
     if twin and sum(cdiv(cdiv(g["rows"], 32), 2) for g in main) >= RB2_MIN_PAIRS:
         agg_kernel = "agg_rb2_kernel"
         wgs = [cdiv(cdiv(g["rows"], 32), 8) for g in main]
@@ -202,6 +220,7 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
     if rest and N > FUSED_MAX_N:
         scatter = scatter_forms(B, N, [dict(E=g["E"], sym=g["name"] == "pair", H=g["name"] != "pair") for g in rest])
     return dict(scatter=scatter, groups=groups, fused_closing=fused, agg_kernel=agg_kernel, agg_wgs=sum(wgs), agg_grid=grid,
+                agg_pos=agg_pos,
                 scene_grid=scene_grid, mlp2=mlp2, n2e=n2e, gather_spw=gather_spw)
 
 
@@ -305,7 +324,8 @@ PLACEHOLDER = 4096      # a 16-aligned non-NULL "device address": a plan query t
 
 
 def launch_descriptors(B: int, N: int, scales: Sequence[int], precision: str = "f16x3", dtype: str = "fp32",
-                       training: bool = False, block: bool = True, with_pair: bool = True) -> Dict:
+                       training: bool = False, block: bool = True, with_pair: bool = True,
+                       types: Optional[Sequence[int]] = None) -> Dict:
     """The C-ABI descriptor arrays the engine passes for the last round of such a forward (arguments as `expected_forms`),
     with the node-form, PoolSpec and closing decisions as `expected_forms` states them and PLACEHOLDER for every device
     address (tests/test_route_cpu.py holds `route.message_passing_route`, which the engine follows, against them).  -> {"twin", "edge": arr, "agg": arr (closing MLP in a launch of its own), "agg_closing": arr
@@ -317,7 +337,7 @@ def launch_descriptors(B: int, N: int, scales: Sequence[int], precision: str = "
     xm = twin or precision != "fp32"
     X = P if xm else 0                              # bf16-core images
     Hh = P if (precision == "f16x3" and not twin) else 0      # fp16 two-part images
-    forms = expected_forms(B, N, scales, precision, dtype, training, block, with_pair)
+    forms = expected_forms(B, N, scales, precision, dtype, training, block, with_pair, types)
     groups = forms["groups"]
     n = len(groups)
     small = N <= FUSED_MAX_N
@@ -374,6 +394,7 @@ def assert_plans_match(forms: Dict, agg, mlp2, n2e, gather, where, scatter=False
     assert (name(agg), sum(agg.wgs[i] for i in range(n)), agg.grid[0]) == (
         forms["agg_kernel"], forms["agg_wgs"], forms["agg_grid"]), where
     assert sorted(agg.pos[i] for i in range(n) if not agg.pre_grid[i]) == list(range(n - len(scene))), where
+    assert [agg.pos[i] for i in range(n)] == forms["agg_pos"], (where, [agg.pos[i] for i in range(n)], forms["agg_pos"])
     assert (mlp2 is None) == (forms["mlp2"] is None) and (n2e is None) == (forms["n2e"] is None), where
     assert (gather is None) == (forms["gather_spw"] is None), where
     if mlp2 is not None:
