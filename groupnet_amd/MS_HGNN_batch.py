@@ -319,6 +319,17 @@ class _MessagePassing(nn.Module):
         return MSHGNNFunction.apply((self,), (H,), (noise_u,), h, *_plist(self))
 
 
+BF16_MAX_BOTTLENECK = 64      # gn_mlp2_bf16: the bf16-core kernels hold at most two 32-wide output tiles
+
+
+def _check_storage_width(bottleneck_dim: int, dtype: torch.dtype) -> None:
+    """bf16 storage runs the closing MLP on the bf16-core kernels alone, whose output ends at 64 columns (the launcher
+    refuses a wider one): said here, before a forward has launched anything, instead of at its last launch."""
+    if dtype == torch.bfloat16 and bottleneck_dim > BF16_MAX_BOTTLENECK:
+        raise ValueError(f"bf16 activations need bottleneck_dim <= {BF16_MAX_BOTTLENECK} (got {bottleneck_dim}): the bf16 "
+                         f"closing MLP kernels write at most {BF16_MAX_BOTTLENECK} columns; run a wider module on fp32 tensors")
+
+
 def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor], Hs: Sequence, noises: Sequence,
                         outs: Sequence[Optional[Tensor]], traces=None, join=None, affinity=None,
                         fuse_closing: bool = False) -> List[Tuple[Tensor, Tensor]]:
@@ -353,6 +364,7 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     nmp = mods[0].nmp_layers
     if any(m.nmp_layers != nmp or m.bottleneck_dim != mods[0].bottleneck_dim for m in mods):
         raise ValueError("grouped modules must share nmp_layers and bottleneck_dim")
+    _check_storage_width(mods[0].bottleneck_dim, hs[0].dtype)
     B, N = hs[0].shape[0], hs[0].shape[1]
     incs = [H if H is None or isinstance(H, ops.Incidence) else ops.Incidence(H) for H in Hs]
     rt = route.message_passing_route(
@@ -530,6 +542,7 @@ class MS_HGNN_oridinary(_MessagePassing):
         N = h_states.shape[1]
         if h_states.shape[0] and N and _needs_grad(self, h_states):
             return self._forward_autograd(h_states, None, noise_u, out)
+        _check_storage_width(self.bottleneck_dim, h_states.dtype)
         if h_states.shape[0] == 0 or N == 0:      # empty batch: nothing to launch
             nf = out if out is not None else h_states.new_empty((h_states.shape[0], N, self.bottleneck_dim))
             return nf, h_states.new_empty((h_states.shape[0], N * N, self.edge_types))
@@ -599,6 +612,7 @@ class MS_HGNN_hyper(_MessagePassing):
                 masks = ops.incidence_masks(H, assume_binary=True) if masks_apply(h_states.shape[1]) else None
             node_feat, factor = self._forward_autograd(h_states, ops.Incidence(H, masks), noise_u, out)
             return node_feat, factor, H
+        _check_storage_width(self.bottleneck_dim, h_states.dtype)      # (before the incidence is built)
         if h_states.shape[0] == 0:                  # empty batch: nothing to launch
             B, N = h_states.shape[0], h_states.shape[1]
             if self.scale > N:

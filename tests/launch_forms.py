@@ -20,6 +20,9 @@ K_PAIR, K_HYPER = 6, 10          # edge types (MS_HGNN_batch.py: MS_HGNN_oridina
 NODE_FORM_MAX_N, NODE_FORM_MAX_K = 16, 12      # route.NODE_FORM_MAX_N / NODE_FORM_MAX_K (ops re-exports the kernel limits)
 SCENE_FORM_MAX_N = 64                          # route.SCENE_FORM_MAX_N
 FUSED_MAX_N = 16                 # route._FUSED_GATHER_MAX_N / _FUSED_SCATTER_MAX_N / ops.POOL_MAX_N
+BOTTLENECK = 64                  # the closing MLP's output width of every case that does not name one
+IMAGE_MAX_DOUT = 64              # weights.closing_mlp / gn_mlp2_*: the bf16-core kernels (and bf16 storage) end here
+ONE_TILE_MAX_DOUT = 32           # mlp2_plan: one 32-wide output tile up to here; the fused closing stage starts above it
 RB2_MIN_PAIRS = 2048             # gn_mlp_mfma.hip rb2_min_pairs() without the test knob
 GS_MIN_WGS = 2048                # gn_graph.hip kGsMinWgs
 GS_LDS_BUDGET = 128 * 1024       # gn_graph.hip kLdsBudget
@@ -123,9 +126,29 @@ def module_types(scales: Sequence[int], with_pair: bool = True, types: Optional[
     return [int(k) for k in types]
 
 
+def mlp2_form(dout: int, rows: int, n_groups: int, precision: str = "f16x3", dtype: str = "fp32", fused_input: bool = True,
+              wide_hyper: bool = False, xs: Optional[bool] = None, dh: int = 128):
+    """(kernel, tiles[2]) of one closing-MLP launch (gn_mlp_mfma.hip mlp2_plan), None where the launcher refuses it.
+    dout: the output width; rows x n_groups: the launch size; fused_input: a group forms its input rows itself
+    (ScatterSpec / NodeAggSpec) or keeps its activations; wide_hyper: a fused scatter over more than 16 hyperedges; xs:
+    GN_MLP2_XS as a bool (None: unset).  Up to IMAGE_MAX_DOUT the 16-bit cores (and bf16 storage) run mlp2_xs_kernel /
+    mlp2_x_kernel by launch size, instantiated with one output tile up to ONE_TILE_MAX_DOUT and with two above it; the
+    fp32 cores run the 4-waves-per-block split kernel on a small launch of plain rows (dh = 128) and mlp2_kernel
+    otherwise, neither instantiated by output tiles (0).  Beyond IMAGE_MAX_DOUT there is no image: fp32 storage runs
+    mlp2_kernel whatever the matrix path (the split kernel holds two output tiles), bf16 storage is refused."""
+    twin = dtype == "bf16"
+    b32 = cdiv(rows, 32)
+    if dout > IMAGE_MAX_DOUT:
+        return None if twin else ("mlp2_kernel", 0)
+    if twin or precision != "fp32":
+        small = (b32 * n_groups <= 1536) if xs is None else xs
+        return ("mlp2_xs_kernel" if small and not wide_hyper else "mlp2_x_kernel"), (1 if dout <= ONE_TILE_MAX_DOUT else 2)
+    return ("mlp2_split_kernel" if dh == 128 and b32 * n_groups <= 1024 and not fused_input else "mlp2_kernel"), 0
+
+
 def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x3", dtype: str = "fp32",
                    training: bool = False, block: bool = True, with_pair: bool = True,
-                   types: Optional[Sequence[int]] = None) -> Dict:
+                   types: Optional[Sequence[int]] = None, bottleneck: int = BOTTLENECK) -> Dict:
     """The forms the launchers pick for one forward of the multiscale block (`block=True`, latency form: closing fused
     where allowed) or of the same modules launched one by one through the module API (`block=False`: no fused closing).
     precision: ops.precision() of the fp32 entry points ('f16x3' | 'bf16x6' | 'fp32'); dtype: 'fp32' | 'bf16' storage.
@@ -133,10 +156,13 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
     Returns {"groups": [per module: {"name", "E", "K", "rows", "node_form", "wpr", "spw"}], "fused_closing",
     "agg_kernel", "agg_wgs", "agg_grid" (of the launch of the groups that are not in the twins' scene form), "agg_pos"
     (per module its position in that launch, -1 for the scene form), "scene_grid",
-    "mlp2", "n2e", "gather_spw", "scatter" (scatter_forms of the stand-alone scatter)}; "scene_grid" / "mlp2" / "n2e" /
-    "gather_spw" / "scatter" are None where that launch does not run.
+    "mlp2", "mlp2_tiles", "mlp2_refused", "n2e", "gather_spw", "scatter" (scatter_forms of the stand-alone scatter)};
+    "scene_grid" / "mlp2" / "n2e" / "gather_spw" / "scatter" are None where that launch does not run.
     with_pair=False: the hyper modules alone (one MS_HGNN_hyper through the module API).
     types: the edge types K of every module in group order, (K_pair, K_hyper, ...) (default: 6 and 10).
+    bottleneck: the output width of the closing MLP of the last round (default 64): the fused closing stage exists for
+    32 < bottleneck <= 64 only, the closing launch's kernel is `mlp2_form`'s; "mlp2_refused": bf16 storage beyond 64, which
+    the launcher refuses ("mlp2" is None there although the forward would need the launch).
 
     These rules restate the launchers' plan functions independently of them: tests/test_launch_plan_cpu.py holds the two
     against each other through the library's plan queries (no GPU), and a kernel trace of tests/test_launch_forms_gpu.py's
@@ -160,7 +186,8 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
     # N <= 16, the pairwise group in its node form, every hyper group with E <= 16 and more than one wave per row block
     # (below 768 row blocks; K >= 4 below 128 row blocks, K >= 2 from there on)
     fused = (block and with_pair and not training and not twin and xm and N <= FUSED_MAX_N and groups[0]["node_form"]
-             and all(g["E"] <= 16 and g["wpr"] > 1 for g in hyp))
+             and all(g["E"] <= 16 and g["wpr"] > 1 for g in hyp)
+             and ONE_TILE_MAX_DOUT < bottleneck <= IMAGE_MAX_DOUT)      # (closing_chain is built for two output tiles)
     if fused:
         for g in hyp:       # agg_launch: `spw = (128 / wpr) / E`, capped at node_cap / N nodes
             g["spw"] = min((128 // g["wpr"]) // g["E"], (160 if g["E"] == 1 else 64) // N)
@@ -191,16 +218,15 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
         agg_kernel, grid = "agg_x_kernel", xcd_grid(wgs)
     else:
         agg_kernel, grid = "agg_mlp_kernel", sum(wgs)
-    # closing MLP launch (gn_mlp_mfma.hip mlp2_launch / mlp2_x_launch); din = 128, dh = 128, dout = 64
-    mlp2 = None
+    # closing MLP launch (gn_mlp_mfma.hip mlp2_plan); din = 128, dh = 128, dout = bottleneck.  Its input rows are formed in
+    # the kernel up to N = 16 (a fused scatter: never the fp32 cores' split kernel) and kept in training
+    mlp2 = mlp2_tiles = None
+    refused = False
     if not fused:
-        n = len(groups)
-        b32 = cdiv(B * N, 32)
-        if xm:
-            mlp2 = "mlp2_xs_kernel" if b32 * n <= 1536 else "mlp2_x_kernel"
-        else:
-            # the fp32 kernels: the 4-waves-per-block split kernel only without a fused scatter (N > 16)
-            mlp2 = "mlp2_split_kernel" if (b32 * n <= 1024 and N > FUSED_MAX_N) else "mlp2_kernel"
+        form = mlp2_form(bottleneck, B * N, len(groups), precision, dtype, fused_input=N <= FUSED_MAX_N or training)
+        refused = form is None
+        if form is not None:
+            mlp2, mlp2_tiles = form
     # node -> edge pooling of the hyper modules (gn_graph.hip node2edge_launch): launched for training, the fp32 cores and
     # N > POOL_MAX_N (the route's `node2edge` launch); row form when `maxE >= 24 || hyper_rows >= 49152`
     n2e = None
@@ -220,8 +246,8 @@ def expected_forms(B: int, N: int, scales: Sequence[int], precision: str = "f16x
     if rest and N > FUSED_MAX_N:
         scatter = scatter_forms(B, N, [dict(E=g["E"], sym=g["name"] == "pair", H=g["name"] != "pair") for g in rest])
     return dict(scatter=scatter, groups=groups, fused_closing=fused, agg_kernel=agg_kernel, agg_wgs=sum(wgs), agg_grid=grid,
-                agg_pos=agg_pos,
-                scene_grid=scene_grid, mlp2=mlp2, n2e=n2e, gather_spw=gather_spw)
+                agg_pos=agg_pos, scene_grid=scene_grid, mlp2=mlp2, mlp2_tiles=mlp2_tiles, mlp2_refused=refused, n2e=n2e,
+                gather_spw=gather_spw)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -325,20 +351,24 @@ PLACEHOLDER = 4096      # a 16-aligned non-NULL "device address": a plan query t
 
 def launch_descriptors(B: int, N: int, scales: Sequence[int], precision: str = "f16x3", dtype: str = "fp32",
                        training: bool = False, block: bool = True, with_pair: bool = True,
-                       types: Optional[Sequence[int]] = None) -> Dict:
+                       types: Optional[Sequence[int]] = None, bottleneck: int = BOTTLENECK) -> Dict:
     """The C-ABI descriptor arrays the engine passes for the last round of such a forward (arguments as `expected_forms`),
     with the node-form, PoolSpec and closing decisions as `expected_forms` states them and PLACEHOLDER for every device
     address (tests/test_route_cpu.py holds `route.message_passing_route`, which the engine follows, against them).  -> {"twin", "edge": arr, "agg": arr (closing MLP in a launch of its own), "agg_closing": arr
     (the closing stage in the aggregation launch), "mlp2": (arr, rows, din, dh, dout, ldy, N, divisor), "n2e": arr or None,
-    "gather": arr or None, "scatter": arr or None}; the group order is that of expected_forms' "groups"."""
+    "gather": arr or None, "scatter": arr or None}; the group order is that of expected_forms' "groups".  bottleneck: the
+    closing MLP's output width — its bf16-core images exist up to IMAGE_MAX_DOUT (weights.closing_mlp), and beyond it the
+    engine passes none (ops.mlp2_grouped)."""
     from groupnet_amd import _lib as L
     P = PLACEHOLDER
     twin = dtype == "bf16"
     xm = twin or precision != "fp32"
     X = P if xm else 0                              # bf16-core images
     Hh = P if (precision == "f16x3" and not twin) else 0      # fp16 two-part images
-    forms = expected_forms(B, N, scales, precision, dtype, training, block, with_pair, types)
+    forms = expected_forms(B, N, scales, precision, dtype, training, block, with_pair, types, bottleneck)
     groups = forms["groups"]
+    d = int(bottleneck)
+    X2, H2 = (X, Hh) if d <= IMAGE_MAX_DOUT else (0, 0)      # the closing MLP's images
     n = len(groups)
     small = N <= FUSED_MAX_N
     pool = not training and xm                      # pooling in the edge kernel (PoolSpec), before the N limit of hyper groups
@@ -361,10 +391,10 @@ def launch_descriptors(B: int, N: int, scales: Sequence[int], precision: str = "
             a = dict(eo=P, W12x=X, W12h=Hh)
             gather.append(L.GatherGroup(ori=P, H=P, eo=P, E=E, sym=0))
         agg.append(L.AggGroup(feat=P, **base, **a))
-        aggc.append(L.AggGroup(**base, **{**a, "ori": P}, m2x=X, m2h=Hh, m2bias=P, y=P, ldy=64 * (1 + n) if block else 64,
-                               dout=64, divisor=float(N)))
+        aggc.append(L.AggGroup(**base, **{**a, "ori": P}, m2x=X2, m2h=H2, m2bias=P, y=P, ldy=d * (1 + n) if block else d,
+                               dout=d, divisor=float(N)))
         keep = dict(in_out=P, hid_out=P) if training else {}
-        m = dict(W=P, bias=P, y=P, Wx=X, Wh=Hh, **keep)
+        m = dict(W=P, bias=P, y=P, Wx=X2, Wh=H2, **keep)
         if g["node_form"]:
             mlp2.append(L.Mlp2Group(feat=P, ori=P, **m))                                   # NodeAggSpec
         elif small:
@@ -374,7 +404,7 @@ def launch_descriptors(B: int, N: int, scales: Sequence[int], precision: str = "
             scatter.append(L.ScatterGroup(feat=P, H=0 if pair else P, ori=P, out=P, E=E, sym=int(pair)))
     arr = lambda cls, xs: (cls * len(xs))(*xs) if xs else None
     return dict(twin=twin, edge=arr(L.EdgeGroup, edge), agg=arr(L.AggGroup, agg), agg_closing=arr(L.AggGroup, aggc),
-                mlp2=(arr(L.Mlp2Group, mlp2), B * N, 128, 128, 64, 64 * (1 + n) if block else 64, N, float(N)),
+                mlp2=(arr(L.Mlp2Group, mlp2), B * N, 128, 128, d, d * (1 + n) if block else d, N, float(N)),
                 n2e=arr(L.N2EGroup, n2e), gather=arr(L.GatherGroup, gather), scatter=arr(L.ScatterGroup, scatter))
 
 
@@ -399,6 +429,7 @@ def assert_plans_match(forms: Dict, agg, mlp2, n2e, gather, where, scatter=False
     assert (gather is None) == (forms["gather_spw"] is None), where
     if mlp2 is not None:
         assert name(mlp2) == forms["mlp2"], (where, name(mlp2))
+        assert forms.get("mlp2_tiles") is None or mlp2.tiles[2] == forms["mlp2_tiles"], (where, mlp2.tiles[2])
     if n2e is not None:
         assert ("rows" if n2e.variant else "banded") == forms["n2e"] and (n2e.EBh == 0) == bool(n2e.variant), where
     if gather is not None:
