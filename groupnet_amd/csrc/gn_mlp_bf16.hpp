@@ -359,6 +359,19 @@ struct WStream {
   }
 };
 
+// The schedule of VALU work in the shadow of MFMAS matrix instructions just issued: one MFMA, VALU slots of VALU work,
+// and with every PERIOD-th MFMA a group of SIZE instructions of class MASK (0x100: LDS reads, 0x020: the global loads of
+// a ring refill).  The parameters are sched_group_barrier's constant arguments; the caller closes with sched_barrier(0).
+template <int MFMAS, int VALU, int PERIOD, int MASK, int SIZE>
+__device__ __forceinline__ void mfma_shadow() {
+#pragma unroll
+  for (int i = 0; i < MFMAS; ++i) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x002, VALU, 0);
+    if (i % PERIOD == 0) __builtin_amdgcn_sched_group_barrier(MASK, SIZE, 0);
+  }
+}
+
 // ---- one layer pair, hidden tile by hidden tile, software-pipelined ------------------------------------------------
 //   out[o] += W1(o, :) post(W0 x + b0)      x: IT input tiles (as parts), HT hidden tiles, OT output tiles
 // A_t = the 2*IT sub-steps that produce hidden tile t, V_t = its VALU work (post: ReLU / scale / optional store,
@@ -413,6 +426,7 @@ __device__ __forceinline__ void layer_pair(Stream& ws, int c0, int s0, const Par
         ws.template step<false>(c0, pos, xi[u >> 1][u & 1], hidn);
         ++pos;
       }
+      // (mfma_shadow's loop written out: as a call, node_stage_kernel<2, float> measured 0.1 us over the parent's range)
 #pragma unroll
       for (int i = 0; i < kMfma; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          // one MFMA
@@ -657,63 +671,13 @@ __device__ __forceinline__ void edge_x_body(const GroupTable<gn_edge_group_t>& T
   lg = lgv[0];
   // (the row block afresh: of the first one nothing but `h` is live across the two chains)
   const RowBlock re = row_block_again(rows, blk);
-  // ordered edge rows whose uniforms this row consumes: itself, or — symmetric pairwise form — the two ordered
-  // edges (i,j) and (j,i) of its unordered pair (worked out behind the chains: nothing of it is live across them)
-  long long o1 = re.row_ld, o2 = re.row_ld;
-  bool diag = true;
-  if (G.sym_N > 0) {
-    const int N = G.sym_N, Pn = gn_pair_count(N);
-    const int b = re.row_ld / Pn, p = re.row_ld - b * Pn;
-    int i, j;
-    gn_pair_decode(p, N, i, j);
-    o1 = (long long)b * N * N + i * N + j;
-    o2 = (long long)b * N * N + j * N + i;
-    diag = i == j;
-  }
+  // (the ordered edges too are worked out behind the chains: nothing of them is live across them)
+  const OrderedEdges oe = ordered_edges(G, re.row_ld);
   // uniforms: read from U or generated from the Philox stream — after the chains (nothing is in flight any more)
-  fetch_uniforms(G.U, pbase, seed, o1, K, h, u1);
-  if (G.sym_N > 0) fetch_uniforms(G.U, pbase, seed, o2, K, h, u2);
+  fetch_uniforms(G.U, pbase, seed, oe.o1, K, h, u1);
+  if (G.sym_N > 0) fetch_uniforms(G.U, pbase, seed, oe.o2, K, h, u2);
   if (G.keep_lgf != nullptr && re.live) store_tile(G.keep_lgf + (size_t)re.row * 32 + 4 * h, lg);
-
-  // Epilogue.  Features 0..K-1 of `lg` are the logits of this lane's row, feature K the factor pre-activation; a
-  // row's features are split over its two lanes (j, h=0) and (j, h=1).
-  float facv = 0.f;
-#pragma unroll
-  for (int r = 0; r < 8; ++r)
-    if (feat_of(r, h) == K) facv = lg[r];
-  facv += __shfl_xor(facv, 32, GN_WAVE);   // exactly one of the two lanes holds it, the other has 0
-  const float sig = 1.f / (1.f + expf(-facv));
-  float d1[8], d2[8];
-  gumbel_softmax_row<P == 1>(lg, u1, K, tau, h, d1);
-  if (G.sym_N > 0) gumbel_softmax_row<P == 1>(lg, u2, K, tau, h, d2);
-  if (re.live) {
-    float* frow = G.edge_feat + (size_t)re.row * K;
-    T* dist = reinterpret_cast<T*>(G.dist);
-    if (G.sym_N == 0) {
-      T* drow = dist + (size_t)re.row * K;
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int f = feat_of(r, h);
-        if (f < K) {
-          st1(drow + f, d1[r]);
-          frow[f] = sig * d1[r];
-        }
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int f = feat_of(r, h);
-        if (f < K) {
-          if (dist != nullptr) {
-            st1(dist + (size_t)o1 * K + f, d1[r]);
-            if (!diag) st1(dist + (size_t)o2 * K + f, d2[r]);
-          }
-          // both ordered edges meet the same typed MLP output downstream; the self-loop has weight 2
-          frow[f] = diag ? 2.f * (sig * d1[r]) : sig * d1[r] + sig * d2[r];
-        }
-      }
-    }
-  }
+  edge_head<P == 1, T>(G, K, re.row, h, re.live, oe, lg, u1, u2, tau);
 }
 // The launch's dynamic LDS is ONE region of at least kRingF4For<P> f32x4 (a static ring and a dynamic stage would not be
 // guaranteed adjacent): first the pool stage, then the weight ring (edge_x_body).
@@ -1480,6 +1444,151 @@ __global__ __launch_bounds__(256, kSceneOcc) void agg_scene_kernel(gn_agg_group_
   }
 }
 
+// ---- A5 on the bf16 cores: the steps the forms of agg_x_body share -----------------------------------------------------
+// (arguments are scalars, not a RowBlock or a per-wave struct by reference: through those agg_x_kernel<2, float, true>
+// spilled more inside its hot loops.  For the same reason the pair form's hidden tile relu(A_i + A_j) * ef_k stays
+// written out at its two sites and the forms stay branches of agg_x_body: DESIGN.md section 4.)
+// [wave][register 0..31][lane]: the partial sums of wpr > 1, and each wave's scratch of the line-layout gather
+using AggPart = float (*)[32][64 + 8];
+
+// The row block's input rows: eo as stored, or gathered from ori — out of the LDS stage (lines == 2, from node hnode0),
+// in the line layout through this wave's own scratch (lines == 1; wpr > 1: every wave of the row block forms the rows
+// itself, the partial sums reuse the scratch at the end), or row by row.
+template <typename T>
+__device__ __forceinline__ void agg_input_rows(const gn_agg_group_t& G, int lines, int hnode0, int row_ld, int lane, int h,
+                                               int blk, const float* stage, float* scratch, f32x16 (&in)[2]) {
+  if (G.eo != nullptr) {
+    load_rows<2>(reinterpret_cast<const T*>(G.eo), GN_FEAT, row_ld, h, in);
+  } else if (lines == 2) {
+    gather_hyper_staged<T>(G, row_ld, h, reinterpret_cast<const T*>(stage), hnode0, in);
+  } else if (lines) {
+    gather_rows_lines<T>(G, blk, G.rows, lane, scratch);
+    __builtin_amdgcn_wave_barrier();
+    read_rows_lines(scratch, lane, in);
+  } else {
+    gather_rows<T>(G, row_ld, h, in);
+  }
+}
+
+// One type of the two-layer form: out += ef_k (W2k relu(W1k x + b1k) + b2k), hidden tile by hidden tile.  ws: the
+// workgroup's WStream at chunk c0, or a wave's XStream (c0 unused); bf0 / bf1: this lane's b2k values (P != 1).
+template <int P, typename Stream>
+__device__ __forceinline__ void agg_type_step(Stream& ws, int c0, const Parts<P> (&xi)[2][2], const f32x16& hid0,
+                                              const float* __restrict__ b1k, const float* __restrict__ b2k, float bf0,
+                                              float bf1, float efk, int h, f32x16 (&out)[2], ovf_t& ovf) {
+  if constexpr (P == 1) {
+    // VALU-lean form: the type's layer 2 accumulates into a temporary that starts at b2_k, ReLU runs on the
+    // packed bf16 operands, and feat += ef_k * (W2k relu(..) + b2k) is 32 FMAs per type — instead of scaling every
+    // hidden value (64 multiplications) and two extra fp32 MFMAs for the bias
+    f32x16 tmp[2];
+    tmp[0] = load_bias_tile(b2k, h);
+    tmp[1] = load_bias_tile(b2k + 32, h);
+    layer_pair<P, 2, 2, 4, true>(ws, c0, 0, xi, hid0, b1k, h, tmp, ovf, [&](int, f32x16&) {});
+#pragma unroll
+    for (int o = 0; o < 2; ++o)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) out[o][r] = fmaf(efk, tmp[o][r], out[o][r]);
+  } else {
+    add_b2_regs(bf0, bf1, efk, h, out);
+    layer_pair<P, 2, 2, 4>(ws, c0, 0, xi, hid0, b1k, h, out, ovf, [&](int, f32x16& hid) { relu_scale16(hid, efk); });
+  }
+}
+
+// Registers reg0 .. reg0 + 3 of a row block, summed over the partials of its wpr waves w0 .. (fixed order, from 0)
+__device__ __forceinline__ f32x4 sum_wave_partials(AggPart part, int w0, int wpr, int reg0, int lane) {
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  for (int jw = 0; jw < wpr; ++jw) {
+    v[0] += part[w0 + jw][reg0 + 0][lane];
+    v[1] += part[w0 + jw][reg0 + 1][lane];
+    v[2] += part[w0 + jw][reg0 + 2][lane];
+    v[3] += part[w0 + jw][reg0 + 3][lane];
+  }
+  return v;
+}
+
+// ---- fused closing stage of a hyper group, behind the exchange of the wave partials: feat of the workgroup's scenes ->
+// LDS, H^T feat and ori of their nodes -> X, closing MLP per 32-node row block (closing_chain).  The summed registers
+// first (all reads of `part` done), then `part`'s LDS is reused: F = feat rows [rows_used][kFPitch], X behind it.
+// (scalar arguments for the spill counts' sake, as the other helpers here: see the head of this section)
+template <int P, typename T>
+__device__ __forceinline__ void agg_fused_closing(const gn_agg_group_t& G, int wg, int wave, int wpr, int sub, int lane,
+                                                  int h, int spw, int rows_used, float* part_dyn, f32x4* wring,
+                                                  ovf_t& ovf) {
+  const int rows = G.rows;
+  const AggPart part = reinterpret_cast<AggPart>(part_dyn);
+  constexpr int kFPitch = GN_FEAT + 4;
+  f32x4 fv[8];
+  const int w0 = wave - sub, nreg = 32 / wpr;
+#pragma unroll
+  for (int u = 0; u < 8; ++u)
+    if (u * 4 < nreg) fv[u] = sum_wave_partials(part, w0, wpr, sub * nreg + u * 4, lane);
+  __syncthreads();
+  float* F = part_dyn;
+  float* X = part_dyn + 64 * kFPitch;
+  {
+    const int lr = (wave / wpr) * 32 + (lane & 31);
+    if (lr < rows_used) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (u * 4 < nreg) {
+          const int reg0 = sub * nreg + u * 4;
+          const int o = reg0 >> 4, q = (reg0 & 15) >> 2;
+          *reinterpret_cast<f32x4*>(F + lr * kFPitch + 32 * o + 8 * q + 4 * h) = fv[u];
+        }
+    }
+  }
+  __syncthreads();
+  const int N = G.N, E = G.E;
+  const int scene0 = wg * spw, B = rows / E;
+  const int nodes = min(spw, B - scene0) * N;                  // node rows of this workgroup (>= 1)
+  const T* orib = reinterpret_cast<const T*>(G.ori);
+  ClosingStream<P> cs;
+  cs.init(pick_image<P>(G.m2x, G.m2h), wave, lane, ovf);
+  for (int nb = 0; nb * 32 < nodes; ++nb) {
+    cs.begin();
+    // X[row][0..63] = (sum_e H[b,e,n] feat[b,e]) / divisor in the order of the fused scatter of gn_mlp2 (e ascending,
+    // fmaf), X[row][64..127] = ori[b,n] / divisor; thread (row = t / 8, piece = t % 8) forms two 16-byte pieces of each
+    const int row = (int)threadIdx.x >> 3, piece = (int)threadIdx.x & 7;
+    const int m = min(nb * 32 + row, nodes - 1);               // node of this workgroup (clamped)
+    const int sl = m / N, n = m - sl * N;
+    const float* hcol = G.H + ((size_t)(scene0 + sl) * E) * N + n;
+    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+    // (the node's incidence column first, all of it in flight at once — E <= 16 here: a load per loop iteration cost
+    // one L2 round trip per hyperedge, 8 k cycles per row block, measured in round 3)
+    float hw[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) hw[e] = e < E ? hcol[(size_t)e * N] : 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+      if (e < E) {
+        const float* fr = F + (sl * E + e) * kFPitch + 4 * piece;
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(fr), v1 = *reinterpret_cast<const f32x4*>(fr + 32);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          a0[c] = fmaf(hw[e], v0[c], a0[c]);
+          a1[c] = fmaf(hw[e], v1[c], a1[c]);
+        }
+      }
+    const T* orow = orib + ((size_t)scene0 * N + m) * GN_FEAT + 4 * piece;
+    f32x4 o0 = ld4(orow), o1 = ld4(orow + 32);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      a0[c] = a0[c] / G.divisor;
+      a1[c] = a1[c] / G.divisor;
+      o0[c] = o0[c] / G.divisor;
+      o1[c] = o1[c] / G.divisor;
+    }
+    float* xr = X + row * kXPitch + 4 * piece;
+    *reinterpret_cast<f32x4*>(xr) = a0;
+    *reinterpret_cast<f32x4*>(xr + 32) = a1;
+    *reinterpret_cast<f32x4*>(xr + 64) = o0;
+    *reinterpret_cast<f32x4*>(xr + 96) = o1;
+    __syncthreads();
+    closing_chain<P, T>(cs, G.m2bias, reinterpret_cast<T*>(G.y), G.ldy, G.dout, scene0 * N + nb * 32, nodes - nb * 32, X,
+                        wring, wave, lane, ovf);
+  }
+}
+
 // PAIRF: the per-pair forms of the pairwise graph are compiled in.  They are what costs the kernel its last registers (28
 // bytes of scratch per lane); since the node form replaced them in the default path the launcher picks the instantiation
 // without them whenever no group of the launch needs one (fp32 path beyond N = 16, GN_NODE_FORM = 0).
@@ -1490,7 +1599,7 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
   // wpr > 1: [wave][register 0..31][lane]; staged pair form: 2 x node rows.  Dynamic: a launch whose groups all run one
   // wave per row block without the stage (the large bf16 configurations) passes 0 bytes and fits more workgroups per CU.
   extern __shared__ __align__(16) float part_dyn[];
-  float (*part)[32][64 + 8] = reinterpret_cast<float (*)[32][64 + 8]>(part_dyn);
+  const AggPart part = reinterpret_cast<AggPart>(part_dyn);
   const int lwg = gn_uniform(gn_xcd_logical(Tb.xs, blockIdx.x));
   if (lwg < 0) return;
   const int gi = find_group(Tb, lwg);
@@ -1568,12 +1677,7 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
     // where one shares a SIMD with a two-layer wave its instructions issue first.  Measured: 57 -> 52 us.
     __builtin_amdgcn_s_setprio(1);
     int i, j;
-    {
-      const int b = rb.row_ld / Pn, p = rb.row_ld - b * Pn;
-      gn_pair_decode(p, N, i, j);
-      i += b * N;
-      j += b * N;
-    }
+    pair_nodes(rb.row_ld, N, Pn, i, j);
     const size_t ldA = (size_t)K * 128;
     const T* Abase = reinterpret_cast<const T*>(G.A);
     ws.begin(img, wring, lane, wave, K * 16 / CH);
@@ -1595,12 +1699,7 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
 #pragma unroll
       for (int u = 0; u < 4; ++u)                    // [W2(0,t) hf0, hf1, W2(1,t) hf0, hf1]
         ws.template step<false>(c0, 4 * t + u, xh[u & 1], out[u >> 1]);
-#pragma unroll
-      for (int m = 0; m < 4 * kMfmaPerSub<P>; ++m) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, P == 2 ? 11 : 7, 0);
-        if (m % kMfmaPerSub<P> == 0) __builtin_amdgcn_sched_group_barrier(0x100, P, 0);
-      }
+      mfma_shadow<4 * kMfmaPerSub<P>, P == 2 ? 11 : 7, kMfmaPerSub<P>, 0x100, P>();
       __builtin_amdgcn_sched_barrier(0);
     };
     if (staged) {
@@ -1693,12 +1792,7 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
     if (any_rows && sub < K) {
       const int N = G.N, Pn = G.E;
       int i, j;
-      {
-        const int b = rb.row_ld / Pn, p = rb.row_ld - b * Pn;
-        gn_pair_decode(p, N, i, j);
-        i += b * N;
-        j += b * N;
-      }
+      pair_nodes(rb.row_ld, N, Pn, i, j);
       const size_t ldA = (size_t)K * 128;
       const T* Ai = reinterpret_cast<const T*>(G.A) + (size_t)i * ldA;
       const T* Aj = reinterpret_cast<const T*>(G.A) + (size_t)j * ldA;
@@ -1736,17 +1830,7 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
     // A_t = tile t of layer 1 (4 sub-steps), ReLU * ef_k, its bf16 part(s), B_t = its contribution to both output
     // tiles (4 sub-steps)) — one hidden tile live --------------------------------------------------------------
     f32x16 in[2];
-    if (G.eo != nullptr) {
-      load_rows<2>(reinterpret_cast<const T*>(G.eo), GN_FEAT, rb.row_ld, h, in);
-    } else if (hstage) {
-      gather_hyper_staged<T>(G, rb.row_ld, h, reinterpret_cast<const T*>(part_dyn), hnode0, in);
-    } else if (Tb.g[gi].lines) {
-      gather_rows_lines<T>(G, blk, rows, lane, &part[wave][0][0]);
-      __builtin_amdgcn_wave_barrier();
-      read_rows_lines(&part[wave][0][0], lane, in);
-    } else {
-      gather_rows<T>(G, rb.row_ld, h, in);
-    }
+    agg_input_rows<T>(G, Tb.g[gi].lines, hnode0, rb.row_ld, lane, h, blk, part_dyn, &part[wave][0][0], in);
     Parts<P> xi[2][2];
     make_parts_tiles<P, 2>(in, xi, ovf);
     ws.begin(img, wring, lane, wave, K * 32 / CH);
@@ -1761,23 +1845,7 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
       float bn0 = 0.f, bn1 = 0.f;
       if constexpr (P != 1) bn0 = b2[kc * 64 + (lane & 31)], bn1 = b2[kc * 64 + 32 + (lane & 31)];
       const f32x16 hid0_next = load_bias_tile(b1 + kc * 128, h);
-      if constexpr (P == 1) {
-        // VALU-lean form: the type's layer 2 accumulates into a temporary that starts at b2_k, ReLU runs on the
-        // packed bf16 operands, and feat += ef_k * (W2k relu(..) + b2k) is 32 FMAs per type — instead of scaling every
-        // hidden value (64 multiplications) and two extra fp32 MFMAs for the bias
-        f32x16 tmp[2];
-        tmp[0] = load_bias_tile(b2 + k * 64, h);
-        tmp[1] = load_bias_tile(b2 + k * 64 + 32, h);
-        layer_pair<P, 2, 2, 4, true>(ws, k * 32 / CH, 0, xi, hid0, b1 + k * 128, h, tmp, ovf, [&](int, f32x16&) {});
-#pragma unroll
-        for (int o = 0; o < 2; ++o)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) out[o][r] = fmaf(efk, tmp[o][r], out[o][r]);
-      } else {
-        add_b2_regs(bf0, bf1, efk, h, out);
-        layer_pair<P, 2, 2, 4>(ws, k * 32 / CH, 0, xi, hid0, b1 + k * 128, h, out, ovf,
-                               [&](int, f32x16& hid) { relu_scale16(hid, efk); });
-      }
+      agg_type_step<P>(ws, k * 32 / CH, xi, hid0, b1 + k * 128, b2 + k * 64, bf0, bf1, efk, h, out, ovf);
       hid0 = hid0_next;
       efk = efk_next, bf0 = bn0, bf1 = bn1;
     }
@@ -1785,18 +1853,7 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
     // ---- two-layer form, wpr > 1: types dealt over the waves of a row block, private register rings ------------------
     if (fused) __builtin_amdgcn_s_setprio(1);
     f32x16 in[2];
-    if (G.eo != nullptr) {
-      load_rows<2>(reinterpret_cast<const T*>(G.eo), GN_FEAT, rb.row_ld, h, in);
-    } else if (hstage) {
-      gather_hyper_staged<T>(G, rb.row_ld, h, reinterpret_cast<const T*>(part_dyn), hnode0, in);
-    } else if (Tb.g[gi].lines) {
-      // (every wave of the row block forms the rows itself, in its own scratch; the partial sums reuse it at the end)
-      gather_rows_lines<T>(G, blk, rows, lane, &part[wave][0][0]);
-      __builtin_amdgcn_wave_barrier();
-      read_rows_lines(&part[wave][0][0], lane, in);
-    } else {
-      gather_rows<T>(G, rb.row_ld, h, in);
-    }
+    agg_input_rows<T>(G, Tb.g[gi].lines, hnode0, rb.row_ld, lane, h, blk, part_dyn, &part[wave][0][0], in);
     Parts<P> xi[2][2];
     make_parts_tiles<P, 2>(in, xi, ovf);
     const f32x4* Wx = reinterpret_cast<const f32x4*>(img) + lane;      // sub-step s of type k: (k*32 + s)
@@ -1810,19 +1867,7 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
       const float efk_next = efrow[kc], bn0 = b2[kc * 64 + (lane & 31)], bn1 = b2[kc * 64 + 32 + (lane & 31)];
       const f32x16 hid0_next = load_bias_tile(b1 + kc * 128, h);
       xs.segment(Wx + (size_t)k * 32 * P * 64, Wx + (size_t)kc * 32 * P * 64, 32);
-      if constexpr (P == 1) {
-        f32x16 tmp[2];
-        tmp[0] = load_bias_tile(b2 + k * 64, h);
-        tmp[1] = load_bias_tile(b2 + k * 64 + 32, h);
-        layer_pair<P, 2, 2, 4, true>(xs, 0, 0, xi, hid0, b1 + k * 128, h, tmp, ovf, [&](int, f32x16&) {});
-#pragma unroll
-        for (int o = 0; o < 2; ++o)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) out[o][r] = fmaf(efk, tmp[o][r], out[o][r]);
-      } else {
-        add_b2_regs(bf0, bf1, efk, h, out);
-        layer_pair<P, 2, 2, 4>(xs, 0, 0, xi, hid0, b1 + k * 128, h, out, ovf, [&](int, f32x16& hid) { relu_scale16(hid, efk); });
-      }
+      agg_type_step<P>(xs, 0, xi, hid0, b1 + k * 128, b2 + k * 64, bf0, bf1, efk, h, out, ovf);
       hid0 = hid0_next;
       efk = efk_next, bf0 = bn0, bf1 = bn1;
     }
@@ -1841,91 +1886,7 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
   // the wpr waves of a row block each finish 32/wpr of its registers
   if constexpr (P != 1) {
     if (fused) {
-      // ---- fused closing stage: feat of the workgroup's scenes -> LDS, H^T feat and ori of their nodes -> X, closing MLP
-      // per 32-node row block (closing_chain).  The summed registers first (all reads of `part` done), then `part`'s LDS
-      // is reused: F = feat rows [rows_used][kFPitch], X behind it.
-      constexpr int kFPitch = GN_FEAT + 4;
-      f32x4 fv[8];
-      const int w0 = wave - sub, nreg = 32 / wpr;
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        if (u * 4 < nreg) {
-          const int reg0 = sub * nreg + u * 4;
-          f32x4 v = {0.f, 0.f, 0.f, 0.f};
-          for (int jw = 0; jw < wpr; ++jw) {
-            v[0] += part[w0 + jw][reg0 + 0][lane];
-            v[1] += part[w0 + jw][reg0 + 1][lane];
-            v[2] += part[w0 + jw][reg0 + 2][lane];
-            v[3] += part[w0 + jw][reg0 + 3][lane];
-          }
-          fv[u] = v;
-        }
-      }
-      __syncthreads();
-      float* F = part_dyn;
-      float* X = part_dyn + 64 * kFPitch;
-      {
-        const int lr = (wave / wpr) * 32 + (lane & 31);
-        if (lr < rows_used) {
-#pragma unroll
-          for (int u = 0; u < 8; ++u)
-            if (u * 4 < nreg) {
-              const int reg0 = sub * nreg + u * 4;
-              const int o = reg0 >> 4, q = (reg0 & 15) >> 2;
-              *reinterpret_cast<f32x4*>(F + lr * kFPitch + 32 * o + 8 * q + 4 * h) = fv[u];
-            }
-        }
-      }
-      __syncthreads();
-      const int N = G.N, E = G.E;
-      const int scene0 = wg * spw, B = rows / E;
-      const int nodes = min(spw, B - scene0) * N;                  // node rows of this workgroup (>= 1)
-      const T* orib = reinterpret_cast<const T*>(G.ori);
-      ClosingStream<P> cs;
-      cs.init(pick_image<P>(G.m2x, G.m2h), wave, lane, ovf);
-      for (int nb = 0; nb * 32 < nodes; ++nb) {
-        cs.begin();
-        // X[row][0..63] = (sum_e H[b,e,n] feat[b,e]) / divisor in the order of the fused scatter of gn_mlp2 (e ascending,
-        // fmaf), X[row][64..127] = ori[b,n] / divisor; thread (row = t / 8, piece = t % 8) forms two 16-byte pieces of each
-        const int row = (int)threadIdx.x >> 3, piece = (int)threadIdx.x & 7;
-        const int m = min(nb * 32 + row, nodes - 1);               // node of this workgroup (clamped)
-        const int sl = m / N, n = m - sl * N;
-        const float* hcol = G.H + ((size_t)(scene0 + sl) * E) * N + n;
-        f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-        // (the node's incidence column first, all of it in flight at once — E <= 16 here: a load per loop iteration cost
-        // one L2 round trip per hyperedge, 8 k cycles per row block, measured in round 3)
-        float hw[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) hw[e] = e < E ? hcol[(size_t)e * N] : 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-          if (e < E) {
-            const float* fr = F + (sl * E + e) * kFPitch + 4 * piece;
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(fr), v1 = *reinterpret_cast<const f32x4*>(fr + 32);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              a0[c] = fmaf(hw[e], v0[c], a0[c]);
-              a1[c] = fmaf(hw[e], v1[c], a1[c]);
-            }
-          }
-        const T* orow = orib + ((size_t)scene0 * N + m) * GN_FEAT + 4 * piece;
-        f32x4 o0 = ld4(orow), o1 = ld4(orow + 32);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          a0[c] = a0[c] / G.divisor;
-          a1[c] = a1[c] / G.divisor;
-          o0[c] = o0[c] / G.divisor;
-          o1[c] = o1[c] / G.divisor;
-        }
-        float* xr = X + row * kXPitch + 4 * piece;
-        *reinterpret_cast<f32x4*>(xr) = a0;
-        *reinterpret_cast<f32x4*>(xr + 32) = a1;
-        *reinterpret_cast<f32x4*>(xr + 64) = o0;
-        *reinterpret_cast<f32x4*>(xr + 96) = o1;
-        __syncthreads();
-        closing_chain<P, T>(cs, G.m2bias, reinterpret_cast<T*>(G.y), G.ldy, G.dout, scene0 * N + nb * 32, nodes - nb * 32, X,
-                            wring, wave, lane, ovf);
-      }
+      agg_fused_closing<P, T>(G, wg, wave, wpr, sub, lane, h, spw, rows_used, part_dyn, wring, ovf);
       return;
     }
   }
@@ -1935,13 +1896,7 @@ __device__ __forceinline__ void agg_x_body(const GroupTable<AggGroup>& Tb, f32x4
     const int nreg = 32 / wpr;
     for (int rr = 0; rr < nreg; rr += 4) {
       const int reg0 = sub * nreg + rr;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      for (int jw = 0; jw < wpr; ++jw) {
-        v[0] += part[w0 + jw][reg0 + 0][lane];
-        v[1] += part[w0 + jw][reg0 + 1][lane];
-        v[2] += part[w0 + jw][reg0 + 2][lane];
-        v[3] += part[w0 + jw][reg0 + 3][lane];
-      }
+      const f32x4 v = sum_wave_partials(part, w0, wpr, reg0, lane);
       const int o = reg0 >> 4, q = (reg0 & 15) >> 2;
       st4(p + 32 * o + 8 * q, v);
     }
@@ -1952,6 +1907,10 @@ __global__ __launch_bounds__(256, P == 1 ? kOccP1 : 2) void agg_x_kernel(GroupTa
   __shared__ f32x4 wring[kRingF4For<P>];
   run_with_fallback<P>([&](auto pc, ovf_t& ovf) { agg_x_body<decltype(pc)::value, T, PAIRF>(Tb, wring, ovf); });
 }
+
+// step_rb's fence choice as a tag, for the two-row-block kernels' phase lambdas
+using Fence = std::integral_constant<bool, true>;
+using NoFence = std::integral_constant<bool, false>;
 
 // ---- A5 typed MLP, bf16 storage, TWO row blocks per wave (large launches, one wave per row-block pair) --------------
 // A P = 1 sub-step is ONE 32-cycle MFMA against one 1-KiB weight operand: with one row block per wave the LDS operand
@@ -2065,16 +2024,9 @@ __global__ __launch_bounds__(256, 2) void agg_rb2_kernel(GroupTable<AggGroup> Tb
     }
   };
   auto shadow = [&]() {                               // 4 sub-steps x RB MFMAs with V's VALU spread between them
-#pragma unroll
-    for (int i = 0; i < 4 * RB; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, 7, 0);
-      if (i % RB == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    }
+    mfma_shadow<4 * RB, 7, RB, 0x100, 1>();
     __builtin_amdgcn_sched_barrier(0);
   };
-  using Fence = std::integral_constant<bool, true>;
-  using NoFence = std::integral_constant<bool, false>;
 #pragma unroll 1
   for (int k = 0; k < K; ++k) {
     const int kn = k + 1 < K ? k + 1 : k;
@@ -2191,8 +2143,15 @@ __global__ __launch_bounds__(256, 2) void edge_rb2_kernel(GroupTable<gn_edge_gro
       make_parts_relu(hidn[b], 1, xh[b][1]);
     }
   };
-  using Fence = std::integral_constant<bool, true>;
-  using NoFence = std::integral_constant<bool, false>;
+  // V in the shadow of the 4 (an A phase, or pair A's B2) or 2 (pair B's B6) sub-steps x RB MFMAs just issued
+  auto shadowA = [&]() {
+    mfma_shadow<4 * RB, 5, RB, 0x100, 1>();
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto shadowB = [&]() {
+    mfma_shadow<2 * RB, 9, RB, 0x100, 1>();
+    __builtin_amdgcn_sched_barrier(0);
+  };
   // ---- pair A: 64 -> 128 -> 64 (positions 0 .. 31) ----
   {
     f32x16 z[RB][2];
@@ -2207,31 +2166,22 @@ __global__ __launch_bounds__(256, 2) void edge_rb2_kernel(GroupTable<gn_edge_gro
         ws.template step_rb<RB, decltype(fence)::value>(
             s0 + u, [&](int b) -> const Parts<1>& { return xh[b][u & 1]; }, [&](int b) -> f32x16& { return z[b][u >> 1]; });
     };
-    auto shadow = [&]() {
-#pragma unroll
-      for (int i = 0; i < 4 * RB; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
-        if (i % RB == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    };
     Parts<1> xa[RB][2], xb[RB][2];
     A(Fence{}, 0, bi0 + 64);
     V(xa);
     A(NoFence{}, 4, bi0 + 96);
-    shadow();
+    shadowA();
     Bm(Fence{}, 8, xa);
     V(xb);
     A(NoFence{}, 12, bd0);               // (bias tiles 0, 1 of pair B)
-    shadow();
+    shadowA();
     Bm(Fence{}, 16, xb);
     V(xa);
     A(NoFence{}, 20, bd0 + 32);
-    shadow();
+    shadowA();
     V(xb);
     Bm(NoFence{}, 24, xa);
-    shadow();
+    shadowA();
     Bm(Fence{}, 28, xb);
 #pragma unroll
     for (int b = 0; b < RB; ++b) make_parts_tiles<1, 2>(z[b], xi[b], ovf_unused);
@@ -2246,24 +2196,6 @@ __global__ __launch_bounds__(256, 2) void edge_rb2_kernel(GroupTable<gn_edge_gro
       for (int u = 0; u < 2; ++u)
         ws.template step_rb<RB, decltype(fence)::value>(
             s0 + u, [&](int b) -> const Parts<1>& { return xh[b][u & 1]; }, [&](int b) -> f32x16& { return lg[b]; });
-    };
-    auto shadowA = [&]() {
-#pragma unroll
-      for (int i = 0; i < 4 * RB; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
-        if (i % RB == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    auto shadowB = [&]() {
-#pragma unroll
-      for (int i = 0; i < 2 * RB; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 9, 0);
-        if (i % RB == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
     };
     Parts<1> xa[RB][2], xb[RB][2];
     auto tile_ptr = [&](int t) { return bd0 + 32 * (t < 7 ? t : 7); };
@@ -2300,59 +2232,14 @@ __global__ __launch_bounds__(256, 2) void edge_rb2_kernel(GroupTable<gn_edge_gro
     shadowB();
     Bm(Fence{}, 78, xb);                  // B7
   }
-  // ---- epilogue, one row block after the other (as edge_x_kernel) ----
+  // ---- epilogue, one row block after the other ----
   const unsigned long long pbase = G.philox_offset + (offset_dev ? *offset_dev : 0ull);
   auto epilogue = [&](const RowBlock& r, const f32x16& lgb) {
-    long long o1 = r.row_ld, o2 = r.row_ld;
-    bool diag = true;
-    if (G.sym_N > 0) {
-      const int N = G.sym_N, Pn = gn_pair_count(N);
-      const int bb = r.row_ld / Pn, p = r.row_ld - bb * Pn;
-      int i, j;
-      gn_pair_decode(p, N, i, j);
-      o1 = (long long)bb * N * N + i * N + j;
-      o2 = (long long)bb * N * N + j * N + i;
-      diag = i == j;
-    }
+    const OrderedEdges oe = ordered_edges(G, r.row_ld);
     float u1[8], u2[8];
-    fetch_uniforms(G.U, pbase, seed, o1, K, h, u1);
-    if (G.sym_N > 0) fetch_uniforms(G.U, pbase, seed, o2, K, h, u2);
-    float facv = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q)
-      if (feat_of(q, h) == K) facv = lgb[q];
-    facv += __shfl_xor(facv, 32, GN_WAVE);
-    const float sig = 1.f / (1.f + expf(-facv));
-    float d1[8], d2[8];
-    gumbel_softmax_row<true>(lgb, u1, K, tau, h, d1);
-    if (G.sym_N > 0) gumbel_softmax_row<true>(lgb, u2, K, tau, h, d2);
-    if (r.live) {
-      float* frow = G.edge_feat + (size_t)r.row * K;
-      T* dist = reinterpret_cast<T*>(G.dist);
-      if (G.sym_N == 0) {
-        T* drow = dist + (size_t)r.row * K;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int f = feat_of(q, h);
-          if (f < K) {
-            st1(drow + f, d1[q]);
-            frow[f] = sig * d1[q];
-          }
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int f = feat_of(q, h);
-          if (f < K) {
-            if (dist != nullptr) {
-              st1(dist + (size_t)o1 * K + f, d1[q]);
-              if (!diag) st1(dist + (size_t)o2 * K + f, d2[q]);
-            }
-            frow[f] = diag ? 2.f * (sig * d1[q]) : sig * d1[q] + sig * d2[q];
-          }
-        }
-      }
-    }
+    fetch_uniforms(G.U, pbase, seed, oe.o1, K, h, u1);
+    if (G.sym_N > 0) fetch_uniforms(G.U, pbase, seed, oe.o2, K, h, u2);
+    edge_head<true, T>(G, K, r.row, h, r.live, oe, lgb, u1, u2, tau);
   };
   epilogue(rb[0], lg[0]);
   epilogue(rb[1], lg[1]);

@@ -263,6 +263,81 @@ __device__ __forceinline__ void fetch_uniforms(const float* __restrict__ U, unsi
   }
 }
 
+// Unordered-pair row of the pairwise graph (Pn pair rows per scene of N nodes) -> the node rows i <= j of its two ends.
+__device__ __forceinline__ void pair_nodes(int row_ld, int N, int Pn, int& i, int& j) {
+  const int b = row_ld / Pn, p = row_ld - b * Pn;
+  gn_pair_decode(p, N, i, j);
+  i += b * N;
+  j += b * N;
+}
+
+// Ordered edge rows whose uniforms (and `dist` rows) an edge-MLP row owns: itself, or — symmetric pairwise form — the two
+// ordered edges (i,j) and (j,i) of its unordered pair; diag: the self-loop (one ordered edge).
+struct OrderedEdges {
+  long long o1, o2;
+  bool diag;
+};
+__device__ __forceinline__ OrderedEdges ordered_edges(const gn_edge_group_t& G, int row_ld) {
+  OrderedEdges e = {row_ld, row_ld, true};
+  if (G.sym_N > 0) {
+    const int N = G.sym_N, Pn = gn_pair_count(N);
+    const int b = row_ld / Pn, p = row_ld - b * Pn;
+    int i, j;
+    gn_pair_decode(p, N, i, j);
+    e.o1 = (long long)b * N * N + i * N + j;
+    e.o2 = (long long)b * N * N + j * N + i;
+    e.diag = i == j;
+  }
+  return e;
+}
+
+// The edge head's epilogue (A4), the one copy every edge kernel calls.  Features 0..K-1 of `lg` are the logits of this
+// lane's row, feature K the factor pre-activation; a row's features are split over its two lanes (j, h=0) and (j, h=1).
+// Writes dist (storage type T) and edge_feat = sigmoid(factor) * dist; u2 is read in the symmetric form only.  K and the
+// row block's row / h / live come as scalars: taken through G and a RowBlock reference, edge_x_kernel<2, float> spilled
+// five registers more behind its range vote.
+template <bool FAST, typename T>
+__device__ __forceinline__ void edge_head(const gn_edge_group_t& G, int K, int row, int h, bool live,
+                                          const OrderedEdges& e, const f32x16& lg, const float (&u1)[8],
+                                          const float (&u2)[8], float tau) {
+  float facv = 0.f;
+#pragma unroll
+  for (int r = 0; r < 8; ++r)
+    if (feat_of(r, h) == K) facv = lg[r];
+  facv += __shfl_xor(facv, 32, GN_WAVE);   // exactly one of the two lanes holds it, the other has 0
+  const float sig = 1.f / (1.f + expf(-facv));
+  float d1[8], d2[8];
+  gumbel_softmax_row<FAST>(lg, u1, K, tau, h, d1);
+  if (G.sym_N > 0) gumbel_softmax_row<FAST>(lg, u2, K, tau, h, d2);
+  if (!live) return;
+  float* frow = G.edge_feat + (size_t)row * K;
+  T* dist = reinterpret_cast<T*>(G.dist);
+  if (G.sym_N == 0) {
+    T* drow = dist + (size_t)row * K;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int f = feat_of(r, h);
+      if (f < K) {
+        st1(drow + f, d1[r]);
+        frow[f] = sig * d1[r];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int f = feat_of(r, h);
+      if (f < K) {
+        if (dist != nullptr) {
+          st1(dist + (size_t)e.o1 * K + f, d1[r]);
+          if (!e.diag) st1(dist + (size_t)e.o2 * K + f, d2[r]);
+        }
+        // both ordered edges meet the same typed MLP output downstream; the self-loop has weight 2
+        frow[f] = e.diag ? 2.f * (sig * d1[r]) : sig * d1[r] + sig * d2[r];
+      }
+    }
+  }
+}
+
 // ---- fused node -> edge pooling: the rows of the edge MLP formed on the fly (gn_edge_group_t.xp) -------------------
 // Lane (row, h) of a 32-row block produces its 32 features of edges[row] exactly as node2edge_kernel writes them
 // (MS_HGNN_batch.py:127-141, 359-370; decomposed attention  att[e,n] = w2 . relu(P_n + (H Qn)_e) + b2).  The 32

@@ -231,26 +231,14 @@ __global__ __launch_bounds__(256, 2) void edge_mlp_gumbel_kernel(GroupTable<gn_e
   const RowBlock rb = row_block(rows, blk);
   f32x16 in[2], z[2], lg[1];
   load_rows<2>(G.edges, GN_FEAT, rb.row_ld, rb.h, in);
-  // Ordered edge rows whose uniforms this row consumes: itself, or — symmetric pairwise form — the two
-  // ordered edges (i,j) and (j,i) of its unordered pair.
-  long long o1 = rb.row_ld, o2 = rb.row_ld;
-  bool diag = true;
-  if (G.sym_N > 0) {
-    const int N = G.sym_N, P = gn_pair_count(N);
-    const int b = rb.row_ld / P, p = rb.row_ld - b * P;
-    int i, j;
-    gn_pair_decode(p, N, i, j);
-    o1 = (long long)b * N * N + i * N + j;
-    o2 = (long long)b * N * N + j * N + i;
-    diag = i == j;
-  }
+  const OrderedEdges oe = ordered_edges(G, rb.row_ld);
   // With a U tensor the loads are issued now, far ahead of the epilogue; Philox values are computed on
   // the VALU after the MFMAs are queued (no HBM traffic, no extra launch).
   float u1[8], u2[8];
   const unsigned long long pbase = G.philox_offset + (offset_dev ? *offset_dev : 0ull);
   if (G.U != nullptr) {
-    fetch_uniforms(G.U, 0ull, 0ull, o1, K, rb.h, u1);
-    if (G.sym_N > 0) fetch_uniforms(G.U, 0ull, 0ull, o2, K, rb.h, u2);
+    fetch_uniforms(G.U, 0ull, 0ull, oe.o1, K, rb.h, u1);
+    if (G.sym_N > 0) fetch_uniforms(G.U, 0ull, 0ull, oe.o2, K, rb.h, u2);
   }
   // Two layer PAIRS (64->128->64 and 64->256->32), each evaluated hidden-tile by hidden-tile: hidden tile t
   // (8 steps) is produced, and while tile t+1 is being produced its ReLU runs in the MFMA shadow; then the
@@ -326,49 +314,11 @@ __global__ __launch_bounds__(256, 2) void edge_mlp_gumbel_kernel(GroupTable<gn_e
     }
   }
   if (G.U == nullptr) {
-    fetch_uniforms(nullptr, pbase, seed, o1, K, rb.h, u1);
-    if (G.sym_N > 0) fetch_uniforms(nullptr, pbase, seed, o2, K, rb.h, u2);
+    fetch_uniforms(nullptr, pbase, seed, oe.o1, K, rb.h, u1);
+    if (G.sym_N > 0) fetch_uniforms(nullptr, pbase, seed, oe.o2, K, rb.h, u2);
   }
   if (G.keep_lgf != nullptr) store_rows<1>(G.keep_lgf, 32, rb.row, rb.h, rb.live, lg);
-
-  // Epilogue.  Features 0..K-1 of `lg` are the logits of this lane's row, feature K the factor
-  // pre-activation; a row's features are split over its two lanes (j, h=0) and (j, h=1).
-  float facv = 0.f;
-#pragma unroll
-  for (int r = 0; r < 8; ++r)
-    if (feat_of(r, rb.h) == K) facv = lg[0][r];
-  facv += __shfl_xor(facv, 32, GN_WAVE);  // exactly one of the two lanes holds it, the other has 0
-  const float sig = 1.f / (1.f + expf(-facv));
-  float d1[8], d2[8];
-  gumbel_softmax_row(lg[0], u1, K, tau, rb.h, d1);
-  if (G.sym_N > 0) gumbel_softmax_row(lg[0], u2, K, tau, rb.h, d2);
-  if (rb.live) {
-    float* frow = G.edge_feat + (size_t)rb.row * K;
-    if (G.sym_N == 0) {
-      float* drow = G.dist + (size_t)rb.row * K;
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int f = feat_of(r, rb.h);
-        if (f < K) {
-          drow[f] = d1[r];
-          frow[f] = sig * d1[r];
-        }
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int f = feat_of(r, rb.h);
-        if (f < K) {
-          if (G.dist != nullptr) {
-            G.dist[(size_t)o1 * K + f] = d1[r];
-            if (!diag) G.dist[(size_t)o2 * K + f] = d2[r];
-          }
-          // both ordered edges meet the same typed MLP output downstream; the self-loop has weight 2
-          frow[f] = diag ? 2.f * (sig * d1[r]) : sig * d1[r] + sig * d2[r];
-        }
-      }
-    }
-  }
+  edge_head<false, float>(G, K, rb.row, rb.h, rb.live, oe, lg[0], u1, u2, tau);
 }
 
 // ---- A5, pairwise graph: layer 1 per node, layer 2 per unordered pair -------------------------------
@@ -463,14 +413,9 @@ __global__ __launch_bounds__(256, 2) void agg_mlp_kernel(GroupTable<AggGroup> T)
       }
     };
     int i = 0, j = 0;
-    {
-      const int b = rb.row_ld / P, p = rb.row_ld - b * P;
-      gn_pair_decode(p, N, i, j);
-      i += b * N - node0;
-      j += b * N - node0;
-    }
-    const float* Si = stage + i * kStagePitch;
-    const float* Sj = stage + j * kStagePitch;
+    pair_nodes(rb.row_ld, N, P, i, j);
+    const float* Si = stage + (i - node0) * kStagePitch;
+    const float* Sj = stage + (j - node0) * kStagePitch;
     WRing ring;
     ring_prime(ring, Wl);
     fetch(0);
@@ -526,12 +471,7 @@ __global__ __launch_bounds__(256, 2) void agg_mlp_kernel(GroupTable<AggGroup> T)
     if (k < K && any_rows) {
       const int N = G.N, P = G.E;
       int i, j;
-      {
-        const int b = rb.row_ld / P, p = rb.row_ld - b * P;
-        gn_pair_decode(p, N, i, j);
-        i += b * N;
-        j += b * N;
-      }
+      pair_nodes(rb.row_ld, N, P, i, j);
       const size_t ldA = (size_t)K * 128;
       const float* Ai = G.A + (size_t)i * ldA;
       const float* Aj = G.A + (size_t)j * ldA;
