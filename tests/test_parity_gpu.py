@@ -11,6 +11,7 @@ import torch
 
 from conftest import case_names, load_case, load_state, uniforms, weights_for
 from oracle import ms_hgnn_oracle as O
+from scene_isolation_cases import prob_gate as _prob_gate
 
 pytestmark = pytest.mark.gpu
 
@@ -889,11 +890,7 @@ def _extreme_magnitudes(in_scale, w_scale, slack):
     d64 = lambda st: {k: v.double() for k, v in st.items()}
     _, fac_p64 = O.ms_hgnn_pairwise_forward(d64(sp), h.double(), [u.double() for u in Up], decomposed=True)
 
-    def prob_gate(got, ref32, ref64):
-        own = float((ref32.double() - ref64).abs().max())               # what fp32 rounding alone does to the oracle
-        err = float((got.detach().cpu().double() - ref64).abs().max())
-        print(f"probabilities: HIP vs float64 oracle {err:.2e}, fp32 oracle vs float64 {own:.2e}")
-        return err <= slack * max(1e-4, 3.0 * own)
+    prob_gate = lambda got, ref32, ref64: _prob_gate(got, ref32, ref64, slack)     # (shared with the scene-isolation tests)
 
     with torch.no_grad():
         a, b = pair(h.to(dev()), noise_u=[u.to(dev()) for u in Up])
