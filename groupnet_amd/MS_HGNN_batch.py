@@ -295,8 +295,8 @@ class _MessagePassing(nn.Module):
     def _edge2node(self, edge_feat: Tensor, ori: Tensor, H: Optional[Tensor], idx: int) -> Tensor:
         return self.edge_aggregation_list[idx]._aggregate(edge_feat, H, ori)
 
-    def _run(self, h: Tensor, H, E: int, noise_u, out: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
-        return run_message_passing([self], [h], [H], [noise_u], [out])[0]
+    def _run(self, h: Tensor, H, E: int, noise_u, out: Optional[Tensor] = None, n_agents=None) -> Tuple[Tensor, Tensor]:
+        return run_message_passing([self], [h], [H], [noise_u], [out], n_agents=n_agents)[0]
 
     def _forward_autograd(self, h: Tensor, H: Optional["ops.Incidence"], noise_u, out: Optional[Tensor]
                           ) -> Tuple[Tensor, Tensor]:
@@ -332,7 +332,7 @@ def _check_storage_width(bottleneck_dim: int, dtype: torch.dtype) -> None:
 
 def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor], Hs: Sequence, noises: Sequence,
                         outs: Sequence[Optional[Tensor]], traces=None, join=None, affinity=None,
-                        fuse_closing: bool = False) -> List[Tuple[Tensor, Tensor]]:
+                        fuse_closing: bool = False, n_agents=None) -> List[Tuple[Tensor, Tensor]]:
     """The message-passing rounds of SEVERAL modules over the same scenes, stage by stage, each stage
     ONE grouped launch (model/MS_HGNN_batch.py:174-195 and :425-441 for every module at once).
 
@@ -357,7 +357,12 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     gather and scatter launches read the masks instead of H, and so does the node->edge launch where it takes its row
     form (bit-identical results) — in inference and in a training forward (`traces`, which receive the masks the step
     runs on: the backward reads them there, so both directions of a step run in one form); otherwise masks are
-    ignored."""
+    ignored.
+    `n_agents` (a ragged batch: `ops.agent_counts`; inference only): scene b holds n_b <= N agents, its first rows, and
+    Hs are the ragged incidences (zero rows and columns >= n_b).  The forward takes the ragged route: the node->edge
+    launch and the scatter launch receive the counts, everything else is row-wise or meets the padding only through
+    zeros of H, and ONE more launch zeroes the padded positions of every node_feat and factors at the end.  Counts that
+    all equal N are no counts."""
     n = len(mods)
     if not (n == len(hs) == len(Hs) == len(noises) == len(outs)) or n == 0:
         raise ValueError("run_message_passing: one h, H, noise and out per module")
@@ -366,13 +371,17 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
         raise ValueError("grouped modules must share nmp_layers and bottleneck_dim")
     _check_storage_width(mods[0].bottleneck_dim, hs[0].dtype)
     B, N = hs[0].shape[0], hs[0].shape[1]
+    counts = ops.agent_counts(n_agents, B, N, hs[0].device)
+    if counts is not None and traces is not None:
+        raise NotImplementedError("n_agents: ragged batches are inference-only")
+    ragged = {} if counts is None else {"n_agents": counts}      # what the two count-aware launches are handed
     incs = [H if H is None or isinstance(H, ops.Incidence) else ops.Incidence(H) for H in Hs]
     rt = route.message_passing_route(
         N, tuple([(g is None, m.edge_types) for g, m in zip(incs, mods)]), twin=hs[0].dtype == torch.bfloat16,
         training=traces is not None, matrix16=ops.BF16X6,
         knobs=route.Knobs(_FUSE_POOL, ops.POOL_MAX_N, ops.node_form_enabled(),
                           ops.incidence_form() == "mask" and all(g is None or g.masks is not None for g in incs)),
-        closing_asked=fuse_closing)
+        closing_asked=fuse_closing, ragged=counts is not None)
     # every module's graph as the ops item tuples take it: the dense H (None: pairwise), sym, the masks where the step
     # reads them.  The pairwise graph is symmetric: edges (i,j) and (j,i) pool the same feature, meet the same typed
     # MLP output and are summed into the same two nodes.  Its per-edge MLPs therefore run once per
@@ -410,7 +419,7 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
         edges: List = [None] * n
         if rt.node2edge:
             for i, e in zip(rt.node2edge, ops.node2edge_grouped([(xpq[i][0], xpq[i][1], dense[i], pks[i]["w2"], pks[i]["b2"],
-                                                                  syms[i], masks[i]) for i in rt.node2edge])):
+                                                                  syms[i], masks[i]) for i in rt.node2edge], **ragged)):
                 edges[i] = e
         for i, r in enumerate(rt.modules):
             if r.pool_in_edge_kernel:
@@ -454,7 +463,7 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
                 return closed, None
         feats = ops.agg_mlp_grouped(items)
         # larger graphs: one stand-alone scatter launch for the modules whose aggregation wrote per-edge features
-        scat = dict(zip(rt.scatter, ops.agg_scatter_grouped([(feats[i], dense[i], oris[i], syms[i], masks[i]) for i in rt.scatter]))) if rt.scatter else {}
+        scat = dict(zip(rt.scatter, ops.agg_scatter_grouped([(feats[i], dense[i], oris[i], syms[i], masks[i]) for i in rt.scatter], **ragged))) if rt.scatter else {}
         # cat(H^T feat, ori) / N is formed inside the MLP kernel that consumes it (node form: H^T feat is what the
         # aggregation kernel wrote), or is the scatter launch's output
         return None, [ops.NodeAggSpec(feats[i], oris[i]) if r.closing_input == route.NODE_AGG else
@@ -503,6 +512,10 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     if traces is not None:
         for t, kd in zip(traces, keep):
             t.tails.append(kd)
+    if counts is not None:      # the padded rows of the outputs went through the row-wise stages: zero them, one launch
+        ops.zero_padding([(x, ops.ZERO_NODE_ROWS) for x in node_feats] +
+                         [(fc, ops.ZERO_PAIR_ROWS if H is None else ops.ZERO_EDGE_ROWS) for fc, H in zip(factors, dense)],
+                         counts)
     return list(zip(node_feats, factors))
 
 
@@ -534,19 +547,26 @@ class MS_HGNN_oridinary(_MessagePassing):
     def edge2node(self, x, rel_rec, rel_send, ori, idx):
         return self._edge2node(x, ori, None, idx)
 
-    def forward(self, h_states, noise_u=None, out=None):
+    def forward(self, h_states, noise_u=None, out=None, n_agents=None):
         """``out`` (optional): where node_feat is written, e.g. a column block of the caller's
         concatenated feature tensor.  Under autograd (an input or a parameter requires grad) the call
-        goes through `groupnet_amd.backward.MSHGNNFunction`: same fused forward, HIP backward."""
+        goes through `groupnet_amd.backward.MSHGNNFunction`: same fused forward, HIP backward.
+        ``n_agents`` (optional; INTEGRATION.md, "Ragged batches"): one count per scene, 1 <= n_b <= N — the first n_b
+        agent rows of scene b are real, the rest is (finite) padding.  Valid node rows and edges (i, j < n_b; the noise
+        is read at the padded index i*N + j) are what the module computes for the scene alone; padded positions of both
+        outputs are zeros.  Inference only."""
         ops._req(h_states, "h_states", (None, None, self.h_dim), ops._ACT_DTYPES)
         N = h_states.shape[1]
+        n_agents = ops.agent_counts(n_agents, h_states.shape[0], N, h_states.device) if h_states.shape[0] and N else None
         if h_states.shape[0] and N and _needs_grad(self, h_states):
+            if n_agents is not None:
+                raise NotImplementedError("n_agents: ragged batches are inference-only (call under torch.no_grad())")
             return self._forward_autograd(h_states, None, noise_u, out)
         _check_storage_width(self.bottleneck_dim, h_states.dtype)
         if h_states.shape[0] == 0 or N == 0:      # empty batch: nothing to launch
             nf = out if out is not None else h_states.new_empty((h_states.shape[0], N, self.bottleneck_dim))
             return nf, h_states.new_empty((h_states.shape[0], N * N, self.edge_types))
-        return self._run(h_states, None, N * N, noise_u, out)
+        return self._run(h_states, None, N * N, noise_u, out, n_agents)
 
 
 class MS_HGNN_hyper(_MessagePassing):
@@ -575,12 +595,13 @@ class MS_HGNN_hyper(_MessagePassing):
         self._build(h_dim, bottleneck_dim, nmp_layers)
         self.listall = False
 
-    def init_adj_attention(self, feat, feat_corr, scale_factor=2):
-        """H (B,E,N) from the affinity matrix (model/MS_HGNN_batch.py:372-388)."""
+    def init_adj_attention(self, feat, feat_corr, scale_factor=2, n_agents=None):
+        """H (B,E,N) from the affinity matrix (model/MS_HGNN_batch.py:372-388).  ``n_agents``: the incidence of a
+        ragged batch (`ops.topk_incidence`)."""
         if feat_corr.dtype == torch.bfloat16:     # ranked in fp32 either way; fp32 corr keeps near-ties apart
             feat_corr = feat_corr.float()
         ops._req(feat_corr, "corr", (feat.shape[0], feat.shape[1], feat.shape[1]))
-        return ops.topk_incidence(feat_corr, [int(scale_factor)])[0]
+        return ops.topk_incidence(feat_corr, [int(scale_factor)], n_agents)[0]
 
     def init_adj_attention_listall(self, feat, feat_corr, scale_factor=2):
         """H (B,E,N) by exhaustive search of the best group per agent (model/MS_HGNN_batch.py:390-414);
@@ -598,13 +619,34 @@ class MS_HGNN_hyper(_MessagePassing):
     def edge2node(self, x, ori, H, idx):
         return self._edge2node(x, ori, H, idx)
 
-    def forward(self, h_states, corr, noise_u=None, H=None, out=None, masks=None):
+    def forward(self, h_states, corr, noise_u=None, H=None, out=None, masks=None, n_agents=None):
         """``H`` (optional) lets a caller that already built the incidence for every scale in one
         fused launch (``ops.affinity_topk``) hand it in; by default it is built here from ``corr``.
         ``masks`` (optional): the `ops.IncidenceMasks` of a caller-supplied ``H``, used when the mask form is
         switched on (`masks_apply`); an ``H`` handed in without them stays dense (it may carry other weights than 0/1),
-        an ``H`` built here gets its masks from the builder."""
+        an ``H`` built here gets its masks from the builder.
+        ``n_agents`` (optional; INTEGRATION.md, "Ragged batches"): one count per scene, 1 <= n_b <= N.  Row i < n_b of
+        H holds the top-min(scale, n_b) of corr[b, i, :n_b], a module with scale == N (the padded size) has its one
+        hyperedge hold the n_b valid agents; a scene with n_b <= scale < N gets n_b identical all-member hyperedges (the
+        E = 1 shortcut is keyed on N).  Valid rows of node_feat and factor are what the module computes for the scene
+        alone; padded positions of the three outputs are zeros; padded rows of h_states and corr must be finite.
+        Inference only, top-k incidence built here only (no ``H=`` / ``masks=``, no ``listall``)."""
         ops._req(h_states, "h_states", (None, None, self.h_dim), ops._ACT_DTYPES)
+        n_agents = (ops.agent_counts(n_agents, h_states.shape[0], h_states.shape[1], h_states.device)
+                    if h_states.shape[0] and h_states.shape[1] else None)
+        if n_agents is not None:
+            if H is not None or masks is not None:
+                raise ValueError("n_agents: the ragged incidence is built here; H= / masks= cannot be handed in with it")
+            if self.listall:
+                raise NotImplementedError("n_agents: the exhaustive (listall) search has no ragged form")
+            if _needs_grad(self, h_states):
+                raise NotImplementedError("n_agents: ragged batches are inference-only (call under torch.no_grad())")
+            if self.scale > h_states.shape[1]:
+                raise RuntimeError("selected index k out of range")
+            _check_storage_width(self.bottleneck_dim, h_states.dtype)
+            H = self.init_adj_attention(h_states, corr, scale_factor=self.scale, n_agents=n_agents)
+            node_feat, factor = self._run(h_states, ops.Incidence(H), H.shape[1], noise_u, out, n_agents)
+            return node_feat, factor, (H if H.dtype == h_states.dtype else H.to(h_states.dtype))
         if h_states.shape[0] and _needs_grad(self, h_states):
             # H is a constant of the backward (top-k selection has no gradient; corr is only used to build it)
             if H is None:

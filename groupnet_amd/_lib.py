@@ -14,10 +14,13 @@ import torch  # noqa: F401  (must be imported before the .so is loaded)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GROUPNET_HIP_LIB") or os.path.join(_HERE, "libgroupnet_hip.so")  # env: tuning builds
-ABI_VERSION = 38
+ABI_VERSION = 39
 
 GN_OK = 0
+GN_ERR_NULL = -1
+GN_ERR_SHAPE = -2
 GN_ERR_K_RANGE = -3
+GN_ERR_ALIGN = -4
 GN_ERR_LDS = -6
 
 _P = ctypes.c_void_p
@@ -75,6 +78,12 @@ class ScatterGroup(ctypes.Structure):
     __slots__ = ()
     c_name = "gn_scatter_group_t"
     _fields_ = [("feat", _P), ("H", _P), ("ori", _P), ("out", _P), ("E", _I), ("sym", _I), ("colmask", _P)]
+
+
+class ZeroItem(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_zero_item_t"
+    _fields_ = [("ptr", _P), ("pitch", ctypes.c_longlong), ("width", _I), ("kind", _I)]
 
 
 class Mlp2Group(ctypes.Structure):
@@ -149,8 +158,12 @@ K_AGG_GATHER, K_AGG_GATHER_MASK = 15, 16      # GN_K_*: the two forms of the sta
 K_AGG_SCENE, K_AGG_GATHER_PAIRWISE = 17, 18   # ... the kernels of a group's own launch (LaunchPlan.pre_kernel)
 K_AFFINITY_TOPK, K_AFFINITY_TOPK_MASKS, K_AFFINITY_BANDED, K_TOPK_INCIDENCE = 19, 20, 21, 22      # ... the graph stage
 K_AGG_SCATTER, K_AGG_SCATTER_MASK, K_AGG_SCATTER_DIRECT, K_AGG_SCATTER_PAIRS = 23, 24, 25, 26     # ... the scatter
-K_LAST = K_AGG_SCATTER_PAIRS
+# ... the ragged entry points
+K_AFFINITY_TOPK_RAGGED, K_TOPK_INCIDENCE_RAGGED, K_NODE2EDGE_RAGGED, K_AGG_SCATTER_RAGGED, K_ZERO_PADDING = 27, 28, 29, 30, 31
+K_LAST = K_ZERO_PADDING
 MAX_GROUPS = 10
+MAX_ZERO_ITEMS = 24
+ZERO_NODE_ROWS, ZERO_EDGE_ROWS, ZERO_PAIR_ROWS = 0, 1, 2      # gn_zero_item_t.kind
 
 # name -> (restype, argtypes); mirrors include/groupnet_hip.h one to one
 SIGNATURES = {
@@ -219,6 +232,27 @@ SIGNATURES = {
     "gn_affinity_topk_plan_bf16": (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I), _I, _I, _I, _I,
                                         ctypes.POINTER(BlockExtras), ctypes.POINTER(_P), ctypes.POINTER(_P),
                                         ctypes.POINTER(LaunchPlan)]),
+    "gn_affinity_topk_ragged_f32": (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I), _I, _I, _I, _I,
+                                         ctypes.POINTER(BlockExtras), _P, _P]),
+    "gn_affinity_topk_ragged_bf16": (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I), _I, _I, _I, _I,
+                                          ctypes.POINTER(BlockExtras), _P, _P]),
+    "gn_affinity_topk_ragged_plan_f32": (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I), _I, _I, _I, _I,
+                                              ctypes.POINTER(BlockExtras), _P, ctypes.POINTER(LaunchPlan)]),
+    "gn_affinity_topk_ragged_plan_bf16": (_I, [_P, _P, ctypes.POINTER(_P), ctypes.POINTER(_I), _I, _I, _I, _I,
+                                               ctypes.POINTER(BlockExtras), _P, ctypes.POINTER(LaunchPlan)]),
+    "gn_topk_incidence_ragged_f32": (_I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_I), _I, _I, _I, _P, _P]),
+    "gn_topk_incidence_ragged_plan_f32": (_I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_I), _I, _I, _I, _P,
+                                               ctypes.POINTER(LaunchPlan)]),
+    "gn_node2edge_ragged_f32": (_I, [ctypes.POINTER(N2EGroup), _I, _I, _I, _P, _P]),
+    "gn_node2edge_ragged_bf16": (_I, [ctypes.POINTER(N2EGroup), _I, _I, _I, _P, _P]),
+    "gn_node2edge_ragged_plan_f32": (_I, [ctypes.POINTER(N2EGroup), _I, _I, _I, _P, ctypes.POINTER(LaunchPlan)]),
+    "gn_node2edge_ragged_plan_bf16": (_I, [ctypes.POINTER(N2EGroup), _I, _I, _I, _P, ctypes.POINTER(LaunchPlan)]),
+    "gn_agg_scatter_ragged_f32": (_I, [ctypes.POINTER(ScatterGroup), _I, _I, _I, _F, _P, _P]),
+    "gn_agg_scatter_ragged_bf16": (_I, [ctypes.POINTER(ScatterGroup), _I, _I, _I, _F, _P, _P]),
+    "gn_agg_scatter_ragged_plan_f32": (_I, [ctypes.POINTER(ScatterGroup), _I, _I, _I, _F, _P, ctypes.POINTER(LaunchPlan)]),
+    "gn_agg_scatter_ragged_plan_bf16": (_I, [ctypes.POINTER(ScatterGroup), _I, _I, _I, _F, _P, ctypes.POINTER(LaunchPlan)]),
+    "gn_zero_padding": (_I, [ctypes.POINTER(ZeroItem), _I, _I, _I, _P, _P]),
+    "gn_zero_padding_plan": (_I, [ctypes.POINTER(ZeroItem), _I, _I, _I, _P, ctypes.POINTER(LaunchPlan)]),
     "gn_gemm_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _F, _F, _P]),
     "gn_gemm_grouped_f32": (_I, [ctypes.POINTER(GemmDesc), _I, _P]),
     "gn_typed_bwd_f32": (_I, [_P, _P, _P, _I, _P, _P, _P, ctypes.c_longlong, _I, _I, _P]),

@@ -55,6 +55,28 @@ __device__ __forceinline__ void emit_ranked(int rank, int N, int b, int i, int c
   }
 }
 
+// ... of a scene with nb <= N valid agents (gn_affinity_topk_ragged_*, gn_topk_incidence_ragged_f32): `rank` counts the
+// columns < nb that beat c, so rank < k selects the top-min(k, nb) of the valid columns; rows and columns >= nb are
+// zeros, and the single hyperedge of a scale-N module holds the nb valid agents.
+template <typename T>
+__device__ __forceinline__ void emit_ranked_ragged(int rank, int nb, int N, int b, int i, int c, const ScaleList& sl) {
+  T* H_cat = reinterpret_cast<T*>(sl.H_cat);
+  const bool valid = i < nb && c < nb;
+  for (int s = 0; s < sl.n; ++s) {
+    if (sl.k[s] == N) {
+      if (i == 0) {
+        const float v = c < nb ? 1.f : 0.f;
+        sl.H[s][(size_t)b * N + c] = v;
+        if (H_cat) st1(H_cat + ((size_t)b * sl.cat_rows + sl.cat_off[s]) * N + c, v);
+      }
+    } else {
+      const float v = valid && rank < sl.k[s] ? 1.f : 0.f;
+      sl.H[s][((size_t)b * N + i) * N + c] = v;
+      if (H_cat) st1(H_cat + ((size_t)b * sl.cat_rows + sl.cat_off[s] + i) * N + c, v);
+    }
+  }
+}
+
 // One workgroup per scene.  f rows are normalised into LDS (stride D+4 floats keeps the
 // 16-byte row reads of different rows on different banks); corr is formed once per UNORDERED pair (the dot product
 // is symmetric term by term, so corr[j][i] is the same bits), optionally written out, and kept in LDS as ranking keys,
@@ -62,11 +84,16 @@ __device__ __forceinline__ void emit_ranked(int rank, int N, int b, int i, int c
 // MASKS (with `ml`): the ranking loop also ORs every member into 2 n_scales N 64-bit words behind the raw inputs (row words
 // of scale s at (2s)N, column words at (2s+1)N; zeroed before the first barrier), which one more barrier later go out
 // coalesced — read off the same ranks as H_s, order-independent, hence deterministic.
-template <typename T, bool MASKS = false>
+// RAGGED (with `n_valid`, stand-alone launch only): scene b has n_valid[b] (clamped to [0, N]) valid agents, its first
+// rows.  Every row is still staged and normalised (padded rows must be finite), the affinity of a pair with a padded end
+// is written as 0, the ranking runs over the valid columns alone (emit_ranked_ragged).
+template <typename T, bool MASKS = false, bool RAGGED = false>
 __device__ __forceinline__ void affinity_topk_body(const T* __restrict__ f, float* __restrict__ corr, const ScaleList& sl,
                                                    int N, int D, const gn_block_extras_t& ex, int b, float* lds,
-                                                   const MaskList* ml = nullptr) {
+                                                   const MaskList* ml = nullptr, const int* n_valid = nullptr) {
   constexpr int kBlock = 256;
+  int nb = N;
+  if constexpr (RAGGED) nb = min(max(n_valid[b], 0), N);
   const int ldq = D + 4;
   float* q = lds;             // N x ldq
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(lds + N * ldq + ((N * ldq) & 1));  // N x N, 8-byte aligned
@@ -131,6 +158,9 @@ __device__ __forceinline__ void affinity_topk_body(const T* __restrict__ f, floa
       acc = fmaf(x[2], y[2], acc);
       acc = fmaf(x[3], y[3], acc);
     }
+    if constexpr (RAGGED) {
+      if (j >= nb) acc = 0.f;      // (i <= j: a padded end)
+    }
     keys[i * N + j] = rank_key(acc, j);
     keys[j * N + i] = rank_key(acc, i);
     if (corr) {
@@ -145,8 +175,13 @@ __device__ __forceinline__ void affinity_topk_body(const T* __restrict__ f, floa
     const unsigned long long* row = keys + i * N;
     const unsigned long long kc = row[c];
     int rank = 0;
-    for (int j = 0; j < N; ++j) rank += row[j] > kc ? 1 : 0;
-    emit_ranked<T>(rank, N, b, i, c, sl);
+    if constexpr (RAGGED) {
+      for (int j = 0; j < nb; ++j) rank += row[j] > kc ? 1 : 0;
+      emit_ranked_ragged<T>(rank, nb, N, b, i, c, sl);
+    } else {
+      for (int j = 0; j < N; ++j) rank += row[j] > kc ? 1 : 0;
+      emit_ranked<T>(rank, N, b, i, c, sl);
+    }
     if constexpr (MASKS) {
       for (int s = 0; s < sl.n; ++s) {
         if (sl.k[s] != N && rank < sl.k[s]) {

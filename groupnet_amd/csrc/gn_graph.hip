@@ -64,6 +64,15 @@ __global__ __launch_bounds__(kBlock) void affinity_topk_masks_kernel(const T* __
   affinity_topk_body<T, true>(f, corr, sl, N, D, ex, (int)blockIdx.x, lds, &ml);
 }
 
+// the same launch over scenes with n_valid[b] <= N agents each (a kernel of its own, as the mask form is)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void affinity_topk_ragged_kernel(const T* __restrict__ f, float* __restrict__ corr,
+                                                                      ScaleList sl, int N, int D, gn_block_extras_t ex,
+                                                                      const int* __restrict__ n_valid) {
+  extern __shared__ __align__(16) float lds[];
+  affinity_topk_body<T, false, true>(f, corr, sl, N, D, ex, (int)blockIdx.x, lds, nullptr, n_valid);
+}
+
 // Bit-mask form of a dense incidence H (B,E,N), E, N <= 64: rowmask (B,E), colmask (B,N).  A workgroup owns kMaskScenes
 // consecutive scenes, whose H tiles are contiguous: coalesced reads, one LDS OR per non-zero entry (top-k rows are sparse),
 // coalesced word writes.  Any entry that is neither 0 nor 1 (a NaN included) raises *nonbinary; its bit is set.
@@ -169,6 +178,29 @@ __global__ __launch_bounds__(kBlock) void topk_incidence_kernel(const float* __r
   }
 }
 
+// The banded top-k over scenes with n_valid[b] <= N agents each: row i < nb ranks its columns < nb (the same rules),
+// everything else of H is zeros, a scale-N hyperedge holds the nb valid agents (emit_ranked_ragged).
+__global__ __launch_bounds__(kBlock) void topk_incidence_ragged_kernel(const float* __restrict__ corr, ScaleList sl, int N,
+                                                                       int RB, const int* __restrict__ n_valid) {
+  extern __shared__ __align__(16) float lds[];  // RB x N
+  const int b = blockIdx.y, i0 = blockIdx.x * RB;
+  const int nr = min(RB, N - i0);
+  const int nb = min(max(n_valid[b], 0), N);
+  const float* src = corr + ((size_t)b * N + i0) * N;
+  for (int idx = threadIdx.x; idx < nr * N; idx += kBlock) lds[idx] = src[idx];
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < nr * N; idx += kBlock) {
+    const int i = idx / N, c = idx - i * N;
+    const float* row = lds + i * N;
+    int rank = 0;
+    if (i0 + i < nb && c < nb) {
+      const float v = row[c];
+      for (int j = 0; j < nb; ++j) rank += beats(row[j], j, v, c) ? 1 : 0;
+    }
+    emit_ranked_ragged<float>(rank, nb, N, b, i0 + i, c, sl);
+  }
+}
+
 // --------------------------------------------------------------------------------------------
 // group tables (kernel arguments, by value): one launch serves the same stage of several modules
 // --------------------------------------------------------------------------------------------
@@ -209,9 +241,11 @@ __device__ __forceinline__ float gn_half_max(float v) {
 __host__ __device__ inline size_t n2e_hyper_scratch_floats(int EB, int N) {
   return (size_t)3 * EB * N + (size_t)EB * 33 + (size_t)3 * EB + 8;
 }
-template <typename TS>
+// RAGGED (here and in the two bodies below; gn_node2edge_ragged_*): scene b pools over its n_valid[b] (clamped to [0, N])
+// valid nodes — the count stands where N enters the softmax: the number of non-members and whether one exists.
+template <typename TS, bool RAGGED = false>
 __device__ __forceinline__ void node2edge_hyper_body(const WaveTable<gn_n2e_group_t>& T, int B, int N, int SG, int EB,
-                                                     int wg) {
+                                                     int wg, const int* __restrict__ n_valid = nullptr) {
   extern __shared__ __align__(16) float lds[];
   constexpr int LDP = GN_FEAT + 1, LDQ = 33;
   const int wave = gn_uniform((int)(threadIdx.x >> 6));
@@ -338,13 +372,15 @@ __device__ __forceinline__ void node2edge_hyper_body(const WaveTable<gn_n2e_grou
     for (int le = threadIdx.x >> 5; le < eb; le += kBlock / 32) {
       const int c = threadIdx.x & 31;
       const int cnt = s_cnt[le];
-      float mx = cnt < N ? 0.f : -INFINITY;
+      int nv = N;
+      if constexpr (RAGGED) nv = min(max(n_valid[b0 + (e0 + le) / E], 0), N);
+      float mx = cnt < nv ? 0.f : -INFINITY;
       for (int m = c; m < cnt; m += 32) mx = fmaxf(mx, s_v[le * N + m]);
       mx = gn_half_max(mx);
       float sum = 0.f;
       for (int m = c; m < cnt; m += 32) sum += expf(s_v[le * N + m] - mx);
       sum = gn_half_sum(sum);
-      sum += gn_nonmember_sum(N - cnt, mx);
+      sum += gn_nonmember_sum(nv - cnt, mx);
       for (int m = c; m < cnt; m += 32) s_v[le * N + m] = expf(s_v[le * N + m] - mx) / sum * s_h[le * N + m];
     }
     __syncthreads();
@@ -382,8 +418,9 @@ __device__ __forceinline__ void node2edge_hyper_body(const WaveTable<gn_n2e_grou
 // the dense row, and every member's weight is the constant 1: fmaf(1, v, Q), (t + b2) * 1 and p * 1 are exact, so on a
 // 0/1 H the rows are bit-identical to the dense instantiation's.
 constexpr int kRowPitch = GN_FEAT + 4;
-template <typename TS, bool WORDS>
-__device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e_group_t>& T, int B, int N, int SG, int wg) {
+template <typename TS, bool WORDS, bool RAGGED = false>
+__device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e_group_t>& T, int B, int N, int SG, int wg,
+                                                          const int* __restrict__ n_valid = nullptr) {
   extern __shared__ __align__(16) float lds[];
   const int gi = gn_uniform(find_wave_group(T, wg));
   const gn_n2e_group_t G = T.g[gi];
@@ -432,6 +469,8 @@ __device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e
       mask |= ((unsigned long long)ohi << 32) | olo;
     }
     const int cnt = __popcll(mask);
+    int nv = N;
+    if constexpr (RAGGED) nv = min(max(n_valid[b0 + s], 0), N);
     float Q[16];
 #pragma unroll
     for (int c = 0; c < 16; ++c) Q[c] = 0.f;
@@ -476,7 +515,7 @@ __device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e
             for (int c = 0; c < 4; ++c) Q[4 * c4 + c] = fmaf(hvv[k], v[c], Q[4 * c4 + c]);
           }
         }
-      float mx = cnt < N ? 0.f : -INFINITY;
+      float mx = cnt < nv ? 0.f : -INFINITY;
 #pragma unroll
       for (int k = 0; k < MK; ++k) {
         vv[k] = 0.f;
@@ -495,7 +534,7 @@ __device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e
           vv[k] = expf(vv[k] - mx);
           sum += vv[k];
         }
-      sum += gn_nonmember_sum(N - cnt, mx);
+      sum += gn_nonmember_sum(nv - cnt, mx);
 #pragma unroll
       for (int k = 0; k < MK; ++k)
         if (k < cnt) {
@@ -522,7 +561,7 @@ __device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e
         }
       }
       // (lanes of rows with fewer members idle through the longer rows' iterations: the shuffle needs the whole pair)
-      float mx = cnt < N ? 0.f : -INFINITY, sum = 0.f;
+      float mx = cnt < nv ? 0.f : -INFINITY, sum = 0.f;
       for (unsigned long long m = mask; __any(m != 0ull); m &= m - 1ull) {
         const bool on = m != 0ull;
         const int n = on ? __builtin_ctzll(m) : 0;
@@ -533,7 +572,7 @@ __device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e
           mx = nm;
         }
       }
-      sum += gn_nonmember_sum(N - cnt, mx);
+      sum += gn_nonmember_sum(nv - cnt, mx);
       for (unsigned long long m = mask; __any(m != 0ull); m &= m - 1ull) {
         const bool on = m != 0ull;
         const int n = on ? __builtin_ctzll(m) : 0;
@@ -565,9 +604,10 @@ __device__ __forceinline__ void node2edge_hyper_rows_body(const WaveTable<gn_n2e
 // same channel), then walks bands of 256 edges: phase A one thread per edge evaluates the two
 // attention logits and the softmax weights, phase B the band's 256 x 16 float4 outputs are written
 // as consecutive 16-byte pieces.
-template <typename TS>
+// RAGGED: only pairs with both ends < the scene's count exist; every other edge row is written as zeros.
+template <typename TS, bool RAGGED = false>
 __device__ __forceinline__ void node2edge_pairwise_body(const gn_n2e_group_t& G, int B, int N, int SG, int bands,
-                                                        int wg) {
+                                                        int wg, const int* __restrict__ n_valid = nullptr) {
   extern __shared__ __align__(16) float lds[];
   constexpr int LDP = GN_FEAT + 1;
   const bool sym = G.sym != 0;
@@ -611,15 +651,20 @@ __device__ __forceinline__ void node2edge_pairwise_body(const gn_n2e_group_t& G,
       const float* pi = s_pq + (size_t)(s * N + i) * LDP;
       const float* pj = s_pq + (size_t)(s * N + j) * LDP;
       float ai = 0.f, aj = 0.f;
-      if (i == j) {
+      int nv = N;
+      if constexpr (RAGGED) nv = min(max(n_valid[b0 + s], 0), N);
+      if (RAGGED && (i >= nv || j >= nv)) {
+        s_w[2 * threadIdx.x] = 0.f;
+        s_w[2 * threadIdx.x + 1] = 0.f;
+      } else if (i == j) {
 #pragma unroll 8
         for (int cch = 0; cch < 32; ++cch) ai = fmaf(s_w2[cch], fmaxf(pi[cch] + 2.f * pi[32 + cch], 0.f), ai);
         ai += b2v;
         // H = 2 on the self-loop: v = 2*att, the other N-1 nodes contribute exp(0)
         const float v = 2.f * ai;
-        const float mx = N > 1 ? fmaxf(v, 0.f) : v;
+        const float mx = nv > 1 ? fmaxf(v, 0.f) : v;
         const float ev = expf(v - mx);
-        const float sum = ev + gn_nonmember_sum(N - 1, mx);
+        const float sum = ev + gn_nonmember_sum(nv - 1, mx);
         s_w[2 * threadIdx.x] = ev / sum * 2.f;
         s_w[2 * threadIdx.x + 1] = 0.f;
       } else {
@@ -631,9 +676,9 @@ __device__ __forceinline__ void node2edge_pairwise_body(const gn_n2e_group_t& G,
         }
         ai += b2v;
         aj += b2v;
-        const float mx = N > 2 ? fmaxf(fmaxf(ai, aj), 0.f) : fmaxf(ai, aj);
+        const float mx = nv > 2 ? fmaxf(fmaxf(ai, aj), 0.f) : fmaxf(ai, aj);
         const float ei = expf(ai - mx), ej = expf(aj - mx);
-        const float sum = (ei + ej) + gn_nonmember_sum(N - 2, mx);
+        const float sum = (ei + ej) + gn_nonmember_sum(nv - 2, mx);
         s_w[2 * threadIdx.x] = ei / sum;
         s_w[2 * threadIdx.x + 1] = ej / sum;
       }
@@ -683,6 +728,25 @@ __global__ __launch_bounds__(kBlock) void node2edge_kernel(WaveTable<gn_n2e_grou
     node2edge_hyper_rows_body<TS, WORDS>(T, B, N, SGh, wg - n_pair_wgs);      // one lane pair per hyperedge (N <= 64)
   } else {
     node2edge_hyper_body<TS>(T, B, N, SGh, EBh, wg - n_pair_wgs);
+  }
+}
+
+// The same launch over scenes with n_valid[b] <= N agents each (gn_node2edge_ragged_*: a kernel of its own; dense H only)
+template <typename TS, bool ROWS>
+__global__ __launch_bounds__(kBlock) void node2edge_ragged_kernel(WaveTable<gn_n2e_group_t> T, PairTable pair, int B, int N,
+                                                                  int SGh, int EBh, XcdSections xs,
+                                                                  const int* __restrict__ n_valid) {
+  const int wg = gn_uniform(gn_xcd_logical(xs, blockIdx.x));
+  if (wg < 0) return;
+  const int n_pair_wgs = pair.first_wg[pair.n];
+  if (wg < n_pair_wgs) {
+    int g = 0;
+    while (g + 1 < pair.n && wg >= pair.first_wg[g + 1]) ++g;
+    node2edge_pairwise_body<TS, true>(pair.g[g], B, N, pair.SG[g], pair.bands[g], wg - pair.first_wg[g], n_valid);
+  } else if constexpr (ROWS) {
+    node2edge_hyper_rows_body<TS, false, true>(T, B, N, SGh, wg - n_pair_wgs, n_valid);
+  } else {
+    node2edge_hyper_body<TS, true>(T, B, N, SGh, EBh, wg - n_pair_wgs, n_valid);
   }
 }
 
@@ -1046,6 +1110,99 @@ __global__ __launch_bounds__(kBlock) void agg_scatter_pairs_kernel(const TS* __r
   }
 }
 
+// Scatter over scenes with n_valid[b] <= N agents each (gn_agg_scatter_ragged_*): blockIdx.y = group, every thread a
+// (scene, node, 4 of the 128 output features) item straight from global memory, as the direct kernel above.  Node n < nb
+// adds its hyperedges (dense H, whose rows and columns >= nb are zeros) or its partners j < nb of the pairwise graph
+// (ordered edges, or sym: the pair sums), and the row is divided by fN, or by nb where fN == 0; rows n >= nb are zeros.
+template <typename TS>
+__global__ __launch_bounds__(kBlock) void agg_scatter_ragged_kernel(ScatterTable T, int B, int N, long long total4, float fN,
+                                                                    const int* __restrict__ n_valid) {
+  const gn_scatter_group_t Gr = T.g[blockIdx.y];
+  const int E = Gr.E;
+  const TS* feat = reinterpret_cast<const TS*>(Gr.feat);
+  const TS* ori = reinterpret_cast<const TS*>(Gr.ori);
+  TS* out = reinterpret_cast<TS*>(Gr.out);
+  for (long long idx = (long long)blockIdx.x * kBlock + threadIdx.x; idx < total4;
+       idx += (long long)gridDim.x * kBlock) {
+    const int d = (int)(idx & 31);
+    const long long bn = idx >> 5;
+    const int b = (int)(bn / N), n = (int)(bn - (long long)b * N);
+    const int nb = min(max(n_valid[b], 0), N);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (n < nb) {
+      if (d >= 16) {
+        acc = ld4(ori + ((size_t)b * N + n) * GN_FEAT + 4 * (d - 16));
+      } else {
+        const TS* f4 = feat + (size_t)b * E * GN_FEAT + 4 * d;
+        if (Gr.H != nullptr) {
+          const float* hcol = Gr.H + (size_t)b * E * N + n;
+          for (int e = 0; e < E; ++e) {
+            const float hv = hcol[(size_t)e * N];
+            if (hv != 0.f) {
+              const f32x4 v = ld4(f4 + (size_t)e * GN_FEAT);
+              acc[0] = fmaf(hv, v[0], acc[0]);
+              acc[1] = fmaf(hv, v[1], acc[1]);
+              acc[2] = fmaf(hv, v[2], acc[2]);
+              acc[3] = fmaf(hv, v[3], acc[3]);
+            }
+          }
+        } else if (Gr.sym) {
+          for (int j = 0; j < nb; ++j) {
+            const f32x4 v = ld4(f4 + (size_t)gn_pair_index(n, j, N) * GN_FEAT);
+            acc[0] += v[0], acc[1] += v[1], acc[2] += v[2], acc[3] += v[3];
+          }
+        } else {
+          for (int j = 0; j < nb; ++j) {
+            const f32x4 v = ld4(f4 + (size_t)(n * N + j) * GN_FEAT);
+            const f32x4 w = ld4(f4 + (size_t)(j * N + n) * GN_FEAT);
+            acc[0] += v[0] + w[0], acc[1] += v[1] + w[1], acc[2] += v[2] + w[2], acc[3] += v[3] + w[3];
+          }
+        }
+      }
+      const float dv = fN != 0.f ? fN : (float)nb;
+      acc = f32x4{acc[0] / dv, acc[1] / dv, acc[2] / dv, acc[3] / dv};
+    }
+    st4(out + 4 * idx, acc);
+  }
+}
+
+// Zeroes the padded positions of a list of tensors in one launch (gn_zero_padding): blockIdx.y = tensor; rows r >= nb of
+// a tensor with N rows per scene (node rows, or the N hyperedge rows of a top-k module), ordered pair rows i*N + j with
+// i >= nb or j >= nb of one with N*N.  Rows are `width` bytes at a pitch of `pitch` bytes, written as 4-byte words where
+// address, width and pitch allow it, else as 2-byte words (a bf16 row of an odd number of elements).
+struct ZeroTable {
+  gn_zero_item_t t[GN_MAX_ZERO_ITEMS];
+};
+// bytes per store of a tensor: 4 where its address, row width and pitch are multiples of 4, else 2
+__host__ __device__ inline int zero_item_unit(const gn_zero_item_t& it) {
+  return ((reinterpret_cast<uintptr_t>(it.ptr) | (uintptr_t)it.width | (uintptr_t)it.pitch) & 3u) == 0 ? 4 : 2;
+}
+__global__ __launch_bounds__(kBlock) void zero_padding_kernel(ZeroTable T, int B, int N, const int* __restrict__ n_valid) {
+  const gn_zero_item_t it = T.t[blockIdx.y];
+  const bool words = zero_item_unit(it) == 4;
+  const int wu = it.width / (words ? 4 : 2);          // units per row
+  const int R = it.kind == GN_ZERO_PAIR_ROWS ? N * N : N;
+  const long long total = (long long)B * R * wu;
+  for (long long idx = (long long)blockIdx.x * kBlock + threadIdx.x; idx < total; idx += (long long)gridDim.x * kBlock) {
+    const long long br = idx / wu;
+    const int c = (int)(idx - br * wu);
+    const int b = (int)(br / R), r = (int)(br - (long long)b * R);
+    const int nb = min(max(n_valid[b], 0), N);
+    bool pad;
+    if (it.kind == GN_ZERO_PAIR_ROWS) {
+      const int i = r / N, j = r - i * N;
+      pad = i >= nb || j >= nb;
+    } else {
+      pad = r >= nb;
+    }
+    if (pad) {
+      unsigned char* row = reinterpret_cast<unsigned char*>(it.ptr) + (size_t)br * it.pitch;
+      if (words) reinterpret_cast<unsigned int*>(row)[c] = 0u;
+      else reinterpret_cast<unsigned short*>(row)[c] = (unsigned short)0;
+    }
+  }
+}
+
 // --------------------------------------------------------------------------------------------
 // Exhaustive hyperedge search (init_adj_attention_listall, model/MS_HGNN_batch.py:390-414): hyperedge i =
 // the group of s agents containing i with the largest total affinity sum_{a,b in group} corr[a][b].
@@ -1190,7 +1347,7 @@ inline int capped_grid(long long work_items, int per_block, int cap = 256 * 16) 
 
 }  // namespace
 
-extern "C" int gn_abi_version(void) { return 38; }
+extern "C" int gn_abi_version(void) { return 39; }
 
 extern "C" const char* gn_kernel_name(int kernel) {
   static const char* const names[] = {"",
@@ -1219,8 +1376,13 @@ extern "C" const char* gn_kernel_name(int kernel) {
                                       "agg_scatter_kernel",
                                       "agg_scatter_mask_kernel",
                                       "agg_scatter_direct_kernel",
-                                      "agg_scatter_pairs_kernel"};
-  return kernel >= 0 && kernel <= GN_K_AGG_SCATTER_PAIRS ? names[kernel] : nullptr;
+                                      "agg_scatter_pairs_kernel",
+                                      "affinity_topk_ragged_kernel",
+                                      "topk_incidence_ragged_kernel",
+                                      "node2edge_ragged_kernel",
+                                      "agg_scatter_ragged_kernel",
+                                      "zero_padding_kernel"};
+  return kernel >= 0 && kernel <= GN_K_ZERO_PADDING ? names[kernel] : nullptr;
 }
 
 extern "C" const char* gn_strerror(int code) {
@@ -1327,6 +1489,34 @@ extern "C" int gn_topk_incidence_plan_f32(const float* corr, float* const* H_lis
   return plan == nullptr ? GN_ERR_NULL : topk_entry(corr, H_list, k_list, n_scales, B, N, nullptr, plan);
 }
 
+// the per-scene agent counts of a ragged entry point: a device array of ints
+static int need_counts(const int* n_valid) {
+  if (n_valid == nullptr) return GN_ERR_NULL;
+  return (reinterpret_cast<uintptr_t>(n_valid) & 3u) != 0 ? GN_ERR_ALIGN : GN_OK;
+}
+static int topk_ragged_entry(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B, int N,
+                             const int* n_valid, gn_stream_t stream, gn_launch_plan_t* plan) {
+  gn_launch_plan_t p;
+  ScaleList sl;
+  gn_launch_plan_t& q = plan != nullptr ? *plan : p;
+  GN_CHECK(need_counts(n_valid));
+  GN_CHECK(topk_plan(corr, H_list, k_list, n_scales, B, N, q, sl));
+  q.kernel = GN_K_TOPK_INCIDENCE_RAGGED;
+  if (plan != nullptr) return GN_OK;
+  gn_allow_big_lds(topk_incidence_ragged_kernel);
+  hipLaunchKernelGGL(topk_incidence_ragged_kernel, dim3(p.grid[0], p.grid[1]), dim3(kBlock), (size_t)p.dyn_lds,
+                     (hipStream_t)stream, corr, sl, N, p.TE, n_valid);
+  return gn_check_launch();
+}
+extern "C" int gn_topk_incidence_ragged_f32(const float* corr, float* const* H_list, const int* k_list, int n_scales,
+                                            int B, int N, const int* n_valid, gn_stream_t stream) {
+  return topk_ragged_entry(corr, H_list, k_list, n_scales, B, N, n_valid, stream, nullptr);
+}
+extern "C" int gn_topk_incidence_ragged_plan_f32(const float* corr, float* const* H_list, const int* k_list, int n_scales,
+                                                 int B, int N, const int* n_valid, gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : topk_ragged_entry(corr, H_list, k_list, n_scales, B, N, n_valid, nullptr, plan);
+}
+
 extern "C" int gn_listall_incidence_f32(const float* corr, float* H, int B, int N, int scale, gn_stream_t stream) {
   GN_REQUIRE_PTR(corr);
   GN_REQUIRE_PTR(H);
@@ -1430,6 +1620,52 @@ extern "C" int gn_affinity_topk_plan_bf16(const void* f, float* corr, float* con
   if (plan == nullptr) return GN_ERR_NULL;
   return affinity_topk_entry<__bf16>({f, corr, H_list, k_list, n_scales, B, N, D, extras, rowmask_list, colmask_list},
                                      nullptr, plan);
+}
+
+// the ragged form of the stand-alone launch: the same job checks (no mask lists), no embedding front-end
+template <typename TS>
+static int affinity_topk_ragged_entry(const AffinityTopkArgs& a, const int* n_valid, gn_stream_t stream,
+                                      gn_launch_plan_t* plan) {
+  gn_launch_plan_t p;
+  ScaleList sl;
+  MaskList ml;
+  gn_launch_plan_t& q = plan != nullptr ? *plan : p;
+  GN_CHECK(need_counts(n_valid));
+  if (a.extras != nullptr && a.extras->x_raw != nullptr) return GN_ERR_SHAPE;
+  GN_CHECK(affinity_topk_plan(a, sizeof(TS) != sizeof(float), q, sl, ml));
+  q.kernel = GN_K_AFFINITY_TOPK_RAGGED;
+  if (plan != nullptr) return GN_OK;
+  const gn_block_extras_t ex = a.extras != nullptr ? *a.extras : gn_block_extras_t{};
+  gn_allow_big_lds(affinity_topk_ragged_kernel<TS>);
+  hipLaunchKernelGGL(affinity_topk_ragged_kernel<TS>, dim3(p.grid[0]), dim3(kBlock), (size_t)p.dyn_lds, (hipStream_t)stream,
+                     reinterpret_cast<const TS*>(a.f), a.corr, sl, a.N, a.D, ex, n_valid);
+  return gn_check_launch();
+}
+extern "C" int gn_affinity_topk_ragged_f32(const float* f, float* corr, float* const* H_list, const int* k_list,
+                                           int n_scales, int B, int N, int D, const gn_block_extras_t* extras,
+                                           const int* n_valid, gn_stream_t stream) {
+  return affinity_topk_ragged_entry<float>({f, corr, H_list, k_list, n_scales, B, N, D, extras, nullptr, nullptr}, n_valid,
+                                           stream, nullptr);
+}
+extern "C" int gn_affinity_topk_ragged_bf16(const void* f, float* corr, float* const* H_list, const int* k_list,
+                                            int n_scales, int B, int N, int D, const gn_block_extras_t* extras,
+                                            const int* n_valid, gn_stream_t stream) {
+  return affinity_topk_ragged_entry<__bf16>({f, corr, H_list, k_list, n_scales, B, N, D, extras, nullptr, nullptr}, n_valid,
+                                            stream, nullptr);
+}
+extern "C" int gn_affinity_topk_ragged_plan_f32(const float* f, float* corr, float* const* H_list, const int* k_list,
+                                                int n_scales, int B, int N, int D, const gn_block_extras_t* extras,
+                                                const int* n_valid, gn_launch_plan_t* plan) {
+  if (plan == nullptr) return GN_ERR_NULL;
+  return affinity_topk_ragged_entry<float>({f, corr, H_list, k_list, n_scales, B, N, D, extras, nullptr, nullptr}, n_valid,
+                                           nullptr, plan);
+}
+extern "C" int gn_affinity_topk_ragged_plan_bf16(const void* f, float* corr, float* const* H_list, const int* k_list,
+                                                 int n_scales, int B, int N, int D, const gn_block_extras_t* extras,
+                                                 const int* n_valid, gn_launch_plan_t* plan) {
+  if (plan == nullptr) return GN_ERR_NULL;
+  return affinity_topk_ragged_entry<__bf16>({f, corr, H_list, k_list, n_scales, B, N, D, extras, nullptr, nullptr}, n_valid,
+                                            nullptr, plan);
 }
 
 extern "C" int gn_incidence_masks_f32(const float* H, int B, int E, int N, unsigned long long* rowmask,
@@ -1560,9 +1796,11 @@ static int node2edge_plan(const gn_n2e_group_t* groups, const unsigned long long
   p.xcd = xs.enabled;
   return GN_OK;
 }
+// n_valid: the per-scene counts of the ragged launch (GN_K_NODE2EDGE_RAGGED), else nullptr
 template <typename TS>
 static int node2edge_launch(const gn_launch_plan_t& p, const gn_n2e_group_t* groups,
-                            const unsigned long long* const* rowmasks, int B, int N, hipStream_t s) {
+                            const unsigned long long* const* rowmasks, int B, int N, hipStream_t s,
+                            const int* n_valid = nullptr) {
   WaveTable<gn_n2e_group_t> T{};
   PairTable P{};
   XcdSections xs{};
@@ -1597,6 +1835,15 @@ static int node2edge_launch(const gn_launch_plan_t& p, const gn_n2e_group_t* gro
     hipLaunchKernelGGL(k, dim3((unsigned)p.grid[0]), dim3(kBlock), (size_t)p.dyn_lds, s, T, P, B, N, p.SGh, p.EBh, xs);
     return gn_check_launch();
   };
+  if (p.kernel == GN_K_NODE2EDGE_RAGGED) {
+    auto ragged = [&](auto k) {
+      gn_allow_big_lds(k);
+      hipLaunchKernelGGL(k, dim3((unsigned)p.grid[0]), dim3(kBlock), (size_t)p.dyn_lds, s, T, P, B, N, p.SGh, p.EBh, xs,
+                         n_valid);
+      return gn_check_launch();
+    };
+    return p.variant ? ragged(node2edge_ragged_kernel<TS, true>) : ragged(node2edge_ragged_kernel<TS, false>);
+  }
   if (p.variant == 2) return launch(node2edge_kernel<TS, true, true>);
   return p.variant ? launch(node2edge_kernel<TS, true>) : launch(node2edge_kernel<TS, false>);
 }
@@ -1639,6 +1886,35 @@ extern "C" int gn_node2edge_masks_plan_bf16(const gn_n2e_group_t* groups, const 
                                             int n_groups, int B, int N, gn_launch_plan_t* plan) {
   if (rowmasks == nullptr || plan == nullptr) return GN_ERR_NULL;
   return node2edge_entry<__bf16>(groups, rowmasks, n_groups, B, N, nullptr, plan);
+}
+
+// the ragged launch: the plan of gn_node2edge_* (no words), its kernel the ragged one
+template <typename TS>
+static int node2edge_ragged_entry(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
+                                  gn_stream_t stream, gn_launch_plan_t* plan) {
+  gn_launch_plan_t p;
+  gn_launch_plan_t& q = plan != nullptr ? *plan : p;
+  GN_CHECK(need_counts(n_valid));
+  GN_CHECK(node2edge_plan(groups, nullptr, n_groups, B, N, sizeof(TS) != sizeof(float), gn_read_switches(), q));
+  q.kernel = GN_K_NODE2EDGE_RAGGED;
+  if (plan != nullptr) return GN_OK;
+  return node2edge_launch<TS>(p, groups, nullptr, B, N, (hipStream_t)stream, n_valid);
+}
+extern "C" int gn_node2edge_ragged_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
+                                       gn_stream_t stream) {
+  return node2edge_ragged_entry<float>(groups, n_groups, B, N, n_valid, stream, nullptr);
+}
+extern "C" int gn_node2edge_ragged_bf16(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
+                                        gn_stream_t stream) {
+  return node2edge_ragged_entry<__bf16>(groups, n_groups, B, N, n_valid, stream, nullptr);
+}
+extern "C" int gn_node2edge_ragged_plan_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
+                                            gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : node2edge_ragged_entry<float>(groups, n_groups, B, N, n_valid, nullptr, plan);
+}
+extern "C" int gn_node2edge_ragged_plan_bf16(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
+                                             gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : node2edge_ragged_entry<__bf16>(groups, n_groups, B, N, n_valid, nullptr, plan);
 }
 
 // workgroups a gather / scatter launch keeps at least when it packs several scenes into one.  2048 = two rounds of the
@@ -1872,6 +2148,99 @@ extern "C" int gn_agg_scatter_plan_f32(const gn_scatter_group_t* groups, int n_g
 extern "C" int gn_agg_scatter_plan_bf16(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
                                         gn_launch_plan_t* plan) {
   return plan == nullptr ? GN_ERR_NULL : scatter_entry<__bf16>(groups, n_groups, B, N, divisor, nullptr, plan);
+}
+
+// The ragged scatter: every group in one launch of agg_scatter_ragged_kernel (pos = the group's index, no launches of
+// their own).  divisor == 0: each scene by its own count.
+static int scatter_ragged_plan(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor, bool twin,
+                               const int* n_valid, gn_launch_plan_t& p) {
+  GN_CHECK(need_counts(n_valid));
+  GN_CHECK(check_groups(groups, n_groups));
+  if (B <= 0 || N <= 0 || !(divisor >= 0.f) || N > 32767) return GN_ERR_SHAPE;
+  plan_begin(p, n_groups);
+  p.precision = twin ? 1 : 0;
+  for (int g = 0; g < n_groups; ++g) {
+    const gn_scatter_group_t& G = groups[g];
+    if (!G.feat || !G.ori || !G.out) return GN_ERR_NULL;
+    if (!gn_aligned16(G.feat) || !gn_aligned16(G.ori) || !gn_aligned16(G.out)) return GN_ERR_ALIGN;
+    if (G.E <= 0 || G.colmask != nullptr) return GN_ERR_SHAPE;      // dense H only
+    if (G.H == nullptr && (long long)G.E != (G.sym ? (long long)gn_pair_count(N) : (long long)N * N)) return GN_ERR_SHAPE;
+    if (G.H != nullptr && G.sym) return GN_ERR_SHAPE;
+    p.pos[g] = g;
+  }
+  p.kernel = GN_K_AGG_SCATTER_RAGGED;
+  p.grid[0] = capped_grid((long long)B * N * 32, kBlock);
+  p.grid[1] = n_groups;
+  for (int g = 0; g < n_groups; ++g) p.wgs[g] = p.grid[0];
+  return GN_OK;
+}
+template <typename TS>
+static int scatter_ragged_entry(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
+                                const int* n_valid, gn_stream_t stream, gn_launch_plan_t* plan) {
+  gn_launch_plan_t p;
+  GN_CHECK(scatter_ragged_plan(groups, n_groups, B, N, divisor, sizeof(TS) != sizeof(float), n_valid,
+                               plan != nullptr ? *plan : p));
+  if (plan != nullptr) return GN_OK;
+  ScatterTable T{};
+  for (int g = 0; g < n_groups; ++g) T.g[g] = groups[g];
+  hipLaunchKernelGGL(agg_scatter_ragged_kernel<TS>, dim3(p.grid[0], p.grid[1]), dim3(kBlock), 0, (hipStream_t)stream, T, B,
+                     N, (long long)B * N * 32, divisor, n_valid);
+  return gn_check_launch();
+}
+extern "C" int gn_agg_scatter_ragged_f32(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
+                                         const int* n_valid, gn_stream_t stream) {
+  return scatter_ragged_entry<float>(groups, n_groups, B, N, divisor, n_valid, stream, nullptr);
+}
+extern "C" int gn_agg_scatter_ragged_bf16(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
+                                          const int* n_valid, gn_stream_t stream) {
+  return scatter_ragged_entry<__bf16>(groups, n_groups, B, N, divisor, n_valid, stream, nullptr);
+}
+extern "C" int gn_agg_scatter_ragged_plan_f32(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
+                                              const int* n_valid, gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL
+                         : scatter_ragged_entry<float>(groups, n_groups, B, N, divisor, n_valid, nullptr, plan);
+}
+extern "C" int gn_agg_scatter_ragged_plan_bf16(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
+                                               const int* n_valid, gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL
+                         : scatter_ragged_entry<__bf16>(groups, n_groups, B, N, divisor, n_valid, nullptr, plan);
+}
+
+// The zeroing launch of a ragged forward: grid (capped, items)
+static int zero_padding_entry(const gn_zero_item_t* items, int n_items, int B, int N, const int* n_valid,
+                              gn_stream_t stream, gn_launch_plan_t* plan) {
+  GN_CHECK(need_counts(n_valid));
+  if (items == nullptr) return GN_ERR_NULL;
+  if (n_items < 1 || n_items > GN_MAX_ZERO_ITEMS || B <= 0 || N <= 0 || N > 32767) return GN_ERR_SHAPE;
+  ZeroTable T{};
+  long long most = 0;
+  for (int g = 0; g < n_items; ++g) {
+    const gn_zero_item_t& it = items[g];
+    if (it.ptr == nullptr) return GN_ERR_NULL;
+    if (it.kind < GN_ZERO_NODE_ROWS || it.kind > GN_ZERO_PAIR_ROWS || it.width <= 0 || it.pitch < it.width) return GN_ERR_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(it.ptr) & 1u) || (it.width & 1) || (it.pitch & 1)) return GN_ERR_ALIGN;
+    const long long words =
+        (long long)B * (it.kind == GN_ZERO_PAIR_ROWS ? (long long)N * N : N) * (it.width / zero_item_unit(it));
+    most = words > most ? words : most;
+    T.t[g] = it;
+  }
+  gn_launch_plan_t p;
+  gn_launch_plan_t& q = plan != nullptr ? *plan : p;
+  plan_begin(q, 0);
+  q.kernel = GN_K_ZERO_PADDING;
+  q.grid[0] = capped_grid(most, kBlock * 4);
+  q.grid[1] = n_items;
+  if (plan != nullptr) return GN_OK;
+  hipLaunchKernelGGL(zero_padding_kernel, dim3(q.grid[0], q.grid[1]), dim3(kBlock), 0, (hipStream_t)stream, T, B, N, n_valid);
+  return gn_check_launch();
+}
+extern "C" int gn_zero_padding(const gn_zero_item_t* items, int n_items, int B, int N, const int* n_valid,
+                               gn_stream_t stream) {
+  return zero_padding_entry(items, n_items, B, N, n_valid, stream, nullptr);
+}
+extern "C" int gn_zero_padding_plan(const gn_zero_item_t* items, int n_items, int B, int N, const int* n_valid,
+                                    gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : zero_padding_entry(items, n_items, B, N, n_valid, nullptr, plan);
 }
 
 // Pitched copy (rows x width bytes, 16-byte pieces): the column block of the feature tensor that a rank ships into its

@@ -114,16 +114,27 @@ class MultiScaleHGNN(nn.Module):
             out.append((B, 1 if s == N else N, m.edge_types))
         return out
 
-    def forward(self, f: Tensor, noise_u: Optional[Sequence] = None, advance=None
+    def forward(self, f: Tensor, noise_u: Optional[Sequence] = None, advance=None, n_agents=None
                 ) -> Tuple[Tensor, Optional[Tensor]]:
         """``noise_u``: optional list with one entry per module (pairwise first), each a tensor or a
         list of ``nmp_layers`` tensors; default draws as the modules do (reference order).
         ``advance`` = (counter, n): add n to the device Philox counter at the START of this forward
-        (used by the captured graph so that every replay draws fresh noise)."""
+        (used by the captured graph so that every replay draws fresh noise).
+        ``n_agents`` (optional; INTEGRATION.md, "Ragged batches"): one count per scene, 1 <= n_b <= N — the first n_b
+        rows of scene b are real agents, the rest is finite padding.  The valid rows of the module columns of ``final``
+        and the valid block of ``new_H`` are what the block computes for each scene alone at its own size; padded
+        positions are zeros (the first D columns of ``final`` stay the copy of f).  The noise keeps its padded shapes.
+        Inference only."""
         ops._req(f, "f", (None, None, self.h_dim), ops._ACT_DTYPES)
         B, N, D = f.shape
         S = len(self.hyper_scales)
         nmp = self.interaction.nmp_layers
+        counts = ops.agent_counts(n_agents, B, N, f.device) if B and N else None
+        if counts is not None:
+            if _needs_grad(self, f):
+                raise NotImplementedError("n_agents: ragged batches are inference-only (call under torch.no_grad())")
+            if any(m.listall for m in self.interaction_hyper):
+                raise NotImplementedError("n_agents: the exhaustive (listall) search has no ragged form")
         if _needs_grad(self, f):
             if f.dtype == torch.bfloat16:
                 # bf16 storage under autograd: the fp32 training path on the up-cast features, results back in bf16
@@ -149,7 +160,9 @@ class MultiScaleHGNN(nn.Module):
         final = torch.empty((B, N, self.out_features), dtype=f.dtype, device=f.device)
         cols = [final[..., D * (1 + i):D * (2 + i)] for i in range(1 + S)]   # written in place by the last MLP
         join = None
-        want_masks = masks_apply(N)       # mask form on and 16 < N <= 64: the fused launch also emits the member words
+        # mask form on and 16 < N <= 64: the fused launch also emits the member words (not for a ragged batch, whose
+        # route reads no masks)
+        want_masks = masks_apply(N) and counts is None
         # asked about the launch built below, mask words included (which cannot change the answer today: at D = 64 and
         # N <= 64 the tile with eight scales of mask words is 58 384 B of the 128 KiB)
         fused = bool(S) and ops.graph_form(N, D, 0, S if want_masks else 0) != "banded"
@@ -171,7 +184,7 @@ class MultiScaleHGNN(nn.Module):
             with (torch.cuda.stream(side) if fork else contextlib.nullcontext()):
                 job = ops.AffinityTail(f, self.hyper_scales, f_out=final[..., :D], want_H_cat=True,
                                        counter=advance[0] if advance else None,
-                                       counter_add=advance[1] if advance else 0, want_masks=want_masks)
+                                       counter_add=advance[1] if advance else 0, want_masks=want_masks, n_agents=counts)
                 if not deferred:
                     job.launch()
             tail = job if deferred else None
@@ -180,7 +193,7 @@ class MultiScaleHGNN(nn.Module):
                 join = lambda: main.wait_stream(side)
         elif S:
             # large N (N*(N+68)*4 B > LDS tile): banded affinity and banded top-k launches, plain copies
-            Hs = ops.topk_incidence(ops.affinity(f if f.dtype == torch.float32 else f.float()), self.hyper_scales)
+            Hs = ops.topk_incidence(ops.affinity(f if f.dtype == torch.float32 else f.float()), self.hyper_scales, counts)
             new_H = torch.cat(Hs, dim=1).to(f.dtype)
             final[..., :D].copy_(f)
             if advance:
@@ -197,8 +210,8 @@ class MultiScaleHGNN(nn.Module):
             # (latency form — `affinity_tail` — also folds the closing MLPs into the aggregation launch: 4 launches)
             run_message_passing(mods, [f] * (1 + S), [None, *Hs], list(noise_u), cols, join=join,
                                 affinity=tail if fused else None,
-                                fuse_closing=self.affinity_tail)
+                                fuse_closing=self.affinity_tail, n_agents=counts)
         else:
             for m, H, u, c in zip(mods, [None, *Hs], noise_u, cols):
-                run_message_passing([m], [f], [H], [u], [c])
+                run_message_passing([m], [f], [H], [u], [c], n_agents=counts)
         return final, new_H

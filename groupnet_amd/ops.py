@@ -162,6 +162,100 @@ class _Probed:
         return False
 
 
+# ---- ragged batches ----------------------------------------------------------------------------
+class AgentCounts:
+    """The per-scene agent counts of a ragged batch ("Ragged batches"), validated: ``counts`` — the B
+    ints on the host, ``N`` — the padded size, ``dev`` — the counts as a (B,) int32 tensor on ``device``, uploaded once,
+    when the first launch asks for it (a forward that refuses the call has then copied nothing).  Made by
+    `agent_counts`; every ``n_agents=`` argument of this module takes one (or what `agent_counts` takes)."""
+    __slots__ = ("counts", "N", "device", "_dev")
+
+    def __init__(self, counts: Tuple[int, ...], N: int, device):
+        self.counts, self.N, self.device, self._dev = counts, N, torch.device(device), None
+
+    @property
+    def dev(self) -> Tensor:
+        if self._dev is None:
+            self._dev = torch.tensor(self.counts, dtype=torch.int32).to(self.device, non_blocking=True)
+        return self._dev
+
+
+def agent_counts(n_agents, B: int, N: int, device) -> Optional[AgentCounts]:
+    """``n_agents`` — a sequence of ints or a CPU integer tensor, one count per scene, 1 <= n_b <= N — as an
+    `AgentCounts` on ``device``, or None when no scene is padded (every count equals N, or ``n_agents`` is None): the
+    caller then takes the full-batch path and gets its bits.  A GPU tensor is refused: reading it would synchronise."""
+    if n_agents is None:
+        return None
+    if isinstance(n_agents, AgentCounts):
+        if len(n_agents.counts) != B or n_agents.N != N:
+            raise ValueError(f"n_agents: counts of {len(n_agents.counts)} scenes padded to {n_agents.N}, "
+                             f"the call has {B} scenes padded to {N}")
+        return n_agents
+    if isinstance(n_agents, torch.Tensor):
+        if n_agents.is_cuda:
+            raise ValueError("n_agents: a sequence of ints or a CPU integer tensor (a GPU tensor would have to be read "
+                             "back: a hidden synchronisation)")
+        if n_agents.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or n_agents.dim() != 1:
+            raise ValueError("n_agents: a 1-D integer tensor")
+        vals = n_agents.tolist()
+    else:
+        try:
+            vals = list(n_agents)
+        except TypeError:
+            raise ValueError("n_agents: a sequence of ints or a CPU integer tensor") from None
+        if any(isinstance(v, bool) or not isinstance(v, int) for v in vals):
+            raise ValueError("n_agents: every count must be an int")
+    if len(vals) != B:
+        raise ValueError(f"n_agents: {B} counts needed (one per scene), got {len(vals)}")
+    if any(not 1 <= v <= N for v in vals):
+        raise ValueError(f"n_agents: every count must lie in 1..{N} (the padded size)")
+    if all(v == N for v in vals):
+        return None
+    if torch.device(device).type != "cuda":
+        raise ValueError("n_agents: the counts go with GPU tensors; groupnet_amd has no CPU path")
+    return AgentCounts(tuple(vals), N, device)
+
+
+ZERO_NODE_ROWS, ZERO_EDGE_ROWS, ZERO_PAIR_ROWS = _lib.ZERO_NODE_ROWS, _lib.ZERO_EDGE_ROWS, _lib.ZERO_PAIR_ROWS
+
+
+def zero_padding(items: Sequence[Tuple[Tensor, int]], n_agents) -> None:
+    """Zero the padded positions of several tensors of a ragged batch in ONE launch (gn_zero_padding).  items =
+    [(tensor, kind)]: ZERO_NODE_ROWS — (B,N,w), rows n >= n_b; ZERO_EDGE_ROWS — the (B,N,w) hyperedge rows of a top-k
+    module, rows e >= n_b (the (B,1,w) rows of a scale-N module are valid: they are skipped here); ZERO_PAIR_ROWS —
+    (B,N*N,w) ordered pair rows with an end >= n_b, or a contiguous (B,N,N) matrix per scene (corr, H, new_H).  A tensor
+    may be a last-dim slice of a wider contiguous one; fp32 or bf16 (rows of an even number of bytes)."""
+    if not isinstance(n_agents, AgentCounts):
+        raise ValueError("zero_padding: n_agents must be an ops.AgentCounts (ops.agent_counts)")
+    B, N = len(n_agents.counts), n_agents.N
+    arr = []
+    for t, kind in items:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 3 and t.shape[0] == B):
+            raise ValueError("zero_padding: (B, rows, width) GPU tensors")
+        if t.dtype not in _ACT_DTYPES:
+            raise ValueError(f"zero_padding: fp32 or bf16 tensors (got {t.dtype})")
+        R, w = t.shape[1], t.shape[2]
+        if kind == ZERO_PAIR_ROWS and (R, w) == (N, N) and t.is_contiguous():
+            R, w, pitch = N * N, 1, 1          # a matrix per scene: one element per ordered pair
+        else:
+            if t.stride(2) != 1 or t.stride(0) != R * t.stride(1):
+                raise ValueError("zero_padding: a contiguous tensor or a last-dim slice of one")
+            pitch = t.stride(1)
+        if kind == ZERO_EDGE_ROWS and R == 1:
+            continue
+        if R != (N * N if kind == ZERO_PAIR_ROWS else N) or kind not in (ZERO_NODE_ROWS, ZERO_EDGE_ROWS, ZERO_PAIR_ROWS):
+            raise ValueError(f"zero_padding: kind {kind} does not go with {R} rows per scene at N = {N}")
+        _same_device(n_agents.dev, t)
+        arr.append(_lib.ZeroItem(ptr=t.data_ptr(), pitch=pitch * t.element_size(), width=w * t.element_size(), kind=kind))
+    if not arr:
+        return
+    if len(arr) > _lib.MAX_ZERO_ITEMS:
+        raise ValueError(f"zero_padding: at most {_lib.MAX_ZERO_ITEMS} tensors per launch")
+    with torch.cuda.device(n_agents.dev.device):
+        check(load().gn_zero_padding((_lib.ZeroItem * len(arr))(*arr), len(arr), B, N, addr(n_agents.dev), stream_handle()),
+              "gn_zero_padding")
+
+
 # ---- A0 / A1 -----------------------------------------------------------------------------------
 def affinity(f: Tensor) -> Tensor:
     """corr = normalize(f) @ normalize(f)^T   (model/GroupNet_nba.py:284-286)."""
@@ -191,18 +285,26 @@ def _scale_args(Hs: List[Tensor], scales: Sequence[int]):
     return Hl, kl, n
 
 
-def topk_incidence(corr: Tensor, scales: Sequence[int]) -> List[Tensor]:
-    """H per scale from corr (MS_HGNN_hyper.init_adj_attention, model/MS_HGNN_batch.py:372-388)."""
+def topk_incidence(corr: Tensor, scales: Sequence[int], n_agents=None) -> List[Tensor]:
+    """H per scale from corr (MS_HGNN_hyper.init_adj_attention, model/MS_HGNN_batch.py:372-388).  ``n_agents`` (ragged
+    batch, `agent_counts`): row i < n_b holds the top-min(scale, n_b) of corr[b, i, :n_b], everything else is zeros and a
+    scale-N hyperedge holds the n_b valid agents (gn_topk_incidence_ragged_f32)."""
     _req(corr, "corr", (None, None, None))
     B, N, N2 = corr.shape
     if N != N2:
         raise ValueError(f"corr: expected (B,N,N), got {tuple(corr.shape)}")
     if not 1 <= len(scales) <= 8:
         raise ValueError("between 1 and 8 scales per call")
+    counts = agent_counts(n_agents, B, N, corr.device)
     Hs = _alloc_incidence(B, N, scales, corr.device)
     Hl, kl, n = _scale_args(Hs, scales)
     with torch.cuda.device(corr.device):
-        check(load().gn_topk_incidence_f32(addr(corr), Hl, kl, n, B, N, stream_handle()), "gn_topk_incidence_f32")
+        if counts is not None:
+            _same_device(corr, counts.dev)
+            check(load().gn_topk_incidence_ragged_f32(addr(corr), Hl, kl, n, B, N, addr(counts.dev), stream_handle()),
+                  "gn_topk_incidence_ragged_f32")
+        else:
+            check(load().gn_topk_incidence_f32(addr(corr), Hl, kl, n, B, N, stream_handle()), "gn_topk_incidence_f32")
     return Hs
 
 
@@ -316,7 +418,7 @@ def graph_form(N: int, D: int, x_dim: int = 0, mask_scales: int = 0) -> str:
 
 def affinity_topk(f: Optional[Tensor], scales: Sequence[int], want_corr: bool = True, f_out: Optional[Tensor] = None,
                   want_H_cat: bool = False, counter: Optional[Tensor] = None, counter_add: int = 0,
-                  embed: Optional[Tuple[Tensor, Tensor, Tensor]] = None, want_masks: bool = False):
+                  embed: Optional[Tuple[Tensor, Tensor, Tensor]] = None, want_masks: bool = False, n_agents=None):
     """Fused A0+A1: f -> (corr, [H_s], H_cat) in one launch.  ``want_masks`` (N <= 64): the launch also writes the
     bit-mask form of every H_s; the LAST return value then is the list of `IncidenceMasks`, one per scale.
 
@@ -324,8 +426,10 @@ def affinity_topk(f: Optional[Tensor], scales: Sequence[int], want_corr: bool = 
     (B, N, D) of a wider contiguous tensor that also receives f; ``want_H_cat`` — also build
     cat(H_s, dim=1); ``counter``/``counter_add`` — advance the device Philox position.
     ``embed`` = (x_raw (B,N,xd), M (D,xd), c (N,D)): f itself is computed in the launch as M x + c[n]
-    (pass f=None, fp32 only); a fourth return value then carries f (B,N,D)."""
-    job = AffinityTail(f, scales, want_corr, f_out, want_H_cat, counter, counter_add, embed, want_masks)
+    (pass f=None, fp32 only); a fourth return value then carries f (B,N,D).
+    ``n_agents`` (ragged batch, `agent_counts`): the incidences and corr of scenes with n_b <= N agents each
+    (gn_affinity_topk_ragged_*: valid blocks as each scene alone, zeros elsewhere); not with ``embed`` or ``want_masks``."""
+    job = AffinityTail(f, scales, want_corr, f_out, want_H_cat, counter, counter_add, embed, want_masks, n_agents)
     job.launch()
     return (job.corr, job.Hs, job.H_cat) + ((job.f,) if embed is not None else ()) + ((job.masks,) if want_masks else ())
 
@@ -337,12 +441,17 @@ class AffinityTail:
     are the attributes ``f``, ``corr``, ``Hs``, ``H_cat``, ``masks`` and ``incidences`` (one `Incidence` per scale: H_s with
     its masks, what `run_message_passing` takes after the pairwise module's None).
     ``want_masks``: also emit the bit-mask form of every H_s (``masks``: one `IncidenceMasks` per scale).  Only the
-    stand-alone launch emits masks, so the job then declines the tail (`fits_tail()` is False)."""
+    stand-alone launch emits masks, so the job then declines the tail (`fits_tail()` is False).
+    ``n_agents`` (ragged batch): the ragged launch, which is never the tail either and takes neither ``embed`` nor
+    ``want_masks``."""
 
     def __init__(self, f: Optional[Tensor], scales: Sequence[int], want_corr: bool = False,
                  f_out: Optional[Tensor] = None, want_H_cat: bool = False, counter: Optional[Tensor] = None,
-                 counter_add: int = 0, embed: Optional[Tuple[Tensor, Tensor, Tensor]] = None, want_masks: bool = False):
+                 counter_add: int = 0, embed: Optional[Tuple[Tensor, Tensor, Tensor]] = None, want_masks: bool = False,
+                 n_agents=None):
         ex = {}
+        if n_agents is not None and (embed is not None or want_masks):
+            raise ValueError("n_agents: the ragged launch has no embedding front-end and emits no masks")
         if embed is not None:
             x_raw, M, c = embed
             _req(x_raw, "x_raw", (None, None, None))
@@ -356,6 +465,7 @@ class AffinityTail:
         _req(f, "f", (None, None, None), _ACT_DTYPES)
         self.f, self.scales = f, [int(s) for s in scales]
         B, N, D = f.shape
+        self.counts = agent_counts(n_agents, B, N, f.device)
         self.corr = torch.empty((B, N, N), dtype=torch.float32, device=f.device) if want_corr else None
         self.Hs = _alloc_incidence(B, N, self.scales, f.device)
         self._Hl, self._kl, n = _scale_args(self.Hs, self.scales)
@@ -387,7 +497,7 @@ class AffinityTail:
 
     def fits_tail(self) -> bool:
         B, N, D = self.f.shape
-        return self.masks is None and graph_form(N, D, int(self._ex.x_dim)) == "tail"
+        return self.masks is None and self.counts is None and graph_form(N, D, int(self._ex.x_dim)) == "tail"
 
     def launch(self) -> None:
         """The stand-alone launch (nothing took the job along)."""
@@ -395,9 +505,15 @@ class AffinityTail:
             return
         B, N, D = self.f.shape
         with torch.cuda.device(self.f.device):
-            check(_fn("gn_affinity_topk", self.f.dtype)(addr(self.f), addr(self.corr), self._Hl, self._kl, len(self.Hs), B, N, D,
-                                                        ctypes.byref(self._ex), self._rl, self._cl, stream_handle()),
-                  "gn_affinity_topk")
+            if self.counts is not None:
+                _same_device(self.f, self.counts.dev)
+                check(_fn("gn_affinity_topk_ragged", self.f.dtype)(
+                    addr(self.f), addr(self.corr), self._Hl, self._kl, len(self.Hs), B, N, D, ctypes.byref(self._ex),
+                    addr(self.counts.dev), stream_handle()), "gn_affinity_topk_ragged")
+            else:
+                check(_fn("gn_affinity_topk", self.f.dtype)(addr(self.f), addr(self.corr), self._Hl, self._kl, len(self.Hs), B, N, D,
+                                                            ctypes.byref(self._ex), self._rl, self._cl, stream_handle()),
+                      "gn_affinity_topk")
         self.done = True
 
 
@@ -479,17 +595,21 @@ def pair_count(N: int) -> int:
     return N * (N + 1) // 2
 
 
-def node2edge_grouped(items: Sequence[tuple]) -> List[Tensor]:
+def node2edge_grouped(items: Sequence[tuple], n_agents=None) -> List[Tensor]:
     """items = [(xp, pq, H or None, w2 (32,), b2 (1,)[, sym[, masks]])] over the same (B, N); returns [edges (B,E,64)].
     w2 / b2 = weight row and bias of attention layer 1, device tensors (the parameters themselves).
     H=None selects the implicit pairwise graph: E = N*N ordered edges, or with sym=True the
     N(N+1)/2 unordered pairs (edges (i,j) and (j,i) carry the same feature).
     ``masks`` (an `IncidenceMasks` of a 0/1 H, N <= 64; every hyper group of a call or none): where the launch takes its
-    row form it reads the row words instead of H (gn_node2edge_masks_*); H stays in the item, the rows are the same."""
+    row form it reads the row words instead of H (gn_node2edge_masks_*); H stays in the item, the rows are the same.
+    ``n_agents`` (ragged batch, `agent_counts`): every scene pools over its own n_b nodes (gn_node2edge_ragged_*): an H
+    must have zero columns >= n_b (the ragged incidences do), pairwise edges with an end >= n_b come out as zeros; no
+    masks."""
     _groups(len(items))
     xp0 = _req(items[0][0], "xp", (None, None, FEAT), _ACT_DTYPES)
     dt = xp0.dtype
     B, N, _ = xp0.shape
+    counts = agent_counts(n_agents, B, N, xp0.device)
     arr = (_lib.N2EGroup * len(items))()
     outs, words = [], []
     for g, item in enumerate(items):
@@ -510,6 +630,8 @@ def node2edge_grouped(items: Sequence[tuple]) -> List[Tensor]:
                 raise ValueError("masks apply to a hyper group (an explicit H) only")
             if not isinstance(masks, IncidenceMasks):
                 raise ValueError("masks: expected an ops.IncidenceMasks")
+            if counts is not None:
+                raise ValueError("n_agents: the ragged node->edge launch reads the dense H, not masks")
             _req(masks.row, "masks.row", (B, E), torch.int64)
             words.append(masks.row)
         else:
@@ -522,7 +644,11 @@ def node2edge_grouped(items: Sequence[tuple]) -> List[Tensor]:
                                b2=b2.data_ptr(), E=E, sym=int(sym))
         outs.append(edges)
     with torch.cuda.device(xp0.device):
-        if any(w is not None for w in words):
+        if counts is not None:
+            _same_device(xp0, counts.dev)
+            check(_fn("gn_node2edge_ragged", dt)(arr, len(items), B, N, addr(counts.dev), stream_handle()),
+                  "gn_node2edge_ragged")
+        elif any(w is not None for w in words):
             rows = (ctypes.c_void_p * len(items))(*[None if w is None else w.data_ptr() for w in words])
             check(_fn("gn_node2edge_masks", dt)(arr, rows, len(items), B, N, stream_handle()), "gn_node2edge_masks")
         else:
@@ -531,8 +657,8 @@ def node2edge_grouped(items: Sequence[tuple]) -> List[Tensor]:
 
 
 def node2edge(xp: Tensor, pq: Tensor, H: Optional[Tensor], w2: Tensor, b2: Tensor, sym: bool = False,
-              masks: Optional["IncidenceMasks"] = None) -> Tensor:
-    return node2edge_grouped([(xp, pq, H, w2, b2, sym, masks)])[0]
+              masks: Optional["IncidenceMasks"] = None, n_agents=None) -> Tensor:
+    return node2edge_grouped([(xp, pq, H, w2, b2, sym, masks)], n_agents)[0]
 
 
 # ---- A4 ------------------------------------------------------------------------------------------
@@ -890,20 +1016,25 @@ def node_linear(x: Tensor, W: Tensor, bias: Tensor, dout: int) -> Tensor:
     return y
 
 
-def agg_scatter_grouped(items: Sequence[tuple], divisor: Optional[float] = None) -> List[Tensor]:
+def agg_scatter_grouped(items: Sequence[tuple], divisor: Optional[float] = None, n_agents=None) -> List[Tensor]:
     """items = [(feat (B,E,64), H or None, ori (B,N,64)[, sym[, masks]])] -> [cat(H^T feat, ori) / divisor
     (B,N,128)]; divisor defaults to N (edge2node, model/MS_HGNN_batch.py:120,355).  ``masks``: as `agg_gather_grouped`
-    (the column words are read)."""
+    (the column words are read).
+    ``n_agents`` (ragged batch, `agent_counts`; gn_agg_scatter_ragged_*): node n < n_b adds its hyperedges / its partners
+    j < n_b, the divisor defaults to each scene's own n_b, rows n >= n_b are zeros; no masks."""
     _groups(len(items))
     o0 = _req(items[0][2], "ori", (None, None, FEAT), _ACT_DTYPES)
     dt = o0.dtype
     B, N, _ = o0.shape
+    counts = agent_counts(n_agents, B, N, o0.device)
     arr = (_lib.ScatterGroup * len(items))()
     outs = []
     for g, item in enumerate(items):
         feat, H, ori = item[:3]
         sym = bool(item[3]) if len(item) > 3 else False
         masks = item[4] if len(item) > 4 else None
+        if masks is not None and counts is not None:
+            raise ValueError("n_agents: the ragged scatter reads the dense H, not masks")
         _req(ori, "ori", (B, N, FEAT), dt)
         E = _edge_count(H, B, N, sym, masks)
         _req(feat, "feat", (B, E, FEAT), dt)
@@ -913,14 +1044,21 @@ def agg_scatter_grouped(items: Sequence[tuple], divisor: Optional[float] = None)
                                    sym=int(sym), colmask=0 if masks is None else masks.col.data_ptr())
         outs.append(out)
     with torch.cuda.device(o0.device):
-        check(_fn("gn_agg_scatter", dt)(arr, len(items), B, N, float(N if divisor is None else divisor),
-                                        stream_handle()), "gn_agg_scatter")
+        if counts is not None:
+            _same_device(o0, counts.dev)
+            if divisor is not None and not divisor > 0:
+                raise ValueError("divisor: positive, or None for each scene's own count")
+            check(_fn("gn_agg_scatter_ragged", dt)(arr, len(items), B, N, float(0.0 if divisor is None else divisor),
+                                                   addr(counts.dev), stream_handle()), "gn_agg_scatter_ragged")
+        else:
+            check(_fn("gn_agg_scatter", dt)(arr, len(items), B, N, float(N if divisor is None else divisor),
+                                            stream_handle()), "gn_agg_scatter")
     return outs
 
 
 def agg_scatter(feat: Tensor, H: Optional[Tensor], ori: Tensor, divisor: Optional[float] = None,
-                sym: bool = False, masks: Optional[IncidenceMasks] = None) -> Tensor:
-    return agg_scatter_grouped([(feat, H, ori, sym, masks)], divisor)[0]
+                sym: bool = False, masks: Optional[IncidenceMasks] = None, n_agents=None) -> Tensor:
+    return agg_scatter_grouped([(feat, H, ori, sym, masks)], divisor, n_agents)[0]
 
 
 # ---- A6 ------------------------------------------------------------------------------------------

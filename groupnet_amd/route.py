@@ -71,12 +71,27 @@ def masks_in_range(N: int) -> bool:
 
 @functools.lru_cache(maxsize=None)
 def message_passing_route(N: int, modules: Tuple[Tuple[bool, int], ...], *, twin: bool, training: bool, matrix16: bool,
-                          knobs: Knobs, closing_asked: bool) -> Route:
+                          knobs: Knobs, closing_asked: bool, ragged: bool = False) -> Route:
     """The route of one forward over N agents.  modules: (pairwise, K edge types) per module in launch order; twin: bf16
     storage; training: the forward keeps what a backward reads; matrix16: the 16-bit-core weight images are in use;
-    closing_asked: the caller would like the aggregation launch to apply the closing MLP."""
+    closing_asked: the caller would like the aggregation launch to apply the closing MLP.
+    ragged: the scenes hold different numbers of agents (N is the padded size; inference only).  The agent count enters
+    the arithmetic in the node->edge pooling and in the scatter, so both run as their own (count-aware) launches and
+    every form that fuses one of them into an MFMA kernel is left out: no pooling in the edge kernel, no node / scene
+    form of the pairwise aggregation (their sums run over all N partners), no closing stage in the aggregation launch,
+    no fused scatter, no masks.  What stays is row-wise or reads the padding only through zero entries of H."""
     if twin and training:
         raise NotImplementedError("the bf16 twins are forward-only")
+    if ragged:
+        if training:
+            raise NotImplementedError("ragged batches are inference-only")
+        mods = [ModuleRoute(False, pairwise and not twin,
+                            (TWIN_PAIR if twin else PAIR) if pairwise else (FUSED_GATHER if N <= _FUSED_GATHER_MAX_N else EO),
+                            False, SCATTER) for pairwise, _ in modules]
+        every = tuple(range(len(mods)))
+        return Route(modules=tuple(mods), node2edge=every,
+                     gather=tuple(i for i, m in enumerate(mods) if m.source == EO), scatter=every, masks=False,
+                     ask_closing=False)
     mods = []
     for pairwise, K in modules:
         # Inference: the pooled edge rows feed only the edge MLP, so its kernel forms them itself and `edges` never

@@ -60,6 +60,19 @@
  *     gn_node2edge_masks_* hand the row form of the node -> edge pooling the same rowmask words, one 8-byte load per
  *     hyperedge instead of a scan of its dense row.  What still reads the dense H: the banded form of the node -> edge
  *     pooling, gn_node2edge_bwd_*, the pooling inside the edge kernel (N <= 16), and everything at N > 64.
+ *   - Ragged batches (ABI 39, additive: new symbols, one new struct and new kernel ids; nothing that existed changed):
+ *     scenes of ONE call may hold different numbers of agents.  Tensors keep the padded shapes (B, N, ...); `n_valid` is
+ *     a DEVICE array of B ints (4-byte aligned, non-NULL, else GN_ERR_NULL / GN_ERR_ALIGN): scene b's first n_valid[b]
+ *     agent rows are real, 1 <= n_valid[b] <= N, the rest is padding.  Every kernel clamps the count it reads to [0, N],
+ *     so no address depends on an unchecked value.  Padded input rows must be FINITE (they are read, multiplied by zero
+ *     weights, and never reach a valid value); every value at a valid position — node rows n < n_b, pairwise edges (i, j)
+ *     with i, j < n_b, hyperedge rows e < n_b or the single row of a scale-N module — is what the same entry point
+ *     computes for scene b alone as an n_b-agent scene.  The count enters the arithmetic in four stages, each with an
+ *     entry point of its own below (gn_affinity_topk_ragged_*, gn_topk_incidence_ragged_f32, gn_node2edge_ragged_*,
+ *     gn_agg_scatter_ragged_*); every other stage is row-wise or reads the padding only through zero entries of H and
+ *     needs no count.  gn_zero_padding zeroes the padded positions of the outputs.
+ *     The E = 1 shortcut of a module with scale == N is keyed on the padded N: a scene with n_b <= scale < N gets n_b
+ *     identical all-member hyperedges (for every scene with n_b > scale the graph is the reference's own).
  */
 #ifndef GROUPNET_HIP_H
 #define GROUPNET_HIP_H
@@ -171,6 +184,23 @@ int gn_affinity_topk_bf16(const void* f, float* corr, float* const* H_list, cons
                           int n_scales, int B, int N, int D, const gn_block_extras_t* extras,
                           unsigned long long* const* rowmask_list, unsigned long long* const* colmask_list,
                           gn_stream_t stream);
+
+/* The stand-alone fused launch over a ragged batch (header comment; ABI 39).  Row i < n_b of H_s holds the
+ * top-min(k_s, n_b) of corr[b, i, :n_b] (the same ranking rules); rows and columns >= n_b of every H_s and of H_cat are
+ * zeros; a scale k_s == N is the single hyperedge (B,1,N) holding exactly the n_b valid agents; corr (may be NULL) holds
+ * the affinities of the valid block and zeros elsewhere.  extras: f_out, H_cat and counter as above (f_out receives
+ * every row of f, padded ones included); the embedding front-end (extras->x_raw) is refused with GN_ERR_SHAPE.  The
+ * launch emits no mask lists and is never the node stage's tail. */
+int gn_affinity_topk_ragged_f32(const float* f, float* corr, float* const* H_list, const int* k_list, int n_scales,
+                                int B, int N, int D, const gn_block_extras_t* extras, const int* n_valid,
+                                gn_stream_t stream);
+int gn_affinity_topk_ragged_bf16(const void* f, float* corr, float* const* H_list, const int* k_list, int n_scales,
+                                 int B, int N, int D, const gn_block_extras_t* extras, const int* n_valid,
+                                 gn_stream_t stream);
+/* gn_topk_incidence_f32 over a ragged batch, the same rules: corr rows and columns >= n_b are not ranked (they may hold
+ * anything finite or not: they are only copied into LDS). */
+int gn_topk_incidence_ragged_f32(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B, int N,
+                                 const int* n_valid, gn_stream_t stream);
 
 /* Bit-mask form (header comment) of a dense incidence H (B,E,N) — a caller-supplied H, gn_listall_incidence_f32's, the
  * banded top-k's of large N, or one that came out of the node stage's tail: rowmask (B,E), colmask (B,N), the incidence
@@ -307,6 +337,16 @@ int gn_node2edge_masks_f32(const gn_n2e_group_t* groups, const unsigned long lon
                            int N, gn_stream_t stream);
 int gn_node2edge_masks_bf16(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks, int n_groups, int B,
                             int N, gn_stream_t stream);
+
+/* The same launch over a ragged batch (header comment; ABI 39): softmax(att * H) * H runs over the scene's n_b nodes —
+ * the non-member term is (n_b - members) exp(0 - max), and the 0 enters the running max only if such a non-member
+ * exists.  Hyper groups: dense H (banded or row form as gn_node2edge_* choose), whose columns >= n_b must be zeros (the
+ * ragged incidence launches write them so); rows of all-zero hyperedges come out as zeros.  Pairwise groups (ordered or
+ * sym): only pairs with both ends < n_b exist; every other edge row is written as zeros. */
+int gn_node2edge_ragged_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
+                            gn_stream_t stream);
+int gn_node2edge_ragged_bf16(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
+                             gn_stream_t stream);
 
 /* ---- A4: per-edge MLPs + Gumbel-softmax edge typing ----------------------------------------
  * Replaces MLP_dict_softmax.forward + gumbel_softmax, MS_HGNN_batch.py:41-53,446-520:
@@ -509,6 +549,35 @@ int gn_agg_scatter_f32(const gn_scatter_group_t* groups, int n_groups, int B, in
 int gn_agg_scatter_bf16(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
                         gn_stream_t stream);
 
+/* The scatter over a ragged batch (header comment; ABI 39), every group in ONE launch of one straightforward kernel:
+ * node n < n_b receives cat(H^T feat, ori)[n] / divisor — a hyper group (dense H; colmask must be NULL) adds its
+ * hyperedges, a pairwise group (ordered, or sym) its partners j < n_b only.  divisor == 0 divides each scene by its own
+ * n_b (edge2node); a positive divisor behaves as in gn_agg_scatter_*.  Rows n >= n_b of out are written as zeros. */
+int gn_agg_scatter_ragged_f32(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
+                              const int* n_valid, gn_stream_t stream);
+int gn_agg_scatter_ragged_bf16(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
+                               const int* n_valid, gn_stream_t stream);
+
+/* Zeroes the padded positions of up to GN_MAX_ZERO_ITEMS tensors of a ragged batch in ONE launch (ABI 39): what a ragged
+ * forward ends with, whatever its number of modules.  `items` is a HOST array.  A tensor is `rows per scene` rows of
+ * `width` bytes at a pitch of `pitch` bytes (a column block of a wider tensor has pitch > width); width, pitch and the
+ * address are multiples of 2, else GN_ERR_ALIGN (rows are written as 4-byte words where all three are multiples of 4,
+ * else as 2-byte words: a bf16 row of an odd number of elements).  kind: GN_ZERO_NODE_ROWS — (B,N,.), rows n >= n_b; GN_ZERO_EDGE_ROWS —
+ * the (B,N,.) hyperedge rows of a top-k module, rows e >= n_b (the single row of a scale-N module is always valid: do
+ * not list it); GN_ZERO_PAIR_ROWS — (B,N*N,.) ordered pair rows i*N + j with i >= n_b or j >= n_b (also an (B,N,N)
+ * matrix with width = the element size: corr, H, new_H).  Valid positions are not touched. */
+#define GN_MAX_ZERO_ITEMS 24
+#define GN_ZERO_NODE_ROWS 0
+#define GN_ZERO_EDGE_ROWS 1
+#define GN_ZERO_PAIR_ROWS 2
+typedef struct {
+  void* ptr;
+  long long pitch;
+  int width;
+  int kind;
+} gn_zero_item_t;
+int gn_zero_padding(const gn_zero_item_t* items, int n_items, int B, int N, const int* n_valid, gn_stream_t stream);
+
 /* ---- A6 / generic two-layer MLP ---------------------------------------------------------------
  * y = W1 relu(W0 x + b0) + b1     (MLP.forward with one hidden layer, MS_HGNN_batch.py:220-229;
  * nmp_mlp_end 128->128->bottleneck and nmp_mlps[even] 128->128->64).
@@ -588,6 +657,12 @@ int gn_mlp2_bf16(const gn_mlp2_group_t* groups, int n_groups, int rows, int din,
 #define GN_K_AGG_SCATTER_DIRECT 25   /* scatter of one group from global memory (its mode is the group's: H, ordered pairs
                                         or, sym, unordered pairs) */
 #define GN_K_AGG_SCATTER_PAIRS 26    /* scatter of the unordered pairs, one workgroup per scene */
+/* ABI 39: the kernels of the ragged entry points */
+#define GN_K_AFFINITY_TOPK_RAGGED 27
+#define GN_K_TOPK_INCIDENCE_RAGGED 28
+#define GN_K_NODE2EDGE_RAGGED 29     /* variant: 0 banded, 1 row form, as GN_K_NODE2EDGE */
+#define GN_K_AGG_SCATTER_RAGGED 30   /* grid (ceil(B N 32 / 256) capped, groups) */
+#define GN_K_ZERO_PADDING 31         /* grid (capped, items); a plan without groups */
 typedef struct {
   int kernel;        /* GN_K_*: the kernel of the launch (gn_kernel_name), instantiated for ... */
   int precision;     /* ... 0: the plain fp32 weight stream, 1: bf16 storage (the twins), 2: f16x3, 3: bf16x6 */
@@ -666,6 +741,27 @@ int gn_affinity_topk_plan_f32(const float* f, float* corr, float* const* H_list,
 int gn_affinity_topk_plan_bf16(const void* f, float* corr, float* const* H_list, const int* k_list, int n_scales, int B,
                                int N, int D, const gn_block_extras_t* extras, unsigned long long* const* rowmask_list,
                                unsigned long long* const* colmask_list, gn_launch_plan_t* plan);
+
+/* The ragged entry points (ABI 39): the plans of their full-batch counterparts with the kernel ids above; n_valid is
+ * tested for NULL and 4-byte alignment like every other address. */
+int gn_affinity_topk_ragged_plan_f32(const float* f, float* corr, float* const* H_list, const int* k_list, int n_scales,
+                                     int B, int N, int D, const gn_block_extras_t* extras, const int* n_valid,
+                                     gn_launch_plan_t* plan);
+int gn_affinity_topk_ragged_plan_bf16(const void* f, float* corr, float* const* H_list, const int* k_list, int n_scales,
+                                      int B, int N, int D, const gn_block_extras_t* extras, const int* n_valid,
+                                      gn_launch_plan_t* plan);
+int gn_topk_incidence_ragged_plan_f32(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B,
+                                      int N, const int* n_valid, gn_launch_plan_t* plan);
+int gn_node2edge_ragged_plan_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
+                                 gn_launch_plan_t* plan);
+int gn_node2edge_ragged_plan_bf16(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
+                                  gn_launch_plan_t* plan);
+int gn_agg_scatter_ragged_plan_f32(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
+                                   const int* n_valid, gn_launch_plan_t* plan);
+int gn_agg_scatter_ragged_plan_bf16(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor,
+                                    const int* n_valid, gn_launch_plan_t* plan);
+int gn_zero_padding_plan(const gn_zero_item_t* items, int n_items, int B, int N, const int* n_valid,
+                         gn_launch_plan_t* plan);
 
 /* ---- backward (training) building blocks — SURVEY.md §8f rank 2 -------------------------------
  * train_hyper_nba.py:116 back-propagates through the two modules.  The backward of the path is
