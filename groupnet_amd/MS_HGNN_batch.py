@@ -362,7 +362,8 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     Hs are the ragged incidences (zero rows and columns >= n_b).  The forward takes the ragged route: the node->edge
     launch and the scatter launch receive the counts, everything else is row-wise or meets the padding only through
     zeros of H, and ONE more launch zeroes the padded positions of every node_feat and factors at the end.  Counts that
-    all equal N are no counts."""
+    all equal N are no counts.  An `ops.StaticAgentCounts` (a captured graph's counts) keeps the ragged route whatever it
+    holds and admits empty slots, n_b = 0: a second small launch then zeroes their single factor row of scale-N modules."""
     n = len(mods)
     if not (n == len(hs) == len(Hs) == len(noises) == len(outs)) or n == 0:
         raise ValueError("run_message_passing: one h, H, noise and out per module")
@@ -516,6 +517,8 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
         ops.zero_padding([(x, ops.ZERO_NODE_ROWS) for x in node_feats] +
                          [(fc, ops.ZERO_PAIR_ROWS if H is None else ops.ZERO_EDGE_ROWS) for fc, H in zip(factors, dense)],
                          counts)
+        if counts.admits_empty:      # an empty slot: the single row of a scale-N module is not padding, yet must be zeros
+            ops.zero_empty_scenes([fc for fc, H in zip(factors, dense) if H is not None and fc.shape[1] == 1], counts)
     return list(zip(node_feats, factors))
 
 

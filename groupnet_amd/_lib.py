@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must be imported before the .so is loaded)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GROUPNET_HIP_LIB") or os.path.join(_HERE, "libgroupnet_hip.so")  # env: tuning builds
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 GN_OK = 0
 GN_ERR_NULL = -1
@@ -164,6 +164,7 @@ K_LAST = K_ZERO_PADDING
 MAX_GROUPS = 10
 MAX_ZERO_ITEMS = 24
 ZERO_NODE_ROWS, ZERO_EDGE_ROWS, ZERO_PAIR_ROWS = 0, 1, 2      # gn_zero_item_t.kind
+COUNTS_NOT_PREFIX, COUNTS_EMPTY = 1, 2                        # GN_COUNTS_*: the status word of gn_agent_counts_u8
 
 # name -> (restype, argtypes); mirrors include/groupnet_hip.h one to one
 SIGNATURES = {
@@ -253,6 +254,10 @@ SIGNATURES = {
     "gn_agg_scatter_ragged_plan_bf16": (_I, [ctypes.POINTER(ScatterGroup), _I, _I, _I, _F, _P, ctypes.POINTER(LaunchPlan)]),
     "gn_zero_padding": (_I, [ctypes.POINTER(ZeroItem), _I, _I, _I, _P, _P]),
     "gn_zero_padding_plan": (_I, [ctypes.POINTER(ZeroItem), _I, _I, _I, _P, ctypes.POINTER(LaunchPlan)]),
+    "gn_zero_empty_scenes": (_I, [ctypes.POINTER(ZeroItem), _I, _I, _P, _P]),
+    "gn_zero_empty_scenes_plan": (_I, [ctypes.POINTER(ZeroItem), _I, _I, _P, ctypes.POINTER(LaunchPlan)]),
+    "gn_agent_counts_u8": (_I, [_P, _I, _I, _P, _P, _P]),
+    "gn_agent_counts_plan_u8": (_I, [_P, _I, _I, _P, _P, ctypes.POINTER(LaunchPlan)]),
     "gn_gemm_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _F, _F, _P]),
     "gn_gemm_grouped_f32": (_I, [ctypes.POINTER(GemmDesc), _I, _P]),
     "gn_typed_bwd_f32": (_I, [_P, _P, _P, _I, _P, _P, _P, ctypes.c_longlong, _I, _I, _P]),

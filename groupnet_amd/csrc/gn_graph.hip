@@ -1203,6 +1203,58 @@ __global__ __launch_bounds__(kBlock) void zero_padding_kernel(ZeroTable T, int B
   }
 }
 
+// Zeroes whole scenes of a list of tensors where the scene is EMPTY, n_valid[b] <= 0 (gn_zero_empty_scenes): blockIdx.y =
+// tensor; scene b of a tensor is `width` bytes at b * `pitch` bytes.  What zero_padding_kernel leaves out — the single
+// hyperedge row of a scale-N module — for the holders of counts that admit an empty slot.
+__global__ __launch_bounds__(kBlock) void zero_empty_scenes_kernel(ZeroTable T, int B, const int* __restrict__ n_valid) {
+  const gn_zero_item_t it = T.t[blockIdx.y];
+  const bool words = zero_item_unit(it) == 4;
+  const int wu = it.width / (words ? 4 : 2);          // units per scene
+  const long long total = (long long)B * wu;
+  for (long long idx = (long long)blockIdx.x * kBlock + threadIdx.x; idx < total; idx += (long long)gridDim.x * kBlock) {
+    const int b = (int)(idx / wu);
+    const int c = (int)(idx - (long long)b * wu);
+    if (n_valid[b] <= 0) {
+      unsigned char* row = reinterpret_cast<unsigned char*>(it.ptr) + (size_t)b * it.pitch;
+      if (words) reinterpret_cast<unsigned int*>(row)[c] = 0u;
+      else reinterpret_cast<unsigned short*>(row)[c] = (unsigned short)0;
+    }
+  }
+}
+
+// Agent counts from a validity mask (gn_agent_counts_u8): one wave per scene, kBlock / 64 scenes per workgroup.  The wave
+// walks the scene's N bytes in chunks of 64, one byte per lane; the ballot of a chunk is its 64 validity bits, lane 0 at
+// bit 0, so the number of trailing ones of the ballot is the chunk's leading run.  The count grows while every chunk so far
+// was all ones; a set bit behind the first zero is a hole.  Everything but the byte load is wave-uniform: lane 0 writes
+// the count with an ordinary store and ORs the flags into the sticky status word.
+__global__ __launch_bounds__(kBlock) void agent_counts_kernel(const unsigned char* __restrict__ valid, int B, int N,
+                                                              int* __restrict__ n_valid, unsigned int* __restrict__ status) {
+  const int lane = threadIdx.x & 63;
+  const int b = gn_uniform((int)(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)));
+  if (b >= B) return;                                   // (whole waves leave: the ballots below see full waves)
+  const unsigned char* row = valid + (size_t)b * N;
+  int count = 0;
+  bool open = true, hole = false;
+  for (int n0 = 0; n0 < N; n0 += 64) {
+    const int n = n0 + lane;
+    const bool v = n < N && row[n] != 0;                // lanes past the row vote 0: the run ends at N at the latest
+    const unsigned long long m = __ballot(v);
+    if (open) {
+      const int run = m == ~0ull ? 64 : __builtin_ctzll(~m);
+      count += run;
+      open = run == 64;
+      hole = hole || (run < 64 && (m >> run) != 0ull);
+    } else {
+      hole = hole || m != 0ull;
+    }
+  }
+  if (lane == 0) {
+    n_valid[b] = count;
+    const unsigned int flags = (hole ? GN_COUNTS_NOT_PREFIX : 0u) | (count == 0 ? GN_COUNTS_EMPTY : 0u);
+    if (flags != 0u) atomicOr(status, flags);
+  }
+}
+
 // --------------------------------------------------------------------------------------------
 // Exhaustive hyperedge search (init_adj_attention_listall, model/MS_HGNN_batch.py:390-414): hyperedge i =
 // the group of s agents containing i with the largest total affinity sum_{a,b in group} corr[a][b].
@@ -1347,7 +1399,7 @@ inline int capped_grid(long long work_items, int per_block, int cap = 256 * 16) 
 
 }  // namespace
 
-extern "C" int gn_abi_version(void) { return 39; }
+extern "C" int gn_abi_version(void) { return 40; }
 
 extern "C" const char* gn_kernel_name(int kernel) {
   static const char* const names[] = {"",
@@ -2241,6 +2293,69 @@ extern "C" int gn_zero_padding(const gn_zero_item_t* items, int n_items, int B, 
 extern "C" int gn_zero_padding_plan(const gn_zero_item_t* items, int n_items, int B, int N, const int* n_valid,
                                     gn_launch_plan_t* plan) {
   return plan == nullptr ? GN_ERR_NULL : zero_padding_entry(items, n_items, B, N, n_valid, nullptr, plan);
+}
+
+// The two launches of a ragged forward that takes its counts from a replaceable device buffer (ABI 40).  Neither kernel
+// has a GN_K_* id: a plan carries GN_K_NONE and the grid.
+// Whole scenes of empty slots: grid (capped, items)
+static int zero_empty_entry(const gn_zero_item_t* items, int n_items, int B, const int* n_valid, gn_stream_t stream,
+                            gn_launch_plan_t* plan) {
+  GN_CHECK(need_counts(n_valid));
+  if (items == nullptr) return GN_ERR_NULL;
+  if (n_items < 1 || n_items > GN_MAX_ZERO_ITEMS || B <= 0) return GN_ERR_SHAPE;
+  ZeroTable T{};
+  long long most = 0;
+  for (int g = 0; g < n_items; ++g) {
+    const gn_zero_item_t& it = items[g];
+    if (it.ptr == nullptr) return GN_ERR_NULL;
+    if (it.width <= 0 || it.pitch < it.width) return GN_ERR_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(it.ptr) & 1u) || (it.width & 1) || (it.pitch & 1)) return GN_ERR_ALIGN;
+    const long long words = (long long)B * (it.width / zero_item_unit(it));
+    most = words > most ? words : most;
+    T.t[g] = it;
+  }
+  gn_launch_plan_t p;
+  gn_launch_plan_t& q = plan != nullptr ? *plan : p;
+  plan_begin(q, 0);
+  q.kernel = GN_K_NONE;
+  q.grid[0] = capped_grid(most, kBlock);
+  q.grid[1] = n_items;
+  if (plan != nullptr) return GN_OK;
+  hipLaunchKernelGGL(zero_empty_scenes_kernel, dim3(q.grid[0], q.grid[1]), dim3(kBlock), 0, (hipStream_t)stream, T, B, n_valid);
+  return gn_check_launch();
+}
+extern "C" int gn_zero_empty_scenes(const gn_zero_item_t* items, int n_items, int B, const int* n_valid, gn_stream_t stream) {
+  return zero_empty_entry(items, n_items, B, n_valid, stream, nullptr);
+}
+extern "C" int gn_zero_empty_scenes_plan(const gn_zero_item_t* items, int n_items, int B, const int* n_valid,
+                                         gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : zero_empty_entry(items, n_items, B, n_valid, nullptr, plan);
+}
+
+// Counts from a validity mask: grid (ceil(B / 4)), one wave per scene
+static int agent_counts_entry(const unsigned char* valid, int B, int N, int* n_valid, unsigned int* status,
+                              gn_stream_t stream, gn_launch_plan_t* plan) {
+  GN_REQUIRE_PTR(valid);
+  GN_REQUIRE_PTR(status);
+  GN_CHECK(need_counts(n_valid));
+  if ((reinterpret_cast<uintptr_t>(status) & 3u) != 0) return GN_ERR_ALIGN;
+  if (B <= 0 || N <= 0) return GN_ERR_SHAPE;
+  gn_launch_plan_t p;
+  gn_launch_plan_t& q = plan != nullptr ? *plan : p;
+  plan_begin(q, 0);
+  q.kernel = GN_K_NONE;
+  q.grid[0] = (B - 1) / (kBlock / 64) + 1;
+  if (plan != nullptr) return GN_OK;
+  hipLaunchKernelGGL(agent_counts_kernel, dim3(q.grid[0]), dim3(kBlock), 0, (hipStream_t)stream, valid, B, N, n_valid, status);
+  return gn_check_launch();
+}
+extern "C" int gn_agent_counts_u8(const unsigned char* valid, int B, int N, int* n_valid, unsigned int* status,
+                                  gn_stream_t stream) {
+  return agent_counts_entry(valid, B, N, n_valid, status, stream, nullptr);
+}
+extern "C" int gn_agent_counts_plan_u8(const unsigned char* valid, int B, int N, int* n_valid, unsigned int* status,
+                                       gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : agent_counts_entry(valid, B, N, n_valid, status, nullptr, plan);
 }
 
 // Pitched copy (rows x width bytes, 16-byte pieces): the column block of the feature tensor that a rank ships into its

@@ -28,17 +28,38 @@ class GraphedMultiScale:
         g = GraphedMultiScale(block, B, N, seed=1234)
         feats, H = g(f)          # f is copied into the graph's input buffer; outputs are the
                                  # graph's static buffers (overwritten by the next call)
+
+    A RAGGED capture (``ragged=True``; INTEGRATION.md, "Ragged batches") replays batches whose scenes hold different
+    numbers of agents, empty slots (count 0) included:
+
+        g = GraphedMultiScale(block, B, N, seed=1234, ragged=True)
+        feats, H = g(f, n_agents=[11, 7, 0, ...])     # counts: a sequence of ints or a CPU integer tensor, 0..N
+        feats, H = g(f, agent_mask=valid)             # ... or a (B,N) bool / uint8 mask that is already on the GPU
+        feats, H = g(f)                               # the previous counts stay
+        g.status()                                    # the mask entry's sticky status word (synchronises)
     """
 
     def __init__(self, block: MultiScaleHGNN, B: int, N: int, seed: int = 0, device: Optional[torch.device] = None,
-                 warmup: int = 2, dtype: torch.dtype = torch.float32, affinity_tail: Optional[bool] = None):
+                 warmup: int = 2, dtype: torch.dtype = torch.float32, affinity_tail: Optional[bool] = None,
+                 ragged: bool = False):
         """``affinity_tail``: capture with `block.affinity_tail` set to this value (None: as the block has it) — True =
         the latency form (affinity + top-k in the first node stage's tail), False = the throughput form for graphs that
-        are replayed side by side on several streams (see `MultiScaleHGNN.affinity_tail`)."""
+        are replayed side by side on several streams (see `MultiScaleHGNN.affinity_tail`).
+        ``ragged``: capture the ragged route with the counts in an `ops.StaticAgentCounts` (``self.counts``), made and
+        filled with N before the capture begins: the graph holds the buffer's address, nothing is uploaded inside it, and
+        the route is the ragged one whatever the counts of a replay are.  Noise keeps the padded shapes and the same
+        ``draws_per_step``; the ragged affinity launch carries the counter bump."""
         p = next(block.parameters())
         self.device = device or p.device
         if self.device.type != "cuda":
             raise ValueError("GraphedMultiScale needs the block on a GPU")
+        self.counts: Optional[ops.StaticAgentCounts] = None
+        if ragged:      # the refusals of the eager ragged forward, before anything is allocated or launched
+            if block.training:
+                raise NotImplementedError("n_agents: ragged batches are inference-only (call block.eval() first)")
+            if any(m.listall for m in block.interaction_hyper):
+                raise NotImplementedError("n_agents: the exhaustive (listall) search has no ragged form")
+            self.counts = ops.StaticAgentCounts(B, N, self.device)
         self.block = block
         self.B, self.N = B, N
         self.seed = int(seed)
@@ -71,13 +92,37 @@ class GraphedMultiScale:
         # offset 0 + device counter: the position is entirely on the device; the first launch of the
         # forward moves the counter past the previous replay's draws
         _mods.set_noise_mode("device", seed=self.seed, offset=0, counter=self.counter)
-        return self.block(self.f_in, advance=(self.counter, self.draws_per_step))
+        return self.block(self.f_in, advance=(self.counter, self.draws_per_step), n_agents=self.counts)
 
-    def __call__(self, f: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
+    def __call__(self, f: Optional[Tensor] = None, n_agents=None, agent_mask: Optional[Tensor] = None
+                 ) -> Tuple[Tensor, Optional[Tensor]]:
+        """``n_agents`` / ``agent_mask`` (ragged captures only, at most one of them): this replay's counts — see
+        `ops.StaticAgentCounts.set` and `set_from_mask`; neither: the previous counts stay.  Both are checked on the host
+        before anything is copied or launched; neither path synchronises."""
+        if n_agents is not None or agent_mask is not None:
+            if self.counts is None:
+                raise ValueError("n_agents / agent_mask: the graph was captured without ragged=True")
+            if n_agents is not None and agent_mask is not None:
+                raise ValueError("n_agents and agent_mask: give at most one of them")
+            if n_agents is not None:
+                vals = ops.count_values(n_agents, self.B, self.N, lowest=0)
+            else:
+                ops._mask_arg(agent_mask, self.B, self.N, self.device)
         if f is not None:
             self.f_in.copy_(f, non_blocking=True)
+        if n_agents is not None:
+            self.counts.set(vals)
+        elif agent_mask is not None:
+            self.counts.set_from_mask(agent_mask)
         self.graph.replay()
         return self.out, self.H
+
+    def status(self) -> int:
+        """The sticky status word of the mask entry (`_lib.COUNTS_NOT_PREFIX` | `_lib.COUNTS_EMPTY`, 0: nothing seen) of
+        a ragged capture.  THE one call here that synchronises: it reads the device word back."""
+        if self.counts is None:
+            raise ValueError("status: the graph was captured without ragged=True")
+        return int(self.counts.status.item()) & 0xFFFFFFFF
 
 
 class GraphedPastEncoder:

@@ -169,9 +169,14 @@ class AgentCounts:
     when the first launch asks for it (a forward that refuses the call has then copied nothing).  Made by
     `agent_counts`; every ``n_agents=`` argument of this module takes one (or what `agent_counts` takes)."""
     __slots__ = ("counts", "N", "device", "_dev")
+    admits_empty = False        # every count is >= 1 (`StaticAgentCounts`: a count of 0, an empty slot, may occur)
 
     def __init__(self, counts: Tuple[int, ...], N: int, device):
         self.counts, self.N, self.device, self._dev = counts, N, torch.device(device), None
+
+    @property
+    def B(self) -> int:
+        return len(self.counts)
 
     @property
     def dev(self) -> Tensor:
@@ -180,17 +185,10 @@ class AgentCounts:
         return self._dev
 
 
-def agent_counts(n_agents, B: int, N: int, device) -> Optional[AgentCounts]:
-    """``n_agents`` — a sequence of ints or a CPU integer tensor, one count per scene, 1 <= n_b <= N — as an
-    `AgentCounts` on ``device``, or None when no scene is padded (every count equals N, or ``n_agents`` is None): the
-    caller then takes the full-batch path and gets its bits.  A GPU tensor is refused: reading it would synchronise."""
-    if n_agents is None:
-        return None
-    if isinstance(n_agents, AgentCounts):
-        if len(n_agents.counts) != B or n_agents.N != N:
-            raise ValueError(f"n_agents: counts of {len(n_agents.counts)} scenes padded to {n_agents.N}, "
-                             f"the call has {B} scenes padded to {N}")
-        return n_agents
+def count_values(n_agents, B: int, N: int, lowest: int = 1) -> List[int]:
+    """The host validation of ``n_agents`` — a sequence of ints or a CPU integer tensor, one count per scene,
+    ``lowest`` <= n_b <= N — as a list of B ints, or ValueError.  Pure: no device is asked.  ``lowest`` is 1 for a
+    call's ``n_agents=`` and 0 for `StaticAgentCounts.set`, whose batches may hold empty slots."""
     if isinstance(n_agents, torch.Tensor):
         if n_agents.is_cuda:
             raise ValueError("n_agents: a sequence of ints or a CPU integer tensor (a GPU tensor would have to be read "
@@ -207,13 +205,129 @@ def agent_counts(n_agents, B: int, N: int, device) -> Optional[AgentCounts]:
             raise ValueError("n_agents: every count must be an int")
     if len(vals) != B:
         raise ValueError(f"n_agents: {B} counts needed (one per scene), got {len(vals)}")
-    if any(not 1 <= v <= N for v in vals):
-        raise ValueError(f"n_agents: every count must lie in 1..{N} (the padded size)")
+    if any(not lowest <= v <= N for v in vals):
+        raise ValueError(f"n_agents: every count must lie in {lowest}..{N} (the padded size)")
+    return vals
+
+
+def agent_counts(n_agents, B: int, N: int, device) -> Optional[AgentCounts]:
+    """``n_agents`` — a sequence of ints or a CPU integer tensor, one count per scene, 1 <= n_b <= N — as an
+    `AgentCounts` on ``device``, or None when no scene is padded (every count equals N, or ``n_agents`` is None): the
+    caller then takes the full-batch path and gets its bits.  A GPU tensor is refused: reading it would synchronise.
+    An `AgentCounts` (a `StaticAgentCounts` included) passes through and keeps the ragged route whatever it holds."""
+    if n_agents is None:
+        return None
+    if isinstance(n_agents, AgentCounts):
+        if n_agents.B != B or n_agents.N != N:
+            raise ValueError(f"n_agents: counts of {n_agents.B} scenes padded to {n_agents.N}, "
+                             f"the call has {B} scenes padded to {N}")
+        return n_agents
+    vals = count_values(n_agents, B, N)
     if all(v == N for v in vals):
         return None
     if torch.device(device).type != "cuda":
         raise ValueError("n_agents: the counts go with GPU tensors; groupnet_amd has no CPU path")
     return AgentCounts(tuple(vals), N, device)
+
+
+class StaticAgentCounts(AgentCounts):
+    """Counts that live in ONE (B,) int32 device buffer for the holder's whole life, with replaceable values: what a
+    captured graph needs (`graphs.GraphedMultiScale(ragged=True)`), since a hipGraph captures the buffer's address.
+    Accepted wherever an `AgentCounts` is, and — as every `AgentCounts` instance — it keeps the ragged route even when
+    every count is N.  A count of 0 is admitted: an EMPTY SLOT, whose outputs are all zeros.  The buffer
+    starts filled with N.
+
+    ``set(counts)`` validates on the host (`count_values`, 0..N) and copies into the buffer asynchronously, ordered on
+    the current stream.  No host synchronisation in steady state: the values are staged in a RING of ``slots`` pinned
+    rows, each with an event recorded behind its copy.  A `set` takes the next row and first waits for that row's
+    event — the copy issued ``slots`` calls ago, which has long run when a replay follows every `set`; the wait returns
+    at once then and blocks only a host that runs more than ``slots`` copies ahead of the GPU.  Two `set`s in a row use
+    two rows, so the second cannot overwrite what the first copy has yet to read.
+
+    ``set_from_mask(valid)`` counts a (B,N) bool / uint8 GPU mask on the device (`counts_from_mask`) straight into the
+    buffer and reads nothing back; what it finds is ORed into ``status`` (one sticky device word, `_lib.COUNTS_*`).
+
+    The host does not know the values after `set_from_mask`, so ``counts`` raises: nothing on the ragged route may depend
+    on the values (it needs ``B`` and ``N`` only)."""
+    __slots__ = ("_B", "status", "_stage", "_events", "_next")
+    admits_empty = True
+
+    def __init__(self, B: int, N: int, device, slots: int = 4):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("n_agents: the counts go with GPU tensors; groupnet_amd has no CPU path")
+        if B < 1 or N < 1 or slots < 1:
+            raise ValueError("StaticAgentCounts: B, N and slots must be positive")
+        self._B, self.N, self.device = int(B), int(N), device
+        self._dev = torch.full((self._B,), self.N, dtype=torch.int32, device=device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=device)
+        self._stage = torch.empty((slots, self._B), dtype=torch.int32).pin_memory()
+        self._events = [None] * slots
+        self._next = 0
+
+    @property
+    def B(self) -> int:
+        return self._B
+
+    @property
+    def counts(self):
+        raise RuntimeError("StaticAgentCounts.counts: the values live on the device only (use B and N)")
+
+    @property
+    def dev(self) -> Tensor:
+        return self._dev
+
+    def set(self, counts) -> None:
+        vals = count_values(counts, self._B, self.N, lowest=0)
+        i = self._next
+        self._next = (i + 1) % len(self._events)
+        if self._events[i] is not None:
+            self._events[i].synchronize()       # the copy that last read this row: done long ago in steady state
+        self._stage[i].copy_(torch.tensor(vals, dtype=torch.int32))
+        with torch.cuda.device(self.device):
+            self._dev.copy_(self._stage[i], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+        self._events[i] = ev
+
+    def set_from_mask(self, valid: Tensor) -> None:
+        counts_from_mask(_mask_arg(valid, self._B, self.N, self.device), out=self._dev, status=self.status)
+
+
+def _mask_arg(valid, B: Optional[int], N: Optional[int], device=None) -> Tensor:
+    """A validity mask as the counts kernel takes it: a contiguous (B,N) bool or uint8 GPU tensor (checked on the host,
+    before anything is launched)."""
+    if not isinstance(valid, torch.Tensor) or not valid.is_cuda:
+        raise ValueError("agent_mask: a (B,N) torch.bool or torch.uint8 tensor on the GPU")
+    if valid.dtype not in (torch.bool, torch.uint8) or valid.dim() != 2 or not valid.is_contiguous():
+        raise ValueError(f"agent_mask: a contiguous (B,N) torch.bool or torch.uint8 tensor (got {valid.dtype}, "
+                         f"{tuple(valid.shape)})")
+    if (B is not None and valid.shape[0] != B) or (N is not None and valid.shape[1] != N) or valid.numel() == 0:
+        raise ValueError(f"agent_mask: expected shape ({B}, {N}), got {tuple(valid.shape)}")
+    if device is not None and valid.device != torch.device(device):
+        raise ValueError(f"tensors on different devices: {device} vs {valid.device}")
+    return valid
+
+
+def counts_from_mask(valid: Tensor, out: Optional[Tensor] = None, status: Optional[Tensor] = None
+                     ) -> Tuple[Tensor, Tensor]:
+    """Agent counts of a (B,N) bool / uint8 GPU validity mask, on the device (gn_agent_counts_u8): out[b] = the length
+    of the LEADING run of valid agents of scene b -> (out (B,) int32, status (1,) int32).  ``status`` is sticky — the
+    launch only ORs into it: `_lib.COUNTS_NOT_PREFIX` when some scene has a valid agent behind an invalid one (those are
+    not counted), `_lib.COUNTS_EMPTY` when some scene has none.  Nothing is read back; given ``out`` / ``status`` are
+    written in place (a fresh ``status`` starts at 0)."""
+    _mask_arg(valid, None, None)
+    B, N = valid.shape
+    if out is None:
+        out = torch.empty((B,), dtype=torch.int32, device=valid.device)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=valid.device)
+    _req(out, "out", (B,), torch.int32)
+    _req(status, "status", (1,), torch.int32)
+    _same_device(valid, out, status)
+    with torch.cuda.device(valid.device):
+        check(load().gn_agent_counts_u8(addr(valid), B, N, addr(out), addr(status), stream_handle()), "gn_agent_counts_u8")
+    return out, status
 
 
 ZERO_NODE_ROWS, ZERO_EDGE_ROWS, ZERO_PAIR_ROWS = _lib.ZERO_NODE_ROWS, _lib.ZERO_EDGE_ROWS, _lib.ZERO_PAIR_ROWS
@@ -227,7 +341,7 @@ def zero_padding(items: Sequence[Tuple[Tensor, int]], n_agents) -> None:
     may be a last-dim slice of a wider contiguous one; fp32 or bf16 (rows of an even number of bytes)."""
     if not isinstance(n_agents, AgentCounts):
         raise ValueError("zero_padding: n_agents must be an ops.AgentCounts (ops.agent_counts)")
-    B, N = len(n_agents.counts), n_agents.N
+    B, N = n_agents.B, n_agents.N
     arr = []
     for t, kind in items:
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 3 and t.shape[0] == B):
@@ -254,6 +368,34 @@ def zero_padding(items: Sequence[Tuple[Tensor, int]], n_agents) -> None:
     with torch.cuda.device(n_agents.dev.device):
         check(load().gn_zero_padding((_lib.ZeroItem * len(arr))(*arr), len(arr), B, N, addr(n_agents.dev), stream_handle()),
               "gn_zero_padding")
+
+
+def zero_empty_scenes(items: Sequence[Tensor], n_agents) -> None:
+    """Zero, in ONE launch, every scene with count 0 of the single-row tensors that `zero_padding` skips — the (B,1,w)
+    factor rows of scale-N modules, which reach an empty slot's row through row-wise stages (gn_zero_empty_scenes).  For
+    holders that admit a count of 0 (`StaticAgentCounts`); scenes with a count >= 1 keep their bits.  fp32 or bf16,
+    contiguous or a last-dim slice of a contiguous tensor."""
+    if not isinstance(n_agents, AgentCounts):
+        raise ValueError("zero_empty_scenes: n_agents must be an ops.AgentCounts")
+    B = n_agents.B
+    arr = []
+    for t in items:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 3 and tuple(t.shape[:2]) == (B, 1)):
+            raise ValueError("zero_empty_scenes: (B, 1, width) GPU tensors")
+        if t.dtype not in _ACT_DTYPES:
+            raise ValueError(f"zero_empty_scenes: fp32 or bf16 tensors (got {t.dtype})")
+        if t.stride(2) != 1 or t.stride(0) < t.shape[2]:
+            raise ValueError("zero_empty_scenes: a contiguous tensor or a last-dim slice of one")
+        _same_device(n_agents.dev, t)
+        arr.append(_lib.ZeroItem(ptr=t.data_ptr(), pitch=t.stride(0) * t.element_size(),
+                                 width=t.shape[2] * t.element_size(), kind=ZERO_EDGE_ROWS))
+    if not arr:
+        return
+    if len(arr) > _lib.MAX_ZERO_ITEMS:
+        raise ValueError(f"zero_empty_scenes: at most {_lib.MAX_ZERO_ITEMS} tensors per launch")
+    with torch.cuda.device(n_agents.dev.device):
+        check(load().gn_zero_empty_scenes((_lib.ZeroItem * len(arr))(*arr), len(arr), B, addr(n_agents.dev), stream_handle()),
+              "gn_zero_empty_scenes")
 
 
 # ---- A0 / A1 -----------------------------------------------------------------------------------

@@ -115,7 +115,7 @@ def default_shard_noise(block, B: int, N: int, start: int, stop: int, device) ->
 
 def sharded_forward(block: Callable[..., Tuple[Tensor, Optional[Tensor]]], f_full: Tensor,
                     noise_full: Optional[Sequence] = None, group=None, gather_H: bool = False,
-                    input_prefix: bool = True):
+                    input_prefix: bool = True, n_agents=None):
     """Run `block` on this rank's scenes of `f_full` (every rank holds the full input, as a
     data-parallel caller would after its own loader) and all-gather the features.
 
@@ -128,6 +128,10 @@ def sharded_forward(block: Callable[..., Tuple[Tensor, Optional[Tensor]]], f_ful
     model/GroupNet_nba.py:301-309).  Every rank already holds those columns for the whole batch (`f_full`), so only the
     COMPUTED columns — the output embeddings, 64*(1+S) of the 64*(2+S) — cross xGMI (5.8 MB instead of 7.2 MB
     per 512 scenes) and the result is assembled as cat(f_full, gathered).  False gathers the whole tensor.
+    ``n_agents`` (a ragged batch; INTEGRATION.md, "Ragged batches"): the FULL batch's counts, a sequence of B ints or a
+    CPU integer tensor.  Every rank passes its own scenes' counts on as `block(f_local, noise_u=..., n_agents=...)`; a
+    rank whose scenes all hold N agents thereby takes the full-batch path.  Without it the block is called without
+    the keyword.
     Returns `(features_full (B, N, F), H_full or local H)`.
     """
     world = dist.get_world_size(group)
@@ -141,7 +145,14 @@ def sharded_forward(block: Callable[..., Tuple[Tensor, Optional[Tensor]]], f_ful
         noise_local = default_shard_noise(block, B, f_full.shape[1], s, e, f_full.device)
     else:
         noise_local = None
-    feats, H = block(f_local, noise_u=noise_local)
+    if n_agents is None:
+        feats, H = block(f_local, noise_u=noise_local)
+    else:
+        if not isinstance(n_agents, torch.Tensor):
+            n_agents = list(n_agents)
+        if len(n_agents) != B:
+            raise ValueError(f"n_agents: {B} counts needed (one per scene of the full batch), got {len(n_agents)}")
+        feats, H = block(f_local, noise_u=noise_local, n_agents=n_agents[s:e])
     D = f_full.shape[-1]
     if input_prefix and feats.shape[-1] > D and feats.dtype == f_full.dtype:
         feats_full = torch.cat((f_full, all_gather_rows(feats[..., D:].contiguous(), B, group)), dim=-1)

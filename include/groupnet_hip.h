@@ -73,6 +73,14 @@
  *     needs no count.  gn_zero_padding zeroes the padded positions of the outputs.
  *     The E = 1 shortcut of a module with scale == N is keyed on the padded N: a scene with n_b <= scale < N gets n_b
  *     identical all-member hyperedges (for every scene with n_b > scale the graph is the reference's own).
+ *   - Ragged batches from a captured graph (ABI 40, additive: four new symbols and two flag values; no struct, no
+ *     signature and no kernel id changed).  A hipGraph captures the ADDRESS of n_valid; the host replaces the values
+ *     between replays.  gn_agent_counts_u8 writes them on the device from a (B,N) validity mask, so a mask that already
+ *     lives on the GPU costs no read-back.  EMPTY SLOTS: n_valid[b] == 0 is a scene without agents (the unfilled tail of
+ *     a static batch).  Every ragged kernel then reads the scene's finite input rows and writes zeros to every output
+ *     position of the scene — its incidences and affinities, its edge rows, its node rows — except the single hyperedge
+ *     row of a scale-N module, which only goes through row-wise stages: gn_zero_empty_scenes zeroes that one.  No kernel
+ *     divides by a count of 0 (the scatter divides only rows n < n_b), and a scene never reads another scene's rows.
  */
 #ifndef GROUPNET_HIP_H
 #define GROUPNET_HIP_H
@@ -578,6 +586,23 @@ typedef struct {
 } gn_zero_item_t;
 int gn_zero_padding(const gn_zero_item_t* items, int n_items, int B, int N, const int* n_valid, gn_stream_t stream);
 
+/* Zeroes whole scenes of up to GN_MAX_ZERO_ITEMS tensors where the scene is an empty slot, n_valid[b] <= 0 (ABI 40): the
+ * single hyperedge row (B,1,.) of a scale-N module, which gn_zero_padding does not take.  `items` is a HOST array; here
+ * `pitch` is the distance between SCENES in bytes and `width` the bytes of a scene that are zeroed (the same alignment
+ * rules and error codes as gn_zero_padding); `kind` is not read.  Scenes with a count >= 1 are not touched. */
+int gn_zero_empty_scenes(const gn_zero_item_t* items, int n_items, int B, const int* n_valid, gn_stream_t stream);
+
+/* Agent counts from a validity mask (ABI 40).  valid: (B,N) bytes on the device, any alignment; n_valid[b] = the length
+ * of the LEADING RUN of non-zero bytes of valid[b,:] (B ints; 4-byte aligned).  `status` is one device word (4-byte
+ * aligned) that the kernel only ever ORs into — sticky: the caller zeroes it once and reads it when it likes:
+ * GN_COUNTS_NOT_PREFIX — some scene has a non-zero byte behind a zero byte (those agents are NOT counted: the library
+ * has no non-prefix form); GN_COUNTS_EMPTY — some scene has count 0 (legal: an empty slot; informational).
+ * One wave per scene, rows beyond 64 agents in chunks of a wave; any N >= 1 and B >= 1, else GN_ERR_SHAPE; a NULL
+ * pointer: GN_ERR_NULL; a misaligned n_valid or status: GN_ERR_ALIGN. */
+#define GN_COUNTS_NOT_PREFIX 1u
+#define GN_COUNTS_EMPTY 2u
+int gn_agent_counts_u8(const unsigned char* valid, int B, int N, int* n_valid, unsigned int* status, gn_stream_t stream);
+
 /* ---- A6 / generic two-layer MLP ---------------------------------------------------------------
  * y = W1 relu(W0 x + b0) + b1     (MLP.forward with one hidden layer, MS_HGNN_batch.py:220-229;
  * nmp_mlp_end 128->128->bottleneck and nmp_mlps[even] 128->128->64).
@@ -762,6 +787,11 @@ int gn_agg_scatter_ragged_plan_bf16(const gn_scatter_group_t* groups, int n_grou
                                     const int* n_valid, gn_launch_plan_t* plan);
 int gn_zero_padding_plan(const gn_zero_item_t* items, int n_items, int B, int N, const int* n_valid,
                          gn_launch_plan_t* plan);
+/* The two launches of ABI 40.  Their kernels have no GN_K_* id (the table above is unchanged): kernel = GN_K_NONE,
+ * grid = (ceil(B / 4)) for the counts — one wave per scene, four to a workgroup — and (capped, items) for the zeroing. */
+int gn_zero_empty_scenes_plan(const gn_zero_item_t* items, int n_items, int B, const int* n_valid, gn_launch_plan_t* plan);
+int gn_agent_counts_plan_u8(const unsigned char* valid, int B, int N, int* n_valid, unsigned int* status,
+                            gn_launch_plan_t* plan);
 
 /* ---- backward (training) building blocks — SURVEY.md §8f rank 2 -------------------------------
  * train_hyper_nba.py:116 back-propagates through the two modules.  The backward of the path is
