@@ -106,6 +106,33 @@ def _needs_grad(mod: nn.Module, *inputs: Optional[Tensor]) -> bool:
     return any(t is not None and t.requires_grad for t in inputs) or any(p.requires_grad for p in _plist(mod))
 
 
+# What a ragged call (``n_agents``) is refused for, by the caller's keyword: the exception and its text
+_RAGGED_REFUSALS = {
+    "handed_in": (ValueError, "n_agents: the ragged incidence is built here; H= / masks= cannot be handed in with it"),
+    "listall": (NotImplementedError, "n_agents: the exhaustive (listall) search has no ragged form"),
+    "grad": (NotImplementedError, "n_agents: ragged batches are inference-only (call under torch.no_grad())"),
+    "training": (NotImplementedError, "n_agents: ragged batches are inference-only (call block.eval() first)"),
+}
+
+
+def refuse_ragged(**holds: bool) -> None:
+    """Raise the first refusal of `_RAGGED_REFUSALS` whose condition holds, in the order the caller names them."""
+    for why, held in holds.items():
+        if held:
+            exc, text = _RAGGED_REFUSALS[why]
+            raise exc(text)
+
+
+def ragged_counts(n_agents, x: Tensor, **refusals: bool) -> Optional[ops.AgentCounts]:
+    """A forward's ``n_agents`` for its (B,N,...) input ``x`` as the validated `ops.AgentCounts`, or None where the call
+    is not ragged (`ops.agent_counts`; an empty batch never is).  A ragged call is refused by `refuse_ragged`."""
+    B, N = x.shape[0], x.shape[1]
+    counts = ops.agent_counts(n_agents, B, N, x.device) if B and N else None
+    if counts is not None:
+        refuse_ragged(**refusals)
+    return counts
+
+
 _warned_grad = False
 
 
@@ -560,10 +587,8 @@ class MS_HGNN_oridinary(_MessagePassing):
         outputs are zeros.  Inference only."""
         ops._req(h_states, "h_states", (None, None, self.h_dim), ops._ACT_DTYPES)
         N = h_states.shape[1]
-        n_agents = ops.agent_counts(n_agents, h_states.shape[0], N, h_states.device) if h_states.shape[0] and N else None
+        n_agents = ragged_counts(n_agents, h_states, grad=_needs_grad(self, h_states))
         if h_states.shape[0] and N and _needs_grad(self, h_states):
-            if n_agents is not None:
-                raise NotImplementedError("n_agents: ragged batches are inference-only (call under torch.no_grad())")
             return self._forward_autograd(h_states, None, noise_u, out)
         _check_storage_width(self.bottleneck_dim, h_states.dtype)
         if h_states.shape[0] == 0 or N == 0:      # empty batch: nothing to launch
@@ -635,15 +660,9 @@ class MS_HGNN_hyper(_MessagePassing):
         alone; padded positions of the three outputs are zeros; padded rows of h_states and corr must be finite.
         Inference only, top-k incidence built here only (no ``H=`` / ``masks=``, no ``listall``)."""
         ops._req(h_states, "h_states", (None, None, self.h_dim), ops._ACT_DTYPES)
-        n_agents = (ops.agent_counts(n_agents, h_states.shape[0], h_states.shape[1], h_states.device)
-                    if h_states.shape[0] and h_states.shape[1] else None)
+        n_agents = ragged_counts(n_agents, h_states, handed_in=H is not None or masks is not None, listall=self.listall,
+                                 grad=_needs_grad(self, h_states))
         if n_agents is not None:
-            if H is not None or masks is not None:
-                raise ValueError("n_agents: the ragged incidence is built here; H= / masks= cannot be handed in with it")
-            if self.listall:
-                raise NotImplementedError("n_agents: the exhaustive (listall) search has no ragged form")
-            if _needs_grad(self, h_states):
-                raise NotImplementedError("n_agents: ragged batches are inference-only (call under torch.no_grad())")
             if self.scale > h_states.shape[1]:
                 raise RuntimeError("selected index k out of range")
             _check_storage_width(self.bottleneck_dim, h_states.dtype)

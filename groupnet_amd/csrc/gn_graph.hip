@@ -1177,10 +1177,21 @@ struct ZeroTable {
 __host__ __device__ inline int zero_item_unit(const gn_zero_item_t& it) {
   return ((reinterpret_cast<uintptr_t>(it.ptr) | (uintptr_t)it.width | (uintptr_t)it.pitch) & 3u) == 0 ? 4 : 2;
 }
+// store units per row of a tensor; `words`: whether a unit is 4 bytes
+__device__ __forceinline__ int zero_row_units(const gn_zero_item_t& it, bool& words) {
+  words = zero_item_unit(it) == 4;
+  return it.width / (words ? 4 : 2);
+}
+// unit c of row `r` of a tensor (rows at the tensor's pitch) becomes zero
+__device__ __forceinline__ void zero_unit(const gn_zero_item_t& it, bool words, long long r, int c) {
+  unsigned char* row = reinterpret_cast<unsigned char*>(it.ptr) + (size_t)r * it.pitch;
+  if (words) reinterpret_cast<unsigned int*>(row)[c] = 0u;
+  else reinterpret_cast<unsigned short*>(row)[c] = (unsigned short)0;
+}
 __global__ __launch_bounds__(kBlock) void zero_padding_kernel(ZeroTable T, int B, int N, const int* __restrict__ n_valid) {
   const gn_zero_item_t it = T.t[blockIdx.y];
-  const bool words = zero_item_unit(it) == 4;
-  const int wu = it.width / (words ? 4 : 2);          // units per row
+  bool words;
+  const int wu = zero_row_units(it, words);
   const int R = it.kind == GN_ZERO_PAIR_ROWS ? N * N : N;
   const long long total = (long long)B * R * wu;
   for (long long idx = (long long)blockIdx.x * kBlock + threadIdx.x; idx < total; idx += (long long)gridDim.x * kBlock) {
@@ -1195,11 +1206,7 @@ __global__ __launch_bounds__(kBlock) void zero_padding_kernel(ZeroTable T, int B
     } else {
       pad = r >= nb;
     }
-    if (pad) {
-      unsigned char* row = reinterpret_cast<unsigned char*>(it.ptr) + (size_t)br * it.pitch;
-      if (words) reinterpret_cast<unsigned int*>(row)[c] = 0u;
-      else reinterpret_cast<unsigned short*>(row)[c] = (unsigned short)0;
-    }
+    if (pad) zero_unit(it, words, br, c);
   }
 }
 
@@ -1208,17 +1215,13 @@ __global__ __launch_bounds__(kBlock) void zero_padding_kernel(ZeroTable T, int B
 // hyperedge row of a scale-N module — for the holders of counts that admit an empty slot.
 __global__ __launch_bounds__(kBlock) void zero_empty_scenes_kernel(ZeroTable T, int B, const int* __restrict__ n_valid) {
   const gn_zero_item_t it = T.t[blockIdx.y];
-  const bool words = zero_item_unit(it) == 4;
-  const int wu = it.width / (words ? 4 : 2);          // units per scene
+  bool words;
+  const int wu = zero_row_units(it, words);           // a scene is one row
   const long long total = (long long)B * wu;
   for (long long idx = (long long)blockIdx.x * kBlock + threadIdx.x; idx < total; idx += (long long)gridDim.x * kBlock) {
     const int b = (int)(idx / wu);
     const int c = (int)(idx - (long long)b * wu);
-    if (n_valid[b] <= 0) {
-      unsigned char* row = reinterpret_cast<unsigned char*>(it.ptr) + (size_t)b * it.pitch;
-      if (words) reinterpret_cast<unsigned int*>(row)[c] = 0u;
-      else reinterpret_cast<unsigned short*>(row)[c] = (unsigned short)0;
-    }
+    if (n_valid[b] <= 0) zero_unit(it, words, b, c);
   }
 }
 
@@ -1498,9 +1501,16 @@ extern "C" int gn_affinity_plan_f32(const float* f, float* corr, int B, int N, i
   return plan == nullptr ? GN_ERR_NULL : affinity_entry(f, corr, B, N, D, nullptr, plan);
 }
 
-// TE: rows of corr per band; sl: the kernel's scale table
-static int topk_plan(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B, int N,
-                     gn_launch_plan_t& p, ScaleList& sl) {
+// the per-scene agent counts of a ragged entry point: a device array of ints
+static int need_counts(const int* n_valid) {
+  if (n_valid == nullptr) return GN_ERR_NULL;
+  return (reinterpret_cast<uintptr_t>(n_valid) & 3u) != 0 ? GN_ERR_ALIGN : GN_OK;
+}
+
+// TE: rows of corr per band; sl: the kernel's scale table; ragged: the launch over per-scene counts (n_valid)
+static int topk_plan(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B, int N, bool ragged,
+                     const int* n_valid, gn_launch_plan_t& p, ScaleList& sl) {
+  if (ragged) GN_CHECK(need_counts(n_valid));
   GN_REQUIRE_PTR(corr);
   if (B <= 0 || N <= 0 || n_scales < 1) return GN_ERR_SHAPE;
   GN_CHECK(fill_scales(sl, H_list, k_list, n_scales, N));
@@ -1511,26 +1521,32 @@ static int topk_plan(const float* corr, float* const* H_list, const int* k_list,
   // enough bands to give the chip >= ~1024 workgroups when B is small
   while (RB > 8 && (long long)B * ((N + RB - 1) / RB) < 1024) RB = (RB + 1) / 2;
   plan_begin(p, 0);
-  p.kernel = GN_K_TOPK_INCIDENCE;
+  p.kernel = ragged ? GN_K_TOPK_INCIDENCE_RAGGED : GN_K_TOPK_INCIDENCE;
   p.TE = RB;
   p.grid[0] = (N + RB - 1) / RB;
   p.grid[1] = B;
   p.dyn_lds = (int)((size_t)RB * N * sizeof(float));
   return GN_OK;
 }
-static int topk_launch(const gn_launch_plan_t& p, const float* corr, const ScaleList& sl, int N, hipStream_t s) {
-  gn_allow_big_lds(topk_incidence_kernel);
-  hipLaunchKernelGGL(topk_incidence_kernel, dim3(p.grid[0], p.grid[1]), dim3(kBlock), (size_t)p.dyn_lds, s, corr, sl, N,
-                     p.TE);
+static int topk_launch(const gn_launch_plan_t& p, const float* corr, const ScaleList& sl, int N, const int* n_valid,
+                       hipStream_t s) {
+  const dim3 grid(p.grid[0], p.grid[1]);
+  if (p.kernel == GN_K_TOPK_INCIDENCE_RAGGED) {
+    gn_allow_big_lds(topk_incidence_ragged_kernel);
+    hipLaunchKernelGGL(topk_incidence_ragged_kernel, grid, dim3(kBlock), (size_t)p.dyn_lds, s, corr, sl, N, p.TE, n_valid);
+  } else {
+    gn_allow_big_lds(topk_incidence_kernel);
+    hipLaunchKernelGGL(topk_incidence_kernel, grid, dim3(kBlock), (size_t)p.dyn_lds, s, corr, sl, N, p.TE);
+  }
   return gn_check_launch();
 }
 static int topk_entry(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B, int N,
-                      gn_stream_t stream, gn_launch_plan_t* plan) {
+                      gn_stream_t stream, gn_launch_plan_t* plan, bool ragged = false, const int* n_valid = nullptr) {
   gn_launch_plan_t p;
   ScaleList sl;
-  const int rc = topk_plan(corr, H_list, k_list, n_scales, B, N, plan != nullptr ? *plan : p, sl);
+  const int rc = topk_plan(corr, H_list, k_list, n_scales, B, N, ragged, n_valid, plan != nullptr ? *plan : p, sl);
   if (rc != GN_OK || plan != nullptr) return rc;
-  return topk_launch(p, corr, sl, N, (hipStream_t)stream);
+  return topk_launch(p, corr, sl, N, n_valid, (hipStream_t)stream);
 }
 extern "C" int gn_topk_incidence_f32(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B,
                                      int N, gn_stream_t stream) {
@@ -1540,33 +1556,13 @@ extern "C" int gn_topk_incidence_plan_f32(const float* corr, float* const* H_lis
                                           int N, gn_launch_plan_t* plan) {
   return plan == nullptr ? GN_ERR_NULL : topk_entry(corr, H_list, k_list, n_scales, B, N, nullptr, plan);
 }
-
-// the per-scene agent counts of a ragged entry point: a device array of ints
-static int need_counts(const int* n_valid) {
-  if (n_valid == nullptr) return GN_ERR_NULL;
-  return (reinterpret_cast<uintptr_t>(n_valid) & 3u) != 0 ? GN_ERR_ALIGN : GN_OK;
-}
-static int topk_ragged_entry(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B, int N,
-                             const int* n_valid, gn_stream_t stream, gn_launch_plan_t* plan) {
-  gn_launch_plan_t p;
-  ScaleList sl;
-  gn_launch_plan_t& q = plan != nullptr ? *plan : p;
-  GN_CHECK(need_counts(n_valid));
-  GN_CHECK(topk_plan(corr, H_list, k_list, n_scales, B, N, q, sl));
-  q.kernel = GN_K_TOPK_INCIDENCE_RAGGED;
-  if (plan != nullptr) return GN_OK;
-  gn_allow_big_lds(topk_incidence_ragged_kernel);
-  hipLaunchKernelGGL(topk_incidence_ragged_kernel, dim3(p.grid[0], p.grid[1]), dim3(kBlock), (size_t)p.dyn_lds,
-                     (hipStream_t)stream, corr, sl, N, p.TE, n_valid);
-  return gn_check_launch();
-}
 extern "C" int gn_topk_incidence_ragged_f32(const float* corr, float* const* H_list, const int* k_list, int n_scales,
                                             int B, int N, const int* n_valid, gn_stream_t stream) {
-  return topk_ragged_entry(corr, H_list, k_list, n_scales, B, N, n_valid, stream, nullptr);
+  return topk_entry(corr, H_list, k_list, n_scales, B, N, stream, nullptr, true, n_valid);
 }
 extern "C" int gn_topk_incidence_ragged_plan_f32(const float* corr, float* const* H_list, const int* k_list, int n_scales,
                                                  int B, int N, const int* n_valid, gn_launch_plan_t* plan) {
-  return plan == nullptr ? GN_ERR_NULL : topk_ragged_entry(corr, H_list, k_list, n_scales, B, N, n_valid, nullptr, plan);
+  return plan == nullptr ? GN_ERR_NULL : topk_entry(corr, H_list, k_list, n_scales, B, N, nullptr, plan, true, n_valid);
 }
 
 extern "C" int gn_listall_incidence_f32(const float* corr, float* H, int B, int N, int scale, gn_stream_t stream) {
@@ -1595,7 +1591,8 @@ extern "C" int gn_listall_incidence_f32(const float* corr, float* H, int B, int 
   return gn_check_launch();
 }
 
-// the job's arguments as gn_affinity_topk_* take them (gn_affinity_job_t plus the mask lists)
+// the job's arguments as gn_affinity_topk_* take them (gn_affinity_job_t plus the mask lists), and the per-scene counts
+// of the ragged form (gn_affinity_topk_ragged_*; n_valid == nullptr without `ragged`)
 struct AffinityTopkArgs {
   const void* f;
   float* corr;
@@ -1605,14 +1602,24 @@ struct AffinityTopkArgs {
   const gn_block_extras_t* extras;
   unsigned long long* const* rowmask_list;
   unsigned long long* const* colmask_list;
+  bool ragged;
+  const int* n_valid;
 };
 // sl, ml: the kernel's scale and mask tables
 static int affinity_topk_plan(const AffinityTopkArgs& a, bool twin, gn_launch_plan_t& p, ScaleList& sl, MaskList& ml) {
+  if (a.ragged) {
+    GN_CHECK(need_counts(a.n_valid));
+    // the ragged form has no embedding front-end and no mask lists
+    if (a.extras != nullptr && a.extras->x_raw != nullptr) return GN_ERR_SHAPE;
+    if (a.rowmask_list != nullptr || a.colmask_list != nullptr) return GN_ERR_SHAPE;
+  }
   size_t tile;
   GN_CHECK(affinity_job_plan(twin, a.f, a.H_list, a.k_list, a.n_scales, a.B, a.N, a.D, a.extras, a.rowmask_list,
                              a.colmask_list, kLdsBudget, sl, ml, tile));
   plan_begin(p, 0);
-  p.kernel = a.rowmask_list != nullptr ? GN_K_AFFINITY_TOPK_MASKS : GN_K_AFFINITY_TOPK;
+  p.kernel = a.ragged                   ? GN_K_AFFINITY_TOPK_RAGGED
+             : a.rowmask_list != nullptr ? GN_K_AFFINITY_TOPK_MASKS
+                                         : GN_K_AFFINITY_TOPK;
   p.precision = twin ? 1 : 0;
   p.grid[0] = a.B;
   p.dyn_lds = (int)tile;
@@ -1623,7 +1630,11 @@ static int affinity_topk_launch(const gn_launch_plan_t& p, const AffinityTopkArg
                                 const MaskList& ml, hipStream_t s) {
   const TS* f = reinterpret_cast<const TS*>(a.f);
   const gn_block_extras_t ex = a.extras != nullptr ? *a.extras : gn_block_extras_t{};
-  if (p.kernel == GN_K_AFFINITY_TOPK_MASKS) {
+  if (p.kernel == GN_K_AFFINITY_TOPK_RAGGED) {
+    gn_allow_big_lds(affinity_topk_ragged_kernel<TS>);
+    hipLaunchKernelGGL(affinity_topk_ragged_kernel<TS>, dim3(p.grid[0]), dim3(kBlock), (size_t)p.dyn_lds, s, f, a.corr, sl,
+                       a.N, a.D, ex, a.n_valid);
+  } else if (p.kernel == GN_K_AFFINITY_TOPK_MASKS) {
     gn_allow_big_lds(affinity_topk_masks_kernel<TS>);
     hipLaunchKernelGGL(affinity_topk_masks_kernel<TS>, dim3(p.grid[0]), dim3(kBlock), (size_t)p.dyn_lds, s, f, a.corr, sl,
                        a.N, a.D, ex, ml);
@@ -1674,50 +1685,32 @@ extern "C" int gn_affinity_topk_plan_bf16(const void* f, float* corr, float* con
                                      nullptr, plan);
 }
 
-// the ragged form of the stand-alone launch: the same job checks (no mask lists), no embedding front-end
-template <typename TS>
-static int affinity_topk_ragged_entry(const AffinityTopkArgs& a, const int* n_valid, gn_stream_t stream,
-                                      gn_launch_plan_t* plan) {
-  gn_launch_plan_t p;
-  ScaleList sl;
-  MaskList ml;
-  gn_launch_plan_t& q = plan != nullptr ? *plan : p;
-  GN_CHECK(need_counts(n_valid));
-  if (a.extras != nullptr && a.extras->x_raw != nullptr) return GN_ERR_SHAPE;
-  GN_CHECK(affinity_topk_plan(a, sizeof(TS) != sizeof(float), q, sl, ml));
-  q.kernel = GN_K_AFFINITY_TOPK_RAGGED;
-  if (plan != nullptr) return GN_OK;
-  const gn_block_extras_t ex = a.extras != nullptr ? *a.extras : gn_block_extras_t{};
-  gn_allow_big_lds(affinity_topk_ragged_kernel<TS>);
-  hipLaunchKernelGGL(affinity_topk_ragged_kernel<TS>, dim3(p.grid[0]), dim3(kBlock), (size_t)p.dyn_lds, (hipStream_t)stream,
-                     reinterpret_cast<const TS*>(a.f), a.corr, sl, a.N, a.D, ex, n_valid);
-  return gn_check_launch();
-}
+// the ragged form of the stand-alone launch (affinity_topk_plan states what it refuses)
 extern "C" int gn_affinity_topk_ragged_f32(const float* f, float* corr, float* const* H_list, const int* k_list,
                                            int n_scales, int B, int N, int D, const gn_block_extras_t* extras,
                                            const int* n_valid, gn_stream_t stream) {
-  return affinity_topk_ragged_entry<float>({f, corr, H_list, k_list, n_scales, B, N, D, extras, nullptr, nullptr}, n_valid,
-                                           stream, nullptr);
+  return affinity_topk_entry<float>({f, corr, H_list, k_list, n_scales, B, N, D, extras, nullptr, nullptr, true, n_valid},
+                                    stream, nullptr);
 }
 extern "C" int gn_affinity_topk_ragged_bf16(const void* f, float* corr, float* const* H_list, const int* k_list,
                                             int n_scales, int B, int N, int D, const gn_block_extras_t* extras,
                                             const int* n_valid, gn_stream_t stream) {
-  return affinity_topk_ragged_entry<__bf16>({f, corr, H_list, k_list, n_scales, B, N, D, extras, nullptr, nullptr}, n_valid,
-                                            stream, nullptr);
+  return affinity_topk_entry<__bf16>({f, corr, H_list, k_list, n_scales, B, N, D, extras, nullptr, nullptr, true, n_valid},
+                                     stream, nullptr);
 }
 extern "C" int gn_affinity_topk_ragged_plan_f32(const float* f, float* corr, float* const* H_list, const int* k_list,
                                                 int n_scales, int B, int N, int D, const gn_block_extras_t* extras,
                                                 const int* n_valid, gn_launch_plan_t* plan) {
   if (plan == nullptr) return GN_ERR_NULL;
-  return affinity_topk_ragged_entry<float>({f, corr, H_list, k_list, n_scales, B, N, D, extras, nullptr, nullptr}, n_valid,
-                                           nullptr, plan);
+  return affinity_topk_entry<float>({f, corr, H_list, k_list, n_scales, B, N, D, extras, nullptr, nullptr, true, n_valid},
+                                    nullptr, plan);
 }
 extern "C" int gn_affinity_topk_ragged_plan_bf16(const void* f, float* corr, float* const* H_list, const int* k_list,
                                                  int n_scales, int B, int N, int D, const gn_block_extras_t* extras,
                                                  const int* n_valid, gn_launch_plan_t* plan) {
   if (plan == nullptr) return GN_ERR_NULL;
-  return affinity_topk_ragged_entry<__bf16>({f, corr, H_list, k_list, n_scales, B, N, D, extras, nullptr, nullptr}, n_valid,
-                                            nullptr, plan);
+  return affinity_topk_entry<__bf16>({f, corr, H_list, k_list, n_scales, B, N, D, extras, nullptr, nullptr, true, n_valid},
+                                     nullptr, plan);
 }
 
 extern "C" int gn_incidence_masks_f32(const float* H, int B, int E, int N, unsigned long long* rowmask,
@@ -1751,14 +1744,16 @@ static void n2e_pair_shape(int B, int N, int E, int& SG, int& bands) {
 // rowmasks: nullptr, or per group the (B,E) member words of a hyper group / NULL (gn_node2edge_masks_*).  Words on every
 // hyper group turn the row form into its word-reading instantiation (variant 2) and change nothing else of the plan;
 // the banded form ignores them.
+// ragged: the launch over per-scene counts (gn_node2edge_ragged_*; no words): the same plan, its kernel the ragged one
 static int node2edge_plan(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks, int n_groups, int B,
-                          int N, bool twin, const GnSwitches& sw, gn_launch_plan_t& p) {
+                          int N, bool ragged, const int* n_valid, bool twin, const GnSwitches& sw, gn_launch_plan_t& p) {
+  if (ragged) GN_CHECK(need_counts(n_valid));
   int rc = check_groups(groups, n_groups);
   if (rc != GN_OK) return rc;
   if (B <= 0 || N <= 0) return GN_ERR_SHAPE;
   p = gn_launch_plan_t{};
   p.n_groups = n_groups;
-  p.kernel = GN_K_NODE2EDGE;
+  p.kernel = ragged ? GN_K_NODE2EDGE_RAGGED : GN_K_NODE2EDGE;
   p.precision = twin ? 1 : 0;
   p.grid[1] = p.grid[2] = 1;
   const size_t per_scene = (size_t)N * (GN_FEAT + GN_FEAT + 1) * sizeof(float);
@@ -1852,7 +1847,7 @@ static int node2edge_plan(const gn_n2e_group_t* groups, const unsigned long long
 template <typename TS>
 static int node2edge_launch(const gn_launch_plan_t& p, const gn_n2e_group_t* groups,
                             const unsigned long long* const* rowmasks, int B, int N, hipStream_t s,
-                            const int* n_valid = nullptr) {
+                            const int* n_valid) {
   WaveTable<gn_n2e_group_t> T{};
   PairTable P{};
   XcdSections xs{};
@@ -1882,31 +1877,26 @@ static int node2edge_launch(const gn_launch_plan_t& p, const gn_n2e_group_t* gro
   T.first[T.n] = waves;
   xs.first[xs.n] = pair_wgs + (int)waves;
   gn_xcd_grid(xs, p.xcd != 0);
-  auto launch = [&](auto k) {
+  auto launch = [&](auto k, auto... counts) {          // counts: n_valid for the ragged kernels, nothing for the others
     gn_allow_big_lds(k);
-    hipLaunchKernelGGL(k, dim3((unsigned)p.grid[0]), dim3(kBlock), (size_t)p.dyn_lds, s, T, P, B, N, p.SGh, p.EBh, xs);
+    hipLaunchKernelGGL(k, dim3((unsigned)p.grid[0]), dim3(kBlock), (size_t)p.dyn_lds, s, T, P, B, N, p.SGh, p.EBh, xs,
+                       counts...);
     return gn_check_launch();
   };
-  if (p.kernel == GN_K_NODE2EDGE_RAGGED) {
-    auto ragged = [&](auto k) {
-      gn_allow_big_lds(k);
-      hipLaunchKernelGGL(k, dim3((unsigned)p.grid[0]), dim3(kBlock), (size_t)p.dyn_lds, s, T, P, B, N, p.SGh, p.EBh, xs,
-                         n_valid);
-      return gn_check_launch();
-    };
-    return p.variant ? ragged(node2edge_ragged_kernel<TS, true>) : ragged(node2edge_ragged_kernel<TS, false>);
-  }
+  if (p.kernel == GN_K_NODE2EDGE_RAGGED)
+    return p.variant ? launch(node2edge_ragged_kernel<TS, true>, n_valid) : launch(node2edge_ragged_kernel<TS, false>, n_valid);
   if (p.variant == 2) return launch(node2edge_kernel<TS, true, true>);
   return p.variant ? launch(node2edge_kernel<TS, true>) : launch(node2edge_kernel<TS, false>);
 }
 template <typename TS>
 static int node2edge_entry(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks, int n_groups, int B,
-                           int N, gn_stream_t stream, gn_launch_plan_t* plan) {
+                           int N, gn_stream_t stream, gn_launch_plan_t* plan, bool ragged = false,
+                           const int* n_valid = nullptr) {
   gn_launch_plan_t p;
-  int rc = node2edge_plan(groups, rowmasks, n_groups, B, N, sizeof(TS) != sizeof(float), gn_read_switches(),
-                          plan != nullptr ? *plan : p);
+  int rc = node2edge_plan(groups, rowmasks, n_groups, B, N, ragged, n_valid, sizeof(TS) != sizeof(float),
+                          gn_read_switches(), plan != nullptr ? *plan : p);
   if (rc != GN_OK || plan != nullptr) return rc;
-  return node2edge_launch<TS>(p, groups, rowmasks, B, N, (hipStream_t)stream);
+  return node2edge_launch<TS>(p, groups, rowmasks, B, N, (hipStream_t)stream, n_valid);
 }
 // (the entry points without words are the all-NULL case of the ones with)
 extern "C" int gn_node2edge_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, gn_stream_t stream) {
@@ -1941,32 +1931,21 @@ extern "C" int gn_node2edge_masks_plan_bf16(const gn_n2e_group_t* groups, const 
 }
 
 // the ragged launch: the plan of gn_node2edge_* (no words), its kernel the ragged one
-template <typename TS>
-static int node2edge_ragged_entry(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
-                                  gn_stream_t stream, gn_launch_plan_t* plan) {
-  gn_launch_plan_t p;
-  gn_launch_plan_t& q = plan != nullptr ? *plan : p;
-  GN_CHECK(need_counts(n_valid));
-  GN_CHECK(node2edge_plan(groups, nullptr, n_groups, B, N, sizeof(TS) != sizeof(float), gn_read_switches(), q));
-  q.kernel = GN_K_NODE2EDGE_RAGGED;
-  if (plan != nullptr) return GN_OK;
-  return node2edge_launch<TS>(p, groups, nullptr, B, N, (hipStream_t)stream, n_valid);
-}
 extern "C" int gn_node2edge_ragged_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
                                        gn_stream_t stream) {
-  return node2edge_ragged_entry<float>(groups, n_groups, B, N, n_valid, stream, nullptr);
+  return node2edge_entry<float>(groups, nullptr, n_groups, B, N, stream, nullptr, true, n_valid);
 }
 extern "C" int gn_node2edge_ragged_bf16(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
                                         gn_stream_t stream) {
-  return node2edge_ragged_entry<__bf16>(groups, n_groups, B, N, n_valid, stream, nullptr);
+  return node2edge_entry<__bf16>(groups, nullptr, n_groups, B, N, stream, nullptr, true, n_valid);
 }
 extern "C" int gn_node2edge_ragged_plan_f32(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
                                             gn_launch_plan_t* plan) {
-  return plan == nullptr ? GN_ERR_NULL : node2edge_ragged_entry<float>(groups, n_groups, B, N, n_valid, nullptr, plan);
+  return plan == nullptr ? GN_ERR_NULL : node2edge_entry<float>(groups, nullptr, n_groups, B, N, nullptr, plan, true, n_valid);
 }
 extern "C" int gn_node2edge_ragged_plan_bf16(const gn_n2e_group_t* groups, int n_groups, int B, int N, const int* n_valid,
                                              gn_launch_plan_t* plan) {
-  return plan == nullptr ? GN_ERR_NULL : node2edge_ragged_entry<__bf16>(groups, n_groups, B, N, n_valid, nullptr, plan);
+  return plan == nullptr ? GN_ERR_NULL : node2edge_entry<__bf16>(groups, nullptr, n_groups, B, N, nullptr, plan, true, n_valid);
 }
 
 // workgroups a gather / scatter launch keeps at least when it packs several scenes into one.  2048 = two rounds of the
@@ -2258,24 +2237,34 @@ extern "C" int gn_agg_scatter_ragged_plan_bf16(const gn_scatter_group_t* groups,
                          : scatter_ragged_entry<__bf16>(groups, n_groups, B, N, divisor, n_valid, nullptr, plan);
 }
 
-// The zeroing launch of a ragged forward: grid (capped, items)
-static int zero_padding_entry(const gn_zero_item_t* items, int n_items, int B, int N, const int* n_valid,
-                              gn_stream_t stream, gn_launch_plan_t* plan) {
+// What the two zeroing entries check and fill alike: the counts, the items, the kernel's table T and `most`, the store
+// units of the largest item.  by_kind: a scene has N rows, or N * N by the item's kind; else (gn_zero_empty_scenes) a scene
+// is one row, and neither N nor the kind is read.
+static int zero_items(const gn_zero_item_t* items, int n_items, int B, int N, bool by_kind, const int* n_valid,
+                      ZeroTable& T, long long& most) {
   GN_CHECK(need_counts(n_valid));
   if (items == nullptr) return GN_ERR_NULL;
-  if (n_items < 1 || n_items > GN_MAX_ZERO_ITEMS || B <= 0 || N <= 0 || N > 32767) return GN_ERR_SHAPE;
-  ZeroTable T{};
-  long long most = 0;
+  if (n_items < 1 || n_items > GN_MAX_ZERO_ITEMS || B <= 0 || (by_kind && (N <= 0 || N > 32767))) return GN_ERR_SHAPE;
+  most = 0;
   for (int g = 0; g < n_items; ++g) {
     const gn_zero_item_t& it = items[g];
     if (it.ptr == nullptr) return GN_ERR_NULL;
-    if (it.kind < GN_ZERO_NODE_ROWS || it.kind > GN_ZERO_PAIR_ROWS || it.width <= 0 || it.pitch < it.width) return GN_ERR_SHAPE;
+    if (by_kind && (it.kind < GN_ZERO_NODE_ROWS || it.kind > GN_ZERO_PAIR_ROWS)) return GN_ERR_SHAPE;
+    if (it.width <= 0 || it.pitch < it.width) return GN_ERR_SHAPE;
     if ((reinterpret_cast<uintptr_t>(it.ptr) & 1u) || (it.width & 1) || (it.pitch & 1)) return GN_ERR_ALIGN;
-    const long long words =
-        (long long)B * (it.kind == GN_ZERO_PAIR_ROWS ? (long long)N * N : N) * (it.width / zero_item_unit(it));
+    const long long rows = !by_kind ? 1 : it.kind == GN_ZERO_PAIR_ROWS ? (long long)N * N : N;
+    const long long words = (long long)B * rows * (it.width / zero_item_unit(it));
     most = words > most ? words : most;
     T.t[g] = it;
   }
+  return GN_OK;
+}
+// The zeroing launch of a ragged forward: grid (capped, items)
+static int zero_padding_entry(const gn_zero_item_t* items, int n_items, int B, int N, const int* n_valid,
+                              gn_stream_t stream, gn_launch_plan_t* plan) {
+  ZeroTable T{};
+  long long most;
+  GN_CHECK(zero_items(items, n_items, B, N, true, n_valid, T, most));
   gn_launch_plan_t p;
   gn_launch_plan_t& q = plan != nullptr ? *plan : p;
   plan_begin(q, 0);
@@ -2300,20 +2289,9 @@ extern "C" int gn_zero_padding_plan(const gn_zero_item_t* items, int n_items, in
 // Whole scenes of empty slots: grid (capped, items)
 static int zero_empty_entry(const gn_zero_item_t* items, int n_items, int B, const int* n_valid, gn_stream_t stream,
                             gn_launch_plan_t* plan) {
-  GN_CHECK(need_counts(n_valid));
-  if (items == nullptr) return GN_ERR_NULL;
-  if (n_items < 1 || n_items > GN_MAX_ZERO_ITEMS || B <= 0) return GN_ERR_SHAPE;
   ZeroTable T{};
-  long long most = 0;
-  for (int g = 0; g < n_items; ++g) {
-    const gn_zero_item_t& it = items[g];
-    if (it.ptr == nullptr) return GN_ERR_NULL;
-    if (it.width <= 0 || it.pitch < it.width) return GN_ERR_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(it.ptr) & 1u) || (it.width & 1) || (it.pitch & 1)) return GN_ERR_ALIGN;
-    const long long words = (long long)B * (it.width / zero_item_unit(it));
-    most = words > most ? words : most;
-    T.t[g] = it;
-  }
+  long long most;
+  GN_CHECK(zero_items(items, n_items, B, 0, false, n_valid, T, most));
   gn_launch_plan_t p;
   gn_launch_plan_t& q = plan != nullptr ? *plan : p;
   plan_begin(q, 0);

@@ -11,6 +11,7 @@ graph itself advances at the end of every replay — each replay draws fresh, re
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, Optional, Sequence, Tuple
 
 import torch
@@ -20,6 +21,35 @@ from . import ops, weights
 from .multiscale import MultiScaleHGNN
 
 Tensor = torch.Tensor
+
+
+@contextlib.contextmanager
+def _noise_state_kept():
+    """Puts the process's noise state back on the way out: the steps of a capture switch it to the device stream."""
+    prev = (_mods._NoiseState.mode, _mods._NoiseState.seed, _mods._NoiseState.offset, _mods._NoiseState.counter)
+    try:
+        yield
+    finally:
+        _mods.set_noise_mode(prev[0], prev[1], prev[2], prev[3])
+
+
+def _capture(graph, device, step: Callable, counter: Tensor, draws_per_step: int, warmup: int,
+             before_capture: Optional[Callable] = None):
+    """The capture protocol of the three graphed classes; returns what the captured ``step()`` returned (the graph's
+    static outputs).  ``before_capture``: run between the warm-up and the capture."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):      # warm-up off the default stream: packs weights, sizes the pool
+        for _ in range(max(1, warmup)):
+            step()
+    torch.cuda.current_stream(device).wait_stream(side)
+    torch.cuda.synchronize(device)
+    # every replay first advances the counter by one step's worth of draws: start one step back
+    counter.fill_(-draws_per_step)
+    if before_capture is not None:
+        before_capture()
+    with torch.cuda.graph(graph):
+        return step()
 
 
 class GraphedMultiScale:
@@ -55,10 +85,7 @@ class GraphedMultiScale:
             raise ValueError("GraphedMultiScale needs the block on a GPU")
         self.counts: Optional[ops.StaticAgentCounts] = None
         if ragged:      # the refusals of the eager ragged forward, before anything is allocated or launched
-            if block.training:
-                raise NotImplementedError("n_agents: ragged batches are inference-only (call block.eval() first)")
-            if any(m.listall for m in block.interaction_hyper):
-                raise NotImplementedError("n_agents: the exhaustive (listall) search has no ragged form")
+            _mods.refuse_ragged(training=block.training, listall=any(m.listall for m in block.interaction_hyper))
             self.counts = ops.StaticAgentCounts(B, N, self.device)
         self.block = block
         self.B, self.N = B, N
@@ -67,26 +94,16 @@ class GraphedMultiScale:
         self.counter = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.draws_per_step = sum(b * e * k for (b, e, k) in block.noise_shapes(B, N)) * block.interaction.nmp_layers
         self.graph = torch.cuda.CUDAGraph()
-        prev = (_mods._NoiseState.mode, _mods._NoiseState.seed, _mods._NoiseState.offset, _mods._NoiseState.counter)
-        prev_tail = block.affinity_tail
-        if affinity_tail is not None:
-            block.affinity_tail = bool(affinity_tail)
-        try:
-            with torch.no_grad(), torch.cuda.device(self.device):
-                side = torch.cuda.Stream(device=self.device)
-                side.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(side):      # warm-up off the default stream: packs weights, sizes the pool
-                    for _ in range(max(1, warmup)):
-                        self._step()
-                torch.cuda.current_stream(self.device).wait_stream(side)
-                torch.cuda.synchronize(self.device)
-                # every replay first advances the counter by one step's worth of draws: start one step back
-                self.counter.fill_(-self.draws_per_step)
-                with torch.cuda.graph(self.graph):
-                    self.out, self.H = self._step()
-        finally:
-            block.affinity_tail = prev_tail
-            _mods.set_noise_mode(prev[0], prev[1], prev[2], prev[3])
+        with _noise_state_kept():
+            prev_tail = block.affinity_tail
+            if affinity_tail is not None:
+                block.affinity_tail = bool(affinity_tail)
+            try:
+                with torch.no_grad(), torch.cuda.device(self.device):
+                    self.out, self.H = _capture(self.graph, self.device, self._step, self.counter, self.draws_per_step,
+                                                warmup)
+            finally:
+                block.affinity_tail = prev_tail
 
     def _step(self) -> Tuple[Tensor, Optional[Tensor]]:
         # offset 0 + device counter: the position is entirely on the device; the first launch of the
@@ -151,22 +168,13 @@ class GraphedPastEncoder:
         self.draws_per_step = B * N * N * enc.interaction.edge_types + sum(
             B * (1 if m.scale == N else N) * m.edge_types for m in hypers)
         self.graph = torch.cuda.CUDAGraph()
-        prev = (_mods._NoiseState.mode, _mods._NoiseState.seed, _mods._NoiseState.offset, _mods._NoiseState.counter)
-        try:
-            with torch.no_grad(), torch.cuda.device(self.device):
-                side = torch.cuda.Stream(device=self.device)
-                side.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(side):
-                    for _ in range(max(1, warmup)):
-                        self._step()
-                torch.cuda.current_stream(self.device).wait_stream(side)
-                torch.cuda.synchronize(self.device)
-                self.counter.fill_(-self.draws_per_step)
-                with torch.cuda.graph(self.graph):
-                    self.out, self.H = self._step()
-        finally:
-            enc.__dict__.pop("_advance", None)
-            _mods.set_noise_mode(prev[0], prev[1], prev[2], prev[3])
+        with _noise_state_kept():
+            try:
+                with torch.no_grad(), torch.cuda.device(self.device):
+                    self.out, self.H = _capture(self.graph, self.device, self._step, self.counter, self.draws_per_step,
+                                                warmup)
+            finally:
+                enc.__dict__.pop("_advance", None)
 
     def _step(self):
         _mods.set_noise_mode("device", seed=self.seed, offset=0, counter=self.counter)
@@ -210,24 +218,14 @@ class GraphedTrainStep:
         self.draws_per_step = sum(b * e * k for (b, e, k) in block.noise_shapes(B, N)) * block.interaction.nmp_layers
         self.graph = torch.cuda.CUDAGraph()
         self._repack: dict = {}
-        prev = (_mods._NoiseState.mode, _mods._NoiseState.seed, _mods._NoiseState.offset, _mods._NoiseState.counter)
-        try:
-            with torch.cuda.device(self.device):
-                side = torch.cuda.Stream(device=self.device)
-                side.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(side):
-                    for _ in range(max(1, warmup)):
-                        self._step()
-                torch.cuda.current_stream(self.device).wait_stream(side)
-                torch.cuda.synchronize(self.device)
-                self.counter.fill_(-self.draws_per_step)
-                _mods.invalidate_weight_caches(block)       # every packing kernel must be part of the graph
-                optimizer.zero_grad(set_to_none=True)       # gradients are allocated from the graph's pool
-                with torch.cuda.graph(self.graph):
-                    self.loss = self._step()
-                _mods.invalidate_weight_caches(block)
-        finally:
-            _mods.set_noise_mode(prev[0], prev[1], prev[2], prev[3])
+        def before_capture():
+            _mods.invalidate_weight_caches(block)       # every packing kernel must be part of the graph
+            optimizer.zero_grad(set_to_none=True)       # gradients are allocated from the graph's pool
+
+        with _noise_state_kept(), torch.cuda.device(self.device):
+            self.loss = _capture(self.graph, self.device, self._step, self.counter, self.draws_per_step, warmup,
+                                 before_capture)
+            _mods.invalidate_weight_caches(block)
 
     def _step(self) -> Tensor:
         _mods.set_noise_mode("device", seed=self.seed, offset=0, counter=self.counter)

@@ -21,7 +21,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .MS_HGNN_batch import MS_HGNN_hyper, MS_HGNN_oridinary, _needs_grad, _plist, masks_apply, run_message_passing
+from .MS_HGNN_batch import (MS_HGNN_hyper, MS_HGNN_oridinary, _needs_grad, _plist, masks_apply, ragged_counts,
+                            run_message_passing)
 
 Tensor = torch.Tensor
 
@@ -129,12 +130,8 @@ class MultiScaleHGNN(nn.Module):
         B, N, D = f.shape
         S = len(self.hyper_scales)
         nmp = self.interaction.nmp_layers
-        counts = ops.agent_counts(n_agents, B, N, f.device) if B and N else None
-        if counts is not None:
-            if _needs_grad(self, f):
-                raise NotImplementedError("n_agents: ragged batches are inference-only (call under torch.no_grad())")
-            if any(m.listall for m in self.interaction_hyper):
-                raise NotImplementedError("n_agents: the exhaustive (listall) search has no ragged form")
+        counts = ragged_counts(n_agents, f, grad=_needs_grad(self, f),
+                               listall=any(m.listall for m in self.interaction_hyper))
         if _needs_grad(self, f):
             if f.dtype == torch.bfloat16:
                 # bf16 storage under autograd: the fp32 training path on the up-cast features, results back in bf16

@@ -44,6 +44,13 @@ def _req(t: Tensor, name: str, shape: Optional[Sequence[Optional[int]]] = None, 
     return t
 
 
+def _counter_arg(counter: Optional[Tensor], name: str = "counter") -> Optional[Tensor]:
+    """A Philox counter as the kernels take it — a 1-element int64 GPU tensor — or None, passed through."""
+    if counter is not None and not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
+        raise ValueError(f"{name}: a 1-element int64 GPU tensor")
+    return counter
+
+
 def _same_device(*ts: Tensor) -> None:
     dev = ts[0].device
     for t in ts[1:]:
@@ -333,22 +340,45 @@ def counts_from_mask(valid: Tensor, out: Optional[Tensor] = None, status: Option
 ZERO_NODE_ROWS, ZERO_EDGE_ROWS, ZERO_PAIR_ROWS = _lib.ZERO_NODE_ROWS, _lib.ZERO_EDGE_ROWS, _lib.ZERO_PAIR_ROWS
 
 
+def _zero_launch(who: str, hint: str, items, n_agents, rows: Optional[int], layout) -> None:
+    """What `zero_padding` and `zero_empty_scenes` (``who``: the caller, and gn_<who> its launcher) do alike: check
+    ``items`` = [(tensor, kind)], build their `_lib.ZeroItem` array and launch it, unless nothing is left to zero.  The
+    admissible shapes are (B, ``rows``, width); ``rows`` None: any row count, and the launcher takes N as well.
+    ``layout(t, kind)`` is the caller's rows-per-scene rule: (pitch, width) of a row in elements, None for a tensor to
+    skip, ValueError for one it refuses."""
+    if not isinstance(n_agents, AgentCounts):
+        raise ValueError(f"{who}: n_agents must be an ops.AgentCounts{hint}")
+    arr = []
+    for t, kind in items:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 3 and t.shape[0] == n_agents.B
+                and rows in (None, t.shape[1])):
+            raise ValueError(f"{who}: (B, {'rows' if rows is None else rows}, width) GPU tensors")
+        if t.dtype not in _ACT_DTYPES:
+            raise ValueError(f"{who}: fp32 or bf16 tensors (got {t.dtype})")
+        row = layout(t, kind)
+        if row is None:
+            continue
+        _same_device(n_agents.dev, t)
+        arr.append(_lib.ZeroItem(ptr=t.data_ptr(), pitch=row[0] * t.element_size(), width=row[1] * t.element_size(),
+                                 kind=kind))
+    if not arr:
+        return
+    if len(arr) > _lib.MAX_ZERO_ITEMS:
+        raise ValueError(f"{who}: at most {_lib.MAX_ZERO_ITEMS} tensors per launch")
+    dims = (n_agents.B, n_agents.N) if rows is None else (n_agents.B,)
+    with torch.cuda.device(n_agents.dev.device):
+        check(getattr(load(), "gn_" + who)((_lib.ZeroItem * len(arr))(*arr), len(arr), *dims, addr(n_agents.dev),
+                                           stream_handle()), "gn_" + who)
+
+
 def zero_padding(items: Sequence[Tuple[Tensor, int]], n_agents) -> None:
     """Zero the padded positions of several tensors of a ragged batch in ONE launch (gn_zero_padding).  items =
     [(tensor, kind)]: ZERO_NODE_ROWS — (B,N,w), rows n >= n_b; ZERO_EDGE_ROWS — the (B,N,w) hyperedge rows of a top-k
     module, rows e >= n_b (the (B,1,w) rows of a scale-N module are valid: they are skipped here); ZERO_PAIR_ROWS —
     (B,N*N,w) ordered pair rows with an end >= n_b, or a contiguous (B,N,N) matrix per scene (corr, H, new_H).  A tensor
     may be a last-dim slice of a wider contiguous one; fp32 or bf16 (rows of an even number of bytes)."""
-    if not isinstance(n_agents, AgentCounts):
-        raise ValueError("zero_padding: n_agents must be an ops.AgentCounts (ops.agent_counts)")
-    B, N = n_agents.B, n_agents.N
-    arr = []
-    for t, kind in items:
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 3 and t.shape[0] == B):
-            raise ValueError("zero_padding: (B, rows, width) GPU tensors")
-        if t.dtype not in _ACT_DTYPES:
-            raise ValueError(f"zero_padding: fp32 or bf16 tensors (got {t.dtype})")
-        R, w = t.shape[1], t.shape[2]
+    def layout(t, kind):
+        N, R, w = n_agents.N, t.shape[1], t.shape[2]
         if kind == ZERO_PAIR_ROWS and (R, w) == (N, N) and t.is_contiguous():
             R, w, pitch = N * N, 1, 1          # a matrix per scene: one element per ordered pair
         else:
@@ -356,18 +386,12 @@ def zero_padding(items: Sequence[Tuple[Tensor, int]], n_agents) -> None:
                 raise ValueError("zero_padding: a contiguous tensor or a last-dim slice of one")
             pitch = t.stride(1)
         if kind == ZERO_EDGE_ROWS and R == 1:
-            continue
+            return None
         if R != (N * N if kind == ZERO_PAIR_ROWS else N) or kind not in (ZERO_NODE_ROWS, ZERO_EDGE_ROWS, ZERO_PAIR_ROWS):
             raise ValueError(f"zero_padding: kind {kind} does not go with {R} rows per scene at N = {N}")
-        _same_device(n_agents.dev, t)
-        arr.append(_lib.ZeroItem(ptr=t.data_ptr(), pitch=pitch * t.element_size(), width=w * t.element_size(), kind=kind))
-    if not arr:
-        return
-    if len(arr) > _lib.MAX_ZERO_ITEMS:
-        raise ValueError(f"zero_padding: at most {_lib.MAX_ZERO_ITEMS} tensors per launch")
-    with torch.cuda.device(n_agents.dev.device):
-        check(load().gn_zero_padding((_lib.ZeroItem * len(arr))(*arr), len(arr), B, N, addr(n_agents.dev), stream_handle()),
-              "gn_zero_padding")
+        return pitch, w
+
+    _zero_launch("zero_padding", " (ops.agent_counts)", items, n_agents, None, layout)
 
 
 def zero_empty_scenes(items: Sequence[Tensor], n_agents) -> None:
@@ -375,27 +399,12 @@ def zero_empty_scenes(items: Sequence[Tensor], n_agents) -> None:
     factor rows of scale-N modules, which reach an empty slot's row through row-wise stages (gn_zero_empty_scenes).  For
     holders that admit a count of 0 (`StaticAgentCounts`); scenes with a count >= 1 keep their bits.  fp32 or bf16,
     contiguous or a last-dim slice of a contiguous tensor."""
-    if not isinstance(n_agents, AgentCounts):
-        raise ValueError("zero_empty_scenes: n_agents must be an ops.AgentCounts")
-    B = n_agents.B
-    arr = []
-    for t in items:
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 3 and tuple(t.shape[:2]) == (B, 1)):
-            raise ValueError("zero_empty_scenes: (B, 1, width) GPU tensors")
-        if t.dtype not in _ACT_DTYPES:
-            raise ValueError(f"zero_empty_scenes: fp32 or bf16 tensors (got {t.dtype})")
+    def layout(t, kind):
         if t.stride(2) != 1 or t.stride(0) < t.shape[2]:
             raise ValueError("zero_empty_scenes: a contiguous tensor or a last-dim slice of one")
-        _same_device(n_agents.dev, t)
-        arr.append(_lib.ZeroItem(ptr=t.data_ptr(), pitch=t.stride(0) * t.element_size(),
-                                 width=t.shape[2] * t.element_size(), kind=ZERO_EDGE_ROWS))
-    if not arr:
-        return
-    if len(arr) > _lib.MAX_ZERO_ITEMS:
-        raise ValueError(f"zero_empty_scenes: at most {_lib.MAX_ZERO_ITEMS} tensors per launch")
-    with torch.cuda.device(n_agents.dev.device):
-        check(load().gn_zero_empty_scenes((_lib.ZeroItem * len(arr))(*arr), len(arr), B, addr(n_agents.dev), stream_handle()),
-              "gn_zero_empty_scenes")
+        return t.stride(0), t.shape[2]
+
+    _zero_launch("zero_empty_scenes", "", [(t, ZERO_EDGE_ROWS) for t in items], n_agents, 1, layout)
 
 
 # ---- A0 / A1 -----------------------------------------------------------------------------------
@@ -627,9 +636,7 @@ class AffinityTail:
         if want_H_cat:
             self.H_cat = torch.empty((B, sum(h.shape[1] for h in self.Hs), N), dtype=f.dtype, device=f.device)
             ex.update(H_cat=self.H_cat.data_ptr())
-        if counter is not None:
-            if not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
-                raise ValueError("counter: a 1-element int64 GPU tensor")
+        if _counter_arg(counter) is not None:
             ex.update(counter=counter.data_ptr(), counter_add=int(counter_add) & (2**64 - 1))
         self._ex = _lib.BlockExtras(**ex)
         self._keep = (f_out, counter)
@@ -810,8 +817,7 @@ class PhiloxNoise:
     __slots__ = ("seed", "offset", "counter")
 
     def __init__(self, seed: int, offset: int = 0, counter: Optional[Tensor] = None):
-        if counter is not None and not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
-            raise ValueError("counter: a 1-element int64 GPU tensor")
+        _counter_arg(counter)
         self.seed, self.offset, self.counter = int(seed) & (2**64 - 1), int(offset), counter
 
 
@@ -1317,8 +1323,7 @@ def philox_uniform(shape: Sequence[int], seed: int, offset: int, device, offset_
     U = torch.empty(tuple(shape), dtype=torch.float32, device=device)
     if not U.is_cuda:
         raise ValueError("philox_uniform: device must be a GPU")
-    if offset_dev is not None and not (offset_dev.is_cuda and offset_dev.dtype == torch.int64 and offset_dev.numel() == 1):
-        raise ValueError("offset_dev: a 1-element int64 GPU tensor")
+    _counter_arg(offset_dev, "offset_dev")
     with torch.cuda.device(U.device):
         check(load().gn_philox_uniform_f32(addr(U), U.numel(), int(seed) & (2**64 - 1), int(offset), addr(offset_dev),
                                            stream_handle()), "gn_philox_uniform_f32")
@@ -1327,8 +1332,7 @@ def philox_uniform(shape: Sequence[int], seed: int, offset: int, device, offset_
 
 def counter_add(counter: Tensor, add: int) -> None:
     """counter += add, in stream order (counter: 1-element int64 GPU tensor)."""
-    if not (counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1):
-        raise ValueError("counter: a 1-element int64 GPU tensor")
+    _counter_arg(counter)
     with torch.cuda.device(counter.device):
         check(load().gn_counter_add_u64(addr(counter), int(add), stream_handle()), "gn_counter_add_u64")
 

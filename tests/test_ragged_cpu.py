@@ -179,6 +179,50 @@ def test_zero_padding_plan():
     assert lb.gn_kernel_name(L.K_LAST + 1) is None
 
 
+def _fields_but_kernel(plan):
+    L, _ = lib()
+    vals = {name: getattr(plan, name) for name, _ in L.LaunchPlan._fields_ if name != "kernel"}
+    return {name: list(v) if isinstance(v, ctypes.Array) else v for name, v in vals.items()}
+
+
+@pytest.mark.parametrize("stem", ["f32", "bf16"])
+def test_ragged_plan_is_the_plain_plan_but_for_the_kernel(stem, monkeypatch):
+    """One plan function per stage decides the plain and the ragged launch: for the same arguments the two plans agree in
+    EVERY field except ``kernel``, which names the ragged kernel and its plain twin.  gn_topk_incidence (fp32 only: it
+    ranks corr) on either side of one band, gn_affinity_topk at both ends of its tile, gn_node2edge in its banded form
+    (by switch at N <= 64, by size beyond) and its row form.  Placeholder addresses: nothing is launched."""
+    L, lb = lib()
+    Hl, kl = _scales()
+    plan, full = L.LaunchPlan(), L.LaunchPlan()
+
+    def same(kernel, twin):
+        assert lb.gn_kernel_name(plan.kernel) == kernel and lb.gn_kernel_name(full.kernel) == twin
+        assert _fields_but_kernel(plan) == _fields_but_kernel(full)
+
+    for B, N in ((2, 11), (1030, 11), (2, 113), (3, 400)):
+        assert lb.gn_topk_incidence_ragged_plan_f32(P, Hl, kl, 2, B, N, P, ctypes.byref(plan)) == L.GN_OK
+        assert lb.gn_topk_incidence_plan_f32(P, Hl, kl, 2, B, N, ctypes.byref(full)) == L.GN_OK
+        same(b"topk_incidence_ragged_kernel", b"topk_incidence_kernel")
+    for B, N, D in ((5, 11, 64), (1, 2, 4), (3, 112, 64)):
+        assert getattr(lb, "gn_affinity_topk_ragged_plan_" + stem)(P, None, Hl, kl, 2, B, N, D, None, P,
+                                                                   ctypes.byref(plan)) == L.GN_OK
+        assert getattr(lb, "gn_affinity_topk_plan_" + stem)(P, None, Hl, kl, 2, B, N, D, None, None, None,
+                                                            ctypes.byref(full)) == L.GN_OK
+        same(b"affinity_topk_ragged_kernel", b"affinity_topk_kernel")
+    for B, N, rows in ((5, 17, "0"), (5, 17, "1"), (300, 50, None), (2, 65, None), (2, 65, "1")):
+        if rows is None:
+            monkeypatch.delenv("GN_N2E_ROWS", raising=False)
+        else:
+            monkeypatch.setenv("GN_N2E_ROWS", rows)
+        g = (L.N2EGroup * 3)(L.N2EGroup(xp=P, pq=P, w2=P, edges=P, b2=P, E=N * N),
+                             L.N2EGroup(xp=P, pq=P, H=P, w2=P, edges=P, b2=P, E=N),
+                             L.N2EGroup(xp=P, pq=P, H=P, w2=P, edges=P, b2=P, E=1))
+        assert getattr(lb, "gn_node2edge_ragged_plan_" + stem)(g, 3, B, N, P, ctypes.byref(plan)) == L.GN_OK
+        assert getattr(lb, "gn_node2edge_plan_" + stem)(g, 3, B, N, ctypes.byref(full)) == L.GN_OK
+        same(b"node2edge_ragged_kernel", b"node2edge_kernel")
+        assert plan.variant == (1 if N <= 64 and rows != "0" else 0)      # both forms were planned
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the holder of the counts
 # ---------------------------------------------------------------------------------------------------------------------
