@@ -11,6 +11,9 @@ MI355X-first choices: affinity and the incidence of EVERY scale come from one fu
 (corr never makes a trip through HBM at all); the 1+S modules are independent given (f, H_s), so
 each stage of all of them is ONE grouped launch (the hyper modules have only B*N edge rows each
 and would leave most of the 256 CUs idle if launched one behind the other).
+
+The graph stage — f to the incidences of every scale — is decided by `route.graph_stage_route` and built by
+`build_graphs`, for the block's inference forward, for `multiscale_autograd` and for the trajectory encoders alike.
 """
 from __future__ import annotations
 
@@ -20,47 +23,35 @@ import contextlib
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import MS_HGNN_batch as _mods
+from . import ops, route
 from .MS_HGNN_batch import (MS_HGNN_hyper, MS_HGNN_oridinary, _needs_grad, _plist, masks_apply, ragged_counts,
                             run_message_passing)
 
 Tensor = torch.Tensor
 
 
-def multiscale_autograd(pair: MS_HGNN_oridinary, hypers: Sequence[MS_HGNN_hyper], scales: Sequence[int], f: Tensor,
-                        noise_u: Optional[Sequence] = None) -> Tuple[Tensor, Optional[Tensor]]:
-    """cat(f, pairwise(f), hyper_s(f, corr)...) and cat(H_s) with autograd attached: incidences from one fused
-    launch (constants of the backward), then ONE `MSHGNNFunction` node over all modules.  In mask form
-    (`masks_apply(N)`) that launch also emits the member words, which the forward and the backward then read."""
-    from .backward import MSHGNNFunction
-    S = len(hypers)
-    fd = f.detach().contiguous()
-    want_masks = masks_apply(fd.shape[1])
-    # (the mask words cannot change the answer today: masks need N <= 64, where the tile at D = 64 with eight scales of
-    # mask words is 58 384 B of the 128 KiB — the question is asked about the launch that is then built)
-    if S and ops.graph_form(fd.shape[1], fd.shape[2], 0, S if want_masks else 0) != "banded":
-        job = ops.AffinityTail(fd, list(scales), want_H_cat=True, want_masks=want_masks)
-        job.launch()
-        Hs, graphs, new_H = job.Hs, job.incidences, job.H_cat
-    elif S:
-        Hs = graphs = ops.topk_incidence(ops.affinity(fd), list(scales))
-        new_H = torch.cat(Hs, dim=1)
-    else:
-        Hs, graphs, new_H = [], [], None
-    mods = (pair, *hypers)
-    if noise_u is None:
-        # draw as the no-grad path (and the reference) does: module-major — every round of the pairwise module,
-        # then scale by scale — so that a seeded training forward sees the noise of the seeded inference forward
-        from .MS_HGNN_batch import _draw_uniform
-        B, N = fd.shape[0], fd.shape[1]
-        shapes = [(B, N * N, pair.edge_types)] + [(B, H.shape[1], m.edge_types) for H, m in zip(Hs, hypers)]
-        noise_u = [[_draw_uniform(shp, fd.device) for _ in range(pair.nmp_layers)] for shp in shapes]
-    nz = tuple(noise_u)
-    if len(nz) != 1 + S:
-        raise ValueError(f"noise_u: need {1 + S} entries (pairwise + one per scale)")
-    params = [p for m in mods for p in _plist(m)]
-    res = MSHGNNFunction.apply(mods, (None, *graphs), nz, *([f] * (1 + S)), *params)
-    return torch.cat([f, *res[0::2]], dim=-1), new_H
+def noise_shapes(pair: MS_HGNN_oridinary, hypers: Sequence[MS_HGNN_hyper], scales: Sequence[int], B: int, N: int
+                 ) -> List[Tuple[int, int, int]]:
+    """(B,E,K) of the uniforms each module draws per message-passing round, pairwise first."""
+    return [(B, N * N, pair.edge_types)] + [(B, 1 if s == N else N, m.edge_types) for s, m in zip(scales, hypers)]
+
+
+def draw_noise(shapes: Sequence[Tuple[int, int, int]], rounds: int, device: torch.device) -> List[list]:
+    """`rounds` uniforms per shape, drawn as the reference does: module-major — every round of the pairwise module, then
+    scale by scale — so that a seeded training forward sees the noise of the seeded inference forward.  Through the
+    engine's `_draw_uniform` as it stands at the time of the call, like the engine's own draws."""
+    return [[_mods._draw_uniform(shp, device) for _ in range(rounds)] for shp in shapes]
+
+
+def graph_route(S: int, B: int, N: int, D: int, facts: route.StageFacts, ragged: bool = False, training: bool = False
+                ) -> route.GraphStage:
+    """`route.graph_stage_route` for a block without the embedding front-end.  The library is asked about the launch that
+    is then built, mask words included (which cannot change the answer today: masks need N <= 64, where the tile at
+    D = 64 with eight scales of mask words is 58 384 B of the 128 KiB)."""
+    masked = masks_apply(N)
+    form = ops.graph_form(N, D, 0, S if route.graph_stage_masks(S, masked, ragged) else 0)
+    return route.graph_stage_route(S, form, B * N, masked=masked, ragged=ragged, training=training, facts=facts)
 
 
 _FORK_STREAMS = {}
@@ -72,6 +63,77 @@ def _fork_stream(device: torch.device) -> "torch.cuda.Stream":
     if st is None:
         st = _FORK_STREAMS[key] = torch.cuda.Stream(device=device)
     return st
+
+
+def build_graphs(r: route.GraphStage, f: Optional[Tensor], scales: Sequence[int], *, width: int = 0, advance=None,
+                 counts=None, embed=None):
+    """The graph stage of a forward, as `r` states it.  ``width``: allocate ``final`` with that many columns (0: no final
+    — a training forward concatenates); ``advance`` = (counter, n): add n to the device Philox counter; ``counts``: the
+    ragged batch's `ops.AgentCounts`; ``embed`` = (x_raw, M, c) with f = None: the fused launch computes f itself.
+    -> (f, the features the modules run on;  incidences, one per scale, what `run_message_passing` takes after the
+    pairwise module's None;  new_H = cat(H_s, dim=1) where the route builds it;  the deferred job for
+    `run_message_passing(affinity=)` or None;  join, to be called after the first node stage when the job runs on the
+    side stream, or None;  final (B, N, width) with f in its first D columns;  cols, its 1+S module slices, written in
+    place by the last MLP)."""
+    x = f if embed is None else embed[0]
+    B, N = x.shape[0], x.shape[1]
+    D = f.shape[2] if embed is None else embed[1].shape[0]
+    S = len(scales)
+    final = cols = job = join = new_H = None
+    incs = []
+    if width:
+        final = torch.empty((B, N, width), dtype=x.dtype, device=x.device)
+        cols = [final[..., D * (1 + i):D * (2 + i)] for i in range(1 + S)]
+    if r.kind == route.FUSED:
+        # one launch: affinity, incidence of every scale, f -> final[..., :D], cat(H_s), Philox bump — on the side stream
+        # where the route forks, handed on unlaunched where it defers
+        side = _fork_stream(x.device) if r.fork else None
+        if r.fork:
+            main = torch.cuda.current_stream(x.device)
+            side.wait_stream(main)
+            join = lambda: main.wait_stream(side)
+        with (torch.cuda.stream(side) if r.fork else contextlib.nullcontext()):
+            # >= 1 scale per launch; N = the cheap all-ones edge, whose incidence is dropped
+            job = ops.AffinityTail(f, list(scales) or [N], f_out=final[..., :D] if width else None, want_H_cat=r.H_cat,
+                                   counter=advance[0] if advance else None, counter_add=advance[1] if advance else 0,
+                                   embed=embed, want_masks=r.masks, n_agents=counts)
+            if not r.deferred:
+                job.launch()
+        f, new_H, incs = job.f, job.H_cat, (job.incidences if S else [])
+    elif r.kind == route.BANDED:
+        # large N (N*(N+68)*4 B > LDS tile): banded affinity and banded top-k launches, plain copies
+        incs = ops.topk_incidence(ops.affinity(f if f.dtype == torch.float32 else f.float()), list(scales), counts)
+        new_H = torch.cat(incs, dim=1).to(f.dtype) if r.H_cat else None
+    if r.own_copy:
+        final[..., :D].copy_(f)
+        if advance:
+            ops.counter_add(advance[0], advance[1])
+    return f, incs, new_H, (job if r.deferred else None), join, final, cols
+
+
+_TRAINING = route.StageFacts(grouped=True, latency_form=False, capturing=False, embed=False, may_defer=False)
+
+
+def multiscale_autograd(pair: MS_HGNN_oridinary, hypers: Sequence[MS_HGNN_hyper], scales: Sequence[int], f: Tensor,
+                        noise_u: Optional[Sequence] = None) -> Tuple[Tensor, Optional[Tensor]]:
+    """cat(f, pairwise(f), hyper_s(f, corr)...) and cat(H_s) with autograd attached: incidences from the graph stage
+    (constants of the backward), then ONE `MSHGNNFunction` node over all modules.  In mask form (`masks_apply(N)`) the
+    fused launch also emits the member words, which the forward and the backward then read.  The device counter is the
+    caller's to bump."""
+    from .backward import MSHGNNFunction
+    S = len(hypers)
+    fd = f.detach().contiguous()
+    B, N, D = fd.shape
+    _, graphs, new_H, *_ = build_graphs(graph_route(S, B, N, D, _TRAINING, training=True), fd, scales)
+    mods = (pair, *hypers)
+    if noise_u is None:
+        noise_u = draw_noise(noise_shapes(pair, hypers, scales, B, N), pair.nmp_layers, fd.device)
+    nz = tuple(noise_u)
+    if len(nz) != 1 + S:
+        raise ValueError(f"noise_u: need {1 + S} entries (pairwise + one per scale)")
+    params = [p for m in mods for p in _plist(m)]
+    res = MSHGNNFunction.apply(mods, (None, *graphs), nz, *([f] * (1 + S)), *params)
+    return torch.cat([f, *res[0::2]], dim=-1), new_H
 
 
 class MultiScaleHGNN(nn.Module):
@@ -110,10 +172,7 @@ class MultiScaleHGNN(nn.Module):
 
     def noise_shapes(self, B: int, N: int) -> List[Tuple[int, int, int]]:
         """(B,E,K) of the uniforms each module draws per message-passing round, pairwise first."""
-        out = [(B, N * N, self.interaction.edge_types)]
-        for s, m in zip(self.hyper_scales, self.interaction_hyper):
-            out.append((B, 1 if s == N else N, m.edge_types))
-        return out
+        return noise_shapes(self.interaction, self.interaction_hyper, self.hyper_scales, B, N)
 
     def forward(self, f: Tensor, noise_u: Optional[Sequence] = None, advance=None, n_agents=None
                 ) -> Tuple[Tensor, Optional[Tensor]]:
@@ -129,7 +188,6 @@ class MultiScaleHGNN(nn.Module):
         ops._req(f, "f", (None, None, self.h_dim), ops._ACT_DTYPES)
         B, N, D = f.shape
         S = len(self.hyper_scales)
-        nmp = self.interaction.nmp_layers
         counts = ragged_counts(n_agents, f, grad=_needs_grad(self, f),
                                listall=any(m.listall for m in self.interaction_hyper))
         if _needs_grad(self, f):
@@ -149,65 +207,22 @@ class MultiScaleHGNN(nn.Module):
                 ops.counter_add(advance[0], advance[1])
             return multiscale_autograd(self.interaction, list(self.interaction_hyper), self.hyper_scales, f, noise_u)
         if noise_u is None:
-            # reference order: every draw of the pairwise module first, then scale by scale
-            from .MS_HGNN_batch import _draw_uniform
-            noise_u = [[_draw_uniform(shp, f.device) for _ in range(nmp)] for shp in self.noise_shapes(B, N)]
+            noise_u = draw_noise(self.noise_shapes(B, N), self.interaction.nmp_layers, f.device)
         elif len(noise_u) != 1 + S:
             raise ValueError(f"noise_u: need {1 + S} entries (pairwise + one per scale)")
-        final = torch.empty((B, N, self.out_features), dtype=f.dtype, device=f.device)
-        cols = [final[..., D * (1 + i):D * (2 + i)] for i in range(1 + S)]   # written in place by the last MLP
-        join = None
-        # mask form on and 16 < N <= 64: the fused launch also emits the member words (not for a ragged batch, whose
-        # route reads no masks)
-        want_masks = masks_apply(N) and counts is None
-        # asked about the launch built below, mask words included (which cannot change the answer today: at D = 64 and
-        # N <= 64 the tile with eight scales of mask words is 58 384 B of the 128 KiB)
-        fused = bool(S) and ops.graph_form(N, D, 0, S if want_masks else 0) != "banded"
-        if fused:
-            # one launch: affinity, incidence of every scale, f -> final[..., :D], cat(H_s), Philox bump.
-            # The node stage of the first round needs only f: inside a graph capture the two launches are forked
-            # (the graph then runs them side by side; eager launches stay on one stream)
-            # — worth it only when the launches are long: at B*N = 5.6 k rows the extra graph edges cost more
-            # (+9 us per replay) than the 7-us overlap saves; at 51 k rows the replay is 33 us shorter
-            fork = self.grouped and f.is_cuda and B * N >= 32768 and torch.cuda.is_current_stream_capturing()
-            main = torch.cuda.current_stream(f.device) if fork else None
-            side = _fork_stream(f.device) if fork else None
-            if fork:
-                side.wait_stream(main)
-            # the launch is DEFERRED where it can be: it rides as the tail workgroups of the first node-stage launch (which
-            # needs only f), or is issued right before it when that launch cannot take it — one launch and one boundary
-            # fewer; forked, ungrouped or emitting masks it is a launch of its own, here
-            deferred = self.grouped and not fork and self.affinity_tail and not want_masks
-            with (torch.cuda.stream(side) if fork else contextlib.nullcontext()):
-                job = ops.AffinityTail(f, self.hyper_scales, f_out=final[..., :D], want_H_cat=True,
-                                       counter=advance[0] if advance else None,
-                                       counter_add=advance[1] if advance else 0, want_masks=want_masks, n_agents=counts)
-                if not deferred:
-                    job.launch()
-            tail = job if deferred else None
-            Hs, new_H = job.incidences, job.H_cat
-            if fork:
-                join = lambda: main.wait_stream(side)
-        elif S:
-            # large N (N*(N+68)*4 B > LDS tile): banded affinity and banded top-k launches, plain copies
-            Hs = ops.topk_incidence(ops.affinity(f if f.dtype == torch.float32 else f.float()), self.hyper_scales, counts)
-            new_H = torch.cat(Hs, dim=1).to(f.dtype)
-            final[..., :D].copy_(f)
-            if advance:
-                ops.counter_add(advance[0], advance[1])
-        else:
-            Hs, new_H = [], None
-            final[..., :D].copy_(f)
-            if advance:
-                ops.counter_add(advance[0], advance[1])
+        facts = route.StageFacts(grouped=self.grouped, latency_form=self.affinity_tail,
+                                 capturing=f.is_cuda and torch.cuda.is_current_stream_capturing(), embed=False,
+                                 may_defer=True)
+        r = graph_route(S, B, N, D, facts, ragged=counts is not None)
+        _, Hs, new_H, job, join, final, cols = build_graphs(r, f, self.hyper_scales, width=self.out_features,
+                                                            advance=advance, counts=counts)
         mods = [self.interaction, *self.interaction_hyper]
         if self.grouped:
             # every stage of the 1+S modules in ONE launch: launches always carry enough workgroups
             # to fill the chip, and nothing depends on how streams map to hardware queues
             # (latency form — `affinity_tail` — also folds the closing MLPs into the aggregation launch: 4 launches)
-            run_message_passing(mods, [f] * (1 + S), [None, *Hs], list(noise_u), cols, join=join,
-                                affinity=tail if fused else None,
-                                fuse_closing=self.affinity_tail, n_agents=counts)
+            run_message_passing(mods, [f] * (1 + S), [None, *Hs], list(noise_u), cols, join=join, affinity=job,
+                                fuse_closing=r.ask_closing, n_agents=counts)
         else:
             for m, H, u, c in zip(mods, [None, *Hs], noise_u, cols):
                 run_message_passing([m], [f], [H], [u], [c], n_agents=counts)

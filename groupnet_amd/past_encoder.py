@@ -28,11 +28,14 @@ from typing import Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import ops
-from .MS_HGNN_batch import (MS_HGNN_hyper, MS_HGNN_oridinary, _NoiseState, _draw_uniform, _needs_grad, _param_key,
-                            masks_apply, run_message_passing)
+from . import ops, route
+from .MS_HGNN_batch import (MS_HGNN_hyper, MS_HGNN_oridinary, _NoiseState, _needs_grad, _param_key, masks_apply,
+                            run_message_passing)
+from .multiscale import build_graphs, draw_noise, multiscale_autograd, noise_shapes
 
 Tensor = torch.Tensor
+# The encoders launch the graph job at once and use neither the tail nor the closing stage
+_ENCODER = route.StageFacts(grouped=True, latency_form=False, capturing=False, embed=True, may_defer=False)
 
 
 class PositionalAgentEncoding(nn.Module):
@@ -122,11 +125,15 @@ class _TrajectoryEncoder(nn.Module):
         cat[10, 2] = 1                                            # IndexError for N <= 10, as the reference
         return cat
 
+    def _graph_form(self, N: int, T: int) -> str:
+        """The library's answer (`ops.graph_form`) for the launch with the embedding front-end over T time steps."""
+        return ops.graph_form(N, self.model_dim, T * self.input_fc.in_features)
+
     def fused_front_end_fits(self, N: int, T: int) -> bool:
         """Whether an eval-mode forward over N agents and T time steps is served by the fused launch (the embedding as
         one affine map inside the affinity + top-k launch): its scene tile, the raw inputs included, within the launch's
         LDS budget.  Beyond it the forward runs the embedding on the HIP GEMM and the banded affinity / top-k pair."""
-        return ops.graph_form(N, self.model_dim, T * self.input_fc.in_features) != "banded"
+        return self._graph_form(N, T) != "banded"
 
     def _check_inputs(self, inputs: Tensor, B: int, N: int) -> int:
         ops._req(inputs, "inputs", (B * N, None, self.input_fc.in_features))
@@ -168,40 +175,27 @@ class _TrajectoryEncoder(nn.Module):
         scales = [m.scale for m in hypers]
         dropout_on = self.training and self.pos_encoder.dropout.p > 0
         if dropout_on or _needs_grad(self, inputs):
-            from .multiscale import multiscale_autograd
             f = self._embed_autograd(inputs, B, N, T)
             final, new_H = multiscale_autograd(self.interaction, hypers, scales, f)
             return final, (new_H if S > 1 else None)
-        final = torch.empty((B, N, D * (2 + S)), dtype=inputs.dtype, device=inputs.device)
-        cols = [final[..., D * (1 + i):D * (2 + i)] for i in range(1 + S)]
-        adv = self.__dict__.get("_advance")      # (device counter, draws per call): set by graphs.GraphedPastEncoder
-        if not self.fused_front_end_fits(N, T):
+        r = route.graph_stage_route(S, self._graph_form(N, T), B * N, masked=masks_apply(N), ragged=False, training=False,
+                                    facts=_ENCODER)
+        if r.kind == route.FUSED:
+            # the embedding as one affine map, evaluated inside the launch
+            f, embed = None, (inputs.reshape(B, N, T * inputs.shape[2]), *self._compose(T, N))
+        else:
             # a scene tile beyond the fused launch's LDS budget (N >= 108 at 20 raw inputs per agent): the embedding layer
             # by layer on the HIP GEMM as the training path runs it (dropout is the identity here), then the banded
-            # affinity and top-k launches; same noise order as below
+            # affinity and top-k launches; same noise order
             with torch.no_grad():
-                f = self._embed_autograd(inputs, B, N, T).contiguous()
-            final[..., :D].copy_(f)
-            if adv:
-                ops.counter_add(adv[0], adv[1])
-            Hs = ops.topk_incidence(ops.affinity(f), scales) if S else []
-            mods = [self.interaction, *hypers]
-            noise = [[_draw_uniform((B, N * N, 6), f.device)]] + [[_draw_uniform((B, H.shape[1], 10), f.device)] for H in Hs]
-            run_message_passing(mods, [f] * (1 + S), [None, *Hs], noise, cols)
-            return final, (torch.cat(Hs, dim=1) if S > 1 else None)
-        M, c = self._compose(T, N)
-        x_raw = inputs.reshape(B, N, T * inputs.shape[2])
-        want_masks = S > 0 and masks_apply(N)     # mask form on and 16 < N <= 64: the launch also emits the member words
-        # >= 1 scale per launch; N = the cheap all-ones edge.  new_H: the reference only builds it from two scales on
-        # (:296); its S==1 path raises
-        job = ops.AffinityTail(None, scales or [N], f_out=final[..., :D], want_H_cat=S > 1, embed=(x_raw, M, c),
-                               counter=adv[0] if adv else None, counter_add=adv[1] if adv else 0, want_masks=want_masks)
-        job.launch()
-        f, incs = job.f, (job.incidences if S else [])
-        mods = [self.interaction, *hypers]
-        noise = [[_draw_uniform((B, N * N, 6), f.device)]] + [[_draw_uniform((B, g.H.shape[1], 10), f.device)] for g in incs]
-        run_message_passing(mods, [f] * (1 + S), [None, *incs], noise, cols)
-        return final, job.H_cat
+                f, embed = self._embed_autograd(inputs, B, N, T).contiguous(), None
+        # `_advance` = (device counter, draws per call): set by graphs.GraphedPastEncoder
+        f, incs, new_H, job, join, final, cols = build_graphs(r, f, scales, width=D * (2 + S), embed=embed,
+                                                              advance=self.__dict__.get("_advance"))
+        noise = draw_noise(noise_shapes(self.interaction, hypers, scales, B, N), self.interaction.nmp_layers, f.device)
+        run_message_passing([self.interaction, *hypers], [f] * (1 + S), [None, *incs], noise, cols, join=join,
+                            affinity=job, fuse_closing=r.ask_closing)
+        return final, new_H
 
 
 class PastEncoder(_TrajectoryEncoder):

@@ -1,5 +1,6 @@
 """The route of a message-passing forward: which launches it consists of and what each is asked to fuse, decided in one
-pure function that `MS_HGNN_batch.run_message_passing` follows.
+pure function that `MS_HGNN_batch.run_message_passing` follows; and the graph stage before it — how f becomes the
+incidences of every scale — decided in another, `graph_stage_route`, that `multiscale.build_graphs` follows.
 
 A leaf module: no torch, no library, no environment.  The launchers' own decisions (work shapes, kernels, whether an
 aggregation launch takes the closing stage it was asked for) stay in their plan functions ("Launch plan").
@@ -67,6 +68,70 @@ class Route:
 def masks_in_range(N: int) -> bool:
     """N lies where the stand-alone gather / scatter and the node->edge launch run and a 64-bit word holds a row."""
     return min(_FUSED_GATHER_MAX_N, _FUSED_SCATTER_MAX_N) < N <= MASK_MAX_N
+
+
+# The graph stage of a block (`GraphStage.kind`): what turns f into the incidences of every scale
+NONE = "none"                   # nothing to build (no scales)
+BANDED = "banded"               # ops.affinity + ops.topk_incidence: the scene tile is beyond the fused launch's LDS budget
+FUSED = "fused"                 # ops.AffinityTail: one job for affinity, every scale's incidence, f -> final, cat(H_s), counter
+
+# Inside a graph capture the fused job and the first node stage (which needs only f) are forked, so the graph runs them
+# side by side — worth it only when the launches are long: at B*N = 5.6 k rows the extra graph edges cost more (+9 us
+# per replay) than the 7-us overlap saves; at 51 k rows the replay is 33 us shorter.  Eager launches stay on one stream.
+FORK_MIN_ROWS = 32768
+
+
+class StageFacts(NamedTuple):
+    """What the caller of a graph stage knows per call."""
+    grouped: bool           # the 1+S modules run as grouped launches (one `run_message_passing` for all of them)
+    latency_form: bool      # the block's `affinity_tail`: one launch and one boundary fewer where they can be saved
+    capturing: bool         # the current stream of a GPU tensor is being captured into a graph
+    embed: bool             # the encoder front-end: f itself comes out of the graph stage
+    may_defer: bool         # the caller can hand the job to its first node stage (the encoders launch it at once)
+
+
+@dataclass(frozen=True)
+class GraphStage:
+    kind: str
+    masks: bool             # the launch emits the member words and the incidences carry them
+    fork: bool              # the job is launched on the side stream; the message passing joins after its first node stage
+    deferred: bool          # the job is handed to the first node stage (its tail workgroups, or issued right before it)
+    own_copy: bool          # the builder copies f into final and bumps the counter itself: no fused launch does it
+    ask_closing: bool       # what the caller passes on as `run_message_passing(fuse_closing=)`
+    H_cat: bool             # cat(H_s) is built (the encoders: from two scales on, as the reference)
+
+
+def graph_stage_masks(S: int, masked: bool, ragged: bool) -> bool:
+    """Whether the fused launch of S scales is asked for the member words: not for a ragged batch, whose route reads no
+    masks and whose launch emits none."""
+    return S > 0 and masked and not ragged
+
+
+@functools.lru_cache(maxsize=None)
+def graph_stage_route(S: int, form: str, rows: int, *, masked: bool, ragged: bool, training: bool,
+                      facts: StageFacts) -> GraphStage:
+    """The graph stage of one forward over S scales.  form: the library's answer for the launch in question
+    (`ops.graph_form`: "tail" | "fused" | "banded" — the tile rule is stated in C only); rows = B*N; masked: the mask form
+    is on and `masks_in_range(N)` holds; training: the forward runs under autograd — it writes into no final and leaves
+    the counter to its caller, and nothing is forked, deferred or asked of the closing stage.
+    ragged (inference only): no masks, and the job — which is never the tail, `AffinityTail.fits_tail` — is still handed
+    on where the caller defers: the first node stage issues it on its own.
+    Whether a deferred job rides as tail workgroups ("tail") or is issued beside the node stage ("fused") is the node
+    stage's decision; here only "banded" or not matters."""
+    if ragged and training:
+        raise NotImplementedError("ragged batches are inference-only")
+    if form != BANDED and (S or facts.embed):
+        kind = FUSED            # the front-end's launch needs >= 1 scale: the builder gives it N, the all-ones edge
+    else:
+        kind = BANDED if S else NONE
+    live = kind == FUSED and not training
+    masks = kind == FUSED and graph_stage_masks(S, masked, ragged)
+    fork = live and facts.grouped and not facts.embed and facts.capturing and rows >= FORK_MIN_ROWS
+    # forked, ungrouped or emitting masks (which only the stand-alone launch does) the job is a launch of its own
+    deferred = live and facts.may_defer and facts.grouped and not fork and facts.latency_form and not masks
+    return GraphStage(kind=kind, masks=masks, fork=fork, deferred=deferred, own_copy=kind != FUSED and not training,
+                      ask_closing=facts.grouped and facts.latency_form and not facts.embed and not training,
+                      H_cat=kind != NONE and S >= (2 if facts.embed else 1))
 
 
 @functools.lru_cache(maxsize=None)
