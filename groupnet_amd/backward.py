@@ -17,7 +17,8 @@ by stage for SEVERAL modules at once, every stage one grouped launch of libgroup
 
 A round j of a module is two blocks: x_j --node2edge_j, edge MLP_j--> (ef_j, dist_j) and
 (ef_j, x_j) --edge2node_j, MLP--> x_{j+1} (or node_feat).  `nmp_layers > 1` (:186-194, :432-440) is
-the same two blocks repeated, walked backwards.
+the same two blocks repeated, walked backwards.  Which forms a round takes is `route.backward_round_route`'s
+answer; `round_backward` follows it through the steps below it, each a function over the modules' `_RoundState`s.
 """
 from __future__ import annotations
 
@@ -26,12 +27,13 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib, ops, weights
+from . import _lib, ops, route, weights
 from ._lib import addr, check, load, stream_handle
+from .MS_HGNN_batch import _GUMBEL_TAU
 from .weights import _HID, _LGF_LD
 
 Tensor = torch.Tensor
-_TAU = 0.5
+D = ops.FEAT
 
 
 class GemmBatch:
@@ -160,6 +162,9 @@ class ModuleTrace:
         self.tails: List[dict] = []          # round j's closing MLP: {"x": cat(H^T feat, ori)/N, "hid": relu(layer 0)}
         self.n2e: List[dict] = []            # round j: {"x1" hidden of node2edge_start_mlp, "xp", "pq", "edges"}
         self.estage: List[dict] = []         # round j's edge MLP: {"z1", "z", "dh1", "lgf"}
+        # what the backward leaves here for its later rounds
+        self.pair_H: Optional[Tensor] = None     # `pairwise_incidence`, where a round walks the pairwise graph's ordered rows
+        self.npar: Dict[int, int] = {}           # round j -> number of parameter elements of its layers
 
 
 def _round_layers(mod, j: int):
@@ -184,235 +189,300 @@ def _bwd_weights(mod, j: int) -> dict:
         plan, a0, d, f, l0, l1))
 
 
+def _arena_floats(npar: int, B: int, N: int, E: int, K: int) -> int:
+    """fp32 elements of the zeroed scratch one module takes from the round's arena (`_Pool`), a multiple of 64."""
+    n = (npar                       # every parameter gradient of the round
+         + 2 * B * N * D            # dxp, dpq
+         + B * E * (2 * K + 4)      # ef (leading dimension K rounded up to 4) and def
+         + B * E * D                # deo
+         # room for what the gradient images hold beyond their parameters (MLP_distribution | MLP_factor layer 1 as
+         # (32, 256), the typed MLPs' output bias in Kp rows) and for the rounding of each take to 4 elements; a take
+         # beyond the arena gets a fill of its own (`_Pool.take`)
+         + B * E * D + 4096)
+    return (n + 63) // 64 * 64
+
+
+class _RoundState:
+    """One module's part of one backward round: what the steps of `round_backward` read and what each of them fills.
+    Tensors are 2-D views: BN = B*N node rows, R = B*E edge rows (E = N(N+1)/2 pair rows where `sym`)."""
+    __slots__ = (
+        # the constructor — the round's inputs and constants:
+        "x", "x2", "H", "masks", "sym",         # x_j (B,N,D) and as (BN,D); dense incidence (None where sym) and its masks
+        "B", "N", "E", "K", "Kp", "R", "BN",    # Kp: K rounded up to 4, the leading dimension of ef
+        "s0", "s1", "a0", "a1", "i", "d", "f", "agg", "e0", "e1",      # the round's layers (`_round_layers`)
+        "tw", "w2", "b2",                       # `_bwd_weights`; attention layer 1 as a vector and its bias
+        "agg2", "y1",                           # the closing MLP's input cat(H^T feat, ori)/N and hidden layer, as kept
+        "dist", "g_y", "g_d",                   # (R', K) dist of the ordered rows; incoming gradients (None: not used)
+        "pool_n", "dx",     # `_arena_floats`; d x_j (BN,D): None until `_edge2node_backward` or `_pooling_backward`
+        # `round_backward`, from the round's one zero fill:
+        "pool",
+        # `_forward_activations`:
+        "x1", "xp", "pq", "edges", "z1", "z", "dh1", "lgf",
+        # `_edge_weights`:
+        "ef", "def_",                           # (R,Kp) ef per edge row; (R,K) its gradient, zero where the module is not live
+        # `_edge2node_backward` (live modules only):
+        "eo2", "Hc", "dy1", "da", "dfeat", "T", "deo",
+        # `_edge_mlp_backward`:
+        "dlgf", "dd1", "dz", "dz1", "dedges",
+        # `_pooling_backward`:
+        "dxp", "dpq", "dx1")
+
+    def __init__(self, t: ModuleTrace, j: int, pair_rows: bool, g_y: Optional[Tensor], g_d: Optional[Tensor]):
+        mod, x = t.mod, t.xs[j]
+        B, N, _ = x.shape
+        # The pairwise graph is symmetric: the ordered edges (i,j) and (j,i) pool the same feature and feed
+        # the same typed MLP, so (as in the forward) every per-edge stage runs on the N(N+1)/2 unordered
+        # pairs; only dist (its own Gumbel noise per ordered edge) stays ordered.
+        self.sym, self.H = t.H is None and pair_rows, t.H
+        if t.H is None and not self.sym:
+            if t.pair_H is None:
+                t.pair_H = pairwise_incidence(B, N, x.device, x.dtype)
+            self.H = t.pair_H
+        E = ops.pair_count(N) if self.sym else self.H.shape[1]
+        K = mod.edge_types
+        (self.s0, self.s1), (self.a0, self.a1), st, self.agg, (self.e0, self.e1) = _round_layers(mod, j)
+        if j not in t.npar:
+            t.npar[j] = sum(p.numel() for m in (mod.node2edge_start_mlp[j], mod.attention_mlp[j], st, self.agg,
+                                                nn.ModuleList([self.e0, self.e1])) for p in m.parameters())
+        self.x, self.x2, self.masks = x, x.reshape(B * N, D), t.masks
+        self.B, self.N, self.E, self.K, self.Kp, self.R, self.BN = B, N, E, K, (K + 3) // 4 * 4, B * E, B * N
+        self.i, self.d, self.f = st.init_MLP.layers, st.MLP_distribution.layers, st.MLP_factor.layers
+        self.tw = _bwd_weights(mod, j)
+        self.w2, self.b2 = _w(self.a1)[0], _b(self.a1)
+        self.agg2, self.y1 = t.tails[j]["x"], t.tails[j]["hid"]
+        self.dist = t.dists[j].reshape(-1, K)
+        self.g_y = None if g_y is None else g_y.reshape(B * N, -1).contiguous()
+        self.g_d = None if g_d is None else g_d.reshape(-1, K).contiguous()
+        self.pool_n = _arena_floats(t.npar[j], B, N, E, K)
+        self.dx = None
+
+    def new(self, *shape: int) -> Tensor:
+        return torch.empty(shape, dtype=torch.float32, device=self.x.device)
+
+
+def _w(lin) -> Tensor:
+    return lin.weight.detach()
+
+
+def _b(lin) -> Tensor:
+    return lin.bias.detach()
+
+
+def _each(S: List[_RoundState], gb: GemmBatch):
+    """The modules of one stage: the problems the loop body adds for them run as ONE grouped launch when the loop ends."""
+    yield from S
+    gb.run()
+
+
+def _wgrad(gb: GemmBatch, grads: dict, pool: _Pool, lin, dY: Tensor, X: Tensor) -> None:
+    """dW = dY^T X of one linear layer, its bias gradient as the side output, both from the zeroed pool."""
+    grads[lin.weight] = gb.add(dY, X, pool.take(*lin.weight.shape), tA=True, accum=True,
+                               colsum=grads.setdefault(lin.bias, pool.take(*lin.bias.shape)))
+
+
+def _forward_activations(S: List[_RoundState], gb: GemmBatch, traces: Sequence[ModuleTrace], j: int, kept: bool) -> None:
+    """x1 .. lgf of round j: taken over from what the fused forward kept (training mode writes these on request), or
+    re-computed.  The forward runs the pairwise module on unordered pairs; if this backward has to use ordered edge rows
+    (N too large for the per-scene node2edge backward), its edge-row activations do not serve."""
+    if kept:
+        for c, tr in zip(S, traces):
+            a, e = tr.n2e[j], tr.estage[j]
+            c.x1, c.xp, c.pq, c.edges = a["x1"], a["xp"].view(-1, D), a["pq"].view(-1, D), a["edges"].view(c.R, D)
+            c.z1, c.z, c.dh1, c.lgf = e["z1"], e["z"], e["dh1"], e["lgf"]
+        return
+    for c in _each(S, gb):
+        c.x1 = gb.add(c.x2, _w(c.s0), c.new(c.BN, 256), tB=True, bias=_b(c.s0), relu=True)
+    for c in _each(S, gb):
+        c.xp = gb.add(c.x1, _w(c.s1), c.new(c.BN, D), tB=True, bias=_b(c.s1))
+    # attention layer 0 on cat(x'_n, e0_e), split by linearity: P = W[:, :64] x' + b, Qn = W[:, 64:] x'
+    for c in _each(S, gb):
+        c.pq = gb.add(c.xp, c.tw["Wpq"], c.new(c.BN, D), tB=True, bias=c.tw["bpq"])
+    edges = ops.node2edge_grouped([(c.xp.view(c.B, c.N, D), c.pq.view(c.B, c.N, D), c.H, c.w2, c.b2, c.sym) for c in S])
+    for c, e in zip(S, edges):
+        c.edges = e.view(c.R, D)
+    for c in _each(S, gb):
+        c.z1 = gb.add(c.edges, _w(c.i[0]), c.new(c.R, 128), tB=True, bias=_b(c.i[0]), relu=True)
+    for c in _each(S, gb):
+        c.z = gb.add(c.z1, _w(c.i[1]), c.new(c.R, D), tB=True, bias=_b(c.i[1]))
+    # hidden layers of MLP_distribution | MLP_factor side by side, then (logits | factor pre-activation)
+    for c in _each(S, gb):
+        c.dh1 = gb.add(c.z, c.tw["Wd0"], c.new(c.R, 256), tB=True, bias=c.tw["bd0"], relu=True)
+    for c in _each(S, gb):
+        c.lgf = gb.add(c.dh1, c.tw["Wd1"], c.new(c.R, _LGF_LD), tB=True, bias=c.tw["bd1"])
+
+
+def _edge_weights(S: List[_RoundState]) -> None:
+    """ef per edge row; for pair rows ef_ij + ef_ji (self-loop rows not doubled: the typed backward works with
+    dfeat = the pair gather of d(H^T feat), which carries the self-loop's 2).  Its leading dimension is padded to a
+    multiple of 4, zero-filled: the GEMMs reading ef stay on the vector path."""
+    for c in S:
+        c.ef = c.pool.take(c.R, c.Kp)
+        with torch.cuda.device(c.x.device):
+            check(load().gn_gumbel_ef_f32(addr(c.dist), addr(c.lgf), addr(c.ef), c.R, c.K, _LGF_LD, c.N if c.sym else 0,
+                                          1.0, c.Kp, stream_handle()), "gn_gumbel_ef_f32")
+        c.def_ = c.pool.take(c.R, c.K)
+
+
+def _edge2node_backward(S: List[_RoundState], gb: GemmBatch) -> None:
+    """Back through edge2node + the closing MLP of the modules whose round output is used: def_ and the ori half of dx."""
+    for c, eo in zip(S, ops.agg_gather_grouped([(c.x, c.H, c.sym, c.masks) for c in S])):
+        c.eo2 = eo.view(c.R, D)
+    for c in _each(S, gb):
+        c.Hc = gb.add(c.eo2, c.tw["W1cat"], c.new(c.R, c.K * _HID), tB=True, bias=c.tw["b1cat"], relu=True)
+    # cat(H^T feat, ori) / N and the closing MLP's hidden layer were kept by the forward (the fused scatter+MLP kernel
+    # writes them on request: agg2, y1), so feat is not re-computed
+    for c in _each(S, gb):
+        c.dy1 = gb.add(c.g_y, _w(c.e1), c.new(c.BN, 128), mask=c.y1)
+    for c in _each(S, gb):
+        c.da = gb.add(c.dy1, _w(c.e0)[:, :D], c.new(c.BN, D), alpha=1.0 / c.N)     # d(H^T feat)
+        c.dx = gb.add(c.dy1, _w(c.e0)[:, D:], c.new(c.BN, D), alpha=1.0 / c.N)     # ori half of the cat
+    dfeats = ops.agg_gather_grouped([(c.da.view(c.B, c.N, D), c.H, c.sym, c.masks) for c in S])    # adjoint of H^T feat
+    for c, df in zip(S, dfeats):
+        c.dfeat = df.view(c.R, D)
+    for c in _each(S, gb):
+        c.T = gb.add(c.dfeat, c.tw["W2cat"], c.new(c.R, c.K * _HID))
+    for c in S:
+        with torch.cuda.device(c.x.device):
+            check(load().gn_typed_bwd_f32(addr(c.T), addr(c.Hc), addr(c.ef), c.Kp, addr(c.dfeat), addr(c.tw["b2mat"]),
+                                          addr(c.def_), c.R, c.K, _HID, stream_handle()), "gn_typed_bwd_f32")
+    # (pair rows: the self-loop's eo = 2 ori, and the pair-form scatter below weighs every row once)
+    # (K = K_types*128 is long and the output has few tiles: split K over workgroups, atomic accumulate)
+    for c in _each(S, gb):
+        c.deo = gb.add(c.T, c.tw["W1cat"], c.pool.take(c.R, D), accum=True,
+                       rs=_pair_row_weights(c.B, c.N, c.x.device) if c.sym else None)
+    # eo = H ori  ->  d ori += H^T d eo  (the scatter kernel with divisor 1; its ori half is unused)
+    scs = ops.agg_scatter_grouped([(c.deo.view(c.B, c.E, D), c.H, c.x, c.sym, c.masks) for c in S], 1.0)
+    for c, sc in zip(S, scs):
+        axpby(c.dx, sc.view(c.BN, 2 * D)[:, :D], 1.0, 1.0)
+
+
+def _edge2node_weight_grads(S: List[_RoundState], gb: GemmBatch, grads: dict) -> None:
+    """The closing MLP's and the K typed MLPs' gradients of the live modules: one grouped launch."""
+    for c in _each(S, gb):
+        K, pool = c.K, c.pool
+        _wgrad(gb, grads, pool, c.e1, c.g_y, c.y1)
+        _wgrad(gb, grads, pool, c.e0, c.dy1, c.agg2)
+        gW1, gb1 = pool.take(K * _HID, D), pool.take(K * _HID)
+        gb.add(c.T, c.eo2, gW1, tA=True, accum=True, colsum=gb1)
+        gb2 = gb.add(c.ef, c.dfeat, pool.take(c.Kp, D), tA=True, accum=True)     # rows >= K stay zero
+        for k, m in enumerate(c.agg.agg_mlp):
+            l0, l1 = m.layers
+            grads[l0.weight], grads[l0.bias] = gW1[k * _HID:(k + 1) * _HID], gb1[k * _HID:(k + 1) * _HID]
+            grads[l1.bias] = gb2[k]
+            # dW2_k = sum_r ef[r,k] dfeat[r] (x) h_k[r]
+            # (as (ef_k h_k)^T dfeat written transposed: 128-row tiles instead of half-empty 64-row ones)
+            grads[l1.weight] = gb.add(c.Hc[:, k * _HID:(k + 1) * _HID], c.dfeat, pool.take(D, _HID), tA=True,
+                                      accum=True, rs=c.ef[:, k], tC=True)
+
+
+def _edge_mlp_backward(S: List[_RoundState], gb: GemmBatch) -> None:
+    """Back through the Gumbel softmax (one grouped launch for all modules: these launches take ~14 us whatever their
+    size) and the edge MLP: def_, g_d -> dedges."""
+    arr = (_lib.GumbelBwdGroup * len(S))()
+    for i, c in enumerate(S):
+        c.dlgf = c.new(c.R, _LGF_LD)
+        arr[i] = _lib.GumbelBwdGroup(dist=c.dist.data_ptr(), lgf=c.lgf.data_ptr(), def_=c.def_.data_ptr(),
+                                     gdist=addr(c.g_d), dlgf=c.dlgf.data_ptr(), rows=c.R, K=c.K,
+                                     sym_N=c.N if c.sym else 0)
+    with torch.cuda.device(S[0].x.device):
+        check(load().gn_gumbel_bwd_grouped_f32(arr, len(S), _LGF_LD, _GUMBEL_TAU, stream_handle()),
+              "gn_gumbel_bwd_grouped_f32")
+    for c in _each(S, gb):
+        c.dd1 = gb.add(c.dlgf, c.tw["Wd1"], c.new(c.R, 256), mask=c.dh1)
+    for c in _each(S, gb):
+        c.dz = gb.add(c.dd1, c.tw["Wd0"], c.new(c.R, D))
+    for c in _each(S, gb):
+        c.dz1 = gb.add(c.dz, _w(c.i[1]), c.new(c.R, 128), mask=c.z1)
+    for c in _each(S, gb):
+        c.dedges = gb.add(c.dz1, _w(c.i[0]), c.new(c.R, D))
+
+
+def _pooling_backward(S: List[_RoundState], gb: GemmBatch, grads: dict, grouped: bool) -> None:
+    """Back through the attention-weighted pooling and the node MLP: dedges -> dx (added to the ori half where the
+    module is live), with the gradients of attention layer 1 out of the node->edge kernel."""
+    for c in S:
+        c.dxp, c.dpq = c.pool.take(c.BN, D), c.pool.take(c.BN, D)
+        grads[c.a1.weight], grads[c.a1.bias] = c.pool.take(1, 32), c.pool.take(1)
+    with torch.cuda.device(S[0].x.device):
+        if grouped:
+            # every module in one launch (blockIdx.y = module): the pairwise module's 88 us and the hyper modules'
+            # 24-41 us side by side instead of end to end
+            arr = (_lib.N2EBwdGroup * len(S))()
+            for i, c in enumerate(S):
+                arr[i] = _lib.N2EBwdGroup(xp=c.xp.data_ptr(), pq=c.pq.data_ptr(), H=addr(c.H), w2=c.w2.data_ptr(),
+                                          b2=c.b2.data_ptr(), dedges=c.dedges.data_ptr(), dxp=c.dxp.data_ptr(),
+                                          dpq=c.dpq.data_ptr(), dw2=grads[c.a1.weight].data_ptr(),
+                                          db2=grads[c.a1.bias].data_ptr(), E=c.E, sym=int(c.sym))
+            check(load().gn_node2edge_bwd_grouped_f32(arr, len(S), S[0].B, S[0].N, stream_handle()),
+                  "gn_node2edge_bwd_grouped_f32")
+        else:
+            for c in S:
+                check(load().gn_node2edge_bwd_f32(addr(c.xp), addr(c.pq), addr(c.H), addr(c.w2), addr(c.b2),
+                                                  addr(c.dedges), addr(c.dxp), addr(c.dpq), addr(grads[c.a1.weight]),
+                                                  addr(grads[c.a1.bias]), c.B, c.N, c.E, int(c.sym), stream_handle()),
+                      "gn_node2edge_bwd_f32")
+    for c in _each(S, gb):
+        gb.add(c.dpq, c.tw["Wpq"], c.dxp, beta=1.0)
+    for c in _each(S, gb):
+        c.dx1 = gb.add(c.dxp, _w(c.s1), c.new(c.BN, 256), mask=c.x1)
+    for c in _each(S, gb):
+        if c.dx is None:
+            c.dx = gb.add(c.dx1, _w(c.s0), c.new(c.BN, D))
+        else:
+            gb.add(c.dx1, _w(c.s0), c.dx, beta=1.0)
+
+
+def _node2edge_weight_grads(S: List[_RoundState], gb: GemmBatch, grads: dict) -> None:
+    """The edge MLP's, the attention layer 0's and the node MLP's gradients of every module: one grouped launch."""
+    for c in _each(S, gb):
+        K, pool = c.K, c.pool
+        # MLP_distribution | MLP_factor: gradients of the side-by-side matrices, handed out as views
+        gWd1, gbd1 = pool.take(_LGF_LD, 256), pool.take(_LGF_LD)
+        gb.add(c.dlgf, c.dh1, gWd1, tA=True, accum=True, colsum=gbd1)
+        grads[c.d[1].weight], grads[c.f[1].weight] = gWd1[:K, :128], gWd1[K:K + 1, 128:]
+        grads[c.d[1].bias], grads[c.f[1].bias] = gbd1[:K], gbd1[K:K + 1]
+        gWd0, gbd0 = pool.take(256, D), pool.take(256)
+        gb.add(c.dd1, c.z, gWd0, tA=True, accum=True, colsum=gbd0)
+        grads[c.d[0].weight], grads[c.f[0].weight] = gWd0[:128], gWd0[128:]
+        grads[c.d[0].bias], grads[c.f[0].bias] = gbd0[:128], gbd0[128:]
+        _wgrad(gb, grads, pool, c.i[1], c.dz, c.z1)
+        _wgrad(gb, grads, pool, c.i[0], c.dz1, c.edges)
+        ga0 = pool.take(32, 2 * D)                               # the (32,128) layout of attention layer 0
+        gb.add(c.dpq[:, :32], c.xp, ga0[:, :D], tA=True, accum=True, colsum=grads.setdefault(c.a0.bias, pool.take(32)))
+        gb.add(c.dpq[:, 32:], c.xp, ga0[:, D:], tA=True, accum=True)
+        grads[c.a0.weight] = ga0
+        _wgrad(gb, grads, pool, c.s1, c.dxp, c.x1)
+        _wgrad(gb, grads, pool, c.s0, c.dx1, c.x2)
+
+
 def round_backward(traces: Sequence[ModuleTrace], j: int, g_ys: Sequence[Optional[Tensor]],
                    g_dists: Sequence[Optional[Tensor]], grads: Dict[nn.Parameter, Tensor]) -> List[Tensor]:
-    """Back through round j of several modules at once.
+    """Back through round j of several modules at once (same B and N: `run_message_passing` groups no others).
 
     g_ys[i] = gradient w.r.t. the output of round j's edge2node + MLP block (node_feat for the last round),
     g_dists[i] = gradient w.r.t. dist_j (the returned `factors` for round 0), either may be None.
     Adds the parameter gradients to `grads`, returns d x_j per module."""
-    n = len(traces)
-    W = lambda l: l.weight.detach()
-    b = lambda l: l.bias.detach()
-    D = ops.FEAT
-    S = []           # per-module state of this round
-    for t, g_y, g_d in zip(traces, g_ys, g_dists):
-        mod, x = t.mod, t.xs[j]
-        B, N, _ = x.shape
-        Hx = t.H
-        scene_fits = (4 * N * D + 64 + 16 * N) * 4 <= 150 * 1024     # gn_node2edge_bwd_f32's per-scene form
-        # The pairwise graph is symmetric: the ordered edges (i,j) and (j,i) pool the same feature and feed
-        # the same typed MLP, so (as in the forward) every per-edge stage runs on the N(N+1)/2 unordered
-        # pairs; only dist (its own Gumbel noise per ordered edge) stays ordered.
-        sym = Hx is None and scene_fits
-        if Hx is None and not sym:
-            Hx = t.__dict__.setdefault("_pair_H", None)
-            if Hx is None:
-                Hx = t._pair_H = pairwise_incidence(B, N, x.device, x.dtype)
-        E = ops.pair_count(N) if sym else Hx.shape[1]
-        K = mod.edge_types
-        (s0, s1), (a0, a1), st, agg, (e0, e1) = _round_layers(mod, j)
-        npar = t.__dict__.setdefault("_npar", {}).get(j)
-        if npar is None:
-            npar = t._npar[j] = sum(p.numel() for m in (mod.node2edge_start_mlp[j], mod.attention_mlp[j], st, agg,
-                                                        nn.ModuleList([e0, e1])) for p in m.parameters())
-        S.append(dict(mod=mod, x=x, x2=x.reshape(B * N, D), H=Hx, masks=t.masks, sym=sym, B=B, N=N, E=E, K=K, R=B * E, s0=s0, s1=s1, a0=a0, a1=a1, i=st.init_MLP.layers, d=st.MLP_distribution.layers,
-                      f=st.MLP_factor.layers, agg=agg, tw=_bwd_weights(mod, j), e0=e0, e1=e1,
-                      tail=t.tails[j], dist=t.dists[j].reshape(-1, K), g_y=None if g_y is None else g_y.reshape(B * N, -1).contiguous(),
-                      g_d=None if g_d is None else g_d.reshape(-1, K).contiguous(),
-                      pool_n=(npar + 2 * B * N * D + B * E * (2 * K + 4 + 2 * D) + 4096 + 63) // 64 * 64))
-    dev = S[0]["x"].device
+    rt = route.backward_round_route(traces[0].xs[j].shape[1], tuple(t.H is None for t in traces))
+    S = [_RoundState(t, j, rt.pair_rows, g_y, g_d) for t, g_y, g_d in zip(traces, g_ys, g_dists)]
     # one zero fill for the accumulate-by-atomics targets of every module of the round
-    arena = torch.zeros(sum(c["pool_n"] for c in S), dtype=torch.float32, device=dev)
+    dev = S[0].x.device
+    arena = torch.zeros(sum(c.pool_n for c in S), dtype=torch.float32, device=dev)
     off = 0
     for c in S:
-        c["pool"] = _Pool(c["pool_n"], dev, arena[off:off + c["pool_n"]])
-        off += c["pool_n"]
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        c.pool = _Pool(c.pool_n, dev, arena[off:off + c.pool_n])
+        off += c.pool_n
     gb = GemmBatch()
-
-    def stage(fn):
-        for c in S:
-            fn(c)
-        gb.run()
-
     with torch.no_grad():
-        # ---------------- what the fused forward kept (training mode writes these on request) ----------------
-        # The forward runs the pairwise module on unordered pairs; if this backward has to use ordered edge rows
-        # (N too large for the per-scene node2edge backward), its edge-row activations are re-computed instead.
-        kept = all(c["sym"] or c["H"] is not None and tr.H is not None for c, tr in zip(S, traces))
-        for c, tr in zip(S, traces):
-            c["w2"], c["b2"] = W(c["a1"])[0], b(c["a1"])
-            if kept:
-                a, e = tr.n2e[j], tr.estage[j]
-                c.update(x1=a["x1"], xp=a["xp"].view(-1, D), pq=a["pq"].view(-1, D), edges=a["edges"].view(c["R"], D),
-                         z1=e["z1"], z=e["z"], dh1=e["dh1"], lgf=e["lgf"])
-        if not kept:
-            stage(lambda c: c.update(x1=gb.add(c["x2"], W(c["s0"]), new(c["B"] * c["N"], 256), tB=True, bias=b(c["s0"]),
-                                               relu=True)))
-            stage(lambda c: c.update(xp=gb.add(c["x1"], W(c["s1"]), new(c["B"] * c["N"], D), tB=True, bias=b(c["s1"]))))
-            # attention layer 0 on cat(x'_n, e0_e), split by linearity: P = W[:, :64] x' + b, Qn = W[:, 64:] x'
-            stage(lambda c: c.update(pq=gb.add(c["xp"], c["tw"]["Wpq"], new(c["B"] * c["N"], D), tB=True, bias=c["tw"]["bpq"])))
-            edges = ops.node2edge_grouped([(c["xp"].view(c["B"], c["N"], D), c["pq"].view(c["B"], c["N"], D), c["H"], c["w2"],
-                                            c["b2"], c["sym"]) for c in S])
-            for c, e in zip(S, edges):
-                c["edges"] = e.view(c["R"], D)
-            stage(lambda c: c.update(z1=gb.add(c["edges"], W(c["i"][0]), new(c["R"], 128), tB=True, bias=b(c["i"][0]),
-                                               relu=True)))
-            stage(lambda c: c.update(z=gb.add(c["z1"], W(c["i"][1]), new(c["R"], D), tB=True, bias=b(c["i"][1]))))
-            # hidden layers of MLP_distribution | MLP_factor side by side, then (logits | factor pre-activation)
-            stage(lambda c: c.update(dh1=gb.add(c["z"], c["tw"]["Wd0"], new(c["R"], 256), tB=True, bias=c["tw"]["bd0"],
-                                                relu=True)))
-            stage(lambda c: c.update(lgf=gb.add(c["dh1"], c["tw"]["Wd1"], new(c["R"], _LGF_LD), tB=True, bias=c["tw"]["bd1"])))
-        for c in S:
-            # ef per edge row; for pair rows ef_ij + ef_ji (self-loop rows not doubled: the typed backward below
-            # works with dfeat = the pair gather of d(H^T feat), which carries the self-loop's 2)
-            # (leading dimension padded to a multiple of 4, zero-filled: the GEMMs reading ef stay on the vector path)
-            c["Kp"] = (c["K"] + 3) // 4 * 4
-            c["ef"] = c["pool"].take(c["R"], c["Kp"])
-            with torch.cuda.device(dev):
-                check(load().gn_gumbel_ef_f32(addr(c["dist"]), addr(c["lgf"]), addr(c["ef"]), c["R"], c["K"], _LGF_LD,
-                                              c["N"] if c["sym"] else 0, 1.0, c["Kp"], stream_handle()), "gn_gumbel_ef_f32")
-            c["def"] = c["pool"].take(c["R"], c["K"])
-            c["dx"] = None
-
-        live = [c for c in S if c["g_y"] is not None]
+        _forward_activations(S, gb, traces, j, rt.kept)
+        _edge_weights(S)
+        live = [c for c in S if c.g_y is not None]
         if live:
-            S_all, S = S, live
-            eos = ops.agg_gather_grouped([(c["x"], c["H"], c["sym"], c["masks"]) for c in S])
-            for c, eo in zip(S, eos):
-                c["eo"], c["eo2"] = eo, eo.view(c["R"], D)
-            stage(lambda c: c.update(Hc=gb.add(c["eo2"], c["tw"]["W1cat"], new(c["R"], c["K"] * _HID), tB=True,
-                                               bias=c["tw"]["b1cat"], relu=True)))
-            # cat(H^T feat, ori) / N and the closing MLP's hidden layer were kept by the forward (the fused
-            # scatter+MLP kernel writes them on request), so feat is not re-computed
-            for c in S:
-                c["agg2"], c["y1"] = c["tail"]["x"], c["tail"]["hid"]
-            # ---------------- back through MLP(edge2node) ----------------
-            stage(lambda c: c.update(dy1=gb.add(c["g_y"], W(c["e1"]), new(c["B"] * c["N"], 128), mask=c["y1"])))
-
-            def dagg_stage(c):
-                inv = 1.0 / c["N"]
-                c["da"] = gb.add(c["dy1"], W(c["e0"])[:, :D], new(c["B"] * c["N"], D), alpha=inv)   # d(H^T feat)
-                c["dx"] = gb.add(c["dy1"], W(c["e0"])[:, D:], new(c["B"] * c["N"], D), alpha=inv)   # ori half of the cat
-            stage(dagg_stage)
-            dfeats = ops.agg_gather_grouped([(c["da"].view(c["B"], c["N"], D), c["H"], c["sym"], c["masks"])
-                                             for c in S])                                      # adjoint of H^T feat
-            for c, df in zip(S, dfeats):
-                c["dfeat"] = df.view(c["R"], D)
-            stage(lambda c: c.update(T=gb.add(c["dfeat"], c["tw"]["W2cat"], new(c["R"], c["K"] * _HID))))
-            for c in S:
-                with torch.cuda.device(dev):
-                    check(load().gn_typed_bwd_f32(addr(c["T"]), addr(c["Hc"]), addr(c["ef"]), c["Kp"], addr(c["dfeat"]),
-                                                  addr(c["tw"]["b2mat"]), addr(c["def"]), c["R"], c["K"], _HID, stream_handle()),
-                          "gn_typed_bwd_f32")
-            # (pair rows: the self-loop's eo = 2 ori, and the pair-form scatter below weighs every row once)
-            # (K = K_types*128 is long and the output has few tiles: split K over workgroups, atomic accumulate)
-            stage(lambda c: c.update(deo=gb.add(c["T"], c["tw"]["W1cat"], c["pool"].take(c["R"], D), accum=True,
-                                                rs=_pair_row_weights(c["B"], c["N"], dev) if c["sym"] else None)))
-            # eo = H ori  ->  d ori += H^T d eo  (the scatter kernel with divisor 1; its ori half is unused)
-            scs = ops.agg_scatter_grouped([(c["deo"].view(c["B"], c["E"], D), c["H"], c["x"], c["sym"], c["masks"])
-                                           for c in S], 1.0)
-            for c, sc in zip(S, scs):
-                axpby(c["dx"], sc.view(c["B"] * c["N"], 2 * D)[:, :D], 1.0, 1.0)
-
-            def e2n_weight_grads(c):
-                K, pool = c["K"], c["pool"]
-                for lin, dY, X in ((c["e1"], c["g_y"], c["y1"]), (c["e0"], c["dy1"], c["agg2"])):
-                    grads[lin.weight] = gb.add(dY, X, pool.take(*lin.weight.shape), tA=True, accum=True,
-                                               colsum=grads.setdefault(lin.bias, pool.take(*lin.bias.shape)))
-                gW1 = gb.add(c["T"], c["eo2"], pool.take(K * _HID, D), tA=True, accum=True,
-                             colsum=c.setdefault("gb1", pool.take(K * _HID)))
-                gb2 = gb.add(c["ef"], c["dfeat"], pool.take(c["Kp"], D), tA=True, accum=True)     # rows >= K stay zero
-                for k, m in enumerate(c["agg"].agg_mlp):
-                    l0, l1 = m.layers
-                    grads[l0.weight], grads[l0.bias] = gW1[k * _HID:(k + 1) * _HID], c["gb1"][k * _HID:(k + 1) * _HID]
-                    grads[l1.bias] = gb2[k]
-                    # dW2_k = sum_r ef[r,k] dfeat[r] (x) h_k[r]
-                    # (as (ef_k h_k)^T dfeat written transposed: 128-row tiles instead of half-empty 64-row ones)
-                    grads[l1.weight] = gb.add(c["Hc"][:, k * _HID:(k + 1) * _HID], c["dfeat"], pool.take(D, _HID), tA=True,
-                                              accum=True, rs=c["ef"][:, k], tC=True)
-            stage(e2n_weight_grads)
-            S = S_all
-
-        # ---------------- back through the edge MLP + Gumbel softmax ----------------
-        # (one grouped launch for all modules: these launches take ~14 us whatever their size)
-        arr = (_lib.GumbelBwdGroup * len(S))()
-        for i, c in enumerate(S):
-            c["dlgf"] = new(c["R"], _LGF_LD)
-            arr[i] = _lib.GumbelBwdGroup(dist=c["dist"].data_ptr(), lgf=c["lgf"].data_ptr(), def_=c["def"].data_ptr(),
-                                         gdist=addr(c["g_d"]), dlgf=c["dlgf"].data_ptr(), rows=c["R"], K=c["K"],
-                                         sym_N=c["N"] if c["sym"] else 0)
-        with torch.cuda.device(dev):
-            check(load().gn_gumbel_bwd_grouped_f32(arr, len(S), _LGF_LD, _TAU, stream_handle()), "gn_gumbel_bwd_grouped_f32")
-
-        stage(lambda c: c.update(dd1=gb.add(c["dlgf"], c["tw"]["Wd1"], new(c["R"], 256), mask=c["dh1"])))
-        stage(lambda c: c.update(dz=gb.add(c["dd1"], c["tw"]["Wd0"], new(c["R"], D))))
-        stage(lambda c: c.update(dz1=gb.add(c["dz"], W(c["i"][1]), new(c["R"], 128), mask=c["z1"])))
-        stage(lambda c: c.update(dedges=gb.add(c["dz1"], W(c["i"][0]), new(c["R"], D))))
-        # ---------------- back through the attention-weighted pooling ----------------
-        for c in S:
-            pool, BN = c["pool"], c["B"] * c["N"]
-            c["dxp"], c["dpq"] = pool.take(BN, D), pool.take(BN, D)
-            grads[c["a1"].weight], grads[c["a1"].bias] = pool.take(1, 32), pool.take(1)
-        N0 = S[0]["N"]
-        scene_form = (4 * N0 * D + 64 + 16 * N0) * 4 <= 150 * 1024 and all(c["B"] == S[0]["B"] and c["N"] == N0 for c in S)
-        if scene_form:
-            # every module in one launch (blockIdx.y = module): the pairwise module's 88 us and the hyper modules' 24-41 us
-            # side by side instead of end to end
-            arr = (_lib.N2EBwdGroup * len(S))()
-            for i, c in enumerate(S):
-                arr[i] = _lib.N2EBwdGroup(xp=c["xp"].data_ptr(), pq=c["pq"].data_ptr(), H=addr(c["H"]), w2=c["w2"].data_ptr(),
-                                          b2=c["b2"].data_ptr(), dedges=c["dedges"].data_ptr(), dxp=c["dxp"].data_ptr(),
-                                          dpq=c["dpq"].data_ptr(), dw2=grads[c["a1"].weight].data_ptr(),
-                                          db2=grads[c["a1"].bias].data_ptr(), E=c["E"], sym=int(c["sym"]))
-            with torch.cuda.device(dev):
-                check(load().gn_node2edge_bwd_grouped_f32(arr, len(S), S[0]["B"], N0, stream_handle()),
-                      "gn_node2edge_bwd_grouped_f32")
-        else:
-            for c in S:
-                with torch.cuda.device(dev):
-                    check(load().gn_node2edge_bwd_f32(addr(c["xp"]), addr(c["pq"]), addr(c["H"]), addr(c["w2"]),
-                                                      addr(c["b2"]), addr(c["dedges"]), addr(c["dxp"]), addr(c["dpq"]),
-                                                      addr(grads[c["a1"].weight]), addr(grads[c["a1"].bias]), c["B"],
-                                                      c["N"], c["E"], int(c["sym"]), stream_handle()),
-                          "gn_node2edge_bwd_f32")
-        stage(lambda c: gb.add(c["dpq"], c["tw"]["Wpq"], c["dxp"], beta=1.0))
-        stage(lambda c: c.update(dx1=gb.add(c["dxp"], W(c["s1"]), new(c["B"] * c["N"], 256), mask=c["x1"])))
-
-        def dx_stage(c):
-            if c["dx"] is None:
-                c["dx"] = gb.add(c["dx1"], W(c["s0"]), new(c["B"] * c["N"], D))
-            else:
-                gb.add(c["dx1"], W(c["s0"]), c["dx"], beta=1.0)
-        stage(dx_stage)
-
-        def n2e_weight_grads(c):
-            K, pool = c["K"], c["pool"]
-
-            def wgrad(lin, dY, X):
-                grads[lin.weight] = gb.add(dY, X, pool.take(*lin.weight.shape), tA=True, accum=True,
-                                           colsum=grads.setdefault(lin.bias, pool.take(*lin.bias.shape)))
-            # MLP_distribution | MLP_factor: gradients of the side-by-side matrices, handed out as views
-            gWd1, gbd1 = pool.take(_LGF_LD, 256), pool.take(_LGF_LD)
-            gb.add(c["dlgf"], c["dh1"], gWd1, tA=True, accum=True, colsum=gbd1)
-            grads[c["d"][1].weight], grads[c["f"][1].weight] = gWd1[:K, :128], gWd1[K:K + 1, 128:]
-            grads[c["d"][1].bias], grads[c["f"][1].bias] = gbd1[:K], gbd1[K:K + 1]
-            gWd0, gbd0 = pool.take(256, D), pool.take(256)
-            gb.add(c["dd1"], c["z"], gWd0, tA=True, accum=True, colsum=gbd0)
-            grads[c["d"][0].weight], grads[c["f"][0].weight] = gWd0[:128], gWd0[128:]
-            grads[c["d"][0].bias], grads[c["f"][0].bias] = gbd0[:128], gbd0[128:]
-            wgrad(c["i"][1], c["dz"], c["z1"])
-            wgrad(c["i"][0], c["dz1"], c["edges"])
-            ga0 = pool.take(32, 2 * D)                               # the (32,128) layout of attention layer 0
-            gb.add(c["dpq"][:, :32], c["xp"], ga0[:, :D], tA=True, accum=True,
-                   colsum=grads.setdefault(c["a0"].bias, pool.take(32)))
-            gb.add(c["dpq"][:, 32:], c["xp"], ga0[:, D:], tA=True, accum=True)
-            grads[c["a0"].weight] = ga0
-            wgrad(c["s1"], c["dxp"], c["x1"])
-            wgrad(c["s0"], c["dx1"], c["x2"])
-        stage(n2e_weight_grads)
-    return [c["dx"].view(c["B"], c["N"], D) for c in S]
+            _edge2node_backward(live, gb)
+            _edge2node_weight_grads(live, gb, grads)
+        _edge_mlp_backward(S, gb)
+        _pooling_backward(S, gb, grads, rt.n2e_grouped)
+        _node2edge_weight_grads(S, gb, grads)
+    return [c.dx.view(c.B, c.N, D) for c in S]
 
 
 def modules_backward(traces: Sequence[ModuleTrace], g_nfs: Sequence[Optional[Tensor]],

@@ -854,6 +854,14 @@ extern "C" int gn_gumbel_bwd_f32(const float* dist, const float* lgf, const floa
   return gn_check_launch();
 }
 
+// The per-scene form of the node->edge backward: one workgroup per scene while the scene's node rows (x', pq and their
+// gradients), the workgroup's 64 sums and four N-vectors per wave fit this budget (N <= 140; route.N2E_BWD_SCENE_MAX_N
+// states the same limit for the Python side).
+constexpr size_t kN2EBwdSceneBudget = 150 * 1024;
+static size_t n2e_bwd_scene_lds(int N) {
+  return ((size_t)4 * N * GN_FEAT + 64 + (size_t)(kB / 64) * 4 * N) * sizeof(float);
+}
+
 extern "C" int gn_node2edge_bwd_f32(const float* xp, const float* pq, const float* H, const float* w2, const float* b2,
                                     const float* dedges, float* dxp, float* dpq, float* dw2, float* db2, int B, int N,
                                     int E, int sym, gn_stream_t stream) {
@@ -863,9 +871,8 @@ extern "C" int gn_node2edge_bwd_f32(const float* xp, const float* pq, const floa
   if (B <= 0 || N <= 0 || E <= 0) return GN_ERR_SHAPE;
   if (sym && H != nullptr) return GN_ERR_SHAPE;
   if (H == nullptr && E != (sym ? gn_pair_count(N) : N * N)) return GN_ERR_SHAPE;
-  // one workgroup per scene while the scene's node rows (x', pq and their gradients) fit in LDS
-  const size_t scene_lds = ((size_t)4 * N * GN_FEAT + 64 + (size_t)(kB / 64) * 4 * N) * sizeof(float);
-  if (scene_lds <= 150 * 1024) {
+  const size_t scene_lds = n2e_bwd_scene_lds(N);
+  if (scene_lds <= kN2EBwdSceneBudget) {
     if (scene_lds > 64 * 1024) gn_allow_big_lds(node2edge_bwd_scene_kernel);
     hipLaunchKernelGGL(node2edge_bwd_scene_kernel, dim3((unsigned)B), dim3(kB), scene_lds, (hipStream_t)stream, xp, pq,
                        H, w2, b2, dedges, dxp, dpq, dw2, db2, N, E, sym);
@@ -905,8 +912,8 @@ extern "C" int gn_node2edge_bwd_grouped_f32(const gn_n2e_bwd_group_t* groups, in
                                             gn_stream_t stream) {
   if (groups == nullptr) return GN_ERR_NULL;
   if (n_groups < 1 || n_groups > GN_MAX_GROUPS || B <= 0 || N <= 0) return GN_ERR_SHAPE;
-  const size_t scene_lds = ((size_t)4 * N * GN_FEAT + 64 + (size_t)(kB / 64) * 4 * N) * sizeof(float);
-  if (scene_lds > 150 * 1024) return GN_ERR_LDS;      // (the per-scene form only: larger N goes module by module)
+  const size_t scene_lds = n2e_bwd_scene_lds(N);
+  if (scene_lds > kN2EBwdSceneBudget) return GN_ERR_LDS;      // (the per-scene form only: larger N goes module by module)
   N2EBwdTable T{};
   for (int g = 0; g < n_groups; ++g) {
     const gn_n2e_bwd_group_t& G = groups[g];

@@ -1,6 +1,7 @@
 """The route of a message-passing forward: which launches it consists of and what each is asked to fuse, decided in one
 pure function that `MS_HGNN_batch.run_message_passing` follows; and the graph stage before it — how f becomes the
-incidences of every scale — decided in another, `graph_stage_route`, that `multiscale.build_graphs` follows.
+incidences of every scale — decided in another, `graph_stage_route`, that `multiscale.build_graphs` follows; and the
+forms of a backward round, `backward_round_route`, that `backward.round_backward` follows.
 
 A leaf module: no torch, no library, no environment.  The launchers' own decisions (work shapes, kernels, whether an
 aggregation launch takes the closing stage it was asked for) stay in their plan functions ("Launch plan").
@@ -17,6 +18,9 @@ NODE_FORM_MAX_N = 16        # node form of the pair form (fp32 storage)
 NODE_FORM_MAX_K = 12
 SCENE_FORM_MAX_N = 64       # the twins' scene form
 MASK_MAX_N = 64             # one 64-bit word per hyperedge / node
+# The per-scene node->edge backward (gn_node2edge_bwd_f32 / _grouped_f32) holds (4*N*64 + 64 + 16*N) floats of a scene in
+# LDS within its 150 KiB budget: 152 576 B at N = 140, 153 664 B at N = 141
+N2E_BWD_SCENE_MAX_N = 140
 
 # The engine's own limits.  Beyond these N the stand-alone gather / scatter kernels (LDS-tiled, high occupancy) beat a
 # per-lane scan of H rows / a per-lane gather of N feature rows in the prologue of an MFMA kernel (latency-bound at 1-2
@@ -186,3 +190,22 @@ def message_passing_route(N: int, modules: Tuple[Tuple[bool, int], ...], *, twin
                  scatter=which(lambda m: m.closing_input == SCATTER),
                  masks=knobs.masked and masks_in_range(N),
                  ask_closing=closing_asked and not training and not twin and N <= _FUSED_SCATTER_MAX_N)
+
+
+@dataclass(frozen=True)
+class BackwardRound:
+    pair_rows: bool         # a pairwise module walks its N(N+1)/2 unordered-pair rows (`sym`), as its forward did; else
+                            # ordered rows and the explicit (B, N*N, N) incidence
+    kept: bool              # every module reads the activations the forward kept; else every module re-computes them
+    n2e_grouped: bool       # one gn_node2edge_bwd_grouped_f32 for all modules, else one gn_node2edge_bwd_f32 per module
+
+
+@functools.lru_cache(maxsize=None)
+def backward_round_route(N: int, pairwise: Tuple[bool, ...]) -> BackwardRound:
+    """The route of one backward round over N agents (`backward.round_backward`).  pairwise: per module of the round.
+    All of it hangs on whether a scene fits the per-scene node->edge backward.  Where it does not, a pairwise module
+    needs ordered edge rows — the general kernel reads an incidence, and the pairwise one exists only per ordered edge —
+    while its forward kept activations per unordered pair: they are re-computed, and since the re-computation is one
+    grouped launch per stage, for every module of the round."""
+    fits = N <= N2E_BWD_SCENE_MAX_N
+    return BackwardRound(pair_rows=fits, kept=fits or not any(pairwise), n2e_grouped=fits)
