@@ -20,7 +20,9 @@
 //          folded into a running maximum (v_max3_f32, 8 instructions per hidden tile), the workgroup votes at the end
 //          of the chain, and a workgroup that saw |operand| > 65000 (or whose weight image is flagged: a weight out of
 //          range) REPEATS its rows on the bf16x6 path of the same kernel (P = 3 below, full fp32 exponent range) and
-//          overwrites what it stored — never a wrong result, and no cost on data within range.  Operands below 2^-14
+//          overwrites what it stored — never a wrong result, and no cost on data within range.  The image's flag is
+//          that of the parameter version it was last split from: every split clears the word before it may raise it,
+//          so an image returns to the fp16 path with the first refresh after its weights are back in range.  Operands below 2^-14
 //          lose their low part (fp16 subnormals): an ABSOLUTE error of 2^-25 per such operand, far below the 1e-5 gate.
 //   P = 1, T = __bf16 — the bf16 twins (BASELINE config 4): activations stored in HBM as bf16,
 //          weights rounded once to bf16, one MFMA per k = 16, fp32 accumulation, bias / ReLU / softmax in fp32;
@@ -166,8 +168,8 @@ __device__ __forceinline__ void run_with_fallback(F body) {
     body(std::integral_constant<int, P>{}, ovf);
   }
 }
-// The flag word behind an fp16 weight image of `substeps` sub-steps (gn_split_f16_f32 sets it when a weight does not
-// fit fp16): nonzero sends the workgroup to the bf16x6 path.
+// The flag word behind an fp16 weight image of `substeps` sub-steps (gn_split_bf16_f32 with parts = 2 clears it and
+// raises it when a weight does not fit fp16): nonzero sends the workgroup to the bf16x6 path.
 // (A scalar load: the word sits in an SGPR until the vote.  In a vector register it is live across the whole chain, and
 // at three waves per SIMD the allocator spilled exactly that register — with a full wait in the prologue.)
 __device__ __forceinline__ int image_flag(const void* image, int substeps) {

@@ -82,6 +82,21 @@ __global__ __launch_bounds__(256) void split_bf16_batch_kernel(const gn_split_jo
   const gn_split_job_t J = jobs[blockIdx.y];
   split_bf16_image(J.packed, reinterpret_cast<__bf16*>(J.out), J.n_tiles, parts);
 }
+// The flag word behind a two-part fp16 image of n_tiles tiles.
+__device__ __forceinline__ int* image_flag_word(void* out, int n_tiles) {
+  return reinterpret_cast<int*>(reinterpret_cast<__bf16*>(out) + (size_t)n_tiles * 2 * 2 * 64 * 8);
+}
+// Clears the flag words of the images a split is about to rebuild, one thread per image, in a launch of its own AHEAD of
+// the split on the same stream: the split's blocks only ever raise the word (atomicOr), so none of them can clear it
+// without racing the others, and a word that is never cleared keeps an image on the bf16x6 path for good after one
+// parameter version with a weight out of range.  jobs == nullptr: the one image (out, n_tiles).
+__global__ __launch_bounds__(64) void clear_image_flags_kernel(const gn_split_job_t* __restrict__ jobs, int n_jobs, void* out,
+                                                              int n_tiles) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n_jobs) return;
+  if (jobs != nullptr) *image_flag_word(jobs[i].out, jobs[i].n_tiles) = 0;
+  else *image_flag_word(out, n_tiles) = 0;
+}
 __device__ __forceinline__ void split_bf16_image(const float* __restrict__ packed, __bf16* __restrict__ out, int n_tiles,
                                                  int parts) {
   const long long total = (long long)n_tiles * 2 * 64 * 8;
@@ -92,12 +107,13 @@ __device__ __forceinline__ void split_bf16_image(const float* __restrict__ packe
     __bf16* o = out + ((tile * 2 + half) * parts * 64 + lane) * 8 + j;
     if (parts == 2) {
       // f16x3 image: x = hi + lo, two fp16 parts (the remainder is exact in fp32).  A weight that does not fit fp16
-      // raises the flag word behind the image: its workgroups then take the bf16x6 path (gn_mlp_bf16.hpp).
+      // raises the flag word behind the image (cleared ahead of this launch: clear_image_flags_kernel): its workgroups
+      // then take the bf16x6 path (gn_mlp_bf16.hpp).
       const _Float16 hi = (_Float16)x;
       const _Float16 lo = (_Float16)(x - (float)hi);
       reinterpret_cast<_Float16*>(o)[0] = hi;
       reinterpret_cast<_Float16*>(o)[64 * 8] = lo;
-      if (!(fabsf(x) <= 65000.f)) atomicOr(reinterpret_cast<int*>(out + (size_t)n_tiles * 2 * 2 * 64 * 8), 1);
+      if (!(fabsf(x) <= 65000.f)) atomicOr(image_flag_word(out, n_tiles), 1);
       continue;
     }
     __bf16 p1, p2, p3;
@@ -784,6 +800,8 @@ extern "C" int gn_split_bf16_f32(const float* packed, void* out, int n_tiles, in
   if (n_tiles < 1 || parts < 1 || parts > 3) return GN_ERR_SHAPE;
   GN_REQUIRE_ALIGNED(out);
   const long long total = (long long)n_tiles * 1024;
+  if (parts == 2)
+    hipLaunchKernelGGL(clear_image_flags_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, nullptr, 1, out, n_tiles);
   hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048)),
                      dim3(256), 0, (hipStream_t)stream, packed, reinterpret_cast<__bf16*>(out), n_tiles, parts);
   return gn_check_launch();
@@ -795,6 +813,9 @@ extern "C" int gn_split_bf16_batch_f32(const gn_split_job_t* jobs_dev, int n_job
   if (n_jobs < 1 || n_jobs > 65535 || max_tiles < 1 || parts < 1 || parts > 3) return GN_ERR_SHAPE;
   const long long total = (long long)max_tiles * 1024;
   const unsigned gx = (unsigned)((total + 255) / 256 < 256 ? (total + 255) / 256 : 256);
+  if (parts == 2)
+    hipLaunchKernelGGL(clear_image_flags_kernel, dim3((unsigned)((n_jobs + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
+                       jobs_dev, n_jobs, nullptr, 0);
   hipLaunchKernelGGL(split_bf16_batch_kernel, dim3(gx, n_jobs), dim3(256), 0, (hipStream_t)stream, jobs_dev, parts);
   return gn_check_launch();
 }

@@ -128,7 +128,7 @@ class XImages:
         src = self.src[name]
         if hit is None:
             n = src.numel() // 1024 * 2 * parts * 64 * 8
-            # (two fp16 parts: + the 16-byte flag word behind the image, zero-initialised once)
+            # (two fp16 parts: + the 16-byte flag word behind the image; every split clears it before it may raise it)
             buf = (torch.zeros(n + 8, dtype=torch.int16, device=src.device) if parts == 2 else
                    torch.empty(n, dtype=torch.int16, device=src.device))
             hit = self.img[(name, parts)] = [buf, -1]

@@ -35,7 +35,7 @@
  *     narrow exponent, so a group that carries `Wh` MUST also carry the corresponding `Wx` image: a workgroup that
  *     meets an operand beyond 65000 in magnitude (or a flagged weight image) repeats its rows on the bf16 path inside
  *     the same launch.  Either all groups of a launch carry `Wh` or none.  The image is followed by a 16-byte FLAG
- *     word the caller zero-initialises once (the split raises it when a weight does not fit fp16).
+ *     word that belongs to the split: every split clears it, then raises it when a weight does not fit fp16.
  *   - Order of the tiles in every bf16-/fp16-core image of a LAYER PAIR  out += W1 act(W0 x)  ("pipeline order", the
  *     order the kernels consume them; weights.pipeline_order): with A_t = the first-layer tiles [W0(t, in 0..IT-1)] that
  *     produce hidden tile t and B_t = the second-layer tiles [W1(0..OT-1, t)] that consume it:
@@ -511,7 +511,8 @@ int gn_agg_mlp_bf16(const gn_agg_group_t* groups, int n_groups, gn_stream_t stre
  * order in which a lane's accumulator registers hold those features.  parts = 3: x = p1 + p2 + p3 (8 mantissa
  * bits each, round to nearest: the fp32-accurate path); parts = 1: p1 = x rounded to bf16 (the bf16 twins);
  * parts = 2: TWO fp16 parts x = hi + lo (the `Wh` images of the f16x3 path) — `out` then holds 16 more bytes behind
- * the image, the FLAG word (zero-initialised by the caller once), which the split raises when |x| > 65000. */
+ * the image, the FLAG word, which every split clears (a one-thread launch ahead of it on `stream`) and then raises
+ * when a weight is not |x| <= 65000 (NaN included): the flag follows the weights of the LAST split. */
 int gn_split_bf16_f32(const float* packed, void* out, int n_tiles, int parts, gn_stream_t stream);
 /* The same for `n_jobs` images in ONE launch (job table in DEVICE memory; max_tiles = the largest n_tiles): what a
  * training step needs after its optimizer update — every weight image of every module, one launch after the one
