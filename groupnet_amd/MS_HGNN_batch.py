@@ -264,14 +264,17 @@ def invalidate_weight_caches(module: nn.Module) -> None:
     """Mark every packed / concatenated weight image below `module` stale.  They are keyed on the parameters'
     (address, in-place version); anything that rewrites parameters behind autograd's back — a replayed
     hipGraph containing the optimizer step — must call this before the next eager use.  (The pack plans
-    themselves — arenas and segment tables — stay; the next use re-runs their one refresh launch.)"""
+    themselves — arenas and segment tables — stay; the next use re-runs their one refresh launch.  A captured inference
+    graph — `graphs.GraphedMultiScale`, `graphs.GraphedPastEncoder` — sees the invalidation too and re-derives its
+    images before its next replay.)"""
+    weights.note_invalidation()
     for m in module.modules():
         d = m.__dict__
         d.pop("_gn_plist", None)
         for c in weights.caches(m):
             c.invalidate()
-        if "_affine" in d:
-            m._affine = None
+        for entry in (d.get("_affine") or {}).values():
+            entry[0] = None         # the composed embedding: its buffers stay, the next use writes them again
 
 
 class _MessagePassing(nn.Module):

@@ -514,6 +514,11 @@ class MSHGNNFunction(torch.autograd.Function):
         with torch.no_grad(), M.training_call():     # a training step: packed-weight caches are not trusted
             res = M.run_message_passing(list(mods), [t.xs[0] for t in traces], list(Hs), list(noises), [None] * n,
                                         traces=traces)
+        # `factors` is an output of this node AND what the backward reads as the first dist: kept as the tensor itself it
+        # would close a cycle ctx -> trace -> output -> grad_fn -> ctx, and the whole autograd graph — the parameters'
+        # AccumulateGrad nodes with the stream they were made on — would outlive the step until a gc pass
+        for t in traces:
+            t.dists = [d.detach() for d in t.dists]
         ctx.traces, ctx.params, ctx.n = traces, params, n
         # the backward reads the LIVE weights (and re-packs them): remember which versions the activations belong to
         ctx.param_key = M._param_key(params)

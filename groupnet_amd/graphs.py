@@ -8,10 +8,17 @@ fork/join included) is captured once into a hipGraph and replayed with one host 
 Noise inside a graph: the host draw of the reference (torch.rand on the CPU) cannot be captured, so
 a graphed forward uses the device Philox stream.  Its position lives in a device counter that the
 graph itself advances at the end of every replay — each replay draws fresh, reproducible noise.
+
+Weights inside a graph: an inference forward trusts the packed weight images (`weights.WeightCache`), so the graphs of
+`GraphedMultiScale` and `GraphedPastEncoder` contain no pack or split launch — they READ the images (pack-plan arenas,
+split images, the encoder's composed embedding) where they lay at capture.  `refresh_weights()` re-derives all of them
+from the live parameters in place; a replay does so by itself after `invalidate_weight_caches`; parameter storage that
+moved means capturing again.  `GraphedTrainStep` re-packs inside its graph.
 """
 from __future__ import annotations
 
 import contextlib
+import gc
 from typing import Callable, Optional, Sequence, Tuple
 
 import torch
@@ -37,6 +44,10 @@ def _capture(graph, device, step: Callable, counter: Tensor, draws_per_step: int
              before_capture: Optional[Callable] = None):
     """The capture protocol of the three graphed classes; returns what the captured ``step()`` returned (the graph's
     static outputs).  ``before_capture``: run between the warm-up and the capture."""
+    # An autograd graph left over from an eager training step keeps the parameters' AccumulateGrad nodes, which run on the
+    # stream they were MADE on: made on the default stream they would pull it into the capture of a training step.  Drop
+    # what only a reference cycle keeps alive, so that the warm-up below makes them anew on its own stream.
+    gc.collect()
     side = torch.cuda.Stream(device=device)
     side.wait_stream(torch.cuda.current_stream(device))
     with torch.cuda.stream(side):      # warm-up off the default stream: packs weights, sizes the pool
@@ -67,6 +78,15 @@ class GraphedMultiScale:
         feats, H = g(f, agent_mask=valid)             # ... or a (B,N) bool / uint8 mask that is already on the GPU
         feats, H = g(f)                               # the previous counts stay
         g.status()                                    # the mask entry's sticky status word (synchronises)
+
+    WEIGHTS.  The graph holds no packing launch: it reads the block's packed weight images in place, as they were when it
+    was captured.  After the parameters changed IN PLACE — `load_state_dict`, an eager optimizer step, a ``.data`` write —
+    call ``g.refresh_weights()``: it re-derives every arena and split image the captured forward reads from the live
+    parameters, at the captured addresses, eagerly on the current stream.  After `invalidate_weight_caches(block)` —
+    which `GraphedTrainStep.__call__` runs after every replay — the next ``g(...)`` refreshes by itself, so one block
+    under a train graph and an eval graph needs no extra call.  A parameter whose STORAGE moved (``p.data = ...``,
+    ``block.to(...)``) cannot be followed: `refresh_weights` raises `RuntimeError`; capture again.  Graphs of one block
+    that replay on several streams share the images: refresh on one stream and order the others behind it.
     """
 
     def __init__(self, block: MultiScaleHGNN, B: int, N: int, seed: int = 0, device: Optional[torch.device] = None,
@@ -99,11 +119,19 @@ class GraphedMultiScale:
             if affinity_tail is not None:
                 block.affinity_tail = bool(affinity_tail)
             try:
-                with torch.no_grad(), torch.cuda.device(self.device):
+                with torch.no_grad(), torch.cuda.device(self.device), weights.seen_caches() as seen:
                     self.out, self.H = _capture(self.graph, self.device, self._step, self.counter, self.draws_per_step,
                                                 warmup)
+                    self._weights = weights.CapturedWeights(seen)
             finally:
                 block.affinity_tail = prev_tail
+
+    def refresh_weights(self) -> None:
+        """Re-derive every packed weight image the captured forward reads from the block's live parameters, in place, on
+        the current stream (see the class docstring).  `RuntimeError`, before anything is launched, where a parameter's
+        storage moved since the capture."""
+        with torch.no_grad(), torch.cuda.device(self.device):
+            self._weights.refresh("GraphedMultiScale.refresh_weights")
 
     def _step(self) -> Tuple[Tensor, Optional[Tensor]]:
         # offset 0 + device counter: the position is entirely on the device; the first launch of the
@@ -131,6 +159,8 @@ class GraphedMultiScale:
             self.counts.set(vals)
         elif agent_mask is not None:
             self.counts.set_from_mask(agent_mask)
+        if self._weights.epoch != weights._EPOCH[0]:      # something was invalidated since the images were derived
+            self.refresh_weights()
         self.graph.replay()
         return self.out, self.H
 
@@ -148,6 +178,10 @@ class GraphedPastEncoder:
 
         g = GraphedPastEncoder(enc.eval(), B, N, seed=7)
         feats, new_H = g(inputs)       # inputs (B*N, T, in_dim) copied into the static buffer; outputs static
+
+    WEIGHTS: as `GraphedMultiScale` — the graph reads the modules' packed images and the composed embedding (M, c) in
+    place; ``g.refresh_weights()`` after the parameters changed in place, by itself after `invalidate_weight_caches`,
+    `RuntimeError` (capture again) where a parameter's storage moved.
     """
 
     def __init__(self, enc, B: int, N: int, seed: int = 0, warmup: int = 2):
@@ -170,11 +204,28 @@ class GraphedPastEncoder:
         self.graph = torch.cuda.CUDAGraph()
         with _noise_state_kept():
             try:
-                with torch.no_grad(), torch.cuda.device(self.device):
+                with torch.no_grad(), torch.cuda.device(self.device), weights.seen_caches() as seen:
                     self.out, self.H = _capture(self.graph, self.device, self._step, self.counter, self.draws_per_step,
                                                 warmup)
+                    self._weights = weights.CapturedWeights(seen)
             finally:
                 enc.__dict__.pop("_advance", None)
+        # the composed embedding the graph reads (kept alive here) and the parameters it was composed from
+        self._affine = enc._compose(enc._length, N)
+        self._front = tuple(enc._front_params())
+        self._front_ptrs = tuple(p.data_ptr() for p in self._front)
+
+    def refresh_weights(self) -> None:
+        """Re-derive, in place and on the current stream, the composed embedding (M, c) and every packed weight image the
+        captured forward reads.  `RuntimeError`, before anything is launched, where a parameter's storage moved."""
+        what = "GraphedPastEncoder.refresh_weights"
+        if tuple(p.data_ptr() for p in self._front) != self._front_ptrs:
+            raise weights.moved_storage(what)
+        self._weights.check(what)
+        with torch.no_grad(), torch.cuda.device(self.device):
+            if any(a is not b for a, b in zip(self.enc._compose(self.enc._length, self.N, fresh=True), self._affine)):
+                raise weights.moved_storage(what)      # (the encoder's own buffers were replaced)
+            self._weights.refresh(what)
 
     def _step(self):
         _mods.set_noise_mode("device", seed=self.seed, offset=0, counter=self.counter)
@@ -184,6 +235,8 @@ class GraphedPastEncoder:
     def __call__(self, inputs: Optional[Tensor] = None):
         if inputs is not None:
             self.x_in.copy_(inputs, non_blocking=True)
+        if self._weights.epoch != weights._EPOCH[0]:
+            self.refresh_weights()
         self.graph.replay()
         return self.out, self.H
 

@@ -90,10 +90,17 @@ class _TrajectoryEncoder(nn.Module):
         return [self.input_fc.weight, self.input_fc.bias, self.input_fc2.weight, self.input_fc2.bias,
                 self.input_fc3.weight, self.input_fc3.bias, self.pos_encoder.fc.weight, self.pos_encoder.fc.bias]
 
-    def _compose(self, T: int, N: int) -> Tuple[Tensor, Tensor]:
-        """(M (D, T*in_dim), c (N, D)) with f = M x + c[n]; lines 269-280 composed in fp64."""
-        key = (_param_key(self._front_params()), T, N, self.pos_encoder.pe.data_ptr())
-        if self._affine is None or self._affine[0] != key:
+    def _compose(self, T: int, N: int, fresh: bool = False) -> Tuple[Tensor, Tensor]:
+        """(M (D, T*in_dim), c (N, D)) with f = M x + c[n]; lines 269-280 composed in fp64.  One persistent (M, c) pair
+        per (T, N, device): a new parameter version is written INTO the pair, so a captured graph that reads the pair
+        (`graphs.GraphedPastEncoder`) can be brought up to date in place.  ``fresh``: compose whatever the fingerprint says
+        (a ``.data`` write does not move it)."""
+        key = (_param_key(self._front_params()), self.pos_encoder.pe.data_ptr())
+        if self._affine is None:
+            self._affine = {}
+        slot = (T, N, self.input_fc.weight.device)
+        entry = self._affine.get(slot)
+        if entry is None or fresh or entry[0] != key:
             with torch.no_grad():
                 D = self.model_dim
                 dd = torch.float64
@@ -113,8 +120,13 @@ class _TrajectoryEncoder(nn.Module):
                     c0 = c0 + W2t @ (Wa @ b_in + Wb @ pe[t] + bfc)
                 c0 = W3a @ c0 + b3
                 c = c0[None, :] + self._category(N, dd, Win.device) @ W3c.t()
-                self._affine = (key, M.float().contiguous(), c.float().contiguous())
-        return self._affine[1], self._affine[2]
+                if entry is None:
+                    entry = self._affine[slot] = [key, M.float().contiguous(), c.float().contiguous()]
+                else:
+                    entry[1].copy_(M)
+                    entry[2].copy_(c)
+                    entry[0] = key
+        return entry[1], entry[2]
 
     @staticmethod
     def _category(N: int, dtype, device) -> Tensor:

@@ -347,6 +347,8 @@ class WeightCache:
             self.plan = PackPlan(params[0].device)
             self.pk = build(self.plan)
             self.ptrs, self.key = ptrs, None
+        if _SEEN[0] is not None:
+            _SEEN[0].append((self, tuple(params)))
         if self.always:
             self.plan.refresh()
             return self.pk
@@ -360,6 +362,73 @@ class WeightCache:
     def invalidate(self) -> None:
         """Distrust the packed images: the next `get` refreshes them (the plan itself stays)."""
         self.key = None
+        _EPOCH[0] += 1
+
+
+# ---- what a captured inference forward reads --------------------------------------------------------------------
+# Under no_grad `WeightCache.get` trusts the packed images, so a forward captured after its warm-up contains no pack or
+# split launch: the graph reads the arenas and the split images where they lie.  `seen_caches` records which caches
+# (with their parameters) a warm-up step asked; `CapturedWeights` keeps their plans and images alive and re-derives all
+# of them in place.  `_EPOCH` counts invalidations (`WeightCache.invalidate`, `note_invalidation`): ONE integer compare
+# tells a replay whether anything was distrusted since its images were last derived.
+_SEEN: list = [None]
+_EPOCH = [0]
+
+
+def note_invalidation() -> None:
+    """Something derived from parameters that is not a `WeightCache` (the encoders' composed embedding) was distrusted."""
+    _EPOCH[0] += 1
+
+
+class seen_caches:
+    """``with seen_caches() as seen:`` — every `WeightCache.get` inside appends (cache, parameters).  Not re-entrant."""
+
+    def __enter__(self) -> list:
+        if _SEEN[0] is not None:
+            raise RuntimeError("seen_caches is not re-entrant")
+        _SEEN[0] = []
+        return _SEEN[0]
+
+    def __exit__(self, *exc):
+        _SEEN[0] = None
+        return False
+
+
+def moved_storage(what: str) -> RuntimeError:
+    return RuntimeError(f"{what}: a parameter's storage moved since the capture; the graph reads the packed images "
+                        "derived from the old storage and cannot follow — capture the graph again")
+
+
+class CapturedWeights:
+    """The pack plans and split images a captured forward reads, as `seen_caches` recorded them right after the
+    capture.  `refresh()` re-derives every one from the live parameters at the captured addresses, on the current
+    stream; `check()` refuses, before anything is launched, where a parameter's storage has moved since."""
+
+    def __init__(self, seen: Sequence[Tuple["WeightCache", tuple]]):
+        self.entries, ids = [], set()
+        for c, params in seen:
+            if id(c) not in ids:
+                ids.add(id(c))
+                self.entries.append((c, params, c.ptrs, c.plan, c.pk))       # (keeps arenas, tables and images alive)
+        self.epoch = _EPOCH[0]
+
+    def check(self, what: str) -> None:
+        for _, params, ptrs, _, _ in self.entries:
+            if tuple(p.data_ptr() for p in params) != ptrs:
+                raise moved_storage(what)
+
+    def refresh(self, what: str) -> None:
+        self.check(what)
+        for c, params, _, plan, pk in self.entries:
+            plan.refresh()
+            xi = pk.get("xi")
+            if xi is not None:
+                xi.bump()
+                for name, parts in list(xi.img):       # every image that exists: the captured forward's are among them
+                    xi.get(name, parts)
+            if c.plan is plan:
+                c.key = _param_key(params)             # what the eager path now may trust as well
+        self.epoch = _EPOCH[0]
 
 
 def cache(owner: nn.Module, name, always: bool = False) -> WeightCache:
