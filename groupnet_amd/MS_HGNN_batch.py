@@ -23,6 +23,7 @@ Differences from the reference that a caller can observe
 """
 from __future__ import annotations
 
+import os
 import warnings
 from typing import Iterator, List, Optional, Sequence, Tuple, Union
 
@@ -106,8 +107,29 @@ def _needs_grad(mod: nn.Module, *inputs: Optional[Tensor]) -> bool:
     return any(t is not None and t.requires_grad for t in inputs) or any(p.requires_grad for p in _plist(mod))
 
 
+# Training on ragged batches (``n_agents`` under autograd) is opt-in: None — not set by `set_ragged_training`, the
+# environment decides per call (GN_RAGGED_TRAINING=1: on).
+_RAGGED_TRAINING: Optional[bool] = None
+
+
+def ragged_training() -> bool:
+    """Whether a forward with ``n_agents`` may run under autograd: what `set_ragged_training` chose, else
+    GN_RAGGED_TRAINING=1 switches it on (read per call).  Off by default: such a call is refused before any launch."""
+    if _RAGGED_TRAINING is not None:
+        return _RAGGED_TRAINING
+    return os.environ.get("GN_RAGGED_TRAINING", "0") == "1"
+
+
+def set_ragged_training(on: Optional[bool]) -> None:
+    """True / False for calls issued from now on; None hands the choice back to the environment."""
+    global _RAGGED_TRAINING
+    _RAGGED_TRAINING = None if on is None else bool(on)
+
+
 # What a ragged call (``n_agents``) is refused for, by the caller's keyword: the exception and its text
 _RAGGED_REFUSALS = {
+    "large": (NotImplementedError, f"n_agents: training on ragged batches needs N <= {route.N2E_BWD_SCENE_MAX_N} (the "
+                                   "count-aware node->edge backward has the per-scene form only)"),
     "handed_in": (ValueError, "n_agents: the ragged incidence is built here; H= / masks= cannot be handed in with it"),
     "listall": (NotImplementedError, "n_agents: the exhaustive (listall) search has no ragged form"),
     "grad": (NotImplementedError, "n_agents: ragged batches are inference-only (call under torch.no_grad())"),
@@ -121,6 +143,13 @@ def refuse_ragged(**holds: bool) -> None:
         if held:
             exc, text = _RAGGED_REFUSALS[why]
             raise exc(text)
+
+
+def ragged_grad_refusals(grad: bool, N: int) -> dict:
+    """What a ragged call under autograd (``grad``) is refused for: everything without the opt-in (`ragged_training`),
+    with it a padded size beyond the per-scene node->edge backward."""
+    on = ragged_training()
+    return dict(grad=grad and not on, large=grad and on and N > route.N2E_BWD_SCENE_MAX_N)
 
 
 def ragged_counts(n_agents, x: Tensor, **refusals: bool) -> Optional[ops.AgentCounts]:
@@ -328,10 +357,11 @@ class _MessagePassing(nn.Module):
     def _run(self, h: Tensor, H, E: int, noise_u, out: Optional[Tensor] = None, n_agents=None) -> Tuple[Tensor, Tensor]:
         return run_message_passing([self], [h], [H], [noise_u], [out], n_agents=n_agents)[0]
 
-    def _forward_autograd(self, h: Tensor, H: Optional["ops.Incidence"], noise_u, out: Optional[Tensor]
-                          ) -> Tuple[Tensor, Tensor]:
+    def _forward_autograd(self, h: Tensor, H: Optional["ops.Incidence"], noise_u, out: Optional[Tensor],
+                          counts: Optional["ops.AgentCounts"] = None) -> Tuple[Tensor, Tensor]:
         """Training path: fused forward + HIP backward through torch.autograd.  ``H``: None or the
-        module's `ops.Incidence`, whose masks the forward and the backward read where `masks_apply` holds."""
+        module's `ops.Incidence`, whose masks the forward and the backward read where `masks_apply` holds.  ``counts``:
+        the ragged batch's counts (`set_ragged_training`); ``H`` is then the ragged incidence."""
         from .backward import MSHGNNFunction
         if out is not None:
             raise ValueError("out= is an inference-time extra; under autograd the module returns a new tensor")
@@ -342,11 +372,11 @@ class _MessagePassing(nn.Module):
             # function at the bf16-rounded inputs, and outputs / the input gradient come back in bf16 (the casts are
             # ordinary differentiable torch ops).
             H = None if H is None else ops.Incidence(H.H.float(), H.masks)
-            nf, fac = MSHGNNFunction.apply((self,), (H,), (noise_u,), h.float(), *_plist(self))
+            nf, fac = MSHGNNFunction.apply((self,), (H,), (noise_u,), counts, h.float(), *_plist(self))
             return nf.to(torch.bfloat16), fac.to(torch.bfloat16)
         if h.dtype != torch.float32:
             raise NotImplementedError("activations must be fp32 or bf16")
-        return MSHGNNFunction.apply((self,), (H,), (noise_u,), h, *_plist(self))
+        return MSHGNNFunction.apply((self,), (H,), (noise_u,), counts, h, *_plist(self))
 
 
 BF16_MAX_BOTTLENECK = 64      # gn_mlp2_bf16: the bf16-core kernels hold at most two 32-wide output tiles
@@ -388,7 +418,8 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     form (bit-identical results) — in inference and in a training forward (`traces`, which receive the masks the step
     runs on: the backward reads them there, so both directions of a step run in one form); otherwise masks are
     ignored.
-    `n_agents` (a ragged batch: `ops.agent_counts`; inference only): scene b holds n_b <= N agents, its first rows, and
+    `n_agents` (a ragged batch: `ops.agent_counts`; with `traces` only under `set_ragged_training`, the traces then
+    receive the counts for the backward): scene b holds n_b <= N agents, its first rows, and
     Hs are the ragged incidences (zero rows and columns >= n_b).  The forward takes the ragged route: the node->edge
     launch and the scatter launch receive the counts, everything else is row-wise or meets the padding only through
     zeros of H, and ONE more launch zeroes the padded positions of every node_feat and factors at the end.  Counts that
@@ -403,8 +434,11 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     _check_storage_width(mods[0].bottleneck_dim, hs[0].dtype)
     B, N = hs[0].shape[0], hs[0].shape[1]
     counts = ops.agent_counts(n_agents, B, N, hs[0].device)
-    if counts is not None and traces is not None:
+    ragged_train = counts is not None and traces is not None
+    if ragged_train and not ragged_training():
         raise NotImplementedError("n_agents: ragged batches are inference-only")
+    if ragged_train and counts.admits_empty:
+        raise NotImplementedError("n_agents: counts that admit empty slots (ops.StaticAgentCounts) are inference-only")
     ragged = {} if counts is None else {"n_agents": counts}      # what the two count-aware launches are handed
     incs = [H if H is None or isinstance(H, ops.Incidence) else ops.Incidence(H) for H in Hs]
     rt = route.message_passing_route(
@@ -412,7 +446,7 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
         training=traces is not None, matrix16=ops.BF16X6,
         knobs=route.Knobs(_FUSE_POOL, ops.POOL_MAX_N, ops.node_form_enabled(),
                           ops.incidence_form() == "mask" and all(g is None or g.masks is not None for g in incs)),
-        closing_asked=fuse_closing, ragged=counts is not None)
+        closing_asked=fuse_closing, ragged=counts is not None, ragged_training=ragged_train)
     # every module's graph as the ops item tuples take it: the dense H (None: pairwise), sym, the masks where the step
     # reads them.  The pairwise graph is symmetric: edges (i,j) and (j,i) pool the same feature, meet the same typed
     # MLP output and are summed into the same two nodes.  Its per-edge MLPs therefore run once per
@@ -424,6 +458,7 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     if traces is not None:
         for t, mk in zip(traces, masks):
             t.masks = mk
+            t.counts = counts
     given = [_noise_iter(u) for u in noises]
 
     def next_u(i: int):
@@ -587,12 +622,14 @@ class MS_HGNN_oridinary(_MessagePassing):
         ``n_agents`` (optional; INTEGRATION.md, "Ragged batches"): one count per scene, 1 <= n_b <= N — the first n_b
         agent rows of scene b are real, the rest is (finite) padding.  Valid node rows and edges (i, j < n_b; the noise
         is read at the padded index i*N + j) are what the module computes for the scene alone; padded positions of both
-        outputs are zeros.  Inference only."""
+        outputs are zeros.  Under autograd only with `set_ragged_training(True)` ("Ragged batches",
+        Training): the input gradient then comes back with rows n >= n_b exactly zero."""
         ops._req(h_states, "h_states", (None, None, self.h_dim), ops._ACT_DTYPES)
         N = h_states.shape[1]
-        n_agents = ragged_counts(n_agents, h_states, grad=_needs_grad(self, h_states))
-        if h_states.shape[0] and N and _needs_grad(self, h_states):
-            return self._forward_autograd(h_states, None, noise_u, out)
+        grad = _needs_grad(self, h_states)
+        n_agents = ragged_counts(n_agents, h_states, **ragged_grad_refusals(grad, N))
+        if h_states.shape[0] and N and grad:
+            return self._forward_autograd(h_states, None, noise_u, out, n_agents)
         _check_storage_width(self.bottleneck_dim, h_states.dtype)
         if h_states.shape[0] == 0 or N == 0:      # empty batch: nothing to launch
             nf = out if out is not None else h_states.new_empty((h_states.shape[0], N, self.bottleneck_dim))
@@ -661,13 +698,20 @@ class MS_HGNN_hyper(_MessagePassing):
         hyperedge hold the n_b valid agents; a scene with n_b <= scale < N gets n_b identical all-member hyperedges (the
         E = 1 shortcut is keyed on N).  Valid rows of node_feat and factor are what the module computes for the scene
         alone; padded positions of the three outputs are zeros; padded rows of h_states and corr must be finite.
-        Inference only, top-k incidence built here only (no ``H=`` / ``masks=``, no ``listall``)."""
+        Top-k incidence built here only (no ``H=`` / ``masks=``, no ``listall``); under autograd only with
+        `set_ragged_training(True)` (INTEGRATION.md, "Ragged batches", Training)."""
         ops._req(h_states, "h_states", (None, None, self.h_dim), ops._ACT_DTYPES)
+        grad = _needs_grad(self, h_states)
         n_agents = ragged_counts(n_agents, h_states, handed_in=H is not None or masks is not None, listall=self.listall,
-                                 grad=_needs_grad(self, h_states))
+                                 **ragged_grad_refusals(grad, h_states.shape[1]))
         if n_agents is not None:
             if self.scale > h_states.shape[1]:
                 raise RuntimeError("selected index k out of range")
+            if grad:
+                # the ragged incidence is a constant of the backward, as H is on the full-batch training path
+                H = self.init_adj_attention(h_states.detach(), corr.detach(), scale_factor=self.scale, n_agents=n_agents)
+                node_feat, factor = self._forward_autograd(h_states, ops.Incidence(H), noise_u, out, n_agents)
+                return node_feat, factor, (H if H.dtype == h_states.dtype else H.to(h_states.dtype))
             _check_storage_width(self.bottleneck_dim, h_states.dtype)
             H = self.init_adj_attention(h_states, corr, scale_factor=self.scale, n_agents=n_agents)
             node_feat, factor = self._run(h_states, ops.Incidence(H), H.shape[1], noise_u, out, n_agents)

@@ -163,7 +163,7 @@ K_AFFINITY_TOPK_RAGGED, K_TOPK_INCIDENCE_RAGGED, K_NODE2EDGE_RAGGED, K_AGG_SCATT
 K_LAST = K_ZERO_PADDING
 MAX_GROUPS = 10
 MAX_ZERO_ITEMS = 24
-ZERO_NODE_ROWS, ZERO_EDGE_ROWS, ZERO_PAIR_ROWS = 0, 1, 2      # gn_zero_item_t.kind
+ZERO_NODE_ROWS, ZERO_EDGE_ROWS, ZERO_PAIR_ROWS, ZERO_SYM_PAIR_ROWS = 0, 1, 2, 4      # gn_zero_item_t.kind (3: refused)
 COUNTS_NOT_PREFIX, COUNTS_EMPTY = 1, 2                        # GN_COUNTS_*: the status word of gn_agent_counts_u8
 
 # name -> (restype, argtypes); mirrors include/groupnet_hip.h one to one
@@ -267,6 +267,8 @@ SIGNATURES = {
     "gn_node2edge_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "gn_gumbel_bwd_grouped_f32": (_I, [ctypes.POINTER(GumbelBwdGroup), _I, _I, _F, _P]),
     "gn_node2edge_bwd_grouped_f32": (_I, [ctypes.POINTER(N2EBwdGroup), _I, _I, _I, _P]),
+    "gn_node2edge_bwd_ragged_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "gn_node2edge_bwd_ragged_grouped_f32": (_I, [ctypes.POINTER(N2EBwdGroup), _I, _I, _I, _P, _P]),
     "gn_philox_uniform_f32": (_I, [_P, _SZ, _U64, _U64, _P, _P]),
     "gn_counter_add_u64": (_I, [_P, _U64, _P]),
     "gn_copy_2d": (_I, [_P, _SZ, _P, _SZ, _SZ, _I, _P]),

@@ -19,6 +19,11 @@ A round j of a module is two blocks: x_j --node2edge_j, edge MLP_j--> (ef_j, dis
 (ef_j, x_j) --edge2node_j, MLP--> x_{j+1} (or node_feat).  `nmp_layers > 1` (:186-194, :432-440) is
 the same two blocks repeated, walked backwards.  Which forms a round takes is `route.backward_round_route`'s
 answer; `round_backward` follows it through the steps below it, each a function over the modules' `_RoundState`s.
+
+A ragged batch (``n_agents`` under autograd, `MS_HGNN_batch.set_ragged_training`): the traces carry the forward's counts
+and the same chain rule runs with four changes ("Ragged training") — the incoming gradients zeroed at padded
+positions (`modules_backward`), 1/n_b for 1/N and the unordered pair rows with a padded end zeroed
+(`_edge2node_backward`), and the count-aware pooling backward gn_node2edge_bwd_ragged_grouped_f32 (`_pooling_backward`).
 """
 from __future__ import annotations
 
@@ -157,6 +162,7 @@ class ModuleTrace:
         self.mod = mod
         self.H = H.H if isinstance(H, ops.Incidence) else H      # dense (None: the pairwise graph)
         self.masks = None                    # `ops.IncidenceMasks` of H where `run_message_passing` ran the step on them
+        self.counts = None                   # `ops.AgentCounts` where `run_message_passing` ran a ragged batch
         self.xs: List[Tensor] = [h]          # node features entering round j
         self.dists: List[Tensor] = []        # dist of round j (B,E,K)
         self.tails: List[dict] = []          # round j's closing MLP: {"x": cat(H^T feat, ori)/N, "hid": relu(layer 0)}
@@ -208,6 +214,7 @@ class _RoundState:
     __slots__ = (
         # the constructor — the round's inputs and constants:
         "x", "x2", "H", "masks", "sym",         # x_j (B,N,D) and as (BN,D); dense incidence (None where sym) and its masks
+        "counts", "inv_n",      # ragged batch: its `ops.AgentCounts` and 1/n_b per node row (BN,); else None and None
         "B", "N", "E", "K", "Kp", "R", "BN",    # Kp: K rounded up to 4, the leading dimension of ef
         "s0", "s1", "a0", "a1", "i", "d", "f", "agg", "e0", "e1",      # the round's layers (`_round_layers`)
         "tw", "w2", "b2",                       # `_bwd_weights`; attention layer 1 as a vector and its bias
@@ -245,6 +252,7 @@ class _RoundState:
             t.npar[j] = sum(p.numel() for m in (mod.node2edge_start_mlp[j], mod.attention_mlp[j], st, self.agg,
                                                 nn.ModuleList([self.e0, self.e1])) for p in m.parameters())
         self.x, self.x2, self.masks = x, x.reshape(B * N, D), t.masks
+        self.counts, self.inv_n = t.counts, None
         self.B, self.N, self.E, self.K, self.Kp, self.R, self.BN = B, N, E, K, (K + 3) // 4 * 4, B * E, B * N
         self.i, self.d, self.f = st.init_MLP.layers, st.MLP_distribution.layers, st.MLP_factor.layers
         self.tw = _bwd_weights(mod, j)
@@ -333,12 +341,21 @@ def _edge2node_backward(S: List[_RoundState], gb: GemmBatch) -> None:
     # writes them on request: agg2, y1), so feat is not re-computed
     for c in _each(S, gb):
         c.dy1 = gb.add(c.g_y, _w(c.e1), c.new(c.BN, 128), mask=c.y1)
+    # (a ragged batch: edge2node divided scene b by its own n_b — the rows of dy1 are scaled by 1/n_b instead of 1/N)
     for c in _each(S, gb):
-        c.da = gb.add(c.dy1, _w(c.e0)[:, :D], c.new(c.BN, D), alpha=1.0 / c.N)     # d(H^T feat)
-        c.dx = gb.add(c.dy1, _w(c.e0)[:, D:], c.new(c.BN, D), alpha=1.0 / c.N)     # ori half of the cat
+        div = dict(alpha=1.0 / c.N) if c.counts is None else dict(rs=c.inv_n)
+        c.da = gb.add(c.dy1, _w(c.e0)[:, :D], c.new(c.BN, D), **div)     # d(H^T feat)
+        c.dx = gb.add(c.dy1, _w(c.e0)[:, D:], c.new(c.BN, D), **div)     # ori half of the cat
     dfeats = ops.agg_gather_grouped([(c.da.view(c.B, c.N, D), c.H, c.sym, c.masks) for c in S])    # adjoint of H^T feat
     for c, df in zip(S, dfeats):
         c.dfeat = df.view(c.R, D)
+    # A ragged batch: the pair gather forms da_i + da_j, so a pair with ONE valid end carries a non-zero row, which
+    # would reach T, def_, deo and the weight gradients: such rows become zero before anything reads them.  (The hyper
+    # modules' H has zero rows e >= n_b and zero columns n >= n_b: their gather and scatter need nothing.)  From here on
+    # every stage is row-wise or linear in its incoming gradient, up to the count-aware pooling backward.
+    ragged_pairs = [(c.dfeat.view(c.B, c.E, D), ops.ZERO_SYM_PAIR_ROWS) for c in S if c.counts is not None and c.sym]
+    if ragged_pairs:
+        ops.zero_padding(ragged_pairs, S[0].counts)
     for c in _each(S, gb):
         c.T = gb.add(c.dfeat, c.tw["W2cat"], c.new(c.R, c.K * _HID))
     for c in S:
@@ -413,8 +430,14 @@ def _pooling_backward(S: List[_RoundState], gb: GemmBatch, grads: dict, grouped:
                                           b2=c.b2.data_ptr(), dedges=c.dedges.data_ptr(), dxp=c.dxp.data_ptr(),
                                           dpq=c.dpq.data_ptr(), dw2=grads[c.a1.weight].data_ptr(),
                                           db2=grads[c.a1.bias].data_ptr(), E=c.E, sym=int(c.sym))
-            check(load().gn_node2edge_bwd_grouped_f32(arr, len(S), S[0].B, S[0].N, stream_handle()),
-                  "gn_node2edge_bwd_grouped_f32")
+            if S[0].counts is None:
+                check(load().gn_node2edge_bwd_grouped_f32(arr, len(S), S[0].B, S[0].N, stream_handle()),
+                      "gn_node2edge_bwd_grouped_f32")
+            else:
+                # a ragged batch: the softmax of a hyperedge ran over the scene's n_b nodes and the pairwise edges
+                # exist only with both ends < n_b — the one stage where the count enters a kernel's arithmetic
+                check(load().gn_node2edge_bwd_ragged_grouped_f32(arr, len(S), S[0].B, S[0].N, addr(S[0].counts.dev),
+                                                                 stream_handle()), "gn_node2edge_bwd_ragged_grouped_f32")
         else:
             for c in S:
                 check(load().gn_node2edge_bwd_f32(addr(c.xp), addr(c.pq), addr(c.H), addr(c.w2), addr(c.b2),
@@ -461,11 +484,25 @@ def round_backward(traces: Sequence[ModuleTrace], j: int, g_ys: Sequence[Optiona
 
     g_ys[i] = gradient w.r.t. the output of round j's edge2node + MLP block (node_feat for the last round),
     g_dists[i] = gradient w.r.t. dist_j (the returned `factors` for round 0), either may be None.
-    Adds the parameter gradients to `grads`, returns d x_j per module."""
-    rt = route.backward_round_route(traces[0].xs[j].shape[1], tuple(t.H is None for t in traces))
+    Adds the parameter gradients to `grads`, returns d x_j per module.
+
+    A ragged batch (the traces carry the forward's `ops.AgentCounts`; DESIGN.md, "Ragged training"): the chain rule is
+    the same, with the incoming gradients zero at padded positions (`modules_backward` sees to the caller's; the d x an
+    earlier round receives from a later one is zero at rows n >= n_b already — there it is a sum of the ori half, a GEMM
+    on rows of dy1 that are zero because the incoming rows are, of the scatter, which meets a padded node only through
+    zero columns of H or through pair rows that `_edge2node_backward` zeroed, and of the node MLP's backward on rows of
+    dxp and dpq that the count-aware pooling backward never writes), 1/n_b for 1/N, the unordered pair rows with a padded
+    end zeroed, and the count-aware pooling backward.  d x_j comes back with rows n >= n_b exactly zero."""
+    counts = traces[0].counts
+    rt = route.backward_round_route(traces[0].xs[j].shape[1], tuple(t.H is None for t in traces), counts is not None)
     S = [_RoundState(t, j, rt.pair_rows, g_y, g_d) for t, g_y, g_d in zip(traces, g_ys, g_dists)]
-    # one zero fill for the accumulate-by-atomics targets of every module of the round
     dev = S[0].x.device
+    if counts is not None:
+        # 1 / n_b per node row, from the device counts (no host read; an empty slot's rows are zero anyway)
+        inv_n = counts.dev.clamp(min=1).to(torch.float32).reciprocal().repeat_interleave(S[0].N)
+        for c in S:
+            c.inv_n = inv_n
+    # one zero fill for the accumulate-by-atomics targets of every module of the round
     arena = torch.zeros(sum(c.pool_n for c in S), dtype=torch.float32, device=dev)
     off = 0
     for c in S:
@@ -488,9 +525,22 @@ def round_backward(traces: Sequence[ModuleTrace], j: int, g_ys: Sequence[Optiona
 def modules_backward(traces: Sequence[ModuleTrace], g_nfs: Sequence[Optional[Tensor]],
                      g_facs: Sequence[Optional[Tensor]]) -> Tuple[List[Tensor], Dict[nn.Parameter, Tensor]]:
     """Gradients of (node_feat, factors) of several modules (same nmp_layers) w.r.t. their h_states and
-    parameters: the rounds walked backwards, each round grouped over the modules."""
+    parameters: the rounds walked backwards, each round grouped over the modules.
+    A ragged batch: the outputs at padded positions are constants (zeros), so whatever the caller's loss put into the
+    gradients there is dropped — in COPIES (the caller's tensors are never written), all of them in one launch."""
     L = traces[0].mod.nmp_layers - 1
     grads: Dict[nn.Parameter, Tensor] = {}
+    counts = traces[0].counts
+    if counts is not None:
+        g_nfs, g_facs, items = list(g_nfs), list(g_facs), []
+        for i, t in enumerate(traces):
+            if g_nfs[i] is not None:
+                g_nfs[i] = g_nfs[i].clone(memory_format=torch.contiguous_format)
+                items.append((g_nfs[i], ops.ZERO_NODE_ROWS))
+            if g_facs[i] is not None and g_facs[i].shape[1] != 1:      # (the single row of a scale-N module is valid)
+                g_facs[i] = g_facs[i].clone(memory_format=torch.contiguous_format)
+                items.append((g_facs[i], ops.ZERO_PAIR_ROWS if t.H is None else ops.ZERO_EDGE_ROWS))
+        ops.zero_padding(items, counts)
     g_ys = list(g_nfs)
     for j in range(L, -1, -1):
         g_ds = list(g_facs) if j == 0 else [None] * len(traces)
@@ -501,19 +551,20 @@ def modules_backward(traces: Sequence[ModuleTrace], g_nfs: Sequence[Optional[Ten
 class MSHGNNFunction(torch.autograd.Function):
     """Several modules on their inputs: forward = the grouped fused HIP path, backward = `modules_backward`.
 
-    apply(mods, Hs, noises, h_0..h_{n-1}, *params) -> (nf_0, fac_0, nf_1, fac_1, ...).  ``Hs``: per module None (the
-    pairwise graph), a dense tensor or an `ops.Incidence`; where `run_message_passing` decides for the mask form it
-    leaves the masks on the traces, and the backward reads them there."""
+    apply(mods, Hs, noises, counts, h_0..h_{n-1}, *params) -> (nf_0, fac_0, nf_1, fac_1, ...).  ``Hs``: per module None
+    (the pairwise graph), a dense tensor or an `ops.Incidence`; where `run_message_passing` decides for the mask form it
+    leaves the masks on the traces, and the backward reads them there.  ``counts``: None, or the `ops.AgentCounts` of a
+    ragged batch (``Hs`` are then the ragged incidences); the traces carry them to the backward the same way."""
 
     @staticmethod
-    def forward(ctx, mods, Hs, noises, *tensors):
+    def forward(ctx, mods, Hs, noises, counts, *tensors):
         from . import MS_HGNN_batch as M
         n = len(mods)
         hs, params = tensors[:n], tensors[n:]
         traces = [ModuleTrace(m, h.detach(), H) for m, h, H in zip(mods, hs, Hs)]
         with torch.no_grad(), M.training_call():     # a training step: packed-weight caches are not trusted
             res = M.run_message_passing(list(mods), [t.xs[0] for t in traces], list(Hs), list(noises), [None] * n,
-                                        traces=traces)
+                                        traces=traces, n_agents=counts)
         # `factors` is an output of this node AND what the backward reads as the first dist: kept as the tensor itself it
         # would close a cycle ctx -> trace -> output -> grad_fn -> ctx, and the whole autograd graph — the parameters'
         # AccumulateGrad nodes with the stream they were made on — would outlive the step until a gc pass
@@ -546,4 +597,4 @@ class MSHGNNFunction(torch.autograd.Function):
                                         [g_facs[i] for i in live])
             for i, dh in zip(live, d):
                 dhs[i] = dh
-        return (None, None, None) + tuple(dhs) + tuple(grads.get(p) for p in ctx.params)
+        return (None, None, None, None) + tuple(dhs) + tuple(grads.get(p) for p in ctx.params)

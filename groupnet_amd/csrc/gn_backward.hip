@@ -14,7 +14,8 @@
 //   gn_gumbel_ef_f32       edge_feat = sigmoid(f) * dist from its saved pieces;
 //   gn_gumbel_bwd_f32      back through fac * softmax((logits + g) / tau) and the sigmoid;
 //   gn_node2edge_bwd_f32   back through the attention-weighted pooling (one workgroup per scene with its rows
-//                          in LDS; beyond that one wave per hyperedge with atomic adds into the node rows).
+//                          in LDS; beyond that one wave per hyperedge with atomic adds into the node rows);
+//   gn_node2edge_bwd_ragged_f32   the same over scenes with their own agent counts (per-scene form only).
 // Gather and scatter are each other's adjoints and reuse the forward kernels.
 #include <stdlib.h>
 
@@ -539,14 +540,25 @@ __global__ __launch_bounds__(kB) void node2edge_bwd_kernel(const float* __restri
 // 33 attention-layer-1 sums per scene.  H == nullptr selects the implicit pairwise graph (E = N*N, edge
 // e = i*N + j joins i and j with weight 1, weight 2 on i when i == j; model/MS_HGNN_batch.py:143-160), or
 // with sym its N(N+1)/2 unordered pairs (the two ordered edges of a pair pool the same feature).
+// RAGGED (gn_node2edge_bwd_ragged_*): the scene holds nb <= N agents, its first rows.  The softmax of a hyperedge runs
+// over nb nodes; only the nb valid node rows are staged and written back; an explicit H is read at its columns < nb and a
+// row without members is skipped; the pairwise graph walks the pairs with both ends < nb, whose dedges rows sit at
+// their index in the PADDED layout (E stays the padded row count).  The LDS layout stays the padded scene's.
+// Without RAGGED nb is N.
+template <bool RAGGED>
 __device__ __forceinline__ void node2edge_bwd_scene_body(
     const float* __restrict__ xp, const float* __restrict__ pq, const float* __restrict__ H,
     const float* __restrict__ w2, const float* __restrict__ b2p, const float* __restrict__ dedges,
     float* __restrict__ dxp,
-    float* __restrict__ dpq, float* __restrict__ dw2, float* __restrict__ db2, int N, int E, int sym, const int b) {
+    float* __restrict__ dpq, float* __restrict__ dw2, float* __restrict__ db2, int N, int E, int sym, const int b,
+    const int nb) {
   extern __shared__ __align__(16) float lds[];
+  if constexpr (RAGGED) {
+    if (nb <= 0) return;      // an empty slot (the whole workgroup): nothing is read, nothing is added
+  }
   const float b2 = *b2p;
   const int NF = N * GN_FEAT;
+  const int VF = RAGGED ? nb * GN_FEAT : NF;       // the valid node rows: what is staged and written back
   float* s_xp = lds;
   float* s_pq = s_xp + NF;
   float* s_dxp = s_pq + NF;
@@ -561,7 +573,7 @@ __device__ __forceinline__ void node2edge_bwd_scene_body(
   float* s_dw = base + 3 * N;
   const float* xpb = xp + (size_t)b * NF;
   const float* pqb = pq + (size_t)b * NF;
-  for (int i = threadIdx.x; i < NF; i += kB) {
+  for (int i = threadIdx.x; i < VF; i += kB) {
     s_xp[i] = xpb[i];
     s_pq[i] = pqb[i];
     s_dxp[i] = 0.f;
@@ -571,11 +583,23 @@ __device__ __forceinline__ void node2edge_bwd_scene_body(
   __syncthreads();
   const float w2c = w2[c];
   float dw2c = 0.f, db2l = 0.f;
-  for (int e = wave; e < E; e += kB / 64) {
+  // the edges the scene walks: every row of an explicit H, the nb*nb (sym: nb(nb+1)/2) valid pairs of the pairwise graph
+  const int Ev = RAGGED && H == nullptr ? (sym ? gn_pair_count(nb) : nb * nb) : E;
+  for (int ev = wave; ev < Ev; ev += kB / 64) {
+    int e = ev;      // the edge's row of dedges
     int cnt = 0;
     if (H == nullptr) {
       int i, j;
-      if (sym) {       // E = N(N+1)/2 unordered pairs, dedges already summed over (i,j) and (j,i)
+      if constexpr (RAGGED) {
+        if (sym) {
+          gn_pair_decode(ev, nb, i, j);
+          e = gn_pair_start(i, N) + (j - i);
+        } else {
+          i = ev / nb;
+          j = ev - i * nb;
+          e = i * N + j;
+        }
+      } else if (sym) {       // E = N(N+1)/2 unordered pairs, dedges already summed over (i,j) and (j,i)
         gn_pair_decode(e, N, i, j);
       } else {
         i = e / N;
@@ -595,9 +619,9 @@ __device__ __forceinline__ void node2edge_bwd_scene_body(
       cnt = i == j ? 1 : 2;
     } else {
       const float* Hrow = H + ((size_t)b * E + e) * N;
-      for (int n0 = 0; n0 < N; n0 += 64) {
+      for (int n0 = 0; n0 < nb; n0 += 64) {
         const int n = n0 + lane;
-        const float hv = n < N ? Hrow[n] : 0.f;
+        const float hv = n < nb ? Hrow[n] : 0.f;
         const unsigned long long mask = __ballot(hv != 0.f);
         if (hv != 0.f) {
           const int pos = cnt + __popcll(mask & ((1ull << lane) - 1ull));
@@ -605,6 +629,9 @@ __device__ __forceinline__ void node2edge_bwd_scene_body(
           s_h[pos] = hv;
         }
         cnt += __popcll(mask);
+      }
+      if constexpr (RAGGED) {
+        if (cnt == 0) continue;      // (wave-uniform) a row without members, e >= nb of a top-k module among them
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -626,13 +653,13 @@ __device__ __forceinline__ void node2edge_bwd_scene_body(
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    float mx = cnt < N ? 0.f : -INFINITY;
+    float mx = cnt < nb ? 0.f : -INFINITY;       // the 0 of a non-member enters the maximum only if one exists
     for (int m = lane; m < cnt; m += 64) mx = fmaxf(mx, s_att[m] * s_h[m]);
     mx = gn_wave_max(mx);
     float sum = 0.f;
     for (int m = lane; m < cnt; m += 64) sum += expf(s_att[m] * s_h[m] - mx);
     sum = gn_wave_sum(sum);
-    sum += gn_nonmember_sum(N - cnt, mx);
+    sum += gn_nonmember_sum(nb - cnt, mx);
     float pd = 0.f;
     for (int m = lane; m < cnt; m += 64) pd += expf(s_att[m] * s_h[m] - mx) / sum * s_dw[m] * s_h[m];
     pd = gn_wave_sum(pd);
@@ -662,19 +689,31 @@ __device__ __forceinline__ void node2edge_bwd_scene_body(
   __syncthreads();
   float* dxpb = dxp + (size_t)b * NF;
   float* dpqb = dpq + (size_t)b * NF;
-  for (int i = threadIdx.x; i < NF; i += kB) {
+  for (int i = threadIdx.x; i < VF; i += kB) {
     dxpb[i] += s_dxp[i];
     dpqb[i] += s_dpq[i];
   }
   if (threadIdx.x < 32) atomicAdd(dw2 + threadIdx.x, s_red[threadIdx.x]);
   if (threadIdx.x == 32) atomicAdd(db2, s_red[32]);
 }
+// scene b's count of a ragged launch, clamped as in every ragged kernel
+__device__ __forceinline__ int n2e_bwd_count(const int* __restrict__ n_valid, int b, int N) {
+  return gn_uniform(min(max(n_valid[b], 0), N));
+}
 __global__ __launch_bounds__(kB) void node2edge_bwd_scene_kernel(
     const float* __restrict__ xp, const float* __restrict__ pq, const float* __restrict__ H,
     const float* __restrict__ w2, const float* __restrict__ b2p, const float* __restrict__ dedges,
     float* __restrict__ dxp, float* __restrict__ dpq, float* __restrict__ dw2, float* __restrict__ db2, int N, int E,
     int sym) {
-  node2edge_bwd_scene_body(xp, pq, H, w2, b2p, dedges, dxp, dpq, dw2, db2, N, E, sym, (int)blockIdx.x);
+  node2edge_bwd_scene_body<false>(xp, pq, H, w2, b2p, dedges, dxp, dpq, dw2, db2, N, E, sym, (int)blockIdx.x, N);
+}
+__global__ __launch_bounds__(kB) void node2edge_bwd_scene_ragged_kernel(
+    const float* __restrict__ xp, const float* __restrict__ pq, const float* __restrict__ H,
+    const float* __restrict__ w2, const float* __restrict__ b2p, const float* __restrict__ dedges,
+    float* __restrict__ dxp, float* __restrict__ dpq, float* __restrict__ dw2, float* __restrict__ db2, int N, int E,
+    int sym, const int* __restrict__ n_valid) {
+  node2edge_bwd_scene_body<true>(xp, pq, H, w2, b2p, dedges, dxp, dpq, dw2, db2, N, E, sym, (int)blockIdx.x,
+                                 n2e_bwd_count(n_valid, (int)blockIdx.x, N));
 }
 // every module of the stage in one launch: blockIdx.y = module, blockIdx.x = scene (the pairwise module's 88 us and the
 // hyper modules' 24-41 us side by side instead of end to end)
@@ -683,7 +722,14 @@ struct N2EBwdTable {
 };
 __global__ __launch_bounds__(kB) void node2edge_bwd_scene_grouped_kernel(N2EBwdTable T, int N) {
   const gn_n2e_bwd_group_t G = T.g[blockIdx.y];
-  node2edge_bwd_scene_body(G.xp, G.pq, G.H, G.w2, G.b2, G.dedges, G.dxp, G.dpq, G.dw2, G.db2, N, G.E, G.sym, (int)blockIdx.x);
+  node2edge_bwd_scene_body<false>(G.xp, G.pq, G.H, G.w2, G.b2, G.dedges, G.dxp, G.dpq, G.dw2, G.db2, N, G.E, G.sym,
+                                  (int)blockIdx.x, N);
+}
+__global__ __launch_bounds__(kB) void node2edge_bwd_scene_ragged_grouped_kernel(N2EBwdTable T, int N,
+                                                                                const int* __restrict__ n_valid) {
+  const gn_n2e_bwd_group_t G = T.g[blockIdx.y];
+  node2edge_bwd_scene_body<true>(G.xp, G.pq, G.H, G.w2, G.b2, G.dedges, G.dxp, G.dpq, G.dw2, G.db2, N, G.E, G.sym,
+                                 (int)blockIdx.x, n2e_bwd_count(n_valid, (int)blockIdx.x, N));
 }
 
 // out[r][c] = alpha * a[r][c] + beta * out[r][c] on (rows x cols) blocks with leading dimensions
@@ -908,9 +954,14 @@ extern "C" int gn_gumbel_bwd_grouped_f32(const gn_gumbel_bwd_group_t* groups, in
   return gn_check_launch();
 }
 
-extern "C" int gn_node2edge_bwd_grouped_f32(const gn_n2e_bwd_group_t* groups, int n_groups, int B, int N,
-                                            gn_stream_t stream) {
+// The grouped per-scene launch, full-batch or (ragged) over the device counts n_valid
+static int n2e_bwd_grouped_entry(const gn_n2e_bwd_group_t* groups, int n_groups, int B, int N, bool ragged,
+                                 const int* n_valid, gn_stream_t stream) {
   if (groups == nullptr) return GN_ERR_NULL;
+  if (ragged) {
+    const int rc = gn_need_counts(n_valid);
+    if (rc != GN_OK) return rc;
+  }
   if (n_groups < 1 || n_groups > GN_MAX_GROUPS || B <= 0 || N <= 0) return GN_ERR_SHAPE;
   const size_t scene_lds = n2e_bwd_scene_lds(N);
   if (scene_lds > kN2EBwdSceneBudget) return GN_ERR_LDS;      // (the per-scene form only: larger N goes module by module)
@@ -924,9 +975,43 @@ extern "C" int gn_node2edge_bwd_grouped_f32(const gn_n2e_bwd_group_t* groups, in
     if (G.H == nullptr && G.E != (G.sym ? gn_pair_count(N) : N * N)) return GN_ERR_SHAPE;
     T.g[g] = G;
   }
+  if (ragged) {
+    if (scene_lds > 64 * 1024) gn_allow_big_lds(node2edge_bwd_scene_ragged_grouped_kernel);
+    hipLaunchKernelGGL(node2edge_bwd_scene_ragged_grouped_kernel, dim3((unsigned)B, n_groups), dim3(kB), scene_lds,
+                       (hipStream_t)stream, T, N, n_valid);
+    return gn_check_launch();
+  }
   if (scene_lds > 64 * 1024) gn_allow_big_lds(node2edge_bwd_scene_grouped_kernel);
   hipLaunchKernelGGL(node2edge_bwd_scene_grouped_kernel, dim3((unsigned)B, n_groups), dim3(kB), scene_lds,
                      (hipStream_t)stream, T, N);
+  return gn_check_launch();
+}
+extern "C" int gn_node2edge_bwd_grouped_f32(const gn_n2e_bwd_group_t* groups, int n_groups, int B, int N,
+                                            gn_stream_t stream) {
+  return n2e_bwd_grouped_entry(groups, n_groups, B, N, false, nullptr, stream);
+}
+extern "C" int gn_node2edge_bwd_ragged_grouped_f32(const gn_n2e_bwd_group_t* groups, int n_groups, int B, int N,
+                                                   const int* n_valid, gn_stream_t stream) {
+  return n2e_bwd_grouped_entry(groups, n_groups, B, N, true, n_valid, stream);
+}
+// (one module: the per-scene kernel with plain arguments, as gn_node2edge_bwd_f32 launches its own)
+extern "C" int gn_node2edge_bwd_ragged_f32(const float* xp, const float* pq, const float* H, const float* w2,
+                                           const float* b2, const float* dedges, float* dxp, float* dpq, float* dw2,
+                                           float* db2, int B, int N, int E, int sym, const int* n_valid,
+                                           gn_stream_t stream) {
+  const void* ptrs[] = {xp, pq, w2, b2, dedges, dxp, dpq, dw2, db2};
+  for (const void* p : ptrs)
+    if (p == nullptr) return GN_ERR_NULL;
+  const int rc = gn_need_counts(n_valid);
+  if (rc != GN_OK) return rc;
+  if (B <= 0 || N <= 0 || E <= 0) return GN_ERR_SHAPE;
+  if (sym && H != nullptr) return GN_ERR_SHAPE;
+  if (H == nullptr && E != (sym ? gn_pair_count(N) : N * N)) return GN_ERR_SHAPE;
+  const size_t scene_lds = n2e_bwd_scene_lds(N);
+  if (scene_lds > kN2EBwdSceneBudget) return GN_ERR_LDS;      // there is no per-wave ragged form
+  if (scene_lds > 64 * 1024) gn_allow_big_lds(node2edge_bwd_scene_ragged_kernel);
+  hipLaunchKernelGGL(node2edge_bwd_scene_ragged_kernel, dim3((unsigned)B), dim3(kB), scene_lds, (hipStream_t)stream, xp,
+                     pq, H, w2, b2, dedges, dxp, dpq, dw2, db2, N, E, sym, n_valid);
   return gn_check_launch();
 }
 

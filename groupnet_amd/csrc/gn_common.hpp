@@ -16,6 +16,12 @@ static inline bool gn_aligned16(const void* p) { return (reinterpret_cast<uintpt
 
 static inline int gn_check_launch() { return hipGetLastError() == hipSuccess ? GN_OK : GN_ERR_LAUNCH; }
 
+// The per-scene counts of a ragged launch: a non-NULL, 4-byte aligned device array
+static inline int gn_need_counts(const int* n_valid) {
+  if (n_valid == nullptr) return GN_ERR_NULL;
+  return (reinterpret_cast<uintptr_t>(n_valid) & 3u) != 0 ? GN_ERR_ALIGN : GN_OK;
+}
+
 #define GN_REQUIRE_PTR(p) \
   do {                    \
     if ((p) == nullptr) return GN_ERR_NULL; \

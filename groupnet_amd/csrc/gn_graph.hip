@@ -1168,7 +1168,7 @@ __global__ __launch_bounds__(kBlock) void agg_scatter_ragged_kernel(ScatterTable
 
 // Zeroes the padded positions of a list of tensors in one launch (gn_zero_padding): blockIdx.y = tensor; rows r >= nb of
 // a tensor with N rows per scene (node rows, or the N hyperedge rows of a top-k module), ordered pair rows i*N + j with
-// i >= nb or j >= nb of one with N*N.  Rows are `width` bytes at a pitch of `pitch` bytes, written as 4-byte words where
+// i >= nb or j >= nb of one with N*N, unordered pair rows (i, j >= i) with j >= nb of one with N(N+1)/2.  Rows are `width` bytes at a pitch of `pitch` bytes, written as 4-byte words where
 // address, width and pitch allow it, else as 2-byte words (a bf16 row of an odd number of elements).
 struct ZeroTable {
   gn_zero_item_t t[GN_MAX_ZERO_ITEMS];
@@ -1188,11 +1188,15 @@ __device__ __forceinline__ void zero_unit(const gn_zero_item_t& it, bool words, 
   if (words) reinterpret_cast<unsigned int*>(row)[c] = 0u;
   else reinterpret_cast<unsigned short*>(row)[c] = (unsigned short)0;
 }
+// rows per scene of a tensor of gn_zero_padding, by its kind
+__host__ __device__ inline int zero_kind_rows(int kind, int N) {
+  return kind == GN_ZERO_PAIR_ROWS ? N * N : kind == GN_ZERO_SYM_PAIR_ROWS ? N * (N + 1) / 2 : N;
+}
 __global__ __launch_bounds__(kBlock) void zero_padding_kernel(ZeroTable T, int B, int N, const int* __restrict__ n_valid) {
   const gn_zero_item_t it = T.t[blockIdx.y];
   bool words;
   const int wu = zero_row_units(it, words);
-  const int R = it.kind == GN_ZERO_PAIR_ROWS ? N * N : N;
+  const int R = zero_kind_rows(it.kind, N);
   const long long total = (long long)B * R * wu;
   for (long long idx = (long long)blockIdx.x * kBlock + threadIdx.x; idx < total; idx += (long long)gridDim.x * kBlock) {
     const long long br = idx / wu;
@@ -1203,6 +1207,10 @@ __global__ __launch_bounds__(kBlock) void zero_padding_kernel(ZeroTable T, int B
     if (it.kind == GN_ZERO_PAIR_ROWS) {
       const int i = r / N, j = r - i * N;
       pad = i >= nb || j >= nb;
+    } else if (it.kind == GN_ZERO_SYM_PAIR_ROWS) {
+      int i, j;
+      gn_pair_decode(r, N, i, j);      // i <= j: the larger end decides
+      pad = j >= nb;
     } else {
       pad = r >= nb;
     }
@@ -1501,16 +1509,10 @@ extern "C" int gn_affinity_plan_f32(const float* f, float* corr, int B, int N, i
   return plan == nullptr ? GN_ERR_NULL : affinity_entry(f, corr, B, N, D, nullptr, plan);
 }
 
-// the per-scene agent counts of a ragged entry point: a device array of ints
-static int need_counts(const int* n_valid) {
-  if (n_valid == nullptr) return GN_ERR_NULL;
-  return (reinterpret_cast<uintptr_t>(n_valid) & 3u) != 0 ? GN_ERR_ALIGN : GN_OK;
-}
-
 // TE: rows of corr per band; sl: the kernel's scale table; ragged: the launch over per-scene counts (n_valid)
 static int topk_plan(const float* corr, float* const* H_list, const int* k_list, int n_scales, int B, int N, bool ragged,
                      const int* n_valid, gn_launch_plan_t& p, ScaleList& sl) {
-  if (ragged) GN_CHECK(need_counts(n_valid));
+  if (ragged) GN_CHECK(gn_need_counts(n_valid));
   GN_REQUIRE_PTR(corr);
   if (B <= 0 || N <= 0 || n_scales < 1) return GN_ERR_SHAPE;
   GN_CHECK(fill_scales(sl, H_list, k_list, n_scales, N));
@@ -1608,7 +1610,7 @@ struct AffinityTopkArgs {
 // sl, ml: the kernel's scale and mask tables
 static int affinity_topk_plan(const AffinityTopkArgs& a, bool twin, gn_launch_plan_t& p, ScaleList& sl, MaskList& ml) {
   if (a.ragged) {
-    GN_CHECK(need_counts(a.n_valid));
+    GN_CHECK(gn_need_counts(a.n_valid));
     // the ragged form has no embedding front-end and no mask lists
     if (a.extras != nullptr && a.extras->x_raw != nullptr) return GN_ERR_SHAPE;
     if (a.rowmask_list != nullptr || a.colmask_list != nullptr) return GN_ERR_SHAPE;
@@ -1747,7 +1749,7 @@ static void n2e_pair_shape(int B, int N, int E, int& SG, int& bands) {
 // ragged: the launch over per-scene counts (gn_node2edge_ragged_*; no words): the same plan, its kernel the ragged one
 static int node2edge_plan(const gn_n2e_group_t* groups, const unsigned long long* const* rowmasks, int n_groups, int B,
                           int N, bool ragged, const int* n_valid, bool twin, const GnSwitches& sw, gn_launch_plan_t& p) {
-  if (ragged) GN_CHECK(need_counts(n_valid));
+  if (ragged) GN_CHECK(gn_need_counts(n_valid));
   int rc = check_groups(groups, n_groups);
   if (rc != GN_OK) return rc;
   if (B <= 0 || N <= 0) return GN_ERR_SHAPE;
@@ -2185,7 +2187,7 @@ extern "C" int gn_agg_scatter_plan_bf16(const gn_scatter_group_t* groups, int n_
 // their own).  divisor == 0: each scene by its own count.
 static int scatter_ragged_plan(const gn_scatter_group_t* groups, int n_groups, int B, int N, float divisor, bool twin,
                                const int* n_valid, gn_launch_plan_t& p) {
-  GN_CHECK(need_counts(n_valid));
+  GN_CHECK(gn_need_counts(n_valid));
   GN_CHECK(check_groups(groups, n_groups));
   if (B <= 0 || N <= 0 || !(divisor >= 0.f) || N > 32767) return GN_ERR_SHAPE;
   plan_begin(p, n_groups);
@@ -2242,17 +2244,18 @@ extern "C" int gn_agg_scatter_ragged_plan_bf16(const gn_scatter_group_t* groups,
 // is one row, and neither N nor the kind is read.
 static int zero_items(const gn_zero_item_t* items, int n_items, int B, int N, bool by_kind, const int* n_valid,
                       ZeroTable& T, long long& most) {
-  GN_CHECK(need_counts(n_valid));
+  GN_CHECK(gn_need_counts(n_valid));
   if (items == nullptr) return GN_ERR_NULL;
   if (n_items < 1 || n_items > GN_MAX_ZERO_ITEMS || B <= 0 || (by_kind && (N <= 0 || N > 32767))) return GN_ERR_SHAPE;
   most = 0;
   for (int g = 0; g < n_items; ++g) {
     const gn_zero_item_t& it = items[g];
     if (it.ptr == nullptr) return GN_ERR_NULL;
-    if (by_kind && (it.kind < GN_ZERO_NODE_ROWS || it.kind > GN_ZERO_PAIR_ROWS)) return GN_ERR_SHAPE;
+    if (by_kind && (it.kind < GN_ZERO_NODE_ROWS || it.kind > GN_ZERO_PAIR_ROWS) && it.kind != GN_ZERO_SYM_PAIR_ROWS)
+      return GN_ERR_SHAPE;
     if (it.width <= 0 || it.pitch < it.width) return GN_ERR_SHAPE;
     if ((reinterpret_cast<uintptr_t>(it.ptr) & 1u) || (it.width & 1) || (it.pitch & 1)) return GN_ERR_ALIGN;
-    const long long rows = !by_kind ? 1 : it.kind == GN_ZERO_PAIR_ROWS ? (long long)N * N : N;
+    const long long rows = !by_kind ? 1 : zero_kind_rows(it.kind, N);
     const long long words = (long long)B * rows * (it.width / zero_item_unit(it));
     most = words > most ? words : most;
     T.t[g] = it;
@@ -2315,7 +2318,7 @@ static int agent_counts_entry(const unsigned char* valid, int B, int N, int* n_v
                               gn_stream_t stream, gn_launch_plan_t* plan) {
   GN_REQUIRE_PTR(valid);
   GN_REQUIRE_PTR(status);
-  GN_CHECK(need_counts(n_valid));
+  GN_CHECK(gn_need_counts(n_valid));
   if ((reinterpret_cast<uintptr_t>(status) & 3u) != 0) return GN_ERR_ALIGN;
   if (B <= 0 || N <= 0) return GN_ERR_SHAPE;
   gn_launch_plan_t p;

@@ -26,7 +26,7 @@ import torch.nn as nn
 from . import MS_HGNN_batch as _mods
 from . import ops, route
 from .MS_HGNN_batch import (MS_HGNN_hyper, MS_HGNN_oridinary, _needs_grad, _plist, masks_apply, ragged_counts,
-                            run_message_passing)
+                            ragged_grad_refusals, run_message_passing)
 
 Tensor = torch.Tensor
 
@@ -44,14 +44,15 @@ def draw_noise(shapes: Sequence[Tuple[int, int, int]], rounds: int, device: torc
     return [[_mods._draw_uniform(shp, device) for _ in range(rounds)] for shp in shapes]
 
 
-def graph_route(S: int, B: int, N: int, D: int, facts: route.StageFacts, ragged: bool = False, training: bool = False
-                ) -> route.GraphStage:
+def graph_route(S: int, B: int, N: int, D: int, facts: route.StageFacts, ragged: bool = False, training: bool = False,
+                ragged_training: bool = False) -> route.GraphStage:
     """`route.graph_stage_route` for a block without the embedding front-end.  The library is asked about the launch that
     is then built, mask words included (which cannot change the answer today: masks need N <= 64, where the tile at
     D = 64 with eight scales of mask words is 58 384 B of the 128 KiB)."""
     masked = masks_apply(N)
     form = ops.graph_form(N, D, 0, S if route.graph_stage_masks(S, masked, ragged) else 0)
-    return route.graph_stage_route(S, form, B * N, masked=masked, ragged=ragged, training=training, facts=facts)
+    return route.graph_stage_route(S, form, B * N, masked=masked, ragged=ragged, training=training, facts=facts,
+                                   ragged_training=ragged_training)
 
 
 _FORK_STREAMS = {}
@@ -115,16 +116,19 @@ _TRAINING = route.StageFacts(grouped=True, latency_form=False, capturing=False, 
 
 
 def multiscale_autograd(pair: MS_HGNN_oridinary, hypers: Sequence[MS_HGNN_hyper], scales: Sequence[int], f: Tensor,
-                        noise_u: Optional[Sequence] = None) -> Tuple[Tensor, Optional[Tensor]]:
+                        noise_u: Optional[Sequence] = None, counts=None) -> Tuple[Tensor, Optional[Tensor]]:
     """cat(f, pairwise(f), hyper_s(f, corr)...) and cat(H_s) with autograd attached: incidences from the graph stage
     (constants of the backward), then ONE `MSHGNNFunction` node over all modules.  In mask form (`masks_apply(N)`) the
     fused launch also emits the member words, which the forward and the backward then read.  The device counter is the
-    caller's to bump."""
+    caller's to bump.  ``counts``: the `ops.AgentCounts` of a ragged batch (`set_ragged_training`) — the graph stage
+    builds the ragged incidences, forward and backward take their count-aware routes."""
     from .backward import MSHGNNFunction
     S = len(hypers)
     fd = f.detach().contiguous()
     B, N, D = fd.shape
-    _, graphs, new_H, *_ = build_graphs(graph_route(S, B, N, D, _TRAINING, training=True), fd, scales)
+    ragged = counts is not None
+    _, graphs, new_H, *_ = build_graphs(graph_route(S, B, N, D, _TRAINING, ragged=ragged, training=True,
+                                                    ragged_training=ragged), fd, scales, counts=counts)
     mods = (pair, *hypers)
     if noise_u is None:
         noise_u = draw_noise(noise_shapes(pair, hypers, scales, B, N), pair.nmp_layers, fd.device)
@@ -132,7 +136,7 @@ def multiscale_autograd(pair: MS_HGNN_oridinary, hypers: Sequence[MS_HGNN_hyper]
     if len(nz) != 1 + S:
         raise ValueError(f"noise_u: need {1 + S} entries (pairwise + one per scale)")
     params = [p for m in mods for p in _plist(m)]
-    res = MSHGNNFunction.apply(mods, (None, *graphs), nz, *([f] * (1 + S)), *params)
+    res = MSHGNNFunction.apply(mods, (None, *graphs), nz, counts, *([f] * (1 + S)), *params)
     return torch.cat([f, *res[0::2]], dim=-1), new_H
 
 
@@ -184,11 +188,11 @@ class MultiScaleHGNN(nn.Module):
         rows of scene b are real agents, the rest is finite padding.  The valid rows of the module columns of ``final``
         and the valid block of ``new_H`` are what the block computes for each scene alone at its own size; padded
         positions are zeros (the first D columns of ``final`` stay the copy of f).  The noise keeps its padded shapes.
-        Inference only."""
+        Under autograd only with `set_ragged_training(True)` ("Ragged batches", Training)."""
         ops._req(f, "f", (None, None, self.h_dim), ops._ACT_DTYPES)
         B, N, D = f.shape
         S = len(self.hyper_scales)
-        counts = ragged_counts(n_agents, f, grad=_needs_grad(self, f),
+        counts = ragged_counts(n_agents, f, **ragged_grad_refusals(_needs_grad(self, f), N),
                                listall=any(m.listall for m in self.interaction_hyper))
         if _needs_grad(self, f):
             if f.dtype == torch.bfloat16:
@@ -197,7 +201,7 @@ class MultiScaleHGNN(nn.Module):
                 if advance:
                     ops.counter_add(advance[0], advance[1])
                 out, new_H = multiscale_autograd(self.interaction, list(self.interaction_hyper), self.hyper_scales,
-                                                 f.float(), noise_u)
+                                                 f.float(), noise_u, counts)
                 return out.to(torch.bfloat16), (None if new_H is None else new_H.to(torch.bfloat16))
             if f.dtype != torch.float32:
                 raise NotImplementedError("activations must be fp32 or bf16")
@@ -205,7 +209,8 @@ class MultiScaleHGNN(nn.Module):
             # the concat is an ordinary differentiable torch.cat
             if advance:
                 ops.counter_add(advance[0], advance[1])
-            return multiscale_autograd(self.interaction, list(self.interaction_hyper), self.hyper_scales, f, noise_u)
+            return multiscale_autograd(self.interaction, list(self.interaction_hyper), self.hyper_scales, f, noise_u,
+                                       counts)
         if noise_u is None:
             noise_u = draw_noise(self.noise_shapes(B, N), self.interaction.nmp_layers, f.device)
         elif len(noise_u) != 1 + S:

@@ -338,6 +338,7 @@ def counts_from_mask(valid: Tensor, out: Optional[Tensor] = None, status: Option
 
 
 ZERO_NODE_ROWS, ZERO_EDGE_ROWS, ZERO_PAIR_ROWS = _lib.ZERO_NODE_ROWS, _lib.ZERO_EDGE_ROWS, _lib.ZERO_PAIR_ROWS
+ZERO_SYM_PAIR_ROWS = _lib.ZERO_SYM_PAIR_ROWS
 
 
 def _zero_launch(who: str, hint: str, items, n_agents, rows: Optional[int], layout) -> None:
@@ -375,8 +376,9 @@ def zero_padding(items: Sequence[Tuple[Tensor, int]], n_agents) -> None:
     """Zero the padded positions of several tensors of a ragged batch in ONE launch (gn_zero_padding).  items =
     [(tensor, kind)]: ZERO_NODE_ROWS — (B,N,w), rows n >= n_b; ZERO_EDGE_ROWS — the (B,N,w) hyperedge rows of a top-k
     module, rows e >= n_b (the (B,1,w) rows of a scale-N module are valid: they are skipped here); ZERO_PAIR_ROWS —
-    (B,N*N,w) ordered pair rows with an end >= n_b, or a contiguous (B,N,N) matrix per scene (corr, H, new_H).  A tensor
-    may be a last-dim slice of a wider contiguous one; fp32 or bf16 (rows of an even number of bytes)."""
+    (B,N*N,w) ordered pair rows with an end >= n_b, or a contiguous (B,N,N) matrix per scene (corr, H, new_H);
+    ZERO_SYM_PAIR_ROWS — (B,N(N+1)/2,w) unordered pair rows (`pair_count`, row-major over i <= j) with an end >= n_b.  A
+    tensor may be a last-dim slice of a wider contiguous one; fp32 or bf16 (rows of an even number of bytes)."""
     def layout(t, kind):
         N, R, w = n_agents.N, t.shape[1], t.shape[2]
         if kind == ZERO_PAIR_ROWS and (R, w) == (N, N) and t.is_contiguous():
@@ -387,7 +389,8 @@ def zero_padding(items: Sequence[Tuple[Tensor, int]], n_agents) -> None:
             pitch = t.stride(1)
         if kind == ZERO_EDGE_ROWS and R == 1:
             return None
-        if R != (N * N if kind == ZERO_PAIR_ROWS else N) or kind not in (ZERO_NODE_ROWS, ZERO_EDGE_ROWS, ZERO_PAIR_ROWS):
+        rows = {ZERO_NODE_ROWS: N, ZERO_EDGE_ROWS: N, ZERO_PAIR_ROWS: N * N, ZERO_SYM_PAIR_ROWS: pair_count(N)}
+        if R != rows.get(kind):
             raise ValueError(f"zero_padding: kind {kind} does not go with {R} rows per scene at N = {N}")
         return pitch, w
 

@@ -113,16 +113,18 @@ def graph_stage_masks(S: int, masked: bool, ragged: bool) -> bool:
 
 @functools.lru_cache(maxsize=None)
 def graph_stage_route(S: int, form: str, rows: int, *, masked: bool, ragged: bool, training: bool,
-                      facts: StageFacts) -> GraphStage:
+                      facts: StageFacts, ragged_training: bool = False) -> GraphStage:
     """The graph stage of one forward over S scales.  form: the library's answer for the launch in question
     (`ops.graph_form`: "tail" | "fused" | "banded" — the tile rule is stated in C only); rows = B*N; masked: the mask form
     is on and `masks_in_range(N)` holds; training: the forward runs under autograd — it writes into no final and leaves
     the counter to its caller, and nothing is forked, deferred or asked of the closing stage.
-    ragged (inference only): no masks, and the job — which is never the tail, `AffinityTail.fits_tail` — is still handed
-    on where the caller defers: the first node stage issues it on its own.
+    ragged: no masks, and the job — which is never the tail, `AffinityTail.fits_tail` — is still handed
+    on where the caller defers: the first node stage issues it on its own.  ragged and training go together only under
+    the caller's opt-in, ragged_training (`MS_HGNN_batch.set_ragged_training`): the stage is then the training one —
+    launched at once, no final, the counter is the caller's — over the counts.
     Whether a deferred job rides as tail workgroups ("tail") or is issued beside the node stage ("fused") is the node
     stage's decision; here only "banded" or not matters."""
-    if ragged and training:
+    if ragged and training and not ragged_training:
         raise NotImplementedError("ragged batches are inference-only")
     if form != BANDED and (S or facts.embed):
         kind = FUSED            # the front-end's launch needs >= 1 scale: the builder gives it N, the all-ones edge
@@ -140,19 +142,23 @@ def graph_stage_route(S: int, form: str, rows: int, *, masked: bool, ragged: boo
 
 @functools.lru_cache(maxsize=None)
 def message_passing_route(N: int, modules: Tuple[Tuple[bool, int], ...], *, twin: bool, training: bool, matrix16: bool,
-                          knobs: Knobs, closing_asked: bool, ragged: bool = False) -> Route:
+                          knobs: Knobs, closing_asked: bool, ragged: bool = False, ragged_training: bool = False) -> Route:
     """The route of one forward over N agents.  modules: (pairwise, K edge types) per module in launch order; twin: bf16
     storage; training: the forward keeps what a backward reads; matrix16: the 16-bit-core weight images are in use;
     closing_asked: the caller would like the aggregation launch to apply the closing MLP.
-    ragged: the scenes hold different numbers of agents (N is the padded size; inference only).  The agent count enters
+    ragged: the scenes hold different numbers of agents (N is the padded size; a training forward only under the
+    caller's opt-in, ragged_training — `MS_HGNN_batch.set_ragged_training`).  The agent count enters
     the arithmetic in the node->edge pooling and in the scatter, so both run as their own (count-aware) launches and
     every form that fuses one of them into an MFMA kernel is left out: no pooling in the edge kernel, no node / scene
     form of the pairwise aggregation (their sums run over all N partners), no closing stage in the aggregation launch,
-    no fused scatter, no masks.  What stays is row-wise or reads the padding only through zero entries of H."""
+    no fused scatter, no masks.  What stays is row-wise or reads the padding only through zero entries of H.  That route
+    already keeps what a backward reads — the node->edge launch's `edges` of every module, the pair form on the per-node
+    first layer (no node form), the scatter launch's tensor as the closing MLP's input — so the ragged training forward
+    takes it as it is."""
     if twin and training:
         raise NotImplementedError("the bf16 twins are forward-only")
     if ragged:
-        if training:
+        if training and not ragged_training:
             raise NotImplementedError("ragged batches are inference-only")
         mods = [ModuleRoute(False, pairwise and not twin,
                             (TWIN_PAIR if twin else PAIR) if pairwise else (FUSED_GATHER if N <= _FUSED_GATHER_MAX_N else EO),
@@ -201,11 +207,16 @@ class BackwardRound:
 
 
 @functools.lru_cache(maxsize=None)
-def backward_round_route(N: int, pairwise: Tuple[bool, ...]) -> BackwardRound:
+def backward_round_route(N: int, pairwise: Tuple[bool, ...], ragged: bool = False) -> BackwardRound:
     """The route of one backward round over N agents (`backward.round_backward`).  pairwise: per module of the round.
     All of it hangs on whether a scene fits the per-scene node->edge backward.  Where it does not, a pairwise module
     needs ordered edge rows — the general kernel reads an incidence, and the pairwise one exists only per ordered edge —
     while its forward kept activations per unordered pair: they are re-computed, and since the re-computation is one
-    grouped launch per stage, for every module of the round."""
+    grouped launch per stage, for every module of the round.
+    ragged: the forward recorded per-scene counts.  The count-aware node->edge backward exists in the per-scene form
+    only (gn_node2edge_bwd_ragged_grouped_f32), so the round is the fitting one or none."""
     fits = N <= N2E_BWD_SCENE_MAX_N
+    if ragged and not fits:
+        raise NotImplementedError(f"the backward of a ragged batch needs N <= {N2E_BWD_SCENE_MAX_N} (got {N}): the "
+                                  "count-aware node->edge backward has the per-scene form only")
     return BackwardRound(pair_rows=fits, kept=fits or not any(pairwise), n2e_grouped=fits)

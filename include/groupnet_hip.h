@@ -574,11 +574,15 @@ int gn_agg_scatter_ragged_bf16(const gn_scatter_group_t* groups, int n_groups, i
  * else as 2-byte words: a bf16 row of an odd number of elements).  kind: GN_ZERO_NODE_ROWS — (B,N,.), rows n >= n_b; GN_ZERO_EDGE_ROWS —
  * the (B,N,.) hyperedge rows of a top-k module, rows e >= n_b (the single row of a scale-N module is always valid: do
  * not list it); GN_ZERO_PAIR_ROWS — (B,N*N,.) ordered pair rows i*N + j with i >= n_b or j >= n_b (also an (B,N,N)
- * matrix with width = the element size: corr, H, new_H).  Valid positions are not touched. */
+ * matrix with width = the element size: corr, H, new_H); GN_ZERO_SYM_PAIR_ROWS (an addition within ABI 40: the
+ * ragged backward's dfeat) — (B,N(N+1)/2,.) unordered pair rows (i, j >= i), row-major, with j >= n_b (an end of the pair
+ * is padding).  Valid positions are not touched.  Any other kind — 3 among them, which ABI 39 and 40 refused and callers
+ * may rely on — is GN_ERR_SHAPE. */
 #define GN_MAX_ZERO_ITEMS 24
 #define GN_ZERO_NODE_ROWS 0
 #define GN_ZERO_EDGE_ROWS 1
 #define GN_ZERO_PAIR_ROWS 2
+#define GN_ZERO_SYM_PAIR_ROWS 4
 typedef struct {
   void* ptr;
   long long pitch;
@@ -891,6 +895,20 @@ int gn_node2edge_bwd_grouped_f32(const gn_n2e_bwd_group_t* groups, int n_groups,
 int gn_node2edge_bwd_f32(const float* xp, const float* pq, const float* H, const float* w2, const float* b2,
                          const float* dedges, float* dxp, float* dpq, float* dw2, float* db2, int B, int N,
                          int E, int sym, gn_stream_t stream);
+/* The same two launches over a ragged batch (header comment, "Ragged batches"; additions within ABI 40): back through
+ * gn_node2edge_ragged_f32.  The arguments of their counterparts plus n_valid (validated as everywhere: GN_ERR_NULL /
+ * GN_ERR_ALIGN), the same in-out convention.  Scene b, n_b = n_valid[b] clamped to [0, N]: the softmax of a hyperedge
+ * runs over the scene's n_b nodes (n_b - members non-members, the 0 in the running maximum only where one exists); an
+ * explicit H is read at its columns n < n_b (the ragged incidences are zero beyond) and a row without members there is
+ * skipped; a pairwise group walks the pairs with both ends < n_b and reads dedges at their PADDED rows (i*N + j, or the
+ * unordered row of (i, j) at size N).  Rows n >= n_b of dxp and dpq are neither read nor written; a scene with
+ * n_b == 0 adds nothing anywhere.  The per-scene form only — one workgroup per scene, the padded scene's LDS request
+ * (4 N 64 + 64 + 16 N) 4 B — so N > 140 is GN_ERR_LDS and nothing is launched. */
+int gn_node2edge_bwd_ragged_grouped_f32(const gn_n2e_bwd_group_t* groups, int n_groups, int B, int N,
+                                        const int* n_valid, gn_stream_t stream);
+int gn_node2edge_bwd_ragged_f32(const float* xp, const float* pq, const float* H, const float* w2, const float* b2,
+                                const float* dedges, float* dxp, float* dpq, float* dw2, float* db2, int B, int N,
+                                int E, int sym, const int* n_valid, gn_stream_t stream);
 
 /* ---- device noise (build's own; the reference draws torch.rand on the host) --------------------
  * U[i] = Philox4x32-10(counter = (i + offset) / 4, key = seed)[(i + offset) % 4] >> 8, scaled to
