@@ -162,6 +162,95 @@ def ragged_counts(n_agents, x: Tensor, **refusals: bool) -> Optional[ops.AgentCo
     return counts
 
 
+# ---------------------------------------------------------------------------------------------
+# agents missing anywhere (``n_agents`` = an `ops.AgentSubset`): compaction, the ragged route, expansion
+# ---------------------------------------------------------------------------------------------
+def subset_of(n_agents, x: Tensor, grad: bool, **refusals: bool) -> Optional["ops.AgentSubset"]:
+    """``n_agents`` as the `ops.AgentSubset` of a forward over the (B,N,...) input ``x``, or None where it is anything
+    else.  A subset call is refused here, before anything is uploaded or launched: a subset of other sizes
+    (ValueError), what a ragged call is refused for (`refuse_ragged`, `ragged_grad_refusals`), and under autograd a
+    subset built from a GPU mask, which admits empty scenes."""
+    if not isinstance(n_agents, ops.AgentSubset):
+        return None
+    ops.agent_counts(n_agents, x.shape[0], x.shape[1], x.device)      # the sizes
+    refuse_ragged(**refusals, **ragged_grad_refusals(grad, x.shape[1]))
+    if grad and n_agents.admits_empty:
+        raise NotImplementedError("n_agents: counts that admit empty slots (a subset built from a GPU mask) are "
+                                  "inference-only")
+    return n_agents
+
+
+def subset_noise(noise_u, shape: Tuple[int, int, int], rounds: int, device) -> Optional[list]:
+    """One module's noise on the subset route, in the ORIGINAL layout: the caller's tensor(s) or `ops.PhiloxNoise`
+    handle(s), checked, as a list per round; without them the host-mode draws of every round, made here as the engine
+    would make them; None in device mode (the draws are those of the compacted batch)."""
+    if noise_u is None:
+        if _NoiseState.mode != "host":
+            return None
+        return [_draw_uniform(shape, device) for _ in range(rounds)]
+    us = [noise_u] if isinstance(noise_u, (torch.Tensor, ops.PhiloxNoise)) else list(noise_u)
+    for u in us:
+        if not isinstance(u, ops.PhiloxNoise):
+            ops._req(u, "noise_u", shape)
+    return us
+
+
+def remap_noise(us: Optional[list], kind: int, items: list) -> Optional[list]:
+    """The compacted twin of a module's noise list: every tensor gets a scratch twin and an item in ``items`` (the
+    caller's compaction launch); handles and the single row of a scale-N module (``kind`` None) pass through."""
+    if us is None or kind is None:
+        return us
+    out = []
+    for u in us:
+        if isinstance(u, torch.Tensor):
+            c = torch.empty_like(u)
+            items.append((u, c, kind))
+            u = c
+        out.append(u)
+    return out
+
+
+class _Remap(torch.autograd.Function):
+    """`ops.remap_rows` of several tensors under autograd: ``to_slots`` False — the compaction (map = order), True —
+    the expansion (map = slot).  Each is the other's adjoint on the positions that carry values: the backward is the
+    same launch with the other map over the incoming gradients, into fresh tensors (the caller's are not written)."""
+
+    @staticmethod
+    def forward(ctx, sub, to_slots: bool, kinds: tuple, *tensors: Tensor):
+        ctx.sub, ctx.to_slots, ctx.kinds = sub, to_slots, kinds
+        srcs = [t.contiguous() for t in tensors]
+        outs = [torch.empty_like(s) for s in srcs]
+        ops.remap_rows(list(zip(srcs, outs, kinds)), sub.slot if to_slots else sub.order)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        res, items = [None] * len(grads), []
+        for i, (g, kind, need) in enumerate(zip(grads, ctx.kinds, ctx.needs_input_grad[3:])):
+            if g is not None and need:
+                g = g.contiguous()
+                res[i] = torch.empty_like(g)
+                items.append((g, res[i], kind))
+        if items:
+            ops.remap_rows(items, ctx.sub.order if ctx.to_slots else ctx.sub.slot)
+        return (None, None, None, *res)
+
+
+def _check_subset_out(out: Optional[Tensor], h: Tensor, width: int) -> None:
+    """A caller's ``out=`` on the subset route: where the expansion writes node_feat, (B,N,width) of h's type."""
+    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == h.dtype
+                                and tuple(out.shape) == (h.shape[0], h.shape[1], width)):
+        raise ValueError(f"out: a GPU tensor of shape {(h.shape[0], h.shape[1], width)} and dtype {h.dtype}")
+
+
+def incidence_item(Hc: Tensor, H: Tensor) -> Tuple[Tensor, Tensor, int]:
+    """The expansion item of one module's incidence: a (B,N,N) top-k H as a matrix of ordered pairs, the single (B,1,N) row
+    of a scale-N module as node rows of its (B,N,1) view."""
+    if Hc.shape[1] == 1 and Hc.shape[2] != 1:
+        return Hc.transpose(1, 2), H.transpose(1, 2), ops.REMAP_NODE_ROWS
+    return Hc, H, ops.REMAP_PAIR_ROWS
+
+
 _warned_grad = False
 
 
@@ -627,6 +716,9 @@ class MS_HGNN_oridinary(_MessagePassing):
         ops._req(h_states, "h_states", (None, None, self.h_dim), ops._ACT_DTYPES)
         N = h_states.shape[1]
         grad = _needs_grad(self, h_states)
+        sub = subset_of(n_agents, h_states, grad)
+        if sub is not None:
+            return self._forward_subset(h_states, noise_u, out, sub, grad)
         n_agents = ragged_counts(n_agents, h_states, **ragged_grad_refusals(grad, N))
         if h_states.shape[0] and N and grad:
             return self._forward_autograd(h_states, None, noise_u, out, n_agents)
@@ -635,6 +727,32 @@ class MS_HGNN_oridinary(_MessagePassing):
             nf = out if out is not None else h_states.new_empty((h_states.shape[0], N, self.bottleneck_dim))
             return nf, h_states.new_empty((h_states.shape[0], N * N, self.edge_types))
         return self._run(h_states, None, N * N, noise_u, out, n_agents)
+
+    def _forward_subset(self, h: Tensor, noise_u, out: Optional[Tensor], sub: "ops.AgentSubset", grad: bool):
+        """``n_agents`` = an `ops.AgentSubset` ("Agents missing anywhere"): ONE launch compacts the
+        features and the noise tensors of every round into scratch, the ragged forward runs on them as with
+        ``n_agents=<counts>``, ONE launch expands node_feat and factors to the original slots and zeroes the rest.
+        Invalid input rows are never read.  Under autograd the two launches are `_Remap` nodes."""
+        B, N = h.shape[0], h.shape[1]
+        if grad and out is not None:
+            raise ValueError("out= is an inference-time extra; under autograd the module returns a new tensor")
+        _check_subset_out(out, h, self.bottleneck_dim)
+        us = subset_noise(noise_u, (B, N * N, self.edge_types), self.nmp_layers, h.device)
+        items: list = []
+        uc = remap_noise(us, ops.REMAP_PAIR_ROWS, items)
+        if grad:
+            if items:
+                ops.remap_rows(items, sub.order)
+            (hc,) = _Remap.apply(sub, False, (ops.REMAP_NODE_ROWS,), h)
+            nf, fac = self.forward(hc, noise_u=uc, n_agents=sub.compacted)
+            return _Remap.apply(sub, True, (ops.REMAP_NODE_ROWS, ops.REMAP_PAIR_ROWS), nf, fac)
+        hc = torch.empty_like(h)
+        ops.remap_rows([(h, hc, ops.REMAP_NODE_ROWS)] + items, sub.order)
+        nfc, facc = self.forward(hc, noise_u=uc, n_agents=sub.compacted)
+        nf = out if out is not None else torch.empty_like(nfc)
+        fac = torch.empty_like(facc)
+        ops.remap_rows([(nfc, nf, ops.REMAP_NODE_ROWS), (facc, fac, ops.REMAP_PAIR_ROWS)], sub.slot)
+        return nf, fac
 
 
 class MS_HGNN_hyper(_MessagePassing):
@@ -702,6 +820,9 @@ class MS_HGNN_hyper(_MessagePassing):
         `set_ragged_training(True)` (INTEGRATION.md, "Ragged batches", Training)."""
         ops._req(h_states, "h_states", (None, None, self.h_dim), ops._ACT_DTYPES)
         grad = _needs_grad(self, h_states)
+        sub = subset_of(n_agents, h_states, grad, handed_in=H is not None or masks is not None, listall=self.listall)
+        if sub is not None:
+            return self._forward_subset(h_states, corr, noise_u, out, sub, grad)
         n_agents = ragged_counts(n_agents, h_states, handed_in=H is not None or masks is not None, listall=self.listall,
                                  **ragged_grad_refusals(grad, h_states.shape[1]))
         if n_agents is not None:
@@ -738,3 +859,44 @@ class MS_HGNN_hyper(_MessagePassing):
             ops._req(H, "H", (h_states.shape[0], None, h_states.shape[1]))
         node_feat, factor = self._run(h_states, ops.Incidence(H, masks), H.shape[1], noise_u, out)
         return node_feat, factor, (H if H.dtype == h_states.dtype else H.to(h_states.dtype))    # type_as(feat), :376,384
+
+    def _forward_subset(self, h: Tensor, corr: Tensor, noise_u, out: Optional[Tensor], sub: "ops.AgentSubset", grad: bool):
+        """``n_agents`` = an `ops.AgentSubset`: as `MS_HGNN_oridinary._forward_subset`, with the caller's ``corr``
+        compacted as a matrix of ordered pairs and H expanded with the other two results.  Hyperedge rows of a top-k
+        module (factor, rows of H, the noise) move like node rows; the single row of a scale-N module stays."""
+        B, N = h.shape[0], h.shape[1]
+        if self.scale > N:
+            raise RuntimeError("selected index k out of range")
+        if grad and out is not None:
+            raise ValueError("out= is an inference-time extra; under autograd the module returns a new tensor")
+        _check_subset_out(out, h, self.bottleneck_dim)
+        ops._req(corr, "corr", (B, N, N), ops._ACT_DTYPES)
+        rows = ops.REMAP_NODE_ROWS if self.scale != N else None      # E = N hyperedge rows, or the one row that stays
+        us = subset_noise(noise_u, (B, 1 if self.scale == N else N, self.edge_types), self.nmp_layers, h.device)
+        cc = torch.empty_like(corr)
+        items: list = [(corr.detach(), cc, ops.REMAP_PAIR_ROWS)]
+        uc = remap_noise(us, rows, items)
+        if grad:
+            ops.remap_rows(items, sub.order)
+            (hc,) = _Remap.apply(sub, False, (ops.REMAP_NODE_ROWS,), h)
+            nfc, facc, Hc = self.forward(hc, cc, noise_u=uc, n_agents=sub.compacted)
+            fac_kind = ops.REMAP_NODE_ROWS if rows is not None else None
+            if fac_kind is None:
+                (nf,), fac = _Remap.apply(sub, True, (ops.REMAP_NODE_ROWS,), nfc), facc
+            else:
+                nf, fac = _Remap.apply(sub, True, (ops.REMAP_NODE_ROWS, fac_kind), nfc, facc)
+            H = torch.empty_like(Hc)
+            ops.remap_rows([incidence_item(Hc, H)], sub.slot)
+            return nf, fac, H
+        hc = torch.empty_like(h)
+        ops.remap_rows([(h, hc, ops.REMAP_NODE_ROWS)] + items, sub.order)
+        nfc, facc, Hc = self.forward(hc, cc, noise_u=uc, n_agents=sub.compacted)
+        nf = out if out is not None else torch.empty_like(nfc)
+        H = torch.empty_like(Hc)
+        back = [(nfc, nf, ops.REMAP_NODE_ROWS), incidence_item(Hc, H)]
+        fac = facc
+        if rows is not None:
+            fac = torch.empty_like(facc)
+            back.append((facc, fac, ops.REMAP_NODE_ROWS))
+        ops.remap_rows(back, sub.slot)
+        return nf, fac, H

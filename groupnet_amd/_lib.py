@@ -86,6 +86,13 @@ class ZeroItem(ctypes.Structure):
     _fields_ = [("ptr", _P), ("pitch", ctypes.c_longlong), ("width", _I), ("kind", _I)]
 
 
+class RemapItem(ctypes.Structure):
+    __slots__ = ()
+    c_name = "gn_remap_item_t"
+    _fields_ = [("src", _P), ("dst", _P), ("src_scene", ctypes.c_longlong), ("dst_scene", ctypes.c_longlong),
+                ("src_pitch", ctypes.c_longlong), ("dst_pitch", ctypes.c_longlong), ("width", _I), ("kind", _I)]
+
+
 class Mlp2Group(ctypes.Structure):
     __slots__ = ()
     c_name = "gn_mlp2_group_t"
@@ -160,11 +167,13 @@ K_AFFINITY_TOPK, K_AFFINITY_TOPK_MASKS, K_AFFINITY_BANDED, K_TOPK_INCIDENCE = 19
 K_AGG_SCATTER, K_AGG_SCATTER_MASK, K_AGG_SCATTER_DIRECT, K_AGG_SCATTER_PAIRS = 23, 24, 25, 26     # ... the scatter
 # ... the ragged entry points
 K_AFFINITY_TOPK_RAGGED, K_TOPK_INCIDENCE_RAGGED, K_NODE2EDGE_RAGGED, K_AGG_SCATTER_RAGGED, K_ZERO_PADDING = 27, 28, 29, 30, 31
-K_LAST = K_ZERO_PADDING
+K_LAST = K_ZERO_PADDING                       # the end of the table: gn_kernel_name(K_LAST + 1) is NULL
+K_AGENT_SUBSET, K_REMAP_ROWS = 40, 41         # ... the subset route (agents missing anywhere), a range of its own
 MAX_GROUPS = 10
 MAX_ZERO_ITEMS = 24
 ZERO_NODE_ROWS, ZERO_EDGE_ROWS, ZERO_PAIR_ROWS, ZERO_SYM_PAIR_ROWS = 0, 1, 2, 4      # gn_zero_item_t.kind (3: refused)
 COUNTS_NOT_PREFIX, COUNTS_EMPTY = 1, 2                        # GN_COUNTS_*: the status word of gn_agent_counts_u8
+REMAP_NODE_ROWS, REMAP_PAIR_ROWS = 0, 1                       # gn_remap_item_t.kind
 
 # name -> (restype, argtypes); mirrors include/groupnet_hip.h one to one
 SIGNATURES = {
@@ -258,6 +267,10 @@ SIGNATURES = {
     "gn_zero_empty_scenes_plan": (_I, [ctypes.POINTER(ZeroItem), _I, _I, _P, ctypes.POINTER(LaunchPlan)]),
     "gn_agent_counts_u8": (_I, [_P, _I, _I, _P, _P, _P]),
     "gn_agent_counts_plan_u8": (_I, [_P, _I, _I, _P, _P, ctypes.POINTER(LaunchPlan)]),
+    "gn_agent_subset_u8": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
+    "gn_agent_subset_plan": (_I, [_P, _I, _I, _P, _P, _P, _P, ctypes.POINTER(LaunchPlan)]),
+    "gn_remap_rows": (_I, [ctypes.POINTER(RemapItem), _I, _I, _I, _P, _P]),
+    "gn_remap_rows_plan": (_I, [ctypes.POINTER(RemapItem), _I, _I, _I, _P, ctypes.POINTER(LaunchPlan)]),
     "gn_gemm_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _F, _F, _P]),
     "gn_gemm_grouped_f32": (_I, [ctypes.POINTER(GemmDesc), _I, _P]),
     "gn_typed_bwd_f32": (_I, [_P, _P, _P, _I, _P, _P, _P, ctypes.c_longlong, _I, _I, _P]),

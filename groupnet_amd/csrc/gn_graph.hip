@@ -1266,6 +1266,93 @@ __global__ __launch_bounds__(kBlock) void agent_counts_kernel(const unsigned cha
   }
 }
 
+// The stable compaction of a validity mask with holes (gn_agent_subset_u8): one wave per scene, as agent_counts_kernel — a
+// byte per lane, the ballot of a chunk is its validity word.  A valid lane's rank is the running base, carried
+// wave-uniformly from chunk to chunk, plus the population count of the ballot bits below it (mbcnt): it writes
+// slot[n] = rank and order[rank] = n, an invalid lane slot[n] = -1.  The ranks of a scene are 0 .. n_b - 1 without gaps,
+// so order[0 .. n_b) is written exactly once; the same wave then fills order[n_b .. N) with -1.  Valid agents keep their
+// relative order.  Lane 0 writes the count and ORs GN_COUNTS_EMPTY into the sticky status word, nothing else.
+__global__ __launch_bounds__(kBlock) void agent_subset_kernel(const unsigned char* __restrict__ valid, int B, int N,
+                                                              int* __restrict__ n_valid, int* __restrict__ order,
+                                                              int* __restrict__ slot, unsigned int* __restrict__ status) {
+  const int lane = threadIdx.x & 63;
+  const int b = gn_uniform((int)(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)));
+  if (b >= B) return;                                   // (whole waves leave: the ballots below see full waves)
+  const unsigned char* row = valid + (size_t)b * N;
+  int* ord = order + (size_t)b * N;
+  int* slt = slot + (size_t)b * N;
+  int base = 0;
+  for (int n0 = 0; n0 < N; n0 += 64) {
+    const int n = n0 + lane;
+    const bool v = n < N && row[n] != 0;                // lanes past the row vote 0
+    const unsigned long long m = __ballot(v);
+    const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
+    if (n < N) {
+      const int rank = base + below;                    // < N: at most n valid agents lie below slot n
+      slt[n] = v ? rank : -1;
+      if (v) ord[rank] = n;
+    }
+    base += __popcll(m);
+  }
+  for (int r = base + lane; r < N; r += 64) ord[r] = -1;
+  if (lane == 0) {
+    n_valid[b] = base;
+    if (base == 0) atomicOr(status, GN_COUNTS_EMPTY);
+  }
+}
+
+// Moves rows through a per-scene index map (gn_remap_rows): blockIdx.y = item; for every destination row,
+// dst[row] = map[...] >= 0 ? src[mapped row] : 0.  With map = order (gn_agent_subset_u8) this compacts a scene's valid
+// rows to the front, with map = slot it expands them back to their slots.  Node rows: row r of scene b comes from row
+// map[b, r]; ordered pair rows: row i*N + j from row map[b, i]*N + map[b, j], zero when either is unmapped.  Every
+// destination unit is written exactly once by the thread that owns it: a gather on the read side, coalesced stores, no
+// atomics.  The store unit of an item — 16, 8, 4 or 2 bytes — is the largest that divides its addresses, strides, pitches
+// and width; it is uniform over a workgroup.  A map entry outside -1 .. N - 1 counts as unmapped.
+struct RemapTable {
+  gn_remap_item_t t[GN_MAX_ZERO_ITEMS];
+};
+__host__ __device__ inline int remap_item_unit(const gn_remap_item_t& it) {
+  const uintptr_t all = reinterpret_cast<uintptr_t>(it.src) | reinterpret_cast<uintptr_t>(it.dst) | (uintptr_t)it.src_scene |
+                        (uintptr_t)it.dst_scene | (uintptr_t)it.src_pitch | (uintptr_t)it.dst_pitch | (uintptr_t)it.width;
+  return (all & 15u) == 0 ? 16 : (all & 7u) == 0 ? 8 : (all & 3u) == 0 ? 4 : 2;
+}
+template <typename U>
+__device__ __forceinline__ void remap_units(const gn_remap_item_t& it, int B, int N, const int* __restrict__ map) {
+  const int wu = it.width / (int)sizeof(U);
+  const bool pairs = it.kind == GN_REMAP_PAIR_ROWS;
+  const int R = pairs ? N * N : N;
+  const long long total = (long long)B * R * wu;
+  const unsigned char* src = reinterpret_cast<const unsigned char*>(it.src);
+  unsigned char* dst = reinterpret_cast<unsigned char*>(it.dst);
+  for (long long idx = (long long)blockIdx.x * kBlock + threadIdx.x; idx < total; idx += (long long)gridDim.x * kBlock) {
+    const long long br = idx / wu;
+    const int c = (int)(idx - br * wu);
+    const int b = (int)(br / R), r = (int)(br - (long long)b * R);
+    const int* mb = map + (size_t)b * N;
+    int m;
+    if (pairs) {
+      const int i = r / N, j = r - i * N;
+      const int mi = mb[i], mj = mb[j];
+      m = (mi >= 0 && mi < N && mj >= 0 && mj < N) ? mi * N + mj : -1;
+    } else {
+      m = mb[r];
+      m = m < N ? m : -1;
+    }
+    U v{};
+    if (m >= 0) v = *reinterpret_cast<const U*>(src + (size_t)b * it.src_scene + (size_t)m * it.src_pitch + sizeof(U) * (size_t)c);
+    *reinterpret_cast<U*>(dst + (size_t)b * it.dst_scene + (size_t)r * it.dst_pitch + sizeof(U) * (size_t)c) = v;
+  }
+}
+__global__ __launch_bounds__(kBlock) void remap_rows_kernel(RemapTable T, int B, int N, const int* __restrict__ map) {
+  const gn_remap_item_t it = T.t[blockIdx.y];
+  switch (remap_item_unit(it)) {
+    case 16: remap_units<f32x4>(it, B, N, map); break;
+    case 8: remap_units<unsigned long long>(it, B, N, map); break;
+    case 4: remap_units<unsigned int>(it, B, N, map); break;
+    default: remap_units<unsigned short>(it, B, N, map); break;
+  }
+}
+
 // --------------------------------------------------------------------------------------------
 // Exhaustive hyperedge search (init_adj_attention_listall, model/MS_HGNN_batch.py:390-414): hyperedge i =
 // the group of s agents containing i with the largest total affinity sum_{a,b in group} corr[a][b].
@@ -1445,6 +1532,9 @@ extern "C" const char* gn_kernel_name(int kernel) {
                                       "node2edge_ragged_kernel",
                                       "agg_scatter_ragged_kernel",
                                       "zero_padding_kernel"};
+  // the subset route's kernels have a range of their own: the table above ends where it ended
+  if (kernel == GN_K_AGENT_SUBSET) return "agent_subset_kernel";
+  if (kernel == GN_K_REMAP_ROWS) return "remap_rows_kernel";
   return kernel >= 0 && kernel <= GN_K_ZERO_PADDING ? names[kernel] : nullptr;
 }
 
@@ -2337,6 +2427,80 @@ extern "C" int gn_agent_counts_u8(const unsigned char* valid, int B, int N, int*
 extern "C" int gn_agent_counts_plan_u8(const unsigned char* valid, int B, int N, int* n_valid, unsigned int* status,
                                        gn_launch_plan_t* plan) {
   return plan == nullptr ? GN_ERR_NULL : agent_counts_entry(valid, B, N, n_valid, status, nullptr, plan);
+}
+
+// The subset of a validity mask with holes: grid (ceil(B / 4)), one wave per scene
+static int agent_subset_entry(const unsigned char* valid, int B, int N, int* n_valid, int* order, int* slot,
+                              unsigned int* status, gn_stream_t stream, gn_launch_plan_t* plan) {
+  GN_REQUIRE_PTR(valid);
+  GN_REQUIRE_PTR(status);
+  GN_CHECK(gn_need_counts(n_valid));
+  GN_CHECK(gn_need_counts(order));
+  GN_CHECK(gn_need_counts(slot));
+  if ((reinterpret_cast<uintptr_t>(status) & 3u) != 0) return GN_ERR_ALIGN;
+  if (B <= 0 || N <= 0) return GN_ERR_SHAPE;
+  gn_launch_plan_t p;
+  gn_launch_plan_t& q = plan != nullptr ? *plan : p;
+  plan_begin(q, 0);
+  q.kernel = GN_K_AGENT_SUBSET;
+  q.grid[0] = (B - 1) / (kBlock / 64) + 1;
+  if (plan != nullptr) return GN_OK;
+  hipLaunchKernelGGL(agent_subset_kernel, dim3(q.grid[0]), dim3(kBlock), 0, (hipStream_t)stream, valid, B, N, n_valid, order,
+                     slot, status);
+  return gn_check_launch();
+}
+extern "C" int gn_agent_subset_u8(const unsigned char* valid, int B, int N, int* n_valid, int* order, int* slot,
+                                  unsigned int* status, gn_stream_t stream) {
+  return agent_subset_entry(valid, B, N, n_valid, order, slot, status, stream, nullptr);
+}
+extern "C" int gn_agent_subset_plan(const unsigned char* valid, int B, int N, int* n_valid, int* order, int* slot,
+                                    unsigned int* status, gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : agent_subset_entry(valid, B, N, n_valid, order, slot, status, nullptr, plan);
+}
+
+// The remap launch: grid (capped, items); the plan also carries the store unit of the first GN_MAX_GROUPS items
+static int remap_rows_entry(const gn_remap_item_t* items, int n_items, int B, int N, const int* map, gn_stream_t stream,
+                            gn_launch_plan_t* plan) {
+  GN_CHECK(gn_need_counts(map));
+  if (items == nullptr) return GN_ERR_NULL;
+  if (n_items < 1 || n_items > GN_MAX_ZERO_ITEMS || B <= 0 || N <= 0 || N > 32767) return GN_ERR_SHAPE;
+  gn_launch_plan_t p;
+  gn_launch_plan_t& q = plan != nullptr ? *plan : p;
+  plan_begin(q, n_items < GN_MAX_GROUPS ? n_items : GN_MAX_GROUPS);
+  RemapTable T{};
+  long long most = 0;
+  int least = 16;
+  for (int g = 0; g < n_items; ++g) {
+    const gn_remap_item_t& it = items[g];
+    if (it.src == nullptr || it.dst == nullptr) return GN_ERR_NULL;
+    if (it.kind != GN_REMAP_NODE_ROWS && it.kind != GN_REMAP_PAIR_ROWS) return GN_ERR_SHAPE;
+    if (it.width <= 0 || it.src_pitch < it.width || it.dst_pitch < it.width || it.src_scene < 0 || it.dst_scene < 0)
+      return GN_ERR_SHAPE;
+    const uintptr_t all = reinterpret_cast<uintptr_t>(it.src) | reinterpret_cast<uintptr_t>(it.dst) | (uintptr_t)it.src_scene |
+                          (uintptr_t)it.dst_scene | (uintptr_t)it.src_pitch | (uintptr_t)it.dst_pitch | (uintptr_t)it.width;
+    if (all & 1u) return GN_ERR_ALIGN;
+    const int unit = remap_item_unit(it);
+    const long long rows = it.kind == GN_REMAP_PAIR_ROWS ? (long long)N * N : N;
+    const long long units = (long long)B * rows * (it.width / unit);
+    most = units > most ? units : most;
+    least = unit < least ? unit : least;
+    if (g < GN_MAX_GROUPS) q.stage[g] = unit;
+    T.t[g] = it;
+  }
+  q.kernel = GN_K_REMAP_ROWS;
+  q.stage_bytes = least;
+  q.grid[0] = capped_grid(most, kBlock * 2);
+  q.grid[1] = n_items;
+  if (plan != nullptr) return GN_OK;
+  hipLaunchKernelGGL(remap_rows_kernel, dim3(q.grid[0], q.grid[1]), dim3(kBlock), 0, (hipStream_t)stream, T, B, N, map);
+  return gn_check_launch();
+}
+extern "C" int gn_remap_rows(const gn_remap_item_t* items, int n_items, int B, int N, const int* map, gn_stream_t stream) {
+  return remap_rows_entry(items, n_items, B, N, map, stream, nullptr);
+}
+extern "C" int gn_remap_rows_plan(const gn_remap_item_t* items, int n_items, int B, int N, const int* map,
+                                  gn_launch_plan_t* plan) {
+  return plan == nullptr ? GN_ERR_NULL : remap_rows_entry(items, n_items, B, N, map, nullptr, plan);
 }
 
 // Pitched copy (rows x width bytes, 16-byte pieces): the column block of the feature tensor that a rank ships into its

@@ -79,6 +79,9 @@ class GraphedMultiScale:
         feats, H = g(f)                               # the previous counts stay
         g.status()                                    # the mask entry's sticky status word (synchronises)
 
+    With ``ragged="subset"`` the mask may have zeros anywhere: agents enter and leave scenes, and every result comes back
+    at the agent's own slot (zeros at invalid ones).
+
     WEIGHTS.  The graph holds no packing launch: it reads the block's packed weight images in place, as they were when it
     was captured.  After the parameters changed IN PLACE — `load_state_dict`, an eager optimizer step, a ``.data`` write —
     call ``g.refresh_weights()``: it re-derives every arena and split image the captured forward reads from the live
@@ -98,15 +101,21 @@ class GraphedMultiScale:
         ``ragged``: capture the ragged route with the counts in an `ops.StaticAgentCounts` (``self.counts``), made and
         filled with N before the capture begins: the graph holds the buffer's address, nothing is uploaded inside it, and
         the route is the ragged one whatever the counts of a replay are.  Noise keeps the padded shapes and the same
-        ``draws_per_step``; the ragged affinity launch carries the counter bump."""
+        ``draws_per_step``; the ragged affinity launch carries the counter bump.
+        ``ragged="subset"`` ("Agents missing anywhere"): the counts live in an `ops.StaticAgentSubset`,
+        and the graph holds the compaction launch, the ragged route and the expansion launch — ``agent_mask=`` then takes
+        masks with holes (the subset kernel runs ahead of the replay, nothing is read back), ``n_agents=`` sets prefix
+        counts, and `status` can only ever show `_lib.COUNTS_EMPTY`."""
         p = next(block.parameters())
         self.device = device or p.device
         if self.device.type != "cuda":
             raise ValueError("GraphedMultiScale needs the block on a GPU")
         self.counts: Optional[ops.StaticAgentCounts] = None
+        if ragged not in (False, True, "subset"):
+            raise ValueError("ragged: False, True or 'subset'")
         if ragged:      # the refusals of the eager ragged forward, before anything is allocated or launched
             _mods.refuse_ragged(training=block.training, listall=any(m.listall for m in block.interaction_hyper))
-            self.counts = ops.StaticAgentCounts(B, N, self.device)
+            self.counts = (ops.StaticAgentSubset if ragged == "subset" else ops.StaticAgentCounts)(B, N, self.device)
         self.block = block
         self.B, self.N = B, N
         self.seed = int(seed)

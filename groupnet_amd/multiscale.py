@@ -192,6 +192,9 @@ class MultiScaleHGNN(nn.Module):
         ops._req(f, "f", (None, None, self.h_dim), ops._ACT_DTYPES)
         B, N, D = f.shape
         S = len(self.hyper_scales)
+        sub = _mods.subset_of(n_agents, f, _needs_grad(self, f), listall=any(m.listall for m in self.interaction_hyper))
+        if sub is not None:
+            return self._forward_subset(f, noise_u, advance, sub, _needs_grad(self, f))
         counts = ragged_counts(n_agents, f, **ragged_grad_refusals(_needs_grad(self, f), N),
                                listall=any(m.listall for m in self.interaction_hyper))
         if _needs_grad(self, f):
@@ -231,4 +234,48 @@ class MultiScaleHGNN(nn.Module):
         else:
             for m, H, u, c in zip(mods, [None, *Hs], noise_u, cols):
                 run_message_passing([m], [f], [H], [u], [c], n_agents=counts)
+        return final, new_H
+
+    def _forward_subset(self, f: Tensor, noise_u, advance, sub: "ops.AgentSubset", grad: bool):
+        """``n_agents`` = an `ops.AgentSubset` ("Agents missing anywhere"): ONE launch compacts f and the
+        noise tensors of every module and round into scratch, the block's ragged forward runs on them as with
+        ``n_agents=<counts>``, ONE launch expands ``final`` — at its full width, so its first D columns are f at valid
+        rows and zeros elsewhere — and the scale blocks of ``new_H``.  Invalid rows of f are never read."""
+        B, N, _ = f.shape
+        S = len(self.hyper_scales)
+        if any(s > N for s in self.hyper_scales):
+            raise RuntimeError("selected index k out of range")
+        if noise_u is not None and len(noise_u) != 1 + S:
+            raise ValueError(f"noise_u: need {1 + S} entries (pairwise + one per scale)")
+        rounds = self.interaction.nmp_layers
+        shapes = self.noise_shapes(B, N)
+        # module-major, as `draw_noise` draws: every round of the pairwise module, then scale by scale
+        us = [_mods.subset_noise(None if noise_u is None else noise_u[i], shp, rounds, f.device)
+              for i, shp in enumerate(shapes)]
+        kinds = [ops.REMAP_PAIR_ROWS] + [None if s == N else ops.REMAP_NODE_ROWS for s in self.hyper_scales]
+        items: list = []
+        uc = [_mods.remap_noise(u, k, items) for u, k in zip(us, kinds)]
+        uc = None if all(u is None for u in uc) else uc
+        if grad:
+            if items:
+                ops.remap_rows(items, sub.order)
+            (fc,) = _mods._Remap.apply(sub, False, (ops.REMAP_NODE_ROWS,), f)
+            outc, Hc = self.forward(fc, uc, advance, n_agents=sub.compacted)
+            (final,) = _mods._Remap.apply(sub, True, (ops.REMAP_NODE_ROWS,), outc)
+            back = []
+        else:
+            fc = torch.empty_like(f)
+            ops.remap_rows([(f, fc, ops.REMAP_NODE_ROWS)] + items, sub.order)
+            outc, Hc = self.forward(fc, uc, advance, n_agents=sub.compacted)
+            final = torch.empty_like(outc)
+            back = [(outc, final, ops.REMAP_NODE_ROWS)]
+        new_H = None
+        if Hc is not None:
+            new_H, e0 = torch.empty_like(Hc), 0
+            for s in self.hyper_scales:      # the scale blocks of cat(H_s, dim=1): E = 1 row where s == N, else N rows
+                E = 1 if s == N else N
+                back.append(_mods.incidence_item(Hc[:, e0:e0 + E], new_H[:, e0:e0 + E]))
+                e0 += E
+        if back:
+            ops.remap_rows(back, sub.slot)
         return final, new_H

@@ -410,6 +410,223 @@ def zero_empty_scenes(items: Sequence[Tensor], n_agents) -> None:
     _zero_launch("zero_empty_scenes", "", [(t, ZERO_EDGE_ROWS) for t in items], n_agents, 1, layout)
 
 
+# ---- agents missing anywhere: the subset of a mask with holes ------------------------------------------------------
+REMAP_NODE_ROWS, REMAP_PAIR_ROWS = _lib.REMAP_NODE_ROWS, _lib.REMAP_PAIR_ROWS
+
+
+class _CompactedCounts(AgentCounts):
+    """The counts of an `AgentSubset` as plain counts: what a forward hands to the ragged route once it has compacted
+    its inputs (the route then runs exactly as with ``n_agents=<counts>``)."""
+    __slots__ = ("_of",)
+
+    def __init__(self, of: "AgentSubset"):
+        self._of, self.N, self.device, self._dev = of, of.N, of.device, None
+
+    admits_empty = property(lambda self: self._of.admits_empty)
+    counts = property(lambda self: self._of.counts)
+    B = property(lambda self: self._of.B)
+    dev = property(lambda self: self._of.dev)
+
+
+class AgentSubset(AgentCounts):
+    """The valid agents of a batch whose scenes have agents missing ANYWHERE ("Agents missing
+    anywhere"), made by `agent_subset`.  As an `AgentCounts` its counts are those of the COMPACTED tensors — valid rows
+    first, in order — so every stage of this module takes it as the counts it is; the three forwards read the two maps
+    besides: ``order`` (B,N) int32 — the slot of the r-th valid agent, -1 behind the last — and ``slot`` (B,N) int32 — the
+    rank of a slot among the valid ones, -1 where it is invalid.  Both come from the device kernel
+    (gn_agent_subset_u8), launched when the first launch asks for them: a forward that refuses the call has uploaded
+    and launched nothing.  ``compacted``: the counts alone (what the ragged route is handed behind the compaction).
+    Built from a GPU mask the values live on the device only: ``counts`` raises, ``admits_empty`` holds and ``status``
+    is the sticky word of the kernel (`_lib.COUNTS_EMPTY` only)."""
+    __slots__ = ("_B", "_counts", "_host", "_order", "_slot", "status", "_plain")
+
+    def __init__(self, B: int, N: int, device, counts: Optional[Tuple[int, ...]] = None, host_mask: Optional[Tensor] = None):
+        self._B, self.N, self.device = int(B), int(N), torch.device(device)
+        self._counts, self._host = counts, host_mask
+        self._dev = self._order = self._slot = self.status = self._plain = None
+
+    @property
+    def admits_empty(self) -> bool:
+        return self._counts is None
+
+    @property
+    def B(self) -> int:
+        return self._B
+
+    @property
+    def counts(self):
+        if self._counts is None:
+            raise RuntimeError("AgentSubset.counts: built from a GPU mask, the values live on the device only")
+        return self._counts
+
+    def _alloc(self, device) -> None:
+        self._dev = torch.empty((self._B,), dtype=torch.int32, device=device)
+        self._order = torch.empty((self._B, self.N), dtype=torch.int32, device=device)
+        self._slot = torch.empty((self._B, self.N), dtype=torch.int32, device=device)
+        if self.status is None:
+            self.status = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def _launch(self, valid: Tensor) -> None:
+        """gn_agent_subset_u8 of a (B,N) GPU mask into the holder's buffers."""
+        with torch.cuda.device(valid.device):
+            check(load().gn_agent_subset_u8(addr(valid), self._B, self.N, addr(self._dev), addr(self._order),
+                                            addr(self._slot), addr(self.status), stream_handle()), "gn_agent_subset_u8")
+
+    def _built(self) -> "AgentSubset":
+        if self._dev is None:      # a host mask: its bytes are uploaded now, the device kernel builds the maps
+            valid = self._host.to(self.device, non_blocking=True)
+            self._alloc(valid.device)
+            self._launch(valid)
+        return self
+
+    @property
+    def dev(self) -> Tensor:
+        return self._built()._dev
+
+    @property
+    def order(self) -> Tensor:
+        return self._built()._order
+
+    @property
+    def slot(self) -> Tensor:
+        return self._built()._slot
+
+    @property
+    def compacted(self) -> AgentCounts:
+        if self._plain is None:
+            self._plain = _CompactedCounts(self)
+        return self._plain
+
+
+def _host_mask(valid) -> Tensor:
+    """A host validity mask — a CPU bool / uint8 tensor, a numpy array of those types or a nested sequence of bools /
+    ints — as a contiguous (B,N) uint8 CPU tensor of 0 / 1, or ValueError."""
+    if isinstance(valid, torch.Tensor):
+        t = valid
+    else:
+        try:
+            t = torch.as_tensor(valid)
+        except Exception:
+            raise ValueError("agent_subset: a (B,N) bool / uint8 mask (tensor, numpy array or nested sequence)") from None
+        if not isinstance(valid, (list, tuple)) and t.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"agent_subset: a bool or uint8 mask (got {t.dtype})")
+        if t.dtype in (torch.int8, torch.int16, torch.int32, torch.int64):      # a nested sequence of ints
+            t = t != 0
+    if t.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"agent_subset: a bool or uint8 mask (got {t.dtype})")
+    if t.dim() != 2 or t.numel() == 0:
+        raise ValueError(f"agent_subset: a (B,N) mask with B, N >= 1 (got shape {tuple(t.shape)})")
+    return (t != 0).to(torch.uint8).contiguous()
+
+
+def agent_subset(valid, device=None) -> Optional[AgentCounts]:
+    """The valid agents of a batch from a (B,N) validity mask (non-zero = valid) with zeros ANYWHERE, as what the
+    forwards' ``n_agents=`` takes.
+    A HOST mask (CPU bool / uint8 tensor, numpy array, nested sequence) is validated here — every scene needs a valid
+    agent, else ValueError — and gives None when everything is valid (the call takes the full-batch path), a plain
+    `AgentCounts` when every scene's mask is a prefix (the ``n_agents=`` call and its bits), else an `AgentSubset` with
+    host-known counts on ``device`` (default: the current GPU).  Nothing is uploaded or launched yet.
+    A GPU mask (contiguous bool / uint8) gives an `AgentSubset` whose values live on the device only: the kernel is
+    launched here, nothing is read back, empty scenes are admitted (their outputs are zeros, ``status`` says so) and the
+    holder is inference-only."""
+    if isinstance(valid, torch.Tensor) and valid.is_cuda:
+        _mask_arg(valid, None, None, device)
+        sub = AgentSubset(valid.shape[0], valid.shape[1], valid.device)
+        sub._alloc(valid.device)
+        sub._launch(valid)
+        return sub
+    m = _host_mask(valid)
+    B, N = m.shape
+    counts = tuple(int(c) for c in m.sum(dim=1).tolist())
+    if min(counts) < 1:
+        raise ValueError("agent_subset: every scene needs at least one valid agent")
+    if all(c == N for c in counts):
+        return None
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise ValueError("agent_subset: the subset goes with GPU tensors; groupnet_amd has no CPU path")
+    if all(bool(m[b, :c].all()) for b, c in enumerate(counts)):
+        return AgentCounts(counts, N, device)
+    return AgentSubset(B, N, device, counts=counts, host_mask=m)
+
+
+class StaticAgentSubset(AgentSubset):
+    """An `AgentSubset` whose counts, ``order`` and ``slot`` live at FIXED device addresses for the holder's whole life,
+    with replaceable values: what `graphs.GraphedMultiScale(ragged="subset")` captures.  It starts with every agent
+    valid.  ``set_from_mask(valid)`` runs gn_agent_subset_u8 of a (B,N) bool / uint8 GPU mask into the buffers — holes
+    are honoured, nothing is read back, an empty scene is ORed into ``status``.  ``set(counts)`` sets prefix counts
+    (0..N, validated on the host) through the staging ring of `StaticAgentCounts`, and the prefix order with them."""
+    __slots__ = ("_ring",)
+
+    def __init__(self, B: int, N: int, device, slots: int = 4):
+        super().__init__(B, N, device)
+        self._ring = StaticAgentCounts(B, N, device, slots)
+        self._alloc(self._ring.device)
+        self._dev = self._ring.dev
+        self._prefix_maps()
+
+    def _prefix_maps(self) -> None:
+        ar = torch.arange(self.N, dtype=torch.int32, device=self._dev.device).expand(self._B, self.N)
+        pref = torch.where(ar < self._dev[:, None], ar, torch.full_like(ar, -1))
+        self._order.copy_(pref)
+        self._slot.copy_(pref)
+
+    def set(self, counts) -> None:
+        self._ring.set(counts)
+        with torch.cuda.device(self._dev.device):
+            self._prefix_maps()
+
+    def set_from_mask(self, valid: Tensor) -> None:
+        self._launch(_mask_arg(valid, self._B, self.N, self._dev.device))
+
+
+def _remap_layout(t: Tensor, kind: int, B: int, N: int):
+    """(scene stride, row pitch, row width) in elements of a tensor of `remap_rows`, or ValueError."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 3 and t.shape[0] == B):
+        raise ValueError("remap_rows: (B, rows, width) GPU tensors")
+    if t.dtype not in _ACT_DTYPES:
+        raise ValueError(f"remap_rows: fp32 or bf16 tensors (got {t.dtype})")
+    R, w = t.shape[1], t.shape[2]
+    if any(s < 0 for s in t.stride()) or (w > 1 and t.stride(2) != 1):
+        raise ValueError("remap_rows: a contiguous tensor, a last-dim slice or a row block of one")
+    if kind == REMAP_PAIR_ROWS and (R, w) == (N, N) and (N == 1 or t.stride(1) == N):
+        return t.stride(0), 1, 1             # a matrix per scene: one element per ordered pair
+    if R != (N * N if kind == REMAP_PAIR_ROWS else N) or kind not in (REMAP_NODE_ROWS, REMAP_PAIR_ROWS):
+        raise ValueError(f"remap_rows: kind {kind} does not go with {R} rows per scene at N = {N}")
+    if R > 1 and t.stride(1) < w:
+        raise ValueError("remap_rows: a contiguous tensor, a last-dim slice or a row block of one")
+    return t.stride(0), max(t.stride(1), w), w
+
+
+def remap_rows(items: Sequence[Tuple[Tensor, Tensor, int]], map: Tensor) -> None:
+    """Move the rows of several tensors through a per-scene index map in ONE launch (gn_remap_rows): items =
+    [(src, dst, kind)], ``map`` (B,N) int32 — `AgentSubset.order` compacts (valid rows first, zeros behind), `.slot`
+    expands (results back at their slots, zeros elsewhere).  REMAP_NODE_ROWS — (B,N,w), destination row r from source
+    row map[b,r]; REMAP_PAIR_ROWS — (B,N*N,w) ordered pair rows, or a (B,N,N) matrix per scene (corr, H, a scale block of
+    new_H).  ``src`` and ``dst`` have one shape and dtype (fp32 or bf16) and must not overlap; each is contiguous, a
+    last-dim slice or a row block of a contiguous tensor (the (B,1,N) row of a scale-N module's H goes as the node kind
+    on its (B,N,1) view).  Every destination position is written: unmapped ones as zeros.  A launch takes
+    `_lib.MAX_ZERO_ITEMS` tensors; a longer list goes in further launches."""
+    _req(map, "map", (None, None), torch.int32)
+    B, N = map.shape
+    arr = []
+    for src, dst, kind in items:
+        ls, ld = _remap_layout(src, kind, B, N), _remap_layout(dst, kind, B, N)
+        if src.shape != dst.shape or src.dtype != dst.dtype or ls[2] != ld[2]:
+            raise ValueError("remap_rows: source and destination of one shape and dtype")
+        _same_device(map, src, dst)
+        es = src.element_size()
+        arr.append(_lib.RemapItem(src=src.data_ptr(), dst=dst.data_ptr(), src_scene=ls[0] * es, dst_scene=ld[0] * es,
+                                  src_pitch=ls[1] * es, dst_pitch=ld[1] * es, width=ls[2] * es, kind=kind))
+    if not arr or B == 0 or N == 0:
+        return
+    with torch.cuda.device(map.device):
+        for i in range(0, len(arr), _lib.MAX_ZERO_ITEMS):      # (more tensors than a launch's table holds: further launches)
+            part = arr[i:i + _lib.MAX_ZERO_ITEMS]
+            check(load().gn_remap_rows((_lib.RemapItem * len(part))(*part), len(part), B, N, addr(map), stream_handle()),
+                  "gn_remap_rows")
+
+
 # ---- A0 / A1 -----------------------------------------------------------------------------------
 def affinity(f: Tensor) -> Tensor:
     """corr = normalize(f) @ normalize(f)^T   (model/GroupNet_nba.py:284-286)."""

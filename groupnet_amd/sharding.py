@@ -132,8 +132,13 @@ def sharded_forward(block: Callable[..., Tuple[Tensor, Optional[Tensor]]], f_ful
     CPU integer tensor.  Every rank passes its own scenes' counts on as `block(f_local, noise_u=..., n_agents=...)`; a
     rank whose scenes all hold N agents thereby takes the full-batch path.  Without it the block is called without
     the keyword.
+    An `ops.AgentSubset` (agents missing anywhere) is refused: slicing a subset over ranks is not built.
     Returns `(features_full (B, N, F), H_full or local H)`.
     """
+    from .ops import AgentSubset
+    if isinstance(n_agents, AgentSubset):
+        raise ValueError("n_agents: sharded_forward does not take an ops.AgentSubset (a subset is not sliced over ranks); "
+                         "pass the full batch's counts, or run the subset on one device")
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     B = f_full.shape[0]

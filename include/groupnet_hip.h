@@ -608,6 +608,46 @@ int gn_zero_empty_scenes(const gn_zero_item_t* items, int n_items, int B, const 
 #define GN_COUNTS_EMPTY 2u
 int gn_agent_counts_u8(const unsigned char* valid, int B, int N, int* n_valid, unsigned int* status, gn_stream_t stream);
 
+/* The subset of a validity mask WITH HOLES (an addition within ABI 40).  valid: (B,N) bytes on the device, any alignment,
+ * non-zero = valid.  With V_b the valid slots of scene b in increasing order and n_b = |V_b|:
+ *   n_valid[b]  = n_b                                                    (B ints)
+ *   order[b,r]  = the slot of the r-th valid agent for r < n_b, else -1  (B*N ints)
+ *   slot[b,n]   = the rank of slot n within V_b, -1 where n is invalid   (B*N ints)
+ * The compaction is stable: valid agents keep their relative order.  `status` is the sticky word of gn_agent_counts_u8;
+ * this entry point ORs in GN_COUNTS_EMPTY only (a scene without a valid agent) and never GN_COUNTS_NOT_PREFIX.  One wave
+ * per scene, rows beyond 64 agents in chunks of a wave with the running base carried from chunk to chunk; any N >= 1 and
+ * B >= 1, else GN_ERR_SHAPE; a NULL pointer: GN_ERR_NULL; a misaligned n_valid, order, slot or status (4 bytes):
+ * GN_ERR_ALIGN. */
+int gn_agent_subset_u8(const unsigned char* valid, int B, int N, int* n_valid, int* order, int* slot, unsigned int* status,
+                       gn_stream_t stream);
+
+/* Moves the rows of up to GN_MAX_ZERO_ITEMS tensors through a per-scene index map in ONE launch (an addition within ABI
+ * 40): for every destination row, dst[row] = map[...] >= 0 ? src[mapped row] : 0.  map: (B,N) ints on the device, entries
+ * in -1 .. N - 1 (anything else counts as -1).  With map = order of gn_agent_subset_u8 this is the COMPACTION of a batch
+ * whose scenes have agents missing anywhere (valid rows first, in order, zeros behind them); with map = slot it is the
+ * EXPANSION of results back to the original slots (zeros at invalid positions).  `items` is a HOST array; every field
+ * is in bytes.  kind: GN_REMAP_NODE_ROWS — N rows per scene, row r of scene b from source row map[b,r];
+ * GN_REMAP_PAIR_ROWS — N*N ordered pair rows, row i*N + j from source row map[b,i]*N + map[b,j], zero when either is -1.
+ * A (B,N,N) matrix is the pair kind with width = the element size (corr, a top-k H, a scale block of new_H through its
+ * own scene stride); the (B,1,N) row of a scale-N module's H is the node kind on its (B,N,1) view.  Every destination
+ * position is written exactly once (no scatter, no atomics).  Store unit per item: the largest of 16 / 8 / 4 / 2 bytes
+ * that divides both addresses, both scene strides, both pitches and the width (256-byte fp32 feature rows: 16; 24-byte
+ * fp32 factor rows: 8; an 18-byte bf16 row: 2); an odd value among them: GN_ERR_ALIGN.  Source and destination of an item
+ * MUST NOT OVERLAP (rows are read after other rows were written).  N <= 32767. */
+#define GN_REMAP_NODE_ROWS 0
+#define GN_REMAP_PAIR_ROWS 1
+typedef struct {
+  const void* src;
+  void* dst;
+  long long src_scene;   /* bytes from a scene to the next */
+  long long dst_scene;
+  long long src_pitch;   /* bytes from a row to the next */
+  long long dst_pitch;
+  int width;             /* bytes of a row that are moved */
+  int kind;              /* GN_REMAP_* */
+} gn_remap_item_t;
+int gn_remap_rows(const gn_remap_item_t* items, int n_items, int B, int N, const int* map, gn_stream_t stream);
+
 /* ---- A6 / generic two-layer MLP ---------------------------------------------------------------
  * y = W1 relu(W0 x + b0) + b1     (MLP.forward with one hidden layer, MS_HGNN_batch.py:220-229;
  * nmp_mlp_end 128->128->bottleneck and nmp_mlps[even] 128->128->64).
@@ -693,6 +733,10 @@ int gn_mlp2_bf16(const gn_mlp2_group_t* groups, int n_groups, int rows, int din,
 #define GN_K_NODE2EDGE_RAGGED 29     /* variant: 0 banded, 1 row form, as GN_K_NODE2EDGE */
 #define GN_K_AGG_SCATTER_RAGGED 30   /* grid (ceil(B N 32 / 256) capped, groups) */
 #define GN_K_ZERO_PADDING 31         /* grid (capped, items); a plan without groups */
+/* additions within ABI 40: the kernels of the subset route, in a range of their own — the table above ends at
+ * GN_K_ZERO_PADDING as it did (callers may rely on gn_kernel_name(32) == NULL); ids 32..39 name no kernel */
+#define GN_K_AGENT_SUBSET 40         /* grid (ceil(B / 4)): one wave per scene */
+#define GN_K_REMAP_ROWS 41           /* grid (capped, items) */
 typedef struct {
   int kernel;        /* GN_K_*: the kernel of the launch (gn_kernel_name), instantiated for ... */
   int precision;     /* ... 0: the plain fp32 weight stream, 1: bf16 storage (the twins), 2: f16x3, 3: bf16x6 */
@@ -797,6 +841,13 @@ int gn_zero_padding_plan(const gn_zero_item_t* items, int n_items, int B, int N,
 int gn_zero_empty_scenes_plan(const gn_zero_item_t* items, int n_items, int B, const int* n_valid, gn_launch_plan_t* plan);
 int gn_agent_counts_plan_u8(const unsigned char* valid, int B, int N, int* n_valid, unsigned int* status,
                             gn_launch_plan_t* plan);
+/* The subset route's two launches (additions within ABI 40).  gn_agent_subset_plan: kernel = GN_K_AGENT_SUBSET, grid =
+ * (ceil(B / 4)).  gn_remap_rows_plan: kernel = GN_K_REMAP_ROWS, grid = (capped, items), n_groups = min(n_items,
+ * GN_MAX_GROUPS), stage[g] = the store unit in bytes (16 / 8 / 4 / 2) of item g for g < GN_MAX_GROUPS, stage_bytes = the
+ * smallest store unit over all items. */
+int gn_agent_subset_plan(const unsigned char* valid, int B, int N, int* n_valid, int* order, int* slot, unsigned int* status,
+                         gn_launch_plan_t* plan);
+int gn_remap_rows_plan(const gn_remap_item_t* items, int n_items, int B, int N, const int* map, gn_launch_plan_t* plan);
 
 /* ---- backward (training) building blocks — SURVEY.md §8f rank 2 -------------------------------
  * train_hyper_nba.py:116 back-propagates through the two modules.  The backward of the path is
