@@ -126,6 +126,28 @@ def set_ragged_training(on: Optional[bool]) -> None:
     _RAGGED_TRAINING = None if on is None else bool(on)
 
 
+# The deterministic backward is opt-in the same way: None — not set by `set_deterministic`, the environment decides per
+# call (GN_DETERMINISTIC=1: on).
+_DETERMINISTIC: Optional[bool] = None
+
+
+def deterministic() -> bool:
+    """Whether a backward sums in a fixed order (`backward.GemmBatch.run` takes gn_gemm_grouped_det_f32, the pooling
+    backward gn_node2edge_bwd_det_grouped_f32): what `set_deterministic` chose, else GN_DETERMINISTIC=1 switches it on
+    (read per call).  Off by default: every call launches what it always did.  torch's own
+    `use_deterministic_algorithms` flag is not read."""
+    if _DETERMINISTIC is not None:
+        return _DETERMINISTIC
+    return os.environ.get("GN_DETERMINISTIC", "0") == "1"
+
+
+def set_deterministic(on: Optional[bool]) -> None:
+    """True / False for calls issued from now on; None hands the choice back to the environment.  A captured graph keeps
+    the form it was captured with."""
+    global _DETERMINISTIC
+    _DETERMINISTIC = None if on is None else bool(on)
+
+
 # What a ragged call (``n_agents``) is refused for, by the caller's keyword: the exception and its text
 _RAGGED_REFUSALS = {
     "large": (NotImplementedError, f"n_agents: training on ragged batches needs N <= {route.N2E_BWD_SCENE_MAX_N} (the "

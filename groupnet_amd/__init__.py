@@ -8,11 +8,11 @@ this package is the ctypes binding plus the drop-in modules.  No CPU fallback ex
 """
 from . import _lib, ops  # noqa: F401
 from .MS_HGNN_batch import (MLP, MLP_dict_softmax, MS_HGNN_hyper, MS_HGNN_oridinary, edge_aggregation,
-                            ragged_training, set_noise_mode, set_ragged_training)
+                            deterministic, ragged_training, set_deterministic, set_noise_mode, set_ragged_training)
 from .ops import agent_subset
 from .past_encoder import FutureEncoder, PastEncoder, PositionalAgentEncoding
 
 __all__ = ["MLP", "MLP_dict_softmax", "MS_HGNN_hyper", "MS_HGNN_oridinary", "edge_aggregation", "ops",
-           "set_noise_mode", "set_ragged_training", "ragged_training", "PastEncoder", "FutureEncoder",
+           "set_noise_mode", "set_ragged_training", "ragged_training", "set_deterministic", "deterministic", "PastEncoder", "FutureEncoder",
            "PositionalAgentEncoding", "agent_subset"]
 __version__ = "0.1.0"

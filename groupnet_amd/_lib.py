@@ -149,6 +149,16 @@ class GemmDesc(ctypes.Structure):
                 ("flags", _I), ("alpha", _F), ("beta", _F)]
 
 
+class GemmDetPlan(ctypes.Structure):
+    """What gn_gemm_grouped_det_f32 would do with a batch (gn_gemm_grouped_det_plan): per-problem arrays in descriptor order."""
+    __slots__ = ()
+    c_name = "gn_gemm_det_plan_t"
+    _N = _I * 128     # GN_GEMM_DET_MAX
+    _L = ctypes.c_longlong * 128
+    _fields_ = [("workspace_bytes", ctypes.c_longlong), ("n", _I), ("n_chains", _I), ("splits", _N), ("kchunk", _N),
+                ("kernel", _N), ("chain", _N), ("cs_chain", _N), ("offset", _L), ("cs_offset", _L)]
+
+
 class LaunchPlan(ctypes.Structure):
     """What a forward launcher would launch (gn_*_plan_*): per-group arrays in the caller's group order."""
     __slots__ = ()
@@ -161,6 +171,8 @@ class LaunchPlan(ctypes.Structure):
 
 
 GEMM_TRANS_A, GEMM_TRANS_B, GEMM_RELU, GEMM_ACCUM, GEMM_TRANS_C = 1, 2, 4, 8, 16
+GEMM_DET_MAX = 128                                        # problems of one gn_gemm_grouped_det_f32
+GEMM_KERNEL_SCALAR, GEMM_KERNEL_VECTOR = 0, 1             # GemmDetPlan.kernel
 K_AGG_GATHER, K_AGG_GATHER_MASK = 15, 16      # GN_K_*: the two forms of the stand-alone gather
 K_AGG_SCENE, K_AGG_GATHER_PAIRWISE = 17, 18   # ... the kernels of a group's own launch (LaunchPlan.pre_kernel)
 K_AFFINITY_TOPK, K_AFFINITY_TOPK_MASKS, K_AFFINITY_BANDED, K_TOPK_INCIDENCE = 19, 20, 21, 22      # ... the graph stage
@@ -273,6 +285,9 @@ SIGNATURES = {
     "gn_remap_rows_plan": (_I, [ctypes.POINTER(RemapItem), _I, _I, _I, _P, ctypes.POINTER(LaunchPlan)]),
     "gn_gemm_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _F, _F, _P]),
     "gn_gemm_grouped_f32": (_I, [ctypes.POINTER(GemmDesc), _I, _P]),
+    "gn_gemm_grouped_det_f32": (_I, [ctypes.POINTER(GemmDesc), _I, _P, _SZ, _P]),
+    "gn_gemm_grouped_det_plan": (_I, [ctypes.POINTER(GemmDesc), _I, ctypes.POINTER(GemmDetPlan)]),
+    "gn_node2edge_bwd_det_grouped_f32": (_I, [ctypes.POINTER(N2EBwdGroup), _I, _I, _I, _P, _P, _P]),
     "gn_typed_bwd_f32": (_I, [_P, _P, _P, _I, _P, _P, _P, ctypes.c_longlong, _I, _I, _P]),
     "gn_axpby2d_f32": (_I, [_P, _I, _P, _I, ctypes.c_longlong, _I, _F, _F, _P]),
     "gn_gumbel_ef_f32": (_I, [_P, _P, _P, ctypes.c_longlong, _I, _I, _I, _F, _I, _P]),

@@ -24,6 +24,10 @@ A ragged batch (``n_agents`` under autograd, `MS_HGNN_batch.set_ragged_training`
 and the same chain rule runs with four changes ("Ragged training") — the incoming gradients zeroed at padded
 positions (`modules_backward`), 1/n_b for 1/N and the unordered pair rows with a padded end zeroed
 (`_edge2node_backward`), and the count-aware pooling backward gn_node2edge_bwd_ragged_grouped_f32 (`_pooling_backward`).
+
+The deterministic mode (`MS_HGNN_batch.set_deterministic`; DESIGN.md, "Deterministic training"): the same stages, with the
+two that sum in an order of their own making replaced by their ordered forms — every `GemmBatch.run` goes to
+gn_gemm_grouped_det_f32 and the pooling backward to gn_node2edge_bwd_det_grouped_f32 (full-batch and ragged).
 """
 from __future__ import annotations
 
@@ -34,7 +38,7 @@ import torch.nn as nn
 
 from . import _lib, ops, route, weights
 from ._lib import addr, check, load, stream_handle
-from .MS_HGNN_batch import _GUMBEL_TAU
+from .MS_HGNN_batch import _GUMBEL_TAU, deterministic
 from .weights import _HID, _LGF_LD
 
 Tensor = torch.Tensor
@@ -78,10 +82,33 @@ class GemmBatch:
     def run(self) -> None:
         if not self.descs:
             return
-        arr = (_lib.GemmDesc * len(self.descs))(*self.descs)
-        with torch.cuda.device(self.device):
-            check(load().gn_gemm_grouped_f32(arr, len(self.descs), stream_handle()), "gn_gemm_grouped_f32")
+        if deterministic():
+            self._run_ordered()
+        else:
+            arr = (_lib.GemmDesc * len(self.descs))(*self.descs)
+            with torch.cuda.device(self.device):
+                check(load().gn_gemm_grouped_f32(arr, len(self.descs), stream_handle()), "gn_gemm_grouped_f32")
         self.descs, self.keep = [], []
+
+    def _run_ordered(self) -> None:
+        """The deterministic mode (`MS_HGNN_batch.set_deterministic`): gn_gemm_grouped_det_f32, whose accumulate problems
+        sum their K splits in a fixed order through a workspace.  Its size is the plan query's answer; it comes from
+        torch's allocator (inside a capture: from the graph's pool, like every other temporary of a step).  A batch
+        beyond the entry's GN_GEMM_DET_MAX problems goes in pieces: a chain that spans two of them continues from the sum
+        the first left in the destination, which is the same order."""
+        lib = load()
+        for i in range(0, len(self.descs), _lib.GEMM_DET_MAX):
+            part = self.descs[i:i + _lib.GEMM_DET_MAX]
+            arr = (_lib.GemmDesc * len(part))(*part)
+            ws, nbytes = None, 0
+            if any(d.flags & _lib.GEMM_ACCUM for d in part):
+                plan = _lib.GemmDetPlan()
+                check(lib.gn_gemm_grouped_det_plan(arr, len(part), plan), "gn_gemm_grouped_det_plan")
+                nbytes = plan.workspace_bytes
+                ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                check(lib.gn_gemm_grouped_det_f32(arr, len(part), addr(ws), nbytes, stream_handle()),
+                      "gn_gemm_grouped_det_f32")
 
 
 def gemm(A: Tensor, Bm: Tensor, transA=False, transB=False, bias=None, mask=None, relu=False, alpha=1.0,
@@ -430,7 +457,14 @@ def _pooling_backward(S: List[_RoundState], gb: GemmBatch, grads: dict, grouped:
                                           b2=c.b2.data_ptr(), dedges=c.dedges.data_ptr(), dxp=c.dxp.data_ptr(),
                                           dpq=c.dpq.data_ptr(), dw2=grads[c.a1.weight].data_ptr(),
                                           db2=grads[c.a1.bias].data_ptr(), E=c.E, sym=int(c.sym))
-            if S[0].counts is None:
+            if deterministic():
+                # the ordered form, full-batch or ragged: one wave per (scene, module) adds a scene's edges in ascending
+                # order, the 33 attention sums of every (module, scene) go through `partials` and are added in scene order
+                partials = torch.empty(len(S) * S[0].B * 33, dtype=torch.float32, device=S[0].x.device)
+                check(load().gn_node2edge_bwd_det_grouped_f32(
+                    arr, len(S), S[0].B, S[0].N, None if S[0].counts is None else addr(S[0].counts.dev), addr(partials),
+                    stream_handle()), "gn_node2edge_bwd_det_grouped_f32")
+            elif S[0].counts is None:
                 check(load().gn_node2edge_bwd_grouped_f32(arr, len(S), S[0].B, S[0].N, stream_handle()),
                       "gn_node2edge_bwd_grouped_f32")
             else:
@@ -494,7 +528,9 @@ def round_backward(traces: Sequence[ModuleTrace], j: int, g_ys: Sequence[Optiona
     dxp and dpq that the count-aware pooling backward never writes), 1/n_b for 1/N, the unordered pair rows with a padded
     end zeroed, and the count-aware pooling backward.  d x_j comes back with rows n >= n_b exactly zero."""
     counts = traces[0].counts
-    rt = route.backward_round_route(traces[0].xs[j].shape[1], tuple(t.H is None for t in traces), counts is not None)
+    # (the deterministic mode: the route refuses an N beyond the ordered pooling backward before anything is launched)
+    det = dict(deterministic=True) if deterministic() else {}
+    rt = route.backward_round_route(traces[0].xs[j].shape[1], tuple(t.H is None for t in traces), counts is not None, **det)
     S = [_RoundState(t, j, rt.pair_rows, g_y, g_d) for t, g_y, g_d in zip(traces, g_ys, g_dists)]
     dev = S[0].x.device
     if counts is not None:

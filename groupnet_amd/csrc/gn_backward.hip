@@ -16,6 +16,9 @@
 //   gn_node2edge_bwd_f32   back through the attention-weighted pooling (one workgroup per scene with its rows
 //                          in LDS; beyond that one wave per hyperedge with atomic adds into the node rows);
 //   gn_node2edge_bwd_ragged_f32   the same over scenes with their own agent counts (per-scene form only).
+//   gn_gemm_grouped_det_f32, gn_node2edge_bwd_det_grouped_f32   the ordered (deterministic) forms of the two stages that
+//                          otherwise sum with float atomics: split-K partials and per-scene attention sums go through a
+//                          caller's workspace and are added in a fixed order; a scene's edges are walked by one wave.
 // Gather and scatter are each other's adjoints and reuse the forward kernels.
 #include <stdlib.h>
 
@@ -78,6 +81,17 @@ struct GemmDesc {
 };
 struct GemmTable {
   GemmDesc d[kMaxDescs];
+  int n;
+};
+// ... of the ordered (deterministic) accumulate form: every (tile, split) workgroup stores its alpha-scaled partial tile
+// at part[split][row][col] (rows x cols as C's: (M x N), with GN_GEMM_TRANS_C (N x M), dense) and its partial column
+// sums at cs_part[split][m]; gemm_det_reduce_kernel adds them to C / colsum in ascending split order
+struct GemmDetDesc : GemmDesc {
+  float* part;
+  float* cs_part;      // or nullptr: no colsum
+};
+struct GemmDetTable {
+  GemmDetDesc d[kMaxDescs];
   int n;
 };
 
@@ -157,8 +171,8 @@ __device__ __forceinline__ void fetch_b4(f32x4 (&vb)[kB4], const float* __restri
   }
 }
 
-template <bool TA, bool TB, bool FAST, bool X6>
-__device__ __forceinline__ void gemm_body(const GemmDesc& D, float (&As)[BK][BM + 4], float (&Bs)[BK][BN + 4]) {
+template <bool TA, bool TB, bool FAST, bool X6, bool DET = false, class Desc = GemmDesc>
+__device__ __forceinline__ void gemm_body(const Desc& D, float (&As)[BK][BM + 4], float (&Bs)[BK][BN + 4]) {
   const int local = (int)blockIdx.x - D.tile0;
   const int split = local / D.gmn, t = local - split * D.gmn;
   const int tm = t / D.gn, tn = t - tm * D.gn;
@@ -289,6 +303,34 @@ __device__ __forceinline__ void gemm_body(const GemmDesc& D, float (&As)[BK][BM 
     }
     __syncthreads();
   }
+  if constexpr (DET) {     // an accumulate problem's partials, plain stores: one writer per element of part / cs_part
+    const float alpha = D.alpha;
+    if (want_cs && tid < BM && m0 + tid < M) D.cs_part[(size_t)split * M + m0 + tid] = cs;
+    if (transC) {          // lane = m, register = n: part is (splits, N, M)
+      const int m = m0 + wave * 32 + l31;
+      if (m < M) {
+#pragma unroll
+        for (int half = 0; half < 2; ++half)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int n = n0 + half * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            if (n < N) D.part[((size_t)split * N + n) * M + m] = alpha * (half ? acc1[r] : acc0[r]);
+          }
+      }
+    } else {               // lane = n, register = m: part is (splits, M, N)
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int n = n0 + half * 32 + l31;
+        if (n >= N) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int m = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          if (m < M) D.part[((size_t)split * M + m) * N + n] = alpha * (half ? acc1[r] : acc0[r]);
+        }
+      }
+    }
+    return;
+  }
   if (want_cs && tid < BM && m0 + tid < M) atomicAdd(D.colsum + m0 + tid, cs);
   const bool accum = D.flags & GN_GEMM_ACCUM, relu = D.flags & GN_GEMM_RELU;
   const float alpha = D.alpha, beta = D.beta;
@@ -336,18 +378,18 @@ __device__ __forceinline__ void gemm_body(const GemmDesc& D, float (&As)[BK][BM 
 // coalesced.  Two kernels so that each keeps its own register budget: the vector-staging one (16-byte aligned
 // operands, K a multiple of 32 — every large problem of the backward) runs 3 workgroups per CU; the scalar one
 // (fp32 matrix cores, v_mfma_f32_32x32x2_f32) takes anything.
-template <bool FAST, bool X6>
-__device__ __forceinline__ void gemm_dispatch(const GemmTable& T, float (&As)[BK][BM + 4], float (&Bs)[BK][BN + 4]) {
+template <bool FAST, bool X6, bool DET = false, class Table = GemmTable>
+__device__ __forceinline__ void gemm_dispatch(const Table& T, float (&As)[BK][BM + 4], float (&Bs)[BK][BN + 4]) {
   int g = 0;
   for (int i = 1; i < T.n; ++i)
     if ((int)blockIdx.x >= T.d[i].tile0) g = i;
   g = gn_uniform(g);
-  const GemmDesc& D = T.d[g];
+  const auto& D = T.d[g];
   const int tt = gn_uniform(D.flags & (GN_GEMM_TRANS_A | GN_GEMM_TRANS_B));
-  if (tt == 0) gemm_body<false, false, FAST, X6>(D, As, Bs);
-  else if (tt == GN_GEMM_TRANS_A) gemm_body<true, false, FAST, X6>(D, As, Bs);
-  else if (tt == GN_GEMM_TRANS_B) gemm_body<false, true, FAST, X6>(D, As, Bs);
-  else gemm_body<true, true, FAST, X6>(D, As, Bs);
+  if (tt == 0) gemm_body<false, false, FAST, X6, DET>(D, As, Bs);
+  else if (tt == GN_GEMM_TRANS_A) gemm_body<true, false, FAST, X6, DET>(D, As, Bs);
+  else if (tt == GN_GEMM_TRANS_B) gemm_body<false, true, FAST, X6, DET>(D, As, Bs);
+  else gemm_body<true, true, FAST, X6, DET>(D, As, Bs);
 }
 
 // vector staging, the products formed on the bf16 matrix cores from three-part splits (fp32-accurate, like the
@@ -362,6 +404,64 @@ __global__ __launch_bounds__(kB) void gemm_mfma_edge_kernel(const GemmTable T) {
   __shared__ float As[BK][BM + 4];
   __shared__ float Bs[BK][BN + 4];
   gemm_dispatch<false, false>(T, As, Bs);
+}
+
+// The ordered form of GN_GEMM_ACCUM (gn_gemm_grouped_det_f32): the same staging and matrix-core phases as the two
+// kernels above — a (tile, split) workgroup forms the bits the atomic form would add — with the partial tile stored
+// instead of added.  Separate kernels: the default ones keep their code and their registers.
+__global__ __launch_bounds__(kB, 3) void gemm_x6_det_kernel(const GemmDetTable T) {
+  __shared__ float As[BK][BM + 4];
+  __shared__ float Bs[BK][BN + 4];
+  gemm_dispatch<true, true, true>(T, As, Bs);
+}
+
+__global__ __launch_bounds__(kB) void gemm_mfma_edge_det_kernel(const GemmDetTable T) {
+  __shared__ float As[BK][BM + 4];
+  __shared__ float Bs[BK][BN + 4];
+  gemm_dispatch<false, false, true>(T, As, Bs);
+}
+
+// ... and its second stage.  An item is one destination (C of a chain of problems, or their colsum as a (1 x M) row):
+// one thread per element forms v = dst; for every member of the chain in descriptor order, for s = 0 .. splits-1:
+// v = v + part[s][element]; dst = v — fp32 adds in one fixed order, one writer per element.
+constexpr int kMaxRedItems = 2 * kMaxDescs;
+struct RedMember {
+  const float* part;   // (splits, rows * cols)
+  int splits;
+  int next;            // the chain's next member, -1 at its end
+};
+struct RedItem {
+  float* dst;
+  int rows, cols, ld;
+  int first;           // its first member
+  int block0;
+  int pad_;
+};
+struct RedTable {
+  RedItem item[kMaxRedItems];
+  RedMember mem[kMaxRedItems];
+  int n_items;
+};
+__global__ __launch_bounds__(kB) void gemm_det_reduce_kernel(const RedTable T) {
+  int g = 0;
+  for (int i = 1; i < T.n_items; ++i)
+    if ((int)blockIdx.x >= T.item[i].block0) g = i;
+  g = gn_uniform(g);
+  const RedItem& I = T.item[g];
+  const long long total = (long long)I.rows * I.cols;
+  const long long idx = (long long)((int)blockIdx.x - I.block0) * kB + threadIdx.x;
+  if (idx >= total) return;
+  const long long r = idx / I.cols;
+  float* d = I.dst + r * I.ld + (idx - r * I.cols);
+  float v = *d;
+  for (int p = I.first; p >= 0;) {
+    p = gn_uniform(p);
+    const float* __restrict__ q = T.mem[p].part + idx;
+    const int splits = T.mem[p].splits;
+    for (int s = 0; s < splits; ++s) v = v + q[(size_t)s * total];
+    p = T.mem[p].next;
+  }
+  *d = v;
 }
 
 __global__ __launch_bounds__(kB) void scale_kernel(float* __restrict__ C, long long total, int N, int ldc, float beta) {
@@ -545,16 +645,27 @@ __global__ __launch_bounds__(kB) void node2edge_bwd_kernel(const float* __restri
 // row without members is skipped; the pairwise graph walks the pairs with both ends < nb, whose dedges rows sit at
 // their index in the PADDED layout (E stays the padded row count).  The LDS layout stays the padded scene's.
 // Without RAGGED nb is N.
-template <bool RAGGED>
+// WAVES: waves per workgroup (the scene's edges go round them).  DET (with WAVES == 1, gn_node2edge_bwd_det_grouped_f32):
+// the one wave walks the scene's edges in ascending order and adds into the LDS rows with plain read-modify-writes —
+// every address belongs to one lane, so a row's contributions are added in edge order; its 33 attention sums go to
+// `part` (33 floats of this (module, scene)) by plain stores instead of into dw2 / db2.
+template <bool RAGGED, int WAVES = kB / 64, bool DET = false>
 __device__ __forceinline__ void node2edge_bwd_scene_body(
     const float* __restrict__ xp, const float* __restrict__ pq, const float* __restrict__ H,
     const float* __restrict__ w2, const float* __restrict__ b2p, const float* __restrict__ dedges,
     float* __restrict__ dxp,
     float* __restrict__ dpq, float* __restrict__ dw2, float* __restrict__ db2, int N, int E, int sym, const int b,
-    const int nb) {
+    const int nb, float* __restrict__ part = nullptr) {
+  static_assert(!DET || WAVES == 1, "the ordered form is one wave per scene");
+  constexpr int kT = WAVES * 64;      // threads of the workgroup
   extern __shared__ __align__(16) float lds[];
   if constexpr (RAGGED) {
-    if (nb <= 0) return;      // an empty slot (the whole workgroup): nothing is read, nothing is added
+    if (nb <= 0) {            // an empty slot (the whole workgroup): nothing is read, nothing is added
+      if constexpr (DET) {
+        if (threadIdx.x < 33) part[threadIdx.x] = 0.f;
+      }
+      return;
+    }
   }
   const float b2 = *b2p;
   const int NF = N * GN_FEAT;
@@ -573,7 +684,7 @@ __device__ __forceinline__ void node2edge_bwd_scene_body(
   float* s_dw = base + 3 * N;
   const float* xpb = xp + (size_t)b * NF;
   const float* pqb = pq + (size_t)b * NF;
-  for (int i = threadIdx.x; i < VF; i += kB) {
+  for (int i = threadIdx.x; i < VF; i += kT) {
     s_xp[i] = xpb[i];
     s_pq[i] = pqb[i];
     s_dxp[i] = 0.f;
@@ -585,7 +696,7 @@ __device__ __forceinline__ void node2edge_bwd_scene_body(
   float dw2c = 0.f, db2l = 0.f;
   // the edges the scene walks: every row of an explicit H, the nb*nb (sym: nb(nb+1)/2) valid pairs of the pairwise graph
   const int Ev = RAGGED && H == nullptr ? (sym ? gn_pair_count(nb) : nb * nb) : E;
-  for (int ev = wave; ev < Ev; ev += kB / 64) {
+  for (int ev = wave; ev < Ev; ev += WAVES) {
     int e = ev;      // the edge's row of dedges
     int cnt = 0;
     if (H == nullptr) {
@@ -668,33 +779,45 @@ __device__ __forceinline__ void node2edge_bwd_scene_body(
       const int n = s_idx[m];
       const float hv = s_h[m];
       const float p = expf(s_att[m] * hv - mx) / sum;
-      atomicAdd(s_dxp + n * GN_FEAT + lane, p * hv * de);
+      if constexpr (DET) s_dxp[n * GN_FEAT + lane] += p * hv * de;
+      else atomicAdd(s_dxp + n * GN_FEAT + lane, p * hv * de);
       const float datt = p * (s_dw[m] * hv - pd) * hv;
       if (lane < 32) {
         const float pre = s_pq[n * GN_FEAT + c] + qlo;
         dw2c = fmaf(datt, fmaxf(pre, 0.f), dw2c);
         const float dpre = pre > 0.f ? datt * w2c : 0.f;
-        atomicAdd(s_dpq + n * GN_FEAT + c, dpre);
+        if constexpr (DET) s_dpq[n * GN_FEAT + c] += dpre;
+        else atomicAdd(s_dpq + n * GN_FEAT + c, dpre);
         dq += dpre;
       }
       db2l += datt;
     }
     const float dq_hi = __shfl(dq, c, GN_WAVE);
     if (lane >= 32)
-      for (int m = 0; m < cnt; ++m) atomicAdd(s_dpq + s_idx[m] * GN_FEAT + lane, s_h[m] * dq_hi);
+      for (int m = 0; m < cnt; ++m) {
+        if constexpr (DET) s_dpq[s_idx[m] * GN_FEAT + lane] += s_h[m] * dq_hi;
+        else atomicAdd(s_dpq + s_idx[m] * GN_FEAT + lane, s_h[m] * dq_hi);
+      }
     __builtin_amdgcn_wave_barrier();   // the lists are rewritten by the next edge of this wave
   }
-  if (lane < 32) atomicAdd(s_red + c, dw2c);
-  if (lane == 0) atomicAdd(s_red + 32, db2l);
+  if constexpr (DET) {
+    if (lane < 32) part[c] = dw2c;
+    if (lane == 0) part[32] = db2l;
+  } else {
+    if (lane < 32) atomicAdd(s_red + c, dw2c);
+    if (lane == 0) atomicAdd(s_red + 32, db2l);
+  }
   __syncthreads();
   float* dxpb = dxp + (size_t)b * NF;
   float* dpqb = dpq + (size_t)b * NF;
-  for (int i = threadIdx.x; i < VF; i += kB) {
+  for (int i = threadIdx.x; i < VF; i += kT) {
     dxpb[i] += s_dxp[i];
     dpqb[i] += s_dpq[i];
   }
-  if (threadIdx.x < 32) atomicAdd(dw2 + threadIdx.x, s_red[threadIdx.x]);
-  if (threadIdx.x == 32) atomicAdd(db2, s_red[32]);
+  if constexpr (!DET) {
+    if (threadIdx.x < 32) atomicAdd(dw2 + threadIdx.x, s_red[threadIdx.x]);
+    if (threadIdx.x == 32) atomicAdd(db2, s_red[32]);
+  }
 }
 // scene b's count of a ragged launch, clamped as in every ragged kernel
 __device__ __forceinline__ int n2e_bwd_count(const int* __restrict__ n_valid, int b, int N) {
@@ -730,6 +853,43 @@ __global__ __launch_bounds__(kB) void node2edge_bwd_scene_ragged_grouped_kernel(
   const gn_n2e_bwd_group_t G = T.g[blockIdx.y];
   node2edge_bwd_scene_body<true>(G.xp, G.pq, G.H, G.w2, G.b2, G.dedges, G.dxp, G.dpq, G.dw2, G.db2, N, G.E, G.sym,
                                  (int)blockIdx.x, n2e_bwd_count(n_valid, (int)blockIdx.x, N));
+}
+// The ordered form (gn_node2edge_bwd_det_grouped_f32): one WAVE per (scene, module); partials (n_groups, B, 33) takes
+// each (module, scene)'s attention sums, and node2edge_bwd_det_sum_kernel — one workgroup per module — adds them to
+// dw2 / db2 in ascending scene order, starting from the buffers' present values (64 scenes at a time through LDS, so
+// that the loads are coalesced and only the adds are serial).
+__global__ __launch_bounds__(64) void node2edge_bwd_scene_det_kernel(N2EBwdTable T, int N, float* __restrict__ partials) {
+  const gn_n2e_bwd_group_t G = T.g[blockIdx.y];
+  node2edge_bwd_scene_body<false, 1, true>(G.xp, G.pq, G.H, G.w2, G.b2, G.dedges, G.dxp, G.dpq, G.dw2, G.db2, N, G.E,
+                                           G.sym, (int)blockIdx.x, N,
+                                           partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 33);
+}
+__global__ __launch_bounds__(64) void node2edge_bwd_scene_det_ragged_kernel(N2EBwdTable T, int N,
+                                                                            float* __restrict__ partials,
+                                                                            const int* __restrict__ n_valid) {
+  const gn_n2e_bwd_group_t G = T.g[blockIdx.y];
+  node2edge_bwd_scene_body<true, 1, true>(G.xp, G.pq, G.H, G.w2, G.b2, G.dedges, G.dxp, G.dpq, G.dw2, G.db2, N, G.E,
+                                          G.sym, (int)blockIdx.x, n2e_bwd_count(n_valid, (int)blockIdx.x, N),
+                                          partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 33);
+}
+constexpr int kSumScenes = 64;
+__global__ __launch_bounds__(kB) void node2edge_bwd_det_sum_kernel(N2EBwdTable T, const float* __restrict__ partials,
+                                                                   int B) {
+  __shared__ float s_p[kSumScenes * 33];
+  const gn_n2e_bwd_group_t G = T.g[blockIdx.x];
+  const float* __restrict__ p = partials + (size_t)blockIdx.x * B * 33;
+  const int t = threadIdx.x;
+  float* dst = t < 32 ? G.dw2 + t : G.db2;
+  float v = t < 33 ? *dst : 0.f;
+  for (int b0 = 0; b0 < B; b0 += kSumScenes) {
+    const int nb = min(kSumScenes, B - b0);
+    for (int i = t; i < nb * 33; i += kB) s_p[i] = p[(size_t)b0 * 33 + i];
+    __syncthreads();
+    if (t < 33)
+      for (int b = 0; b < nb; ++b) v = v + s_p[b * 33 + t];
+    __syncthreads();
+  }
+  if (t < 33) *dst = v;
 }
 
 // out[r][c] = alpha * a[r][c] + beta * out[r][c] on (rows x cols) blocks with leading dimensions
@@ -816,6 +976,40 @@ static int gemm_validate(const gn_gemm_desc_t& d) {
   return GN_OK;
 }
 
+// The launch form of one problem — a function of its own descriptor alone: the staging kernel (vector: 16-byte aligned
+// operands, K a multiple of 32), the K split of an accumulate problem and the tiles.  Both grouped launchers and the
+// plan query use it.
+struct GemmForm {
+  bool vec;
+  int gm, gn, splits, kchunk;
+  long long wgs;
+};
+static GemmForm gemm_form(const gn_gemm_desc_t& d) {
+  GemmForm f;
+  const bool tA = d.flags & GN_GEMM_TRANS_A, tB = d.flags & GN_GEMM_TRANS_B;
+  f.vec = ((uintptr_t)d.A & 15) == 0 && ((uintptr_t)d.B & 15) == 0 && d.lda % 4 == 0 && d.ldb % 4 == 0 &&
+          d.K % BK == 0 && (!tA || (d.M % 4 == 0)) && (tB || (d.N % 4 == 0));
+  f.gm = (d.M + BM - 1) / BM;
+  f.gn = (d.N + BN - 1) / BN;
+  int splits = 1;
+  if (d.flags & GN_GEMM_ACCUM) {   // long K over few tiles: split K over workgroups
+    // (swept on the whole training step at B=512: >= 256 rows per split, ~512 workgroups per problem)
+    splits = (512 + f.gm * f.gn - 1) / (f.gm * f.gn);
+    const int max_splits = (d.K + 255) / 256;
+    splits = splits > max_splits ? max_splits : splits;
+  }
+  f.kchunk = ((d.K + splits - 1) / splits + BK - 1) / BK * BK;
+  f.splits = (d.K + f.kchunk - 1) / f.kchunk;
+  f.wgs = (long long)f.gm * f.gn * f.splits;
+  return f;
+}
+static void gemm_fill(GemmDesc& g, const gn_gemm_desc_t& d, const GemmForm& f, long long tile0) {
+  g.A = d.A; g.B = d.B; g.C = d.C; g.bias = d.bias; g.mask = d.mask; g.rs = d.rs; g.colsum = d.colsum;
+  g.M = d.M; g.N = d.N; g.K = d.K; g.lda = d.lda; g.ldb = d.ldb; g.ldc = d.ldc; g.ldmask = d.ldmask;
+  g.rs_ld = d.rs_ld; g.flags = d.flags & 31; g.alpha = d.alpha; g.beta = d.beta;
+  g.tile0 = (int)tile0; g.gn = f.gn; g.gmn = f.gm * f.gn; g.kchunk = f.kchunk;
+}
+
 extern "C" int gn_gemm_grouped_f32(const gn_gemm_desc_t* descs, int n, gn_stream_t stream) {
   GN_REQUIRE_PTR(descs);
   if (n < 1) return GN_ERR_SHAPE;
@@ -836,33 +1030,178 @@ extern "C" int gn_gemm_grouped_f32(const gn_gemm_desc_t* descs, int n, gn_stream
   };
   for (int i = 0; i < n; ++i) {
     const gn_gemm_desc_t& d = descs[i];
-    const bool tA = d.flags & GN_GEMM_TRANS_A, tB = d.flags & GN_GEMM_TRANS_B;
-    const bool vec = ((uintptr_t)d.A & 15) == 0 && ((uintptr_t)d.B & 15) == 0 && d.lda % 4 == 0 && d.ldb % 4 == 0 &&
-                     d.K % BK == 0 && (!tA || (d.M % 4 == 0)) && (tB || (d.N % 4 == 0)) &&
-                     (!d.rs || true);
-    const int which = vec ? 0 : 1;
-    const int gm = (d.M + BM - 1) / BM, gn = (d.N + BN - 1) / BN;
-    int splits = 1;
-    if (d.flags & GN_GEMM_ACCUM) {   // long K over few tiles: split K, partial sums by atomics
-      // (swept on the whole training step at B=512: >= 256 rows per split, ~512 workgroups per problem)
-      splits = (512 + gm * gn - 1) / (gm * gn);
-      const int max_splits = (d.K + 255) / 256;
-      splits = splits > max_splits ? max_splits : splits;
-    }
-    int kchunk = ((d.K + splits - 1) / splits + BK - 1) / BK * BK;
-    splits = (d.K + kchunk - 1) / kchunk;
-    const long long mine = (long long)gm * gn * splits;
+    const GemmForm f = gemm_form(d);      // (an accumulate problem: partial sums by atomics)
+    const int which = f.vec ? 0 : 1;
+    const long long mine = f.wgs;
     if (mine > 0x7fffffffLL) return GN_ERR_SHAPE;
     if (T[which].n == kMaxDescs || tiles[which] + mine > 0x7fffffffLL) flush(which);
-    GemmDesc& g = T[which].d[T[which].n++];
-    g.A = d.A; g.B = d.B; g.C = d.C; g.bias = d.bias; g.mask = d.mask; g.rs = d.rs; g.colsum = d.colsum;
-    g.M = d.M; g.N = d.N; g.K = d.K; g.lda = d.lda; g.ldb = d.ldb; g.ldc = d.ldc; g.ldmask = d.ldmask;
-    g.rs_ld = d.rs_ld; g.flags = d.flags & 31; g.alpha = d.alpha; g.beta = d.beta;
-    g.tile0 = (int)tiles[which]; g.gn = gn; g.gmn = gm * gn; g.kchunk = kchunk;
+    gemm_fill(T[which].d[T[which].n++], d, f, tiles[which]);
     tiles[which] += mine;
   }
   flush(0);
   flush(1);
+  return gn_check_launch();
+}
+
+// ---- the ordered accumulate form --------------------------------------------------------------------------------
+// Element overlap of two (rows x cols, ld) destinations that are not identical.  Disjoint address ranges: none.  The
+// same ld: decided exactly (column slices of one matrix interleave without sharing an element).  Different ld with
+// intersecting ranges: taken as an overlap.
+static bool gemm_dst_overlap(const float* a, int ar, int ac, int ald, const float* b, int br, int bc, int bld) {
+  const float* a_end = a + (size_t)(ar - 1) * ald + ac;
+  const float* b_end = b + (size_t)(br - 1) * bld + bc;
+  if (a_end <= b || b_end <= a) return false;
+  if (ald != bld || ((uintptr_t)a & 3) != ((uintptr_t)b & 3)) return true;
+  if (b < a) return gemm_dst_overlap(b, br, bc, bld, a, ar, ac, ald);
+  const long long d = b - a, ld = ald;
+  const long long q = d / ld, rem = d - q * ld;
+  // b's row r sits in a's coordinates at row q + r, columns [rem, rem + bc), the part past ld wrapping into row q + r + 1
+  const bool same_row = rem < ac && q <= ar - 1;                     // rows q .. q + br - 1 against 0 .. ar - 1 (q >= 0)
+  const bool wrapped = rem + bc > ld && q + 1 <= ar - 1;             // columns [0, rem + bc - ld) of rows q + 1 ..
+  return same_row || wrapped;
+}
+
+static int gemm_det_layout(const gn_gemm_desc_t* descs, int n, gn_gemm_det_plan_t* plan) {
+  GN_REQUIRE_PTR(descs);
+  GN_REQUIRE_PTR(plan);
+  if (n < 1 || n > GN_GEMM_DET_MAX) return GN_ERR_SHAPE;
+  for (int i = 0; i < n; ++i) {
+    const int rc = gemm_validate(descs[i]);
+    if (rc != GN_OK) return rc;
+  }
+  *plan = gn_gemm_det_plan_t{};
+  plan->n = n;
+  long long floats = 0;
+  for (int i = 0; i < n; ++i) {
+    const gn_gemm_desc_t& d = descs[i];
+    const GemmForm f = gemm_form(d);
+    if (f.wgs > 0x7fffffffLL) return GN_ERR_SHAPE;
+    plan->splits[i] = f.splits;
+    plan->kchunk[i] = f.kchunk;
+    plan->kernel[i] = f.vec ? GN_GEMM_KERNEL_VECTOR : GN_GEMM_KERNEL_SCALAR;
+    plan->chain[i] = plan->cs_chain[i] = -1;
+    plan->offset[i] = plan->cs_offset[i] = -1;
+    if (!(d.flags & GN_GEMM_ACCUM)) continue;
+    const bool tC = d.flags & GN_GEMM_TRANS_C;
+    const int rows = tC ? d.N : d.M, cols = tC ? d.M : d.N;
+    plan->chain[i] = i;
+    if (d.colsum) plan->cs_chain[i] = i;
+    for (int j = 0; j < i; ++j) {
+      const gn_gemm_desc_t& e = descs[j];
+      if (!(e.flags & GN_GEMM_ACCUM)) continue;
+      const bool tE = e.flags & GN_GEMM_TRANS_C;
+      const int er = tE ? e.N : e.M, ec = tE ? e.M : e.N;
+      if (e.C == d.C && e.ldc == d.ldc && e.M == d.M && e.N == d.N && tE == tC) {
+        if (plan->chain[i] == i) plan->chain[i] = plan->chain[j];
+      } else if (gemm_dst_overlap(e.C, er, ec, e.ldc, d.C, rows, cols, d.ldc)) {
+        return GN_ERR_SHAPE;
+      }
+      if (d.colsum && e.colsum) {
+        if (e.colsum == d.colsum && e.M == d.M) {
+          if (plan->cs_chain[i] == i) plan->cs_chain[i] = plan->cs_chain[j];
+        } else if (gemm_dst_overlap(e.colsum, 1, e.M, e.M, d.colsum, 1, d.M, d.M)) {
+          return GN_ERR_SHAPE;
+        }
+      }
+    }
+    for (int j = 0; j < n; ++j) {       // a colsum inside a C of the call (its own included)
+      const gn_gemm_desc_t& e = descs[j];
+      if (!(e.flags & GN_GEMM_ACCUM)) continue;
+      const bool tE = e.flags & GN_GEMM_TRANS_C;
+      if (d.colsum && gemm_dst_overlap(d.colsum, 1, d.M, d.M, e.C, tE ? e.N : e.M, tE ? e.M : e.N, e.ldc))
+        return GN_ERR_SHAPE;
+    }
+    plan->offset[i] = floats * 4;
+    floats += ((long long)f.splits * rows * cols + 3) / 4 * 4;      // every region starts 16-byte aligned
+    if (d.colsum) {
+      plan->cs_offset[i] = floats * 4;
+      floats += ((long long)f.splits * d.M + 3) / 4 * 4;
+    }
+  }
+  for (int i = 0; i < n; ++i) plan->n_chains += plan->chain[i] == i;
+  plan->workspace_bytes = floats * 4;
+  return GN_OK;
+}
+
+extern "C" int gn_gemm_grouped_det_plan(const gn_gemm_desc_t* descs, int n, gn_gemm_det_plan_t* plan) {
+  return gemm_det_layout(descs, n, plan);
+}
+
+extern "C" int gn_gemm_grouped_det_f32(const gn_gemm_desc_t* descs, int n, void* workspace, size_t workspace_bytes,
+                                       gn_stream_t stream) {
+  gn_gemm_det_plan_t P;
+  int rc = gemm_det_layout(descs, n, &P);
+  if (rc != GN_OK) return rc;
+  if (P.workspace_bytes > 0) {
+    GN_REQUIRE_PTR(workspace);
+    GN_REQUIRE_ALIGNED(workspace);
+    if ((long long)workspace_bytes < P.workspace_bytes) return GN_ERR_SHAPE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = static_cast<float*>(workspace);
+  // Accumulate problems go through the ordered kernels in batches of kMaxDescs, each batch followed by its reduction (a
+  // chain that continues in a later batch goes on from the sum the earlier one left in the destination: the same
+  // order); a run of other problems is a call of the default launcher, which has one writer per element already.
+  GemmDetTable T[2];           // [0] vector staging, [1] scalar staging
+  RedTable R;
+  long long tiles[2] = {0, 0}, red_blocks = 0;
+  int batch = 0, n_mem = 0;
+  int item_chain[kMaxRedItems], item_cs[kMaxRedItems], last_mem[kMaxRedItems];
+  T[0].n = T[1].n = R.n_items = 0;
+  auto flush = [&]() {
+    if (T[0].n) hipLaunchKernelGGL(gemm_x6_det_kernel, dim3((unsigned)tiles[0]), dim3(kB), 0, s, T[0]);
+    if (T[1].n) hipLaunchKernelGGL(gemm_mfma_edge_det_kernel, dim3((unsigned)tiles[1]), dim3(kB), 0, s, T[1]);
+    if (R.n_items) hipLaunchKernelGGL(gemm_det_reduce_kernel, dim3((unsigned)red_blocks), dim3(kB), 0, s, R);
+    T[0].n = T[1].n = R.n_items = 0;
+    tiles[0] = tiles[1] = red_blocks = 0;
+    batch = n_mem = 0;
+  };
+  // one more member of the destination (chain id `chain`, C or colsum): a new item of this batch, or the tail of its list
+  auto member = [&](int chain, bool is_cs, float* dst, int rows, int cols, int ld, const float* part, int splits) {
+    int it = -1;
+    for (int k = 0; k < R.n_items; ++k)
+      if (item_chain[k] == chain && item_cs[k] == (int)is_cs) it = k;
+    RedMember& m = R.mem[n_mem];
+    m.part = part; m.splits = splits; m.next = -1;
+    if (it < 0) {
+      it = R.n_items++;
+      item_chain[it] = chain; item_cs[it] = (int)is_cs;
+      RedItem& I = R.item[it];
+      I.dst = dst; I.rows = rows; I.cols = cols; I.ld = ld; I.first = n_mem; I.block0 = (int)red_blocks; I.pad_ = 0;
+      red_blocks += ((long long)rows * cols + kB - 1) / kB;
+    } else {
+      R.mem[last_mem[it]].next = n_mem;
+    }
+    last_mem[it] = n_mem++;
+  };
+  for (int i = 0; i < n;) {
+    if (!(descs[i].flags & GN_GEMM_ACCUM)) {
+      int j = i;
+      while (j < n && !(descs[j].flags & GN_GEMM_ACCUM)) ++j;
+      rc = gn_gemm_grouped_f32(descs + i, j - i, stream);
+      if (rc != GN_OK) return rc;
+      i = j;
+      continue;
+    }
+    const gn_gemm_desc_t& d = descs[i];
+    const GemmForm f = gemm_form(d);
+    const int which = f.vec ? 0 : 1;
+    const bool tC = d.flags & GN_GEMM_TRANS_C;
+    const int rows = tC ? d.N : d.M, cols = tC ? d.M : d.N;
+    if (batch == kMaxDescs || tiles[which] + f.wgs > 0x7fffffffLL ||
+        red_blocks + ((long long)rows * cols + kB - 1) / kB + (d.M + kB - 1) / kB > 0x7fffffffLL)
+      flush();
+    GemmDetDesc& g = T[which].d[T[which].n++];
+    gemm_fill(g, d, f, tiles[which]);
+    g.part = ws + P.offset[i] / 4;
+    g.cs_part = d.colsum ? ws + P.cs_offset[i] / 4 : nullptr;
+    tiles[which] += f.wgs;
+    ++batch;
+    member(P.chain[i], false, d.C, rows, cols, d.ldc, g.part, f.splits);
+    if (d.colsum) member(P.cs_chain[i], true, d.colsum, 1, d.M, d.M, g.cs_part, f.splits);
+    ++i;
+  }
+  flush();
   return gn_check_launch();
 }
 
@@ -984,6 +1323,41 @@ static int n2e_bwd_grouped_entry(const gn_n2e_bwd_group_t* groups, int n_groups,
   if (scene_lds > 64 * 1024) gn_allow_big_lds(node2edge_bwd_scene_grouped_kernel);
   hipLaunchKernelGGL(node2edge_bwd_scene_grouped_kernel, dim3((unsigned)B, n_groups), dim3(kB), scene_lds,
                      (hipStream_t)stream, T, N);
+  return gn_check_launch();
+}
+// The ordered form: one wave per (scene, module), the 33 attention sums through `partials`, then the scene-order sum.
+// The LDS limit is the default form's (four waves' lists), so both forms serve the same N.
+extern "C" int gn_node2edge_bwd_det_grouped_f32(const gn_n2e_bwd_group_t* groups, int n_groups, int B, int N,
+                                                const int* n_valid, float* partials, gn_stream_t stream) {
+  if (groups == nullptr || partials == nullptr) return GN_ERR_NULL;
+  if (((uintptr_t)partials & 3u) != 0) return GN_ERR_ALIGN;
+  if (n_valid != nullptr) {
+    const int rc = gn_need_counts(n_valid);
+    if (rc != GN_OK) return rc;
+  }
+  if (n_groups < 1 || n_groups > GN_MAX_GROUPS || B <= 0 || N <= 0) return GN_ERR_SHAPE;
+  if (n2e_bwd_scene_lds(N) > kN2EBwdSceneBudget) return GN_ERR_LDS;
+  N2EBwdTable T{};
+  for (int g = 0; g < n_groups; ++g) {
+    const gn_n2e_bwd_group_t& G = groups[g];
+    const void* ptrs[] = {G.xp, G.pq, G.w2, G.b2, G.dedges, G.dxp, G.dpq, G.dw2, G.db2};
+    for (const void* p : ptrs)
+      if (p == nullptr) return GN_ERR_NULL;
+    if (G.E <= 0 || (G.sym && G.H != nullptr)) return GN_ERR_SHAPE;
+    if (G.H == nullptr && G.E != (G.sym ? gn_pair_count(N) : N * N)) return GN_ERR_SHAPE;
+    T.g[g] = G;
+  }
+  const size_t lds = ((size_t)4 * N * GN_FEAT + 64 + (size_t)4 * N) * sizeof(float);     // one wave's lists
+  hipStream_t s = (hipStream_t)stream;
+  if (n_valid != nullptr) {
+    if (lds > 64 * 1024) gn_allow_big_lds(node2edge_bwd_scene_det_ragged_kernel);
+    hipLaunchKernelGGL(node2edge_bwd_scene_det_ragged_kernel, dim3((unsigned)B, n_groups), dim3(64), lds, s, T, N,
+                       partials, n_valid);
+  } else {
+    if (lds > 64 * 1024) gn_allow_big_lds(node2edge_bwd_scene_det_kernel);
+    hipLaunchKernelGGL(node2edge_bwd_scene_det_kernel, dim3((unsigned)B, n_groups), dim3(64), lds, s, T, N, partials);
+  }
+  hipLaunchKernelGGL(node2edge_bwd_det_sum_kernel, dim3((unsigned)n_groups), dim3(kB), 0, s, T, partials, B);
   return gn_check_launch();
 }
 extern "C" int gn_node2edge_bwd_grouped_f32(const gn_n2e_bwd_group_t* groups, int n_groups, int B, int N,

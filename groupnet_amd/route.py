@@ -207,15 +207,21 @@ class BackwardRound:
 
 
 @functools.lru_cache(maxsize=None)
-def backward_round_route(N: int, pairwise: Tuple[bool, ...], ragged: bool = False) -> BackwardRound:
+def backward_round_route(N: int, pairwise: Tuple[bool, ...], ragged: bool = False, *,
+                         deterministic: bool = False) -> BackwardRound:
     """The route of one backward round over N agents (`backward.round_backward`).  pairwise: per module of the round.
     All of it hangs on whether a scene fits the per-scene node->edge backward.  Where it does not, a pairwise module
     needs ordered edge rows — the general kernel reads an incidence, and the pairwise one exists only per ordered edge —
     while its forward kept activations per unordered pair: they are re-computed, and since the re-computation is one
     grouped launch per stage, for every module of the round.
     ragged: the forward recorded per-scene counts.  The count-aware node->edge backward exists in the per-scene form
-    only (gn_node2edge_bwd_ragged_grouped_f32), so the round is the fitting one or none."""
+    only (gn_node2edge_bwd_ragged_grouped_f32), so the round is the fitting one or none.
+    deterministic: the caller asks for the ordered pooling backward (gn_node2edge_bwd_det_grouped_f32), which also has
+    the per-scene form only: the fitting round, unchanged, or none."""
     fits = N <= N2E_BWD_SCENE_MAX_N
+    if deterministic and not fits:
+        raise NotImplementedError(f"the deterministic backward needs N <= {N2E_BWD_SCENE_MAX_N} (got {N}): the ordered "
+                                  "node->edge backward has the per-scene form only")
     if ragged and not fits:
         raise NotImplementedError(f"the backward of a ragged batch needs N <= {N2E_BWD_SCENE_MAX_N} (got {N}): the "
                                   "count-aware node->edge backward has the per-scene form only")

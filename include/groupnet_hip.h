@@ -897,6 +897,51 @@ int gn_gemm_grouped_f32(const gn_gemm_desc_t* descs, int n, gn_stream_t stream);
 int gn_gemm_f32(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
                 int transA, int transB, const float* bias, const float* mask, int ldmask, int relu,
                 float alpha, float beta, gn_stream_t stream);
+/* The ordered (deterministic) form of the grouped launch (additions within ABI 40): the same descriptors, and a result
+ * that is bit-identical from run to run.
+ *   - A problem without GN_GEMM_ACCUM has one writer per element already: it runs as in gn_gemm_grouped_f32 and returns
+ *     its bits.
+ *   - An accumulate problem keeps gn_gemm_grouped_f32's form — the staging kernel (vector: A, B 16-byte aligned, lda,
+ *     ldb multiples of 4, K a multiple of 32, M (transA) / N (not transB) multiples of 4; else scalar), the tiles and the
+ *     split rule: with t = ceil(M/128) ceil(N/64) tiles, s0 = min(ceil(512/t), ceil(K/256)),
+ *     kchunk = ceil(ceil(K/s0)/32) 32, splits = ceil(K/kchunk); split s covers k in [s kchunk, min(K, (s+1) kchunk)).
+ *     Each (tile, split) workgroup stores its alpha-scaled partial tile — the value the atomic form would add — to the
+ *     caller's workspace at part[s][row][col] (dense, C's orientation) and, where colsum is set, its partial column sums
+ *     at cs_part[s][m], by plain stores.  A second kernel of the same call then forms, per destination element,
+ *         v = C_old;  for s = 0 .. splits-1:  v = v + part[s];  C = v
+ *     in fp32, one thread per element, and colsum[m] the same way from cs_part.
+ *   - Accumulate problems of one call with the IDENTICAL destination (the same C, ldc, M, N and GN_GEMM_TRANS_C; or the
+ *     same colsum and M) form a chain: their partials are added in descriptor order, split order within each, into the
+ *     one running v.  Accumulate destinations (C's and colsums) that share an element without being identical:
+ *     GN_ERR_SHAPE, nothing launched (the same ld: decided per element, so column slices of one matrix pass; different
+ *     ld with intersecting address ranges: refused).
+ *   - A problem's result depends on its own descriptor alone (shapes, leading dimensions, flags, alignment, values),
+ *     not on the other problems of the call, its position, the device's size or the environment.
+ *   - n <= GN_GEMM_DET_MAX, else GN_ERR_SHAPE.  workspace: device memory, 16-byte aligned (GN_ERR_ALIGN), at least
+ *     gn_gemm_grouped_det_plan's workspace_bytes (GN_ERR_SHAPE), NULL only where that is 0 (GN_ERR_NULL); its content
+ *     before and after the call is of no interest.  The launcher never allocates.
+ * gn_gemm_grouped_det_plan: pure host arithmetic — per problem splits, kchunk, the staging kernel, the chain (the index of
+ * the first problem of the call with its destination; -1: not an accumulate problem), the same for colsum (-1: none), the
+ * byte offsets of part and cs_part in the workspace (-1: none), and the workspace's size; returns what the launcher
+ * returns for the same descriptors (the workspace apart). */
+#define GN_GEMM_DET_MAX 128
+#define GN_GEMM_KERNEL_SCALAR 0
+#define GN_GEMM_KERNEL_VECTOR 1
+typedef struct {
+  long long workspace_bytes;
+  int n;
+  int n_chains;
+  int splits[GN_GEMM_DET_MAX];
+  int kchunk[GN_GEMM_DET_MAX];
+  int kernel[GN_GEMM_DET_MAX];
+  int chain[GN_GEMM_DET_MAX];
+  int cs_chain[GN_GEMM_DET_MAX];
+  long long offset[GN_GEMM_DET_MAX];
+  long long cs_offset[GN_GEMM_DET_MAX];
+} gn_gemm_det_plan_t;
+int gn_gemm_grouped_det_f32(const gn_gemm_desc_t* descs, int n, void* workspace, size_t workspace_bytes,
+                            gn_stream_t stream);
+int gn_gemm_grouped_det_plan(const gn_gemm_desc_t* descs, int n, gn_gemm_det_plan_t* plan);
 /* out (rows x cols, ldo) = alpha * a (rows x cols, lda) + beta * out — slices, scalings and sums of
  * gradients without leaving the library. */
 int gn_axpby2d_f32(float* out, int ldo, const float* a, int lda, long long rows, int cols, float alpha,
@@ -960,6 +1005,19 @@ int gn_node2edge_bwd_ragged_grouped_f32(const gn_n2e_bwd_group_t* groups, int n_
 int gn_node2edge_bwd_ragged_f32(const float* xp, const float* pq, const float* H, const float* w2, const float* b2,
                                 const float* dedges, float* dxp, float* dpq, float* dw2, float* db2, int B, int N,
                                 int E, int sym, const int* n_valid, gn_stream_t stream);
+/* The ordered (deterministic) form of the grouped per-scene launch (addition within ABI 40), full-batch (n_valid == NULL)
+ * or ragged (n_valid: the device counts, validated and clamped as above; a scene with n_b == 0 adds nothing).  One WAVE
+ * per (scene, module) walks the scene's edges in ascending order — rows of an explicit H, or the pairs in the order (and
+ * with the ragged addressing) of the default form — and adds each edge's contributions to the scene's dxp / dpq rows in
+ * LDS by plain read-modify-writes, every address owned by one lane: a row's sum is start + edge 0 + edge 1 + ..., the
+ * scene's rows then added once to dxp / dpq as before.  The 33 sums of attention layer 1 of (module g, scene b) go to
+ * partials[(g B + b) 33 ..] (32 of dw2, then db2; an empty scene writes zeros) by plain stores, and a second kernel of the
+ * same call forms dw2[c] = dw2_old[c] + partial(b = 0)[c] + partial(1)[c] + ... in ascending scene order, db2 likewise.
+ * partials: n_groups B 33 floats of device memory (NULL: GN_ERR_NULL; 4-byte aligned, else GN_ERR_ALIGN), content of no
+ * interest before or after.  The per-scene form only, with the default form's limit: N > 140 is GN_ERR_LDS and nothing
+ * is launched. */
+int gn_node2edge_bwd_det_grouped_f32(const gn_n2e_bwd_group_t* groups, int n_groups, int B, int N, const int* n_valid,
+                                     float* partials, gn_stream_t stream);
 
 /* ---- device noise (build's own; the reference draws torch.rand on the host) --------------------
  * U[i] = Philox4x32-10(counter = (i + offset) / 4, key = seed)[(i + offset) % 4] >> 8, scaled to
