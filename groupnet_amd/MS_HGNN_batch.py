@@ -23,6 +23,7 @@ Differences from the reference that a caller can observe
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import warnings
 from typing import Iterator, List, Optional, Sequence, Tuple, Union
@@ -114,7 +115,10 @@ _RAGGED_TRAINING: Optional[bool] = None
 
 def ragged_training() -> bool:
     """Whether a forward with ``n_agents`` may run under autograd: what `set_ragged_training` chose, else
-    GN_RAGGED_TRAINING=1 switches it on (read per call).  Off by default: such a call is refused before any launch."""
+    GN_RAGGED_TRAINING=1 switches it on (read per call).  Off by default: such a call is refused before any launch.
+    Inside `ragged_train_graph_scope` it is on whatever the two say."""
+    if _TRAIN_GRAPH_SCOPE[0]:
+        return True
     if _RAGGED_TRAINING is not None:
         return _RAGGED_TRAINING
     return os.environ.get("GN_RAGGED_TRAINING", "0") == "1"
@@ -124,6 +128,29 @@ def set_ragged_training(on: Optional[bool]) -> None:
     """True / False for calls issued from now on; None hands the choice back to the environment."""
     global _RAGGED_TRAINING
     _RAGGED_TRAINING = None if on is None else bool(on)
+
+
+# The step of a ragged `graphs.GraphedTrainStep` is its own opt-in: how many `ragged_train_graph_scope`s are open.
+_TRAIN_GRAPH_SCOPE = [0]
+
+
+@contextlib.contextmanager
+def ragged_train_graph_scope():
+    """Entered by `graphs.GraphedTrainStep._step` alone, around the step of a ragged capture: inside it a forward with
+    ``n_agents`` runs under autograd whatever `set_ragged_training` / GN_RAGGED_TRAINING say (`ragged_training`), and so
+    do holders that admit empty slots (`trains_empty_slots`: `ops.StaticAgentCounts`, a subset whose values live on the
+    device).  Every other refusal of a ragged call holds inside it as well.  Closed on the way out, an exception
+    included; scopes nest."""
+    _TRAIN_GRAPH_SCOPE[0] += 1
+    try:
+        yield
+    finally:
+        _TRAIN_GRAPH_SCOPE[0] -= 1
+
+
+def trains_empty_slots() -> bool:
+    """Whether counts that admit empty slots may run under autograd: inside `ragged_train_graph_scope` only."""
+    return _TRAIN_GRAPH_SCOPE[0] > 0
 
 
 # The deterministic backward is opt-in the same way: None — not set by `set_deterministic`, the environment decides per
@@ -196,7 +223,7 @@ def subset_of(n_agents, x: Tensor, grad: bool, **refusals: bool) -> Optional["op
         return None
     ops.agent_counts(n_agents, x.shape[0], x.shape[1], x.device)      # the sizes
     refuse_ragged(**refusals, **ragged_grad_refusals(grad, x.shape[1]))
-    if grad and n_agents.admits_empty:
+    if grad and n_agents.admits_empty and not trains_empty_slots():
         raise NotImplementedError("n_agents: counts that admit empty slots (a subset built from a GPU mask) are "
                                   "inference-only")
     return n_agents
@@ -548,7 +575,7 @@ def run_message_passing(mods: Sequence["_MessagePassing"], hs: Sequence[Tensor],
     ragged_train = counts is not None and traces is not None
     if ragged_train and not ragged_training():
         raise NotImplementedError("n_agents: ragged batches are inference-only")
-    if ragged_train and counts.admits_empty:
+    if ragged_train and counts.admits_empty and not trains_empty_slots():
         raise NotImplementedError("n_agents: counts that admit empty slots (ops.StaticAgentCounts) are inference-only")
     ragged = {} if counts is None else {"n_agents": counts}      # what the two count-aware launches are handed
     incs = [H if H is None or isinstance(H, ops.Incidence) else ops.Incidence(H) for H in Hs]

@@ -568,7 +568,7 @@ def modules_backward(traces: Sequence[ModuleTrace], g_nfs: Sequence[Optional[Ten
     grads: Dict[nn.Parameter, Tensor] = {}
     counts = traces[0].counts
     if counts is not None:
-        g_nfs, g_facs, items = list(g_nfs), list(g_facs), []
+        g_nfs, g_facs, items, single = list(g_nfs), list(g_facs), [], []
         for i, t in enumerate(traces):
             if g_nfs[i] is not None:
                 g_nfs[i] = g_nfs[i].clone(memory_format=torch.contiguous_format)
@@ -576,7 +576,13 @@ def modules_backward(traces: Sequence[ModuleTrace], g_nfs: Sequence[Optional[Ten
             if g_facs[i] is not None and g_facs[i].shape[1] != 1:      # (the single row of a scale-N module is valid)
                 g_facs[i] = g_facs[i].clone(memory_format=torch.contiguous_format)
                 items.append((g_facs[i], ops.ZERO_PAIR_ROWS if t.H is None else ops.ZERO_EDGE_ROWS))
+            elif g_facs[i] is not None and counts.admits_empty:
+                # ... except in an EMPTY slot, where the forward zeroed it (`ops.zero_empty_scenes`): a constant too
+                g_facs[i] = g_facs[i].clone(memory_format=torch.contiguous_format)
+                single.append(g_facs[i])
         ops.zero_padding(items, counts)
+        if single:
+            ops.zero_empty_scenes(single, counts)
     g_ys = list(g_nfs)
     for j in range(L, -1, -1):
         g_ds = list(g_facs) if j == 0 else [None] * len(traces)

@@ -24,7 +24,7 @@ from typing import Callable, Optional, Sequence, Tuple
 import torch
 
 from . import MS_HGNN_batch as _mods
-from . import ops, weights
+from . import ops, route, weights
 from .multiscale import MultiScaleHGNN
 
 Tensor = torch.Tensor
@@ -61,6 +61,49 @@ def _capture(graph, device, step: Callable, counter: Tensor, draws_per_step: int
         before_capture()
     with torch.cuda.graph(graph):
         return step()
+
+
+def _counts_holder(ragged, B: int, N: int, device, refuse: Callable):
+    """The count holder of a capture by its ``ragged=`` argument — False: None, True: an `ops.StaticAgentCounts`,
+    "subset": an `ops.StaticAgentSubset` — made, and filled with N, before the capture begins.  ``refuse``: the
+    capture's own refusals of a ragged route, run before anything is allocated."""
+    if ragged not in (False, True, "subset"):
+        raise ValueError("ragged: False, True or 'subset'")
+    if not ragged:
+        return None
+    refuse()
+    return (ops.StaticAgentSubset if ragged == "subset" else ops.StaticAgentCounts)(B, N, device)
+
+
+def _checked_counts(holder, B: int, N: int, device, n_agents, agent_mask):
+    """The host validation of a replay's ``n_agents`` / ``agent_mask`` for a graphed class's ``__call__``, before
+    anything is copied or launched: at most one of them, on a ragged capture only (``holder``) -> the validated count
+    values, or None where no counts were given."""
+    if n_agents is None and agent_mask is None:
+        return None
+    if holder is None:
+        raise ValueError("n_agents / agent_mask: the graph was captured without ragged=True")
+    if n_agents is not None and agent_mask is not None:
+        raise ValueError("n_agents and agent_mask: give at most one of them")
+    if n_agents is not None:
+        return ops.count_values(n_agents, B, N, lowest=0)
+    ops._mask_arg(agent_mask, B, N, device)
+    return None
+
+
+def _set_counts(holder, vals, agent_mask) -> None:
+    """What `_checked_counts` admitted, into the holder: the values through its staging ring, or the mask through its
+    device kernel; neither synchronises."""
+    if vals is not None:
+        holder.set(vals)
+    elif agent_mask is not None:
+        holder.set_from_mask(agent_mask)
+
+
+def _status(holder) -> int:
+    if holder is None:
+        raise ValueError("status: the graph was captured without ragged=True")
+    return int(holder.status.item()) & 0xFFFFFFFF
 
 
 class GraphedMultiScale:
@@ -110,12 +153,10 @@ class GraphedMultiScale:
         self.device = device or p.device
         if self.device.type != "cuda":
             raise ValueError("GraphedMultiScale needs the block on a GPU")
-        self.counts: Optional[ops.StaticAgentCounts] = None
-        if ragged not in (False, True, "subset"):
-            raise ValueError("ragged: False, True or 'subset'")
-        if ragged:      # the refusals of the eager ragged forward, before anything is allocated or launched
-            _mods.refuse_ragged(training=block.training, listall=any(m.listall for m in block.interaction_hyper))
-            self.counts = (ops.StaticAgentSubset if ragged == "subset" else ops.StaticAgentCounts)(B, N, self.device)
+        # (the refusals of the eager ragged forward, before anything is allocated or launched)
+        self.counts: Optional[ops.StaticAgentCounts] = _counts_holder(
+            ragged, B, N, self.device, lambda: _mods.refuse_ragged(
+                training=block.training, listall=any(m.listall for m in block.interaction_hyper)))
         self.block = block
         self.B, self.N = B, N
         self.seed = int(seed)
@@ -153,21 +194,10 @@ class GraphedMultiScale:
         """``n_agents`` / ``agent_mask`` (ragged captures only, at most one of them): this replay's counts — see
         `ops.StaticAgentCounts.set` and `set_from_mask`; neither: the previous counts stay.  Both are checked on the host
         before anything is copied or launched; neither path synchronises."""
-        if n_agents is not None or agent_mask is not None:
-            if self.counts is None:
-                raise ValueError("n_agents / agent_mask: the graph was captured without ragged=True")
-            if n_agents is not None and agent_mask is not None:
-                raise ValueError("n_agents and agent_mask: give at most one of them")
-            if n_agents is not None:
-                vals = ops.count_values(n_agents, self.B, self.N, lowest=0)
-            else:
-                ops._mask_arg(agent_mask, self.B, self.N, self.device)
+        vals = _checked_counts(self.counts, self.B, self.N, self.device, n_agents, agent_mask)
         if f is not None:
             self.f_in.copy_(f, non_blocking=True)
-        if n_agents is not None:
-            self.counts.set(vals)
-        elif agent_mask is not None:
-            self.counts.set_from_mask(agent_mask)
+        _set_counts(self.counts, vals, agent_mask)
         if self._weights.epoch != weights._EPOCH[0]:      # something was invalidated since the images were derived
             self.refresh_weights()
         self.graph.replay()
@@ -176,9 +206,7 @@ class GraphedMultiScale:
     def status(self) -> int:
         """The sticky status word of the mask entry (`_lib.COUNTS_NOT_PREFIX` | `_lib.COUNTS_EMPTY`, 0: nothing seen) of
         a ragged capture.  THE one call here that synchronises: it reads the device word back."""
-        if self.counts is None:
-            raise ValueError("status: the graph was captured without ragged=True")
-        return int(self.counts.status.item()) & 0xFFFFFFFF
+        return _status(self.counts)
 
 
 class GraphedPastEncoder:
@@ -264,14 +292,42 @@ class GraphedTrainStep:
     the graph so every replay draws fresh Gumbel noise.  Everything that depends on parameter values (packed
     weight images) is rebuilt inside the graph; after a replay the eager caches are dropped, so eager calls
     between replays see the updated parameters.  Optimizers must be capturable (SGD is; Adam with
-    ``capturable=True``)."""
+    ``capturable=True``).
+
+    A RAGGED capture (``ragged=True``; INTEGRATION.md, "Ragged batches", Training from a captured graph) trains on
+    batches whose scenes hold different numbers of agents, empty slots (count 0) included:
+
+        step = GraphedTrainStep(block, opt, loss_fn, B, N, target_shapes=[(B, N, 2)], seed=7, ragged=True)
+        loss = step(f, target, n_agents=[11, 7, 0, ...])   # counts: a sequence of ints or a CPU integer tensor, 0..N
+        loss = step(f, target, agent_mask=valid)           # ... or a (B,N) bool / uint8 mask that is already on the GPU
+        loss = step(f, target)                             # the previous counts stay
+        step.status()                                      # the mask entry's sticky status word (synchronises)
+
+    The loss is then called as ``loss_fn(final_feature, new_H, *targets, valid=valid)`` with ``valid`` a (B,N) bool
+    tensor made inside the graph at every replay — true at the real agents — so that it can normalise over them; an
+    empty slot adds exactly zero to every parameter gradient.  With ``ragged="subset"`` the mask may have zeros
+    anywhere, as in `GraphedMultiScale`.  The capture is its own opt-in: it needs no `set_ragged_training`, and the
+    eager refusals stay as they are."""
 
     def __init__(self, block: MultiScaleHGNN, optimizer: torch.optim.Optimizer, loss_fn: Callable, B: int, N: int,
-                 target_shapes: Sequence[Tuple[int, ...]] = (), seed: int = 0, warmup: int = 3):
+                 target_shapes: Sequence[Tuple[int, ...]] = (), seed: int = 0, warmup: int = 3, ragged: bool = False):
+        """``ragged``: False, True or "subset", as in `GraphedMultiScale`: the counts live in an `ops.StaticAgentCounts` /
+        `ops.StaticAgentSubset` (``self.counts``), made and filled with N before the capture; the graph holds its
+        address and — for "subset" — the compaction, the ragged training route and the expansion.  What the eager ragged
+        training refuses is refused here, before anything is allocated or launched: a ``listall`` module, N beyond the
+        per-scene node->edge backward, a scale beyond N."""
         p = next(block.parameters())
         self.device = p.device
         if self.device.type != "cuda":
             raise ValueError("GraphedTrainStep needs the block on a GPU")
+
+        def refuse():
+            _mods.refuse_ragged(large=N > route.N2E_BWD_SCENE_MAX_N, listall=any(m.listall for m in block.interaction_hyper))
+            if any(s > N for s in block.hyper_scales):
+                raise RuntimeError("selected index k out of range")
+
+        self.counts: Optional[ops.StaticAgentCounts] = _counts_holder(ragged, B, N, self.device, refuse)
+        self.B, self.N = B, N
         self.block, self.optimizer, self.loss_fn = block, optimizer, loss_fn
         self.seed = int(seed)
         self.f_in = torch.zeros((B, N, block.h_dim), dtype=torch.float32, device=self.device)
@@ -294,19 +350,43 @@ class GraphedTrainStep:
         self.optimizer.zero_grad(set_to_none=True)
         # every packed weight image of the step from TWO launches at its head (weights.repack_scope: the first warm-up step
         # records which plans / images a step touches)
-        with weights.repack_scope(self._repack):
+        # (a ragged capture is its own opt-in: the scope admits ``n_agents`` under autograd, and holders with empty slots)
+        scope = contextlib.nullcontext() if self.counts is None else _mods.ragged_train_graph_scope()
+        with weights.repack_scope(self._repack), scope:
             with torch.enable_grad():
-                out, H = self.block(self.f_in, advance=(self.counter, self.draws_per_step))
-                loss = self.loss_fn(out, H, *self.targets)
+                if self.counts is None:
+                    out, H = self.block(self.f_in, advance=(self.counter, self.draws_per_step))
+                    loss = self.loss_fn(out, H, *self.targets)
+                else:
+                    out, H = self.block(self.f_in, advance=(self.counter, self.draws_per_step), n_agents=self.counts)
+                    loss = self.loss_fn(out, H, *self.targets, valid=self._valid())
             loss.backward()
         self.optimizer.step()
         return loss.detach()
 
-    def __call__(self, f: Optional[Tensor] = None, *targets: Tensor) -> Tensor:
+    def _valid(self) -> Tensor:
+        """(B,N) bool, true at the real agents, from the holder's device values (nothing is read back): the slots with a
+        rank of a subset, else the first n_b of every scene."""
+        if isinstance(self.counts, ops.AgentSubset):
+            return self.counts.slot >= 0
+        return torch.arange(self.N, dtype=torch.int32, device=self.device)[None, :] < self.counts.dev[:, None]
+
+    def __call__(self, f: Optional[Tensor] = None, *targets: Tensor, n_agents=None, agent_mask: Optional[Tensor] = None
+                 ) -> Tensor:
+        """``n_agents`` / ``agent_mask`` (ragged captures only, at most one of them): this replay's counts, as in
+        `GraphedMultiScale.__call__` — checked on the host before anything is copied or launched; neither: the previous
+        counts stay."""
+        vals = _checked_counts(self.counts, self.B, self.N, self.device, n_agents, agent_mask)
         if f is not None:
             self.f_in.copy_(f, non_blocking=True)
         for dst, src in zip(self.targets, targets):
             dst.copy_(src, non_blocking=True)
+        _set_counts(self.counts, vals, agent_mask)
         self.graph.replay()
         _mods.invalidate_weight_caches(self.block)
         return self.loss
+
+    def status(self) -> int:
+        """The sticky status word of the mask entry of a ragged capture, as `GraphedMultiScale.status`.  THE one call
+        here that synchronises."""
+        return _status(self.counts)
